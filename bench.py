@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the temporal-walk-matrix hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,10 +11,17 @@ state + update() of the batch (the decoder-level unit of SURVEY.md §8d).  Workl
 starts.  Prints ONE JSON line (rank 0):
   value / ms_per_step   the K timed steps (ONE run_stream call, planning included; its argument views of the resident stream are
                         built before the clock starts), max over ranks
+A plain run does only that: set-up, warm-up, the timed steps, the line.  --full adds the secondary figures:
+  timed_regions.plain_call / .with_host_copy   the same steps through run_stream, and with the inputs copied from host memory
   roofline              the kernel those K steps ran on, timed live with HIP events over the same K batches
   epoch                 one epoch of the config's own stream (C2: 157 474 edges): wall clock, cold and with the plan replayed
   long_stream           2 048 batches of the same stream: the regime of streams of millions of edges
   cpu_baseline, dropin  the torch-CPU port on the host cores; the per-batch module API from host arrays
+  col_sharded, c4_rows  (N > 1) the column-sharded ablation and C4 through the row-sharded runner
+--dump-outputs DIR (one GPU): after the timed steps, what the last timed call handed back -- out_pos / out_neg, the pair features
+of its K batches, and the tables P[1..L] after its last batch -- as DIR/<name>.npy (float32; rows beyond a per-array budget are a
+fixed, seeded sample, their indices in DIR/<name>_rows.npy as float64; 64 MB in all at most).  The inputs are seeded: the same
+arguments give the same inputs in every run.
 """
 import argparse
 import os
@@ -365,6 +372,31 @@ def copy_bandwidth_gbs(dev):
 
 
 METRIC = "temporal edges/sec (proj-update + pairwise readout)"
+DUMP_BYTES = 64_000_000       # --dump-outputs: everything written, headers and row indices included, stays below this
+
+
+def dump_outputs(out_dir, named, tails=None):
+    """--dump-outputs: every (name, tensor) of `named` as out_dir/<name>.npy, float32, one row per leading index.  An array larger
+    than its even share of DUMP_BYTES is written as a fixed sample of its rows -- drawn by a RandomState seeded with the row count, so
+    that arrays of as many rows (out_pos / out_neg) keep the same rows, plus the last tails[name] rows always -- with the row
+    indices, ascending, in out_dir/<name>_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BYTES - (1 << 20)) // len(named)
+    for name, x in named:
+        x = x.detach().float().reshape(x.shape[0], -1)
+        n, row_b = x.shape[0], 4 * x.shape[1]
+        rows_path = os.path.join(out_dir, f"{name}_rows.npy")
+        if n * row_b <= share:
+            np.save(os.path.join(out_dir, f"{name}.npy"), x.cpu().numpy())
+            if os.path.exists(rows_path):
+                os.remove(rows_path)
+            continue
+        k = max(1, share // (row_b + 8))
+        tail = min((tails or {}).get(name, 0), k)
+        head = np.random.RandomState(n % (1 << 32)).choice(n - tail, k - tail, replace=False)
+        rows = np.concatenate([np.sort(head), np.arange(n - tail, n)]).astype(np.int64)
+        np.save(os.path.join(out_dir, f"{name}.npy"), x.index_select(0, torch.from_numpy(rows).to(x.device)).cpu().numpy())
+        np.save(rows_path, rows.astype(np.float64))
 
 
 def _error_line(n_gpus, msg, **extra):
@@ -489,8 +521,21 @@ def main():
     ap.add_argument("--config", default="C2")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dropin", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (roofline, epoch, long stream, plain / host-copy calls, drop-in, CPU "
+                         "baseline; at N > 1 the column-sharded and C4 legs); a plain run times only the headline steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call computed as DIR/<name>.npy (one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
+    if args.dump_outputs and ((args.gpus or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
+                              or os.environ.get("TPNET_BENCH_FORCE_DIST") == "1"):
+        if os.environ.get("RANK", "0") == "0":
+            print(_error_line(args.gpus or int(os.environ.get("WORLD_SIZE", "1")),
+                              "--dump-outputs is for the one-GPU path (a sharded run's outputs stay on their ranks)"), flush=True)
+        raise SystemExit(2)
     # --gpus N with nobody having launched the ranks (the way the driver runs --gpus 1): this process starts them as a child
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus or 1) > 1:
@@ -785,7 +830,11 @@ def main():
         # ---- the kernel those steps ran on, timed live: an extra pass over the same batches
         bpe_ = bytes_per_edge(d_, L)
         info = {}
-        if single_sched:
+        if not args.full:
+            # (a plain run: no extra pass; the schedule is the one the timed call was set up for)
+            if not single_sched:
+                info["schedule"] = "windowed" if will_window else "batch"
+        elif single_sched:
             runner.rp.reset_random_projections()
             sl_ = slice(W * Bg_, (W + k_steps) * Bg_)
             info["roof"] = roof_pass(a_src[sl_], a_dst[sl_], a_neg[sl_], a_t[sl_], k_steps * Bg_, 0.0, float(t_host[(W + k_steps) * Bg_ - 1]),
@@ -905,7 +954,7 @@ def main():
         # the timed steps go through the module's PREPARED call (RandomProjectionModule.prepare_stream: the arguments' devices / dtypes /
         # shapes checked and the call's flags formed once, before the clock -- what an epoch loop that runs the same stream every epoch
         # holds on to); the same steps through plain run_stream (arguments checked inside the region, ~10 us of a ~130-us region) are
-        # timed behind them and reported beside `value` as timed_regions.plain_call
+        # timed behind them (--full) and reported beside `value` as timed_regions.plain_call
         def prep(a, b_):
             s_, d_, n_, t_, op_, on_, te_, sched = prep_args(a, b_)
             return rp.prepare_stream(s_, d_, n_, t_, Bg, out_pos=op_, out_neg=on_, t_end=te_, schedule=sched, replay=False)
@@ -931,9 +980,13 @@ def main():
                 rp.reset_random_projections()
             regions.append(time_leg(run, K, prep))
         elapsed = float(np.median(regions))
+        if args.dump_outputs:
+            # what the last timed call handed back: the features of its K batches and the tables after its last batch
+            dump_outputs(args.dump_outputs, [("out_pos", out_pos), ("out_neg", out_neg)] +
+                         [(f"P{i}", rp.random_projections[i]) for i in range(1, L + 1)], tails={"out_pos": Bg, "out_neg": Bg})
         plain_regions = []
         copy_regions = []
-        if n_regions > 1:
+        if n_regions > 1 and args.full:
             for r_ in range(5):
                 rp.reset_random_projections()
                 plain_regions.append(time_leg(run_plain, K, prep_args))
@@ -993,16 +1046,18 @@ def main():
         if shard == "single" and len(regions) > 1:
             line["timed_regions"] = {"n": len(regions), "value_is": "median", "wall_us": [r_ * 1e6 for r_ in regions],
                                      "first_region": {"value": K * Bg / regions[0], "ms_per_step": regions[0] * 1e3 / K},
-                                     "call": "rp.prepare_stream(...) before the clock, the prepared call inside it",
-                                     "plain_call": {"value": K * Bg / float(np.median(plain_regions)),
-                                                    "wall_us": [r_ * 1e6 for r_ in plain_regions],
-                                                    "what": "the same steps through rp.run_stream (its argument checks inside the "
-                                                            "region), median of five regions timed behind the nine"},
-                                     "with_host_copy": {"value": K * Bg / float(np.median(copy_regions)),
-                                                        "wall_us": [r_ * 1e6 for r_ in copy_regions],
-                                                        "what": "the PCIe-inclusive rate: src / dst / neg / t of the timed steps copied from "
-                                                                "pinned host memory inside the region (four asynchronous copies, "
-                                                                f"{K * Bg * 32} bytes), then the same prepared call; median of five regions"}}
+                                     "call": "rp.prepare_stream(...) before the clock, the prepared call inside it"}
+            if plain_regions:
+                line["timed_regions"]["plain_call"] = {
+                    "value": K * Bg / float(np.median(plain_regions)), "wall_us": [r_ * 1e6 for r_ in plain_regions],
+                    "what": "the same steps through rp.run_stream (its argument checks inside the region), median of five regions "
+                            "timed behind the nine"}
+            if copy_regions:
+                line["timed_regions"]["with_host_copy"] = {
+                    "value": K * Bg / float(np.median(copy_regions)), "wall_us": [r_ * 1e6 for r_ in copy_regions],
+                    "what": "the PCIe-inclusive rate: src / dst / neg / t of the timed steps copied from pinned host memory inside "
+                            f"the region (four asynchronous copies, {K * Bg * 32} bytes), then the same prepared call; median of five "
+                            "regions"}
         if extra:
             line.update(extra)
         write_line(json.dumps(line))
@@ -1010,7 +1065,7 @@ def main():
     # second leg at N > 1: the column-sharded layout (ablation) on the same workload, behind a watchdog (a collective that
     # never returns must not cost the main line)
     row_info = None
-    if shard == "rows" and cols_ok and world > 1 and os.environ.get("TPNET_BENCH_COLS_LEG", "1") != "0":
+    if args.full and shard == "rows" and cols_ok and world > 1 and os.environ.get("TPNET_BENCH_COLS_LEG", "1") != "0":
         import threading
         state = {"done": False}
 
@@ -1039,7 +1094,7 @@ def main():
     extra = {}
 
     resident = 28.0 * N * d < 256e6
-    if rank == 0 and shard == "single":
+    if args.full and rank == 0 and shard == "single":
         sl = slice(W * Bg, (W + K) * Bg)
         rp.reset_random_projections()
         roof = roof_pass(d_src[sl], d_dst[sl], d_neg[sl], d_t[sl], K * B, 0.0, float(t[(W + K) * B - 1]), out_pos, out_neg)
@@ -1206,7 +1261,7 @@ def main():
         extra["backend"] = backend
     if shard == "rows":
         roof = rows_info.get("roof")
-        if os.environ.get("TPNET_BENCH_C4_LEG", "1") != "0" and (world > 1 or os.environ.get("TPNET_BENCH_C4_LEG") == "1"):
+        if args.full and os.environ.get("TPNET_BENCH_C4_LEG", "1") != "0" and (world > 1 or os.environ.get("TPNET_BENCH_C4_LEG") == "1"):
             try:
                 c4 = CONFIGS["C4"]
                 B4 = int(os.environ.get("TPNET_BENCH_C4_BATCH", c4["B"]))
@@ -1232,9 +1287,9 @@ def main():
         dist = None
     if rank == 0:
         cpu = dropin = None
-        if shard == "single" and not args.no_dropin:
+        if args.full and shard == "single" and not args.no_dropin:
             dropin = dropin_rate(cfg, rp, src, dst, neg, t)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             if shard == "single":
                 cpu = cpu_baseline(cfg, src, dst, neg, t, N, P0.numpy())
             else:

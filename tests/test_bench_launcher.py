@@ -135,3 +135,38 @@ def test_a_launch_that_outlives_its_limit_is_ended_with_its_ranks(monkeypatch, t
         time.sleep(0.1)
     else:
         raise AssertionError("the stand-in rank survived its launcher")
+
+
+def test_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """--dump-outputs: float32 arrays, whole when they fit their share of the budget, else a fixed seeded sample of rows that always
+    holds the last batch (its row indices beside it, float64); everything written stays below DUMP_BYTES, and the same call writes
+    the same files."""
+    import numpy as np
+    import torch
+    b = _bench()
+    big = torch.arange(1_200_000 * 64, dtype=torch.float32).reshape(-1, 64)          # 307 MB: sampled
+    small = torch.randn(9228, 128)                                                   # 4.7 MB: whole
+    named = [("out_pos", big), ("out_neg", big + 1)] + [(f"P{i}", small * i) for i in (1, 2, 3)]
+    runs = []
+    for sub in ("a", "b"):
+        d = tmp_path / sub
+        b.dump_outputs(str(d), named, tails={"out_pos": 1000, "out_neg": 1000})
+        runs.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+        assert sum(f.stat().st_size for f in d.iterdir()) < b.DUMP_BYTES
+    a, again = runs
+    assert sorted(a) == ["P1.npy", "P2.npy", "P3.npy", "out_neg.npy", "out_neg_rows.npy", "out_pos.npy", "out_pos_rows.npy"]
+    assert all(np.array_equal(a[k], again[k]) for k in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    np.testing.assert_array_equal(a["P2.npy"], (small * 2).numpy())
+    rows = a["out_pos_rows.npy"]
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+    assert rows[-1000:].tolist() == list(range(1_199_000, 1_200_000))
+    np.testing.assert_array_equal(a["out_pos.npy"][:, 0], rows * 64)
+    np.testing.assert_array_equal(a["out_neg.npy"], a["out_pos.npy"] + 1)
+
+
+def test_dump_outputs_is_refused_on_the_sharded_path():
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", "unused"], {})
+    assert r.returncode == 2
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["value"] is None and "--dump-outputs" in line["error"] and line["n_gpus"] == 2

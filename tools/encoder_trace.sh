@@ -1,12 +1,13 @@
 #!/bin/bash
-# development: kernel timeline of one batch of the device-resident encoder-level loop of bench.py
+# development: kernel timeline of one batch of the device-resident encoder-level loop of bench.py --full.  usage: tools/encoder_trace.sh OUTDIR
 R=${GRAFT_REPO_ROOT:-/root/repo}
+O=$(realpath -m "${1:?usage: tools/encoder_trace.sh OUTDIR}"); mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rm -rf $R/gpurun_out/enc_trace
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/enc_trace -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $R/gpurun_out/enc_trace.json 2> $R/gpurun_out/enc_trace.err
+rm -rf $O/enc_trace
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/enc_trace -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/enc_trace.json 2> $O/enc_trace.err
 python3 - <<PY
 import csv,glob,os
-f=sorted(glob.glob('$R/gpurun_out/enc_trace/*/*_kernel_trace.csv'), key=os.path.getmtime)[-1]
+f=sorted(glob.glob('$O/enc_trace/*/*_kernel_trace.csv'), key=os.path.getmtime)[-1]
 rows=sorted(csv.DictReader(open(f)), key=lambda r:int(r['Start_Timestamp']))
 idx=[i for i,r in enumerate(rows) if 'k_encoder_sample' in r['Kernel_Name']]
 # fp32-class loop comes first, the bf16 loop after: take a batch in the first third
