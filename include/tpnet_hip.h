@@ -311,7 +311,10 @@ int tpnet_run_stream(const tpnet_state* st, const int64_t* src, const int64_t* d
  * is ONE chunk, or (since ABI 6) up to 64 chunks whose plans find room side by side in front of the one version log they share
  * (tpnet_stream_workspace_bytes sizes the workspace for that) --; a later call with equal arguments, the same workspace and the same two signatures skips the planning and only
  * resolves the negatives' readout references again (tag->replayed = 1).  The CALLER vouches with the signatures:
- *   stream_sig: identifies the CONTENTS of src / dst / t (equal value = unchanged arrays; 0 = never replay);
+ *   stream_sig: identifies the CONTENTS of src / dst / t (equal value = unchanged arrays; 0 = never replay).  Equal pointers are
+ *               not equal arrays: memory that was freed and handed to another array comes back at the same address, so the
+ *               value must name the arrays themselves (tpnet_amd keys it on the live tensor objects, their addresses and version
+ *               counters) and change whenever one of them was written or replaced;
  *   table_sig:  identifies the table's per-node (current copy, reference time) state before the call -- e.g. one constant
  *               for "just after tpnet_state_init(t0)" per t0, a fresh value after anything else wrote the state (0 = never).
  * A stream on the per-batch schedule that is ONE chunk (up to ~2 M edges) replays its plan too: that plan is a function of src / dst / t,

@@ -15,6 +15,7 @@ How the state is held:
     (reload, load_state_dict, .to(), direct `.data` assignment -- detected through data_ptr/_version).
 """
 import ctypes as C
+import itertools
 import math
 import weakref
 
@@ -41,6 +42,28 @@ def _ptr_or_null(t):
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
+
+
+def _owners(*tensors):
+    """The objects that own the tensors' memory: the base each one is a view of (a view keeps its base alive), else the tensor."""
+    return tuple(None if x is None else (x if x._base is None else x._base) for x in tensors)
+
+
+class _Held:
+    """Which live tensors a cached plan was built from: weak references to their owners (_owners) and a generation number that no
+    other _Held has.  An address and torch's version counter do not name an array: a freed block goes to the next tensor of its
+    size, whose counter starts at 0 again.  While the very objects a plan was built from are alive, their memory has not been
+    handed on -- so a plan is reused only if `same(_owners(...))` (and the addresses and version counters are the same)."""
+    __slots__ = ("refs", "gen")
+    _gens = itertools.count(1)
+
+    def __init__(self, owners):
+        self.refs = tuple(None if o is None else weakref.ref(o) for o in owners)
+        self.gen = next(_Held._gens)
+
+    def same(self, owners) -> bool:
+        return len(owners) == len(self.refs) and all((r is None) if o is None else (r is not None and r() is o)
+                                                     for r, o in zip(self.refs, owners))
 
 
 _OWNERS = weakref.WeakValueDictionary()      # id(module) -> module, for the lazy layer list below
@@ -101,7 +124,7 @@ class PreparedStream:
     it runs the stream.  Attributes: the tensors it reads (`src`, `dst`, `neg`, `t`: their contents are read at every call) and
     writes (`out_pos`, `out_neg`: what the call returns)."""
     __slots__ = ("rp", "src", "dst", "neg", "t", "E", "batch_size", "nb", "want_pos", "want_neg", "out_pos", "out_neg", "t_end",
-                 "flags", "replay", "exact", "dev", "ptrs", "ws_need", "ws_cap")
+                 "flags", "replay", "exact", "dev", "ptrs", "owners", "ws_need", "ws_cap")
 
     def __call__(self):
         return self.rp._run_prepared(self)
@@ -534,7 +557,7 @@ class RandomProjectionModule(nn.Module):
         if self._eng is not None and not self._params_valid:
             self._materialize()                                    # the Parameters carry the state into the copy
         d = dict(self.__dict__)
-        for k in ("_eng", "_pin_ring", "_param_refs", "_st_cache"):
+        for k in ("_eng", "_pin_ring", "_param_refs", "_st_cache", "_plan_held"):
             d.pop(k, None)
         d["_eng"] = None
         d["_engine_valid"] = False
@@ -1100,8 +1123,10 @@ class RandomProjectionModule(nn.Module):
         checking per call that a 20-batch stream of ~130 us notices.  What `train_link_prediction.py:234-253` does every epoch (the
         same chronological arrays from a reset table) is one prepared call per split, called once per epoch (a new `neg` every epoch:
         write it into the tensor the call holds -- `call.neg.copy_(...)` -- or prepare again).  The call holds references to its
-        tensors; their CONTENTS are read when it runs (and torch's version counters decide whether the plan of an earlier run may be
-        replayed, exactly as in run_stream); replacing a tensor's storage (`resize_`, `set_`) behind a prepared call is not supported."""
+        tensors; their CONTENTS are read when it runs.  The plan of an earlier run is replayed, exactly as in run_stream, only for the
+        same live src / dst / t objects (or views of the same live bases) at the same addresses with unchanged version counters: a
+        stream built anew -- even in the block a freed one left -- is planned again.  Replacing a tensor's storage (`resize_`,
+        `set_`) behind a prepared call is not supported."""
         self._ensure_engine()
         dev = self._dev()
         E = int(src.numel())
@@ -1143,6 +1168,7 @@ class RandomProjectionModule(nn.Module):
         p.flags, p.replay, p.exact, p.dev = flags, replay, self.exact, dev
         p.ptrs = (src.data_ptr(), dst.data_ptr(), neg.data_ptr() if neg is not None else 0, t.data_ptr(),
                   out_pos.data_ptr() if want_pos else 0, out_neg.data_ptr() if want_neg else 0)
+        p.owners = _owners(src, dst, t)
         p.ws_cap = self.stream_log_cap_bytes
         need = 0
         if E > 0:
@@ -1169,18 +1195,23 @@ class RandomProjectionModule(nn.Module):
         t_out = C.c_double(0.0)
         # a stream that is run again on the same table state (every epoch of train_link_prediction.py:234-253: reset, then the
         # same chronological batches) replays its plan: the tag tells the C side that src / dst / t hold what they held when
-        # the plan in the workspace was built (torch bumps a tensor's _version on every in-place write; a write through a raw
-        # pointer or .data is not seen -- pass replay=False then) and names the table's per-node state
+        # the plan in the workspace was built -- the same live objects as then (_Held: a new tensor in a freed block has the old
+        # address and _version 0), unchanged since (torch bumps a tensor's _version on every in-place write; a write through a
+        # raw pointer or .data is not seen -- pass replay=False then) -- and names the table's per-node state
         tag = None
         ps, pd, pn, pt, pop, pon = p.ptrs
         if p.replay is not False and self.plan_replay:
             tag = self.__dict__.get("_plan_tag")
             if tag is None:
                 tag = self.__dict__["_plan_tag"] = _lib.PlanTag()
+            held = self.__dict__.get("_plan_held")
+            if held is None or not held.same(p.owners):
+                held = self.__dict__["_plan_held"] = _Held(p.owners)
             tag.table_sig = self._table_sig
-            tag.stream_sig = (hash((ps, src._version, pd, dst._version, pt, t._version, E)) & 0xFFFFFFFFFFFFFFFF) | 1
+            tag.stream_sig = (hash((held.gen, ps, src._version, pd, dst._version, pt, t._version, E)) & 0xFFFFFFFFFFFFFFFF) | 1
         else:
             self._drop_plan()
+        self.__dict__["_rows_plan_sig"] = None          # (this call writes the workspace: the row shard's plan there is gone)
         t_end = p.t_end
         fast = _lib.fast()
         if fast is not None:

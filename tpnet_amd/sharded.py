@@ -37,6 +37,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .random_projection import _Held, _owners
 
 # development: issue the collectives even with a single rank (exercises the RCCL calls on a one-GPU box)
 _FORCE = os.environ.get("TPNET_DEV_FORCE_COLLECTIVES") == "1"
@@ -419,9 +420,10 @@ class ShardedStreamRunner:
 
     @staticmethod
     def _stream_sig(src, dst, neg, t, E, B):
-        """Identifies the CONTENTS of a call's stream tensors the way RandomProjectionModule.run_stream does (storage + torch's
-        in-place version counters): an equal value = the same arrays, unchanged -- what lets a runner keep a stream's exchange plan
-        and its kernels' plan across calls (every epoch of train_link_prediction.py:234-253 runs the same stream again)."""
+        """The addresses and torch's in-place version counters of a call's stream tensors.  With the same live objects behind them
+        (_exchange_plan: a new tensor in a freed block has the old address and _version 0) an equal value = the same arrays,
+        unchanged -- what lets a runner keep a stream's exchange plan and its kernels' plan across calls (every epoch of
+        train_link_prediction.py:234-253 runs the same stream again)."""
         parts = [E, B]
         for x in (src, dst, neg, t):
             parts += [None, 0] if x is None else [x.data_ptr(), x._version]
@@ -581,6 +583,38 @@ class ShardedStreamRunner:
     # nothing else used the module's workspace and the clock it starts from is the same -- the plan of its kernels
     reuse_plans = True
 
+    def _exchange_plan(self, src, dst, neg, t, B):
+        """The stream's exchange plan and relabelled ids (relabel_targeted), and the _Held of the tensors it was made from: the
+        cached one if src / dst / neg / t are the very objects it was made from, at the same addresses, unchanged (the plan holds
+        the relabelled negatives: a fresh `neg` in the block a freed one left is a new plan)."""
+        E = int(src.numel())
+        sig = self._stream_sig(src, dst, neg, t, E, B) if self.reuse_plans else None
+        owners = _owners(src, dst, neg, t)
+        xc = self.__dict__.get("_xplan_cache")
+        if sig is not None and xc is not None and xc[0] == sig and xc[2].same(owners):
+            return xc[1], xc[2]
+        R = self.relabel_targeted_device(src, dst, neg, B) if self.device_plan else None   # (checks the ids' range itself)
+        if R is None:
+            ends = [src, dst] + ([neg] if neg is not None else [])  # (the lists key on batch * N + node: a bad id would alias)
+            if int(torch.stack([x.min() for x in ends]).min()) < 0 or int(torch.stack([x.max() for x in ends]).max()) >= self.N:
+                raise IndexError(f"node id out of range for {self.N} nodes")
+            R = self.relabel_targeted(src, dst, neg, B)
+        # (the device plan's lists live in the runner's scratch, which the NEXT cold plan overwrites -- and that plan replaces
+        # this one in the one-entry cache at the same time; the module's own plan is dropped below for the same reason)
+        R["scnt"] = np.ascontiguousarray(R["send_cnt"], dtype=np.int64)
+        R["rcnt"] = np.ascontiguousarray(R["recv_cnt"], dtype=np.int64)
+        R["stot"] = R["scnt"].sum(axis=1)
+        R["sstart_"] = np.ascontiguousarray(R["sstart"] if "sstart" in R else
+                                            np.concatenate([[0], np.cumsum(R["stot"])[:-1]]), dtype=np.int64)
+        R["smax"] = max(int(R["stot"].max()), 1)
+        held = _Held(owners)
+        if sig is not None:
+            self.__dict__["_xplan_cache"] = (sig, R, held)
+        # a plan the module's workspace still holds was built on OTHER relabelled arrays: nothing may be replayed across a cold
+        # exchange plan
+        self.rp._drop_plan()
+        return R, held
+
     def _send_buffers(self, d, L, smax, dev):
         """The pack launch's two send buffers, kept across calls (torch.zeros of both per call sat inside every timed region)."""
         b = self.__dict__.get("_send_bufs")
@@ -624,29 +658,7 @@ class ShardedStreamRunner:
             t_end = float(np.asarray(t_host_last, dtype=np.float64)[-1]) if t_host_last is not None else float(t[-1].item())
             return dict(E=E, B=B, nb=nb, out_pos=out_pos, out_neg=out_neg, now=rp._now_host, ls=src, ld=dst, ln=neg, t=t,
                         t_last=np.array([t_end], dtype=np.float64), windowed=True, comm=None, nccl=False)
-        sig = self._stream_sig(src, dst, neg, t, E, B) if self.reuse_plans else None
-        xc = self.__dict__.get("_xplan_cache")
-        R = xc[1] if (sig is not None and xc is not None and xc[0] == sig) else None
-        if R is None:
-            R = self.relabel_targeted_device(src, dst, neg, B) if self.device_plan else None   # (checks the ids' range itself)
-            if R is None:
-                ends = [src, dst] + ([neg] if neg is not None else [])  # (the lists key on batch * N + node: a bad id would alias)
-                if int(torch.stack([x.min() for x in ends]).min()) < 0 or int(torch.stack([x.max() for x in ends]).max()) >= self.N:
-                    raise IndexError(f"node id out of range for {self.N} nodes")
-                R = self.relabel_targeted(src, dst, neg, B)
-            # (the device plan's lists live in the runner's scratch, which the NEXT cold plan overwrites -- and that plan replaces
-            # this one in the one-entry cache at the same time; the module's own plan is dropped below for the same reason)
-            R["scnt"] = np.ascontiguousarray(R["send_cnt"], dtype=np.int64)
-            R["rcnt"] = np.ascontiguousarray(R["recv_cnt"], dtype=np.int64)
-            R["stot"] = R["scnt"].sum(axis=1)
-            R["sstart_"] = np.ascontiguousarray(R["sstart"] if "sstart" in R else
-                                                np.concatenate([[0], np.cumsum(R["stot"])[:-1]]), dtype=np.int64)
-            R["smax"] = max(int(R["stot"].max()), 1)
-            if sig is not None:
-                self.__dict__["_xplan_cache"] = (sig, R)
-            # a plan the module's workspace still holds was built on OTHER relabelled arrays (a freed tensor's address can come back
-            # with the same version counter: nothing may be replayed across a cold exchange plan)
-            rp._drop_plan()
+        R, held = self._exchange_plan(src, dst, neg, t, B)
         if t_host_last is None:
             last_idx = torch.clamp(torch.arange(1, nb + 1, device=dev) * B, max=E) - 1
             t_last = t[last_idx].cpu().numpy()
@@ -685,7 +697,8 @@ class ShardedStreamRunner:
         ws = rp._workspace(E, B, keep_plan=True)
         st = rp._state()
         stream = rp._stream()
-        psig = (sig, rp._now_host, lam, flags, ws.data_ptr(), ws.numel()) if sig is not None else None
+        # (the kernels' plan is a function of the relabelled arrays -- the exchange plan `held` names -- t, the clock and the flags)
+        psig = (held.gen, rp._now_host, lam, flags, ws.data_ptr(), ws.numel()) if self.reuse_plans else None
         if psig is None or rp.__dict__.get("_rows_plan_sig") != psig:
             rp._drop_plan()
             _lib.check(lib.tpnet_plan_stream(C.byref(st), ls.data_ptr(), ld.data_ptr(), t.data_ptr(), E, B, rp._now_host,
