@@ -102,7 +102,7 @@ typedef struct tpnet_state {
                                        stream: N * 12 bytes <= batch * L * d * 4).  Same bits again */
 
 #define TPNET_FLAG_NO_MFMA_READOUT 256u /* tpnet_pair_gram_anchored and the encoder calls built on it: keep the vector-ALU readout where
-                                       the matrix-core one applies (rows of 64 / 128 floats, L = 3, K >= 4: split-bf16 operands,
+                                       the matrix-core one applies (rows of 36..160 floats, d % 4 == 0, L = 3, K >= 4: split-bf16 operands,
                                        three pieces per value, fp32 accumulation -- fp32 class, other summation order) */
 
 const char* tpnet_strerror(int status);
@@ -245,10 +245,12 @@ int tpnet_host_update(const tpnet_state* st, tpnet_stage* stage, const int64_t* 
  * (2L+2)^2 floats laid out and scaled like tpnet_pair_gram's -- with out2 = out1 + n_rows*K*(2L+2)^2 this IS the reference's
  * get_pair_wise_feature(tile(neigh, 2), concat(repeat(a1, K), repeat(a2, K))) before self.mlp.  One lane group walks a row:
  * the anchors' rows are fetched once per row (not once per pair) and stay in registers, their own Gram blocks are reduced
- * once per row.  Needs rows of exactly one chunk of 16-byte vectors (d = 64, 128, 256, 512: tpnet_pair_gram_anchored_supported
- * returns 1); other shapes take tpnet_pair_gram_shared / tpnet_pair_gram.  Rows of 64 / 128 floats with L = 3 and K >= 4 are
- * served by the matrix cores (csrc/encoder_mfma.hip: 16 x 16 x 32 bf16 products on operands split into three bf16 pieces, fp32
- * accumulation over d inside the pipe -- no cross-lane reduction; TPNET_FLAG_NO_MFMA_READOUT keeps the vector-ALU walk). */
+ * once per row.  Needs rows of whole 16-byte vectors inside one chunk (d % 4 == 0 and 36 <= d <= 512, the reference's default
+ * widths 120 / 140 / 160 included: tpnet_pair_gram_anchored_supported returns 1; a row that does not fill the chunk reads as
+ * zeros past its end); other shapes take tpnet_pair_gram_shared / tpnet_pair_gram.  Rows of 36..160 floats with L = 3 and
+ * K >= 4 are served by the matrix cores (csrc/encoder_mfma.hip: 16 x 16 x 32 bf16 products on operands split into three bf16
+ * pieces, fp32 accumulation over d inside the pipe -- no cross-lane reduction; d = 64 / 128 in whole 32-deep steps, every other
+ * width with the last step masked; TPNET_FLAG_NO_MFMA_READOUT keeps the vector-ALU walk). */
 int tpnet_pair_gram_anchored(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
                              int64_t n_rows, int32_t K, double now_time, double lambda, uint32_t flags, float* out1,
                              float* out2, void* stream);
@@ -507,15 +509,15 @@ int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, in
 
 /* The first half of tpnet_encoder_gram alone: the rows [src; other] at tile(t, 2), their anchors and their K sampled neighbours,
  * laid out in `scratch` (rounded up to 256): nodes int64[2B] | times double[2B] | a1 int64[2B] | a2 int64[2B] | neigh int64[2B][K]
- * | (rows of <= 128 floats: the call's pairs spelled out for the generic readout) u int64[4BK] | v int64[4BK]. */
+ * | (rows of <= 128 floats that the matrix-core readout does not serve: the call's pairs spelled out for the generic readout) u int64[4BK] | v int64[4BK]. */
 int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src,
                        const int64_t* other, const double* t, int64_t B, int32_t K, void* scratch, size_t scratch_bytes,
                        void* stream);
 
-/* The encoder's call INCLUDING self.mlp (models/TPNet.py:311-324, 129; L = 3, rows of one chunk of 16-byte vectors): gram =
+/* The encoder's call INCLUDING self.mlp (models/TPNet.py:311-324, 129; L = 3, rows as tpnet_pair_gram_anchored needs them): gram =
  * tpnet_pair_gram_anchored's output [2][n_rows*K][64] (kept: what a backward pass needs), out = mlp(gram) in the fp32 class
  * (tpnet_mlp64_f32's kernel), both on `stream`: the encoder's call as ONE crossing.  Where tpnet_encoder_fused_supported
- * returns 1 (rows of 64 / 128 floats, K >= 4, mlp->wimg given) readout and dense layers are ONE launch on the matrix cores
+ * returns 1 (rows of 36..160 floats with d % 4 == 0, K >= 4, mlp->wimg given) readout and dense layers are ONE launch on the matrix cores
  * (csrc/encoder_mfma.hip) and gram may be NULL: the pre-mlp features are then never written. */
 int tpnet_encoder_fused_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp);
 int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,

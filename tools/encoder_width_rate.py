@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Developer tool: the encoder's call (models/TPNet.py:311-324, 129) at a given row width, on C2's shape (B = 1 000, K = 20: 80 000
+pairs per call) and C3's (B = 10 000), every route the build under `--tree` has for it, alternated inside one process:
+
+  anchored   get_pair_wise_feature_anchored(neigh, a1, a2) on device ids: one launch on the matrix cores where served
+  dev_uv     get_pair_wise_feature(u, v) on device id tensors: general pair kernel, then self.mlp
+  host_uv    get_pair_wise_feature(u, v) on host arrays, as the reference's encoder issues it (pattern recognised where served)
+
+    tools/encoder_width_rate.py --dim 120 128 140 160 [--shapes C2 C3] [--reps 11] [--inner 10] [--tree OTHER_CHECKOUT] [--json OUT]
+
+One repeat = HIP events around `inner` calls, then a synchronise; per (shape, width, route) the median and the range over the
+repeats, in us per call.  `--tree` imports tpnet_amd from another (built) checkout: the same command on the parent commit gives the
+A/B.  A route the build does not have at a width is listed with its error."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--dim", type=int, nargs="+", default=[120, 128, 140, 160])
+ap.add_argument("--shapes", nargs="+", default=["C2", "C3"])
+ap.add_argument("--K", type=int, default=20)
+ap.add_argument("--reps", type=int, default=11)
+ap.add_argument("--inner", type=int, default=10)
+ap.add_argument("--routes", nargs="+", default=["anchored", "dev_uv", "host_uv"])
+ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--json", default=None)
+ap.add_argument("--once", action="store_true", help="one call per (shape, width, route) and no timing: for a kernel trace")
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.tree))
+import tpnet_amd                                                    # noqa: E402
+from tpnet_amd.stream import CONFIGS, synthetic_stream             # noqa: E402
+
+dev = torch.device("cuda:0")
+D = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+
+def one_repeat(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.inner):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / args.inner * 1e3
+
+
+results = []
+for cfg in args.shapes:
+    c = CONFIGS[cfg]
+    B, K = c["B"], args.K
+    E = 6 * B
+    src, dst, t, N = synthetic_stream(c["U"], c["I"], E, c["span"] * E / c["E"], 0)
+    rng = np.random.RandomState(1)
+    n = 2 * B
+    neigh = rng.randint(1, N, (n, K)).astype(np.int64)
+    a1, a2 = np.tile(src[-B:], 2), np.tile(dst[-B:], 2)
+    u = np.tile(neigh.reshape(-1), 2)
+    v = np.concatenate([np.repeat(a1, K), np.repeat(a2, K)])
+    neigh_d, a1_d, a2_d, u_d, v_d = D(neigh), D(a1), D(a2), D(u), D(v)
+    calls, checks = {}, {}
+    for d in args.dim:
+        torch.manual_seed(d)
+        rp = tpnet_amd.RandomProjectionModule(node_num=N, edge_num=c["E"], dim_factor=10, num_layer=3, time_decay_weight=c["lam"],
+                                              device="cuda:0", use_matrix=False, beginning_time=np.float64(0.0), not_scale=False,
+                                              enforce_dim=d).to(dev)
+        rp.run_stream(D(src), D(dst), None, D(t), B, want_neg=False, want_pos=False)
+        routes = {"anchored": lambda rp=rp: rp.get_pair_wise_feature_anchored(neigh_d, a1_d, a2_d),
+                  "dev_uv": lambda rp=rp: rp.get_pair_wise_feature(u_d, v_d),
+                  "host_uv": lambda rp=rp: rp.get_pair_wise_feature(u, v)}
+        ref = None
+        for name in args.routes:
+            try:
+                with torch.no_grad():
+                    y = routes[name]()                              # warm-up (and: does the build have this route here?)
+                    torch.cuda.synchronize()
+                    if ref is None:
+                        ref = y
+                    checks[(d, name)] = float((y - ref).abs().max() / ref.abs().max())
+                calls[(d, name)] = routes[name]
+            except Exception as e:                                  # noqa: BLE001
+                results.append(dict(shape=cfg, d=d, route=name, pairs=int(u.size), error=f"{type(e).__name__}: {e}"[:200]))
+    if args.once:
+        continue
+    times = {k: [] for k in calls}
+    with torch.no_grad():
+        for k, fn in calls.items():                                 # warmed up: one untimed repeat each
+            one_repeat(fn)
+        for _ in range(args.reps):                                  # the variants take turns inside the run
+            for k, fn in calls.items():
+                times[k].append(one_repeat(fn))
+    for (d, name), ts in times.items():
+        results.append(dict(shape=cfg, d=d, route=name, pairs=int(u.size), median_us=round(float(np.median(ts)), 2),
+                            min_us=round(min(ts), 2), max_us=round(max(ts), 2), reps=len(ts),
+                            rel_diff_to_first_route=checks[(d, name)]))
+for r in results:
+    print(json.dumps(r), flush=True)
+if args.json:
+    with open(args.json, "w") as f:
+        json.dump(dict(tree=os.path.abspath(args.tree), results=results), f, indent=1)

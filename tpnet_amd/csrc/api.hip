@@ -465,11 +465,13 @@ int tpnet_pair_gram_anchored(const tpnet_state* st, const int64_t* neigh, const 
     if (n_rows < 0 || K < 0 || (n_rows > 0 && K > 0 && (!neigh || !a1 || !a2 || !out1 || !out2))) return TPNET_ERR_BAD_ARG;
     if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;
     if (n_rows > 0 && K > 0 && !pair_gram_anchored_supported(*st)) {
-        // rows that are not one chunk of 16-byte vectors (d = 120, 140, use_matrix ...): the generic kernel, one launch per
-        // anchor side, on index arrays the caller would otherwise build -- not available without them: report it
+        // rows that are not whole 16-byte vectors (d % 4 != 0: 110, 130, 150 ...), narrower than 36 or wider than 512 floats: the
+        // generic kernel, one launch per anchor side, on index arrays the caller would otherwise build -- not available without
+        // them: report it
         return TPNET_ERR_BAD_ARG;
     }
-    // rows of 64 / 128 floats: the same blocks on the matrix cores (encoder_mfma.hip, fp32 class)
+    // rows of 36..160 floats: the same blocks on the matrix cores (encoder_mfma.hip, fp32 class); everything else that is
+    // supported (K < 4, unaligned outputs, wider rows, the flag): the vector-ALU walk
     if ((flags & TPNET_FLAG_NO_MFMA_READOUT) == 0 && encoder_mfma_supported(*st, n_rows, K) && !((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15))
         return launch_encoder_gram_mfma(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
     return launch_pair_gram_anchored(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);

@@ -18,6 +18,9 @@
 // contiguous bytes -- and reach the operand layout through ds_bpermute_b32 (the LDS crossbar, no LDS memory).
 // The 4 x 4 blocks leave the accumulators through an LDS tile of 8 feature rows per wave (the [w | anchor]^2 layout of
 // get_pair_wise_feature, mirrored), are clamped / log-scaled there (models/TPNet.py:127-128) and stored as whole 256-byte rows.
+// Row widths: d % 4 == 0, 36 <= d <= 160, in KS = ceil(d / 32) steps.  d = 64 / 128 fill their steps (FULL); every other width --
+// the reference's default rule gives 120 / 140 / 160 (models/TPNet.py:30-33) -- runs its last step with the pieces past the row's
+// end supplied as zeros (load_rows); nothing behind the accumulators depends on d.
 #include "device_common.hpp"
 
 namespace tpnet {
@@ -104,14 +107,18 @@ __device__ __forceinline__ f32x4 mm_step(const SplitOp<SPLIT>& a, const SplitOp<
     return c;
 }
 
-// 16 rows of 32 KS floats, one row pointer per load-layout lane (already offset by the lane's 16-byte piece), scaled by the
-// row's pending decay: raw[s][0..3] = floats 32 s + 4 p .., raw[s][4..7] = floats 32 s + 16 + 4 p ..
-template <int KS>
-__device__ __forceinline__ void load_rows(const float* __restrict__ rp, float (&raw)[KS][8]) {
+// 16 rows of KS 32-deep steps, one row pointer per load-layout lane (already offset by the lane's 16-byte piece):
+// raw[s][0..3] = floats 32 s + 4 p .., raw[s][4..7] = floats 32 s + 16 + 4 p ..
+// FULL: a row is exactly 32 KS floats.  !FULL: a row is d floats, 32 (KS - 1) < d <= 32 KS, d % 4 == 0: a piece is loaded only if
+// it lies inside the row (`left` = d - 4 p, the floats from the lane's first piece to the row's end) and is zero otherwise -- a
+// zero k-position adds exactly 0 to every product, and what follows a row in memory (the next node's row) is never read.
+template <int KS, bool FULL>
+__device__ __forceinline__ void load_rows(const float* __restrict__ rp, int left, float (&raw)[KS][8]) {
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-        const float4 x = *reinterpret_cast<const float4*>(rp + 32 * s);
-        const float4 y = *reinterpret_cast<const float4*>(rp + 32 * s + 16);
+        float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
+        if (FULL || 32 * s + 4 <= left) x = *reinterpret_cast<const float4*>(rp + 32 * s);
+        if (FULL || 32 * s + 20 <= left) y = *reinterpret_cast<const float4*>(rp + 32 * s + 16);
         raw[s][0] = x.x; raw[s][1] = x.y; raw[s][2] = x.z; raw[s][3] = x.w;
         raw[s][4] = y.x; raw[s][5] = y.y; raw[s][6] = y.z; raw[s][7] = y.w;
     }
@@ -171,7 +178,7 @@ __device__ __forceinline__ void mm_step2(const SplitOp<SPLIT>& a, const SplitOp<
 // in one of two LDS tiles for the consumer wave (sync[0] = tiles published, sync[1] = tiles taken, sync[2 + 2 b] / [3 + 2 b] =
 // first slot / validity of the tile in buffer b) and are stored only if out1 is given.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int KS, int SPLIT, bool HANDOFF>
+template <int KS, bool FULL, int SPLIT, bool HANDOFF>
 __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* __restrict__ neigh, const int64_t* __restrict__ a1,
                                            const int64_t* __restrict__ a2, int n_rows, int K, int T, int slot_begin, int slot_end,
                                            double now, double lambda, uint32_t flags, float* __restrict__ out1,
@@ -182,7 +189,8 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
     const int lr = lane >> 2, lp = lane & 3;       // load layout: row lr, 16-byte piece lp of a 64-byte segment
     const int pull = (4 * c + g) * 4;              // ds_bpermute address: operand lane (c, g) <- load lane 4 c + g
     const int l_layer = lr & 3;                    // load layout: the row's layer; its neighbour (or anchor) index is lr >> 2 = g
-    const int d = 32 * KS;
+    const int d = FULL ? 32 * KS : S.d;            // row stride; KS = ceil(d / 32) steps, the last one masked when !FULL
+    const int left = d - 4 * lp;
     const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
     const bool do_scale = !(flags & TPNET_FLAG_NOT_SCALE);
 
@@ -236,14 +244,14 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
         auto issue_tile = [&](int t) {             // rows of tile t of the group (load layout: neighbour g of the tile)
             const int sl = 4 * t + g;
             const int wv = __shfl(w, sl), cp = __shfl(mv.copy, sl);
-            load_rows<KS>(row_ptr(wv, cp, l_layer), raw);
+            load_rows<KS, FULL>(row_ptr(wv, cp, l_layer), left, raw);
         };
         auto issue_anchors = [&](int n0) {         // the 16 anchor rows of nodes n0, n0 + 1 (load layout: anchor index g)
             int al = 2 * (n0 - nfirst) + g;        // lane that holds anchor (n0 + (g >> 1), side g & 1)
             al = al > 63 ? 63 : al;
             const int id = __shfl(aid, al), cp = __shfl(am.copy, al);
             pre_g = __shfl(am.g, al);
-            load_rows<KS>(row_ptr(id, cp, l_layer), ra);
+            load_rows<KS, FULL>(row_ptr(id, cp, l_layer), left, ra);
             pre_n0 = n0;
         };
         issue_tile(0);
@@ -398,7 +406,7 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
 }
 
 // out1 / out2: the pre-mlp features of the two anchor sides, rows [slot][64]
-template <int KS, int SPLIT>
+template <int KS, bool FULL, int SPLIT>
 __global__ __launch_bounds__(EMB) void k_encoder_gram_mfma(tpnet_state S, const int64_t* __restrict__ neigh,
                                                            const int64_t* __restrict__ a1, const int64_t* __restrict__ a2,
                                                            int n_rows, int K, int T, int tpw, double now, double lambda,
@@ -408,8 +416,8 @@ __global__ __launch_bounds__(EMB) void k_encoder_gram_mfma(tpnet_state S, const 
     const int wid = blockIdx.x * (EMB / 64) + wave;
     const int slot_begin = wid * tpw * 4;
     const int slot_end = (slot_begin + tpw * 4 < T) ? slot_begin + tpw * 4 : T;
-    (void)walk_tiles<KS, SPLIT, false>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags, out1, out2,
-                                       stg_all + wave * (8 * EM_RS), nullptr);
+    (void)walk_tiles<KS, FULL, SPLIT, false>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags, out1, out2,
+                                             stg_all + wave * (8 * EM_RS), nullptr);
 }
 
 // ReLU in ONE instruction: the signed-integer maximum of the bits and 0 (fmaxf / med3 cost a canonicalising v_max first; inline
@@ -531,7 +539,7 @@ __device__ __forceinline__ void dense_consumer(const char* smem, const float* st
 }
 
 // gram (may be null): the pre-mlp features [2][T][64]; y = self.mlp(features), rows [side * T + slot]
-template <int KS, int SPLIT>
+template <int KS, bool FULL, int SPLIT>
 __global__ __launch_bounds__(EMF_B) void k_encoder_fused(tpnet_state S, const int64_t* __restrict__ neigh, const int64_t* __restrict__ a1,
                                                          const int64_t* __restrict__ a2, int n_rows, int K, int T, int tpw, double now,
                                                          double lambda, uint32_t flags, float* __restrict__ gram,
@@ -570,16 +578,19 @@ __global__ __launch_bounds__(EMF_B) void k_encoder_fused(tpnet_state S, const in
     float* stg = reinterpret_cast<float*>(smem + EMF_STG + p * EMF_PP);
     int* sync = reinterpret_cast<int*>(smem + EMF_SYNC) + p * 8;
     if (wave < EMF_NP) {
-        const int done = walk_tiles<KS, SPLIT, true>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags, gram,
-                                                     gram ? gram + (int64_t)T * 64 : nullptr, stg, sync);
+        const int done = walk_tiles<KS, FULL, SPLIT, true>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags,
+                                                           gram, gram ? gram + (int64_t)T * 64 : nullptr, stg, sync);
         if (done == 0) __syncthreads();            // (a producer without tiles still owes the workgroup its barrier)
     } else
         dense_consumer(smem, stg, sync, (slot_end - slot_begin + 3) >> 2, T, slot_end, y);
 }
 
+static inline int encoder_steps(int d) { return (d + 31) / 32; }      // KS: 32-deep steps of a row of d floats
+
 bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K) {
     static const int off = TPNET_DEV_INT(NO_ENCODER_MFMA, 0);
-    return !off && st.L == 3 && (st.d == 64 || st.d == 128) && K >= 4 && st.N < (int64_t)1 << 31 && n_rows > 0 &&
+    // rows of whole 16-byte vectors, 2..5 steps of 32: d = 64 / 128 unmasked, every other width with a masked last step
+    return !off && st.L == 3 && st.d % 4 == 0 && st.d >= 36 && st.d <= 160 && K >= 4 && st.N < (int64_t)1 << 31 && n_rows > 0 &&
            n_rows * (int64_t)K < ((int64_t)1 << 31) / 64;
 }
 
@@ -597,11 +608,18 @@ int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const 
     if (tpw < 2) tpw = 2;
     const int nwaves = (ntiles + tpw - 1) / tpw;
     const int grid = (nwaves + EMB / 64 - 1) / (EMB / 64);
-#define TPNET_EM_LAUNCH(KS_, SP_)                                                                                              \
-    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, SP_>), dim3(grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, tpw, \
-                       now, lambda, flags, out1, out2)
-    if (st.d == 128) { if (split_dev == 2) TPNET_EM_LAUNCH(4, 2); else TPNET_EM_LAUNCH(4, 3); }
-    else { if (split_dev == 2) TPNET_EM_LAUNCH(2, 2); else TPNET_EM_LAUNCH(2, 3); }
+#define TPNET_EM_LAUNCH(KS_, FULL_, SP_)                                                                                        \
+    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, FULL_, SP_>), dim3(grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+                       tpw, now, lambda, flags, out1, out2)
+    if (st.d == 128) { if (split_dev == 2) TPNET_EM_LAUNCH(4, true, 2); else TPNET_EM_LAUNCH(4, true, 3); }
+    else if (st.d == 64) { if (split_dev == 2) TPNET_EM_LAUNCH(2, true, 2); else TPNET_EM_LAUNCH(2, true, 3); }
+    else                                           // (the two-piece split is a measuring aid of the whole widths only)
+        switch (encoder_steps(st.d)) {
+            case 2: TPNET_EM_LAUNCH(2, false, 3); break;
+            case 3: TPNET_EM_LAUNCH(3, false, 3); break;
+            case 4: TPNET_EM_LAUNCH(4, false, 3); break;
+            default: TPNET_EM_LAUNCH(5, false, 3); break;
+        }
 #undef TPNET_EM_LAUNCH
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
@@ -615,10 +633,14 @@ static bool encoder_fused_available() {
     if (encoder_fused_state == 0) {
         static const int off = TPNET_DEV_INT(NO_ENCODER_FUSED, 0);
         bool ok = !off;
-        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(k_encoder_fused<4, 3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, EMF_LDS) == hipSuccess;
-        ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(k_encoder_fused<2, 3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, EMF_LDS) == hipSuccess;
+        const void* const kernels[] = {reinterpret_cast<const void*>(k_encoder_fused<4, true, 3>),
+                                       reinterpret_cast<const void*>(k_encoder_fused<2, true, 3>),
+                                       reinterpret_cast<const void*>(k_encoder_fused<2, false, 3>),
+                                       reinterpret_cast<const void*>(k_encoder_fused<3, false, 3>),
+                                       reinterpret_cast<const void*>(k_encoder_fused<4, false, 3>),
+                                       reinterpret_cast<const void*>(k_encoder_fused<5, false, 3>)};
+        for (const void* k : kernels)
+            ok = ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, EMF_LDS) == hipSuccess;
         (void)hipGetLastError();
         encoder_fused_state = ok ? 1 : -1;
     }
@@ -643,12 +665,19 @@ int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int6
     if (tpw < 2) tpw = 2;
     const int nprod = (ntiles + tpw - 1) / tpw;
     const int grid = (nprod + EMF_NP - 1) / EMF_NP;
-    if (st.d == 128)
-        hipLaunchKernelGGL((k_encoder_fused<4, 3>), dim3(grid), dim3(EMF_B), EMF_LDS, s, st, neigh, a1, a2, (int)n_rows, K, T, tpw, now,
-                           lambda, flags, gram, reinterpret_cast<const float4*>(mlp->wimg), out);
+#define TPNET_EMF_LAUNCH(KS_, FULL_)                                                                                              \
+    hipLaunchKernelGGL((k_encoder_fused<KS_, FULL_, 3>), dim3(grid), dim3(EMF_B), EMF_LDS, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+                       tpw, now, lambda, flags, gram, reinterpret_cast<const float4*>(mlp->wimg), out)
+    if (st.d == 128) TPNET_EMF_LAUNCH(4, true);
+    else if (st.d == 64) TPNET_EMF_LAUNCH(2, true);
     else
-        hipLaunchKernelGGL((k_encoder_fused<2, 3>), dim3(grid), dim3(EMF_B), EMF_LDS, s, st, neigh, a1, a2, (int)n_rows, K, T, tpw, now,
-                           lambda, flags, gram, reinterpret_cast<const float4*>(mlp->wimg), out);
+        switch (encoder_steps(st.d)) {
+            case 2: TPNET_EMF_LAUNCH(2, false); break;
+            case 3: TPNET_EMF_LAUNCH(3, false); break;
+            case 4: TPNET_EMF_LAUNCH(4, false); break;
+            default: TPNET_EMF_LAUNCH(5, false); break;
+        }
+#undef TPNET_EMF_LAUNCH
     if (hipGetLastError() != hipSuccess) {             // (a runtime that refuses the launch: the callers fall back for good)
         encoder_fused_state = -1;
         return TPNET_ERR_BAD_ARG;

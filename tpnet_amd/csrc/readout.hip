@@ -98,7 +98,7 @@ __global__ __launch_bounds__(RB) void k_pair_gram_anchored(tpnet_state S, const 
     // into chunks so that the launch still fills the chip
     const int nch = (K + KC - 1) / KC;
     const int64_t units = n_rows * nch;
-    if constexpr (FULL) {
+    if constexpr (W == 4 && LPP >= 16) {       // one chunk of 16-byte vectors per row; !FULL: the chunk's tail lanes hold zeros
         for (int64_t base = (int64_t)blockIdx.x * GPB; base < units; base += (int64_t)gridDim.x * GPB) {
             const int64_t un = base + g;
             const bool valid = un < units;
@@ -113,7 +113,8 @@ __global__ __launch_bounds__(RB) void k_pair_gram_anchored(tpnet_state S, const 
 
 bool pair_gram_anchored_supported(const tpnet_state& st) {
     const Geom gm = pick_geom(st.d);
-    return gm.w == 4 && st.d == gm.lpp * gm.vpl * 4 && gm.lpp >= 16;      // rows of exactly one chunk of 16-byte vectors
+    // rows of whole 16-byte vectors inside ONE chunk of a geometry of >= 16 lanes: d % 4 == 0 and 36 <= d <= 512
+    return gm.w == 4 && gm.lpp >= 16 && st.d <= gm.lpp * gm.vpl * 4;
 }
 
 int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
@@ -123,7 +124,7 @@ int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const
     if (!pair_gram_anchored_supported(st)) return TPNET_ERR_BAD_ARG;
     // (measured and not kept, round 3: the 16-lane x 2-vector geometry for rows of 128 floats -- 80 000 pairs 40.4 us against 35.3)
     TPNET_DISPATCH(({
-        if constexpr (FULL && LPP >= 16) {
+        if constexpr (W == 4 && LPP >= 16) {
             static const int kc_env = TPNET_DEV_INT(ANCHOR_KC, 0);
             int64_t kc = ((int64_t)K * n_rows + 8191) / 8192;            // >= ~8192 units in the launch
             kc = kc < 4 ? 4 : (kc > K ? K : kc);

@@ -618,8 +618,9 @@ __device__ __forceinline__ void gram_anchored(const tpnet_state& S, const int64_
     using C = GramCfg<LPP, L>;
     using AC = AnchorCfg<LPP, L>;
     constexpr int NR = C::NR, NN = C::NN, F = VPL * W;
-    static_assert(FULL, "gram_anchored: rows of exactly one chunk");
+    // one chunk per row (d <= LPP * VPL * W); !FULL: lanes whose vector lies past the row's end hold zeros
     const int d = S.d;
+    const int nvec = d / W;
     const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
     bool aok = valid && (uint64_t)a1 < (uint64_t)S.N && (uint64_t)a2 < (uint64_t)S.N;
     if (valid && !aok && gl == 0) atomicAdd(S.err, 1u);
@@ -633,13 +634,17 @@ __device__ __forceinline__ void gram_anchored(const tpnet_state& S, const int64_
             const MetaView m = read_meta(meta, ids[s], READER_BID, now, lambda);
             const float* qb = S.q + ((int64_t)m.copy * S.N + ids[s]) * ((int64_t)L * d);
 #pragma unroll
-            for (int j = 0; j < VPL; ++j) ldv<W>(S.p0 + ids[s] * (int64_t)d, j * LPP + gl, &fa[s][0][j * W]);
+            for (int j = 0; j < VPL; ++j)
+                ldv_maybe<W, FULL>(S.p0 + ids[s] * (int64_t)d, j * LPP + gl, j * LPP + gl < nvec,
+                                   &fa[s][0][j * W]);
             float g = 1.0f;
 #pragma unroll
             for (int i = 1; i <= L; ++i) {
                 g *= m.g;
 #pragma unroll
-                for (int j = 0; j < VPL; ++j) ldv<W>(qb + (int64_t)(i - 1) * d, j * LPP + gl, &fa[s][i][j * W]);
+                for (int j = 0; j < VPL; ++j)
+                    ldv_maybe<W, FULL>(qb + (int64_t)(i - 1) * d, j * LPP + gl, j * LPP + gl < nvec,
+                                       &fa[s][i][j * W]);
 #pragma unroll
                 for (int k = 0; k < F; ++k) fa[s][i][k] *= g;
             }
@@ -714,11 +719,15 @@ __device__ __forceinline__ void gram_anchored(const tpnet_state& S, const int64_
             const int cp = __shfl(my_m.copy, j, LPP);
             const float* qb = S.q + ((int64_t)cp * S.N + w) * ((int64_t)L * d);
 #pragma unroll
-            for (int jj = 0; jj < VPL; ++jj) ldv<W>(S.p0 + w * (int64_t)d, jj * LPP + gl, &fn[0][jj * W]);
+            for (int jj = 0; jj < VPL; ++jj)
+                ldv_maybe<W, FULL>(S.p0 + w * (int64_t)d, jj * LPP + gl, jj * LPP + gl < nvec,
+                                   &fn[0][jj * W]);
 #pragma unroll
             for (int i = 1; i <= L; ++i) {
 #pragma unroll
-                for (int jj = 0; jj < VPL; ++jj) ldv<W>(qb + (int64_t)(i - 1) * d, jj * LPP + gl, &fn[i][jj * W]);
+                for (int jj = 0; jj < VPL; ++jj)
+                    ldv_maybe<W, FULL>(qb + (int64_t)(i - 1) * d, jj * LPP + gl, jj * LPP + gl < nvec,
+                                       &fn[i][jj * W]);
             }
         };
         issue(0);

@@ -148,7 +148,7 @@ bool pair_gram_anchored_supported(const tpnet_state& st);
 int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
                               int64_t n_rows, int K, double now, double lambda, uint32_t flags, float* out1, float* out2,
                               hipStream_t s);
-// encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 64 / 128 floats, L = 3, K >= 4
+// encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 36..160 floats (d % 4 == 0), L = 3, K >= 4
 bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K);
 int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                              int K, double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s);

@@ -749,7 +749,8 @@ class RandomProjectionModule(nn.Module):
         if n > 8192 and n % 2 == 0 and not self.fused_mlp and self._plist()[0].device.type == "cuda":
             # the encoder's call as the reference issues it (models/TPNet.py:311-316: src = tile(neigh, 2), dst = concat(repeat(a1, K),
             # repeat(a2, K)) on the host): recognised in one pass over the two arrays in C; n / 2 neighbour ids + 2 n / (2 K) anchors
-            # go up instead of 2 n ids, the anchored readout and the dense layers run as one call
+            # go up instead of 2 n ids, the anchored readout and the dense layers run as one call (dim % 4 == 0, 36 <= dim <= 512;
+            # one launch on the matrix cores up to dim = 160)
             feats = self._encoder_pattern_features(src, dst_node_ids, n)
             if feats is not None:
                 return feats
@@ -844,8 +845,9 @@ class RandomProjectionModule(nn.Module):
         rows), two anchors per row (the edge's src and dst).  Returns [2, n*K, (2L+2)^2]: G(neighbour, first anchor) for every
         (row, neighbour), then G(neighbour, second anchor) -- viewed as [2*n*K, .] this is the reference's
         get_pair_wise_feature(tile(neighbours, 2), concat(repeat(first, K), repeat(second, K))) pair order.  One lane group per
-        row keeps both anchors' rows in registers for its K neighbours (tpnet_pair_gram_anchored); rows of 64 / 128 floats with
-        L = 3 and K >= 4 take the matrix cores (csrc/encoder_mfma.hip) unless matrix_cores=False."""
+        row keeps both anchors' rows in registers for its K neighbours (tpnet_pair_gram_anchored).  Served: rows of whole 16-byte
+        vectors, dim % 4 == 0 and 36 <= dim <= 512 (the reference's default widths 120, 140, 160 among them); rows of 36..160
+        floats with L = 3 and K >= 4 take the matrix cores (csrc/encoder_mfma.hip) unless matrix_cores=False."""
         self._ensure_engine()
         if isinstance(neighbor_ids, torch.Tensor):
             if neighbor_ids.dim() != 2:
@@ -862,7 +864,8 @@ class RandomProjectionModule(nn.Module):
             raise ValueError("one first and one second anchor per row of neighbor_ids")
         lib = _lib.load()
         if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
-            raise _lib.TPNetHipError(f"pair_gram_anchored needs dim in (64, 128, 256, 512), not {self.dim}: use pair_gram_shared")
+            raise _lib.TPNetHipError(f"pair_gram_anchored needs dim % 4 == 0 and 36 <= dim <= 512, not {self.dim}: "
+                                     "use pair_gram_shared")
         wd = self._to_device(self._check_ids(w, "neighbor_ids"))[0]
         a1, a2 = self._to_device(self._check_ids(first_anchor_ids, "first_anchor_ids"),
                                  self._check_ids(second_anchor_ids, "second_anchor_ids"))
@@ -883,7 +886,8 @@ class RandomProjectionModule(nn.Module):
 
     def _gram_buffer(self, n_rows, K, prep, n, NG):
         """Where the pre-mlp features of an encoder call go when no backward pass needs them: nowhere (None) if readout and dense
-        layers are ONE launch (tpnet_encoder_fused_supported), else a scratch tensor between the two launches."""
+        layers are ONE launch (tpnet_encoder_fused_supported: rows of 36..160 floats, dim % 4 == 0, K >= 4), else a scratch tensor
+        between the two launches."""
         if _lib.load().tpnet_encoder_fused_supported(self._st_ref(), n_rows, K, prep[2]):
             return None
         return torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
@@ -898,7 +902,7 @@ class RandomProjectionModule(nn.Module):
 
     def get_pair_wise_feature_anchored(self, neighbor_ids, first_anchor_ids, second_anchor_ids):
         """Extension: the encoder's call (models/TPNet.py:313-316) from its natural arguments; [2*n*K, (2L+2)^2] in the
-        reference's row order, self.mlp applied."""
+        reference's row order, self.mlp applied.  Needs what pair_gram_anchored needs (dim % 4 == 0, 36 <= dim <= 512)."""
         prep = self._overlapped_mlp() if self._plist()[0].device.type == "cuda" else None
         if prep is not None and isinstance(neighbor_ids, torch.Tensor) and neighbor_ids.is_cuda:
             self._ensure_engine()
