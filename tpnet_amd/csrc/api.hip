@@ -2,18 +2,26 @@
 // synchronisation; everything is enqueued on the caller's stream.
 #include "tpnet_common.h"
 
-#include <cstdlib>
 #include <cstring>
-#include <vector>
 
 namespace tpnet {
 thread_local int g_last_hip_error = 0;
 
-static int check_state(const tpnet_state* st) {
+int check_state(const tpnet_state* st) {
     if (!st || !st->p0 || !st->q || !st->meta || !st->err) return TPNET_ERR_BAD_ARG;
     if (st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS) return TPNET_ERR_BAD_ARG;
     if (st->N >= (1ll << 31)) return TPNET_ERR_BAD_ARG;
     return TPNET_OK;
+}
+
+// the largest n < hi with fits(n), where fits(hi) is false and fits grows no truer with n; 0: none
+template <class F> static int64_t most_that_fit(int64_t hi, F fits) {
+    int64_t lo = 0;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) / 2;
+        if (fits(mid)) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 // largest chunk (multiple of `batch`, at most E) whose plan fits the workspace.  Contribution indices are 32-bit inside a
@@ -22,24 +30,16 @@ static int64_t max_chunk(size_t ws_bytes, int64_t E, int64_t batch) {
     const int64_t hard = ((int64_t)1 << 30) / batch * batch;
     const int64_t lim = (E < hard || hard < batch) ? E : hard;
     if (plan_bytes(lim, batch) <= ws_bytes) return lim;
-    int64_t lo = 0, hi = (lim + batch - 1) / batch;  // in batches; lo fits (0), hi does not
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) / 2;
-        if (plan_bytes(mid * batch, batch) <= ws_bytes) lo = mid; else hi = mid;
-    }
-    return lo * batch;
+    return batch * most_that_fit((lim + batch - 1) / batch, [&](int64_t n) { return plan_bytes(n * batch, batch) <= ws_bytes; });
 }
 
 struct StepTimer {
     hipEvent_t* ev = nullptr;  // one pair per chunk, around its loop of step launches (plan kernels excluded)
     int64_t n = 0, cap = 0;    // pairs recorded / available
     int64_t launches = 0;      // step launches between the recorded pairs
-    int64_t batches = 0;       // batches those launches covered
     int64_t edges = 0;         // edges those launches covered
-    // windowed path: L+2 events per timed window (before the first update launch, after each launch)
-    hipEvent_t* wev = nullptr;
-    int64_t wn = 0, wcap = 0;  // windows recorded / available
-    int64_t wedges = 0;        // edges of the recorded windows
+    bool begin(hipStream_t s) { return n < cap && ((void)hipEventRecord(ev[2 * n], s), true); }      // false: no pair left
+    void end(hipStream_t s, int64_t nl, int64_t ne) { (void)hipEventRecord(ev[2 * n + 1], s); ++n; launches += nl; edges += ne; }
 };
 
 // The plans of a multi-chunk stream side by side -- one region per chunk, each with every array of a plan but the version log --
@@ -54,23 +54,18 @@ static size_t arena_bytes(int64_t N, int d, int L, int64_t E, int64_t chunk, int
 }
 
 // edges per window (*Ew_out) and the most a chunk may cover whatever the workspace (whole windows, or all of E); 0: not windowed
-static int64_t window_chunk_limit(int64_t N, int d, int L, int64_t E, int64_t batch, uint32_t flags, int* K_out, int64_t* Ew_out) {
-    const int K = wplan_window_batches(batch, d, L);
+static int64_t window_chunk_limit(const tpnet_state& st, int64_t E, int64_t batch, uint32_t flags, int* K_out, int64_t* Ew_out) {
+    const int K = wplan_window_batches(batch, st.d, st.L);
     if (K == 0) return 0;
     *K_out = K;
     int64_t Ew = (int64_t)K * batch;
     // packed rows of (2L+2)(2L+3)/2 floats: every chunk's output must start on a 16-byte boundary (launch_wstep)
-    const int NN = 2 * L + 2;
+    const int NN = 2 * st.L + 2;
     if ((flags & TPNET_FLAG_PACKED) && ((NN * (NN + 1) / 2) % 4) != 0 && Ew % 4 != 0) Ew *= (Ew % 2 == 0) ? 2 : 4;
     *Ew_out = Ew;
-    int64_t cap = wplan_max_chunk_edges(batch, d, L);                // the version log of a chunk is bounded
-    // batches that fit one workgroup's LDS: chunks of at most 64 windows, which the hashed planner serves (wplan3.hip) -- ONE set
-    // of plan kernels whatever the stream's length (a chunk that falls to the sorted planner meets rocPRIM's large-size sort
-    // kernels for the first time in the middle of a long call: HIP resolves a kernel at its first launch, ~0.3 ms each)
-    // (the dense planner, wplan_dense.hip: one launch, up to 256 windows)
-    const bool dense = !(flags & (TPNET_FLAG_PLAN_SORTED | TPNET_FLAG_PLAN_HASHED)) && wplan_dense_eligible(N, d, L, batch);
-    const int64_t maxw = dense ? 256 : WIN_MAX_WINDOWS;
-    if (batch <= PLAN_ONE_MAX && !(flags & TPNET_FLAG_PLAN_SORTED) && cap > maxw * Ew) cap = maxw * Ew;
+    int64_t cap = wplan_max_chunk_edges(batch, st.d, st.L);           // the version log of a chunk is bounded, and
+    const int64_t maxw = choose_wplanner(st, nullptr, 0, batch, 0, flags).max_windows;      // so are the windows its planner serves
+    if (maxw > 0 && cap > maxw * Ew) cap = maxw * Ew;
     const int64_t hard = cap / Ew * Ew;
     return (E <= cap) ? E : hard;
 }
@@ -92,71 +87,43 @@ static int64_t window_chunk(const tpnet_state& st, size_t ws_bytes, int64_t E, i
     // 198; until round 4, with the hashed planner and lane-group walks of chains up to 52 contributions: from 24).  Larger batches keep
     // the chunk planner's crossover (two device-wide sorts).
     static const int min_nb3 = TPNET_DEV_INT(WIN_MIN_BATCHES, 16);
-    const int min_nb = batch <= PLAN_ONE_MAX ? min_nb3 : 56;
+    const int64_t min_nb = (flags & TPNET_FLAG_SCHED_WINDOWED) ? 4 : (batch <= PLAN_ONE_MAX ? min_nb3 : 56);
     int64_t Ew = 0;
-    const int64_t lim = window_chunk_limit(st.N, st.d, st.L, E, batch, flags, K_out, &Ew);
-    if (lim == 0 || nb < ((flags & TPNET_FLAG_SCHED_WINDOWED) ? 4 : min_nb)) return 0;
+    const int64_t lim = window_chunk_limit(st, E, batch, flags, K_out, &Ew);
+    if (lim == 0 || nb < min_nb) return 0;
     if ((lim + batch - 1) / batch < 4) return 0;
-    const bool lim_fits = wplan_bytes(lim, batch, st.N, st.d, st.L) <= ws_bytes;
+    // does a chunk of c edges fit -- as one region of an arena (every chunk's plan kept, side by side: several chunks, at most
+    // ARENA_MAX_CHUNKS, and a planner that keeps something to replay), or as a plan on its own
+    const bool arena_ok = region_out && choose_wplanner(st, nullptr, 0, batch, 0, flags).replayable;
+    auto fits = [&](int64_t c, bool arena) {
+        if (!arena) return wplan_bytes(c, batch, st.N, st.d, st.L) <= ws_bytes;
+        return arena_ok && c < E && (E + c - 1) / c <= ARENA_MAX_CHUNKS && arena_bytes(st.N, st.d, st.L, E, c, batch) <= ws_bytes;
+    };
+    auto take = [&](int64_t c, bool arena) { if (arena) *region_out = arena_region_bytes(st.N, st.d, st.L, c, batch); return c; };
+    // in order of preference.  The whole stream as one chunk:
+    const bool lim_fits = fits(lim, false);
     if (lim_fits && lim >= E) return lim;
-    if (region_out && batch <= PLAN_ONE_MAX && !(flags & TPNET_FLAG_PLAN_SORTED)) {      // (the sorted planner keeps nothing to replay)
-        // several chunks: the largest chunk (whole windows, at least two chunks, at most ARENA_MAX_CHUNKS) whose arena fits, if any
-        // (the log grows with the chunk, the per-node arrays of the regions with the number of chunks: not monotone, and at most
-        // 256 candidates -- a chunk is at most 256 windows)
-        int64_t hi = lim / Ew;                                          // (lim < E: whole windows; else lim = E did not fit)
-        if (hi * Ew >= E) hi = (E - 1) / Ew;
-        int64_t lo = (E + ARENA_MAX_CHUNKS * Ew - 1) / (ARENA_MAX_CHUNKS * Ew);
-        if (lo < 1) lo = 1;
-        if (lo * Ew < 4 * batch) lo = (4 * batch + Ew - 1) / Ew;
-        for (int64_t w = hi; w >= lo; --w)
-            if (arena_bytes(st.N, st.d, st.L, E, w * Ew, batch) <= ws_bytes) {
-                *region_out = arena_region_bytes(st.N, st.d, st.L, w * Ew, batch);
-                return w * Ew;
-            }
-    }
+    // several chunks of whole windows, at least four batches each, in an arena: the largest chunk that fits (the log grows with the
+    // chunk, the per-node arrays of the regions with the number of chunks: not monotone, and at most 256 candidates)
+    for (int64_t w = arena_ok ? lim / Ew : 0; w * Ew >= 4 * batch; --w)
+        if (fits(w * Ew, true)) return take(w * Ew, true);
+    // the largest chunk its planner serves, else the most whole windows, planned anew every time
     if (lim_fits) return lim;
-    int64_t lo = 0, hi = (lim + Ew - 1) / Ew;       // in windows; lo fits (0), hi does not
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) / 2;
-        if (wplan_bytes(mid * Ew, batch, st.N, st.d, st.L) <= ws_bytes) lo = mid; else hi = mid;
-    }
-    if (lo > 0) return lo * Ew;
+    const int64_t nw = most_that_fit((lim + Ew - 1) / Ew, [&](int64_t w) { return fits(w * Ew, false); });
+    if (nw > 0) return nw * Ew;
     // not even one window of Kmax batches (a caller who capped the version log below that): chunks of fewer batches -- the window
     // length is chosen per chunk (window_batches_for) -- down to what the pipeline still wins at; a replayable layout first
     const int K = *K_out;
     const int64_t u = Ew / K;                                              // one batch (packed rows: whole 16 bytes of output)
-    const int64_t n_min = ((flags & TPNET_FLAG_SCHED_WINDOWED) ? 4 : min_nb) * batch;
-    if (region_out && batch <= PLAN_ONE_MAX && !(flags & TPNET_FLAG_PLAN_SORTED))
-        for (int64_t n = K - 1; n >= 1 && n * u >= n_min; --n) {
-            const int64_t c = n * u;
-            if (c < E && (E + c - 1) / c <= ARENA_MAX_CHUNKS && arena_bytes(st.N, st.d, st.L, E, c, batch) <= ws_bytes) {
-                *region_out = arena_region_bytes(st.N, st.d, st.L, c, batch);
-                return c;
-            }
-        }
-    for (int64_t n = K - 1; n >= 1 && n * u >= n_min; --n)
-        if (n * u < E && wplan_bytes(n * u, batch, st.N, st.d, st.L) <= ws_bytes) return n * u;
+    for (const bool arena : {true, false})
+        for (int64_t n = K - 1; n >= 1 && n * u >= min_nb * batch; --n)
+            if (n * u < E && fits(n * u, arena)) return take(n * u, arena);
     return 0;
-}
-
-// Batches per window of a chunk of nb batches.  A pipeline of nw windows is nw + L dependent launches, each a fixed floor
-// (~10 us: kernel boundary + the dependent loads of its longest unit) plus its share of the bandwidth work (~2.5 us per batch
-// at C2): few long windows for short streams.  Measured (tools/short_trace.sh, sum of the pipeline launches): 20 batches as
-// 1 / 2 / 4 windows 127 / 85 / 110 us; 158 batches at 12 / 16 / 24 per window 493 / 472 / 450 us; long streams: the cap of 24
-// (tools/degree_sensitivity.py).
-static int window_batches_for(int64_t nb, int Kmax) {
-    static const int fixed = TPNET_DEV_INT(WINDOW_FIXED, 0);
-    if (fixed > 0) return fixed < Kmax ? fixed : Kmax;
-    static const int num = TPNET_DEV_INT(WINDOW_SQ, 5);
-    int K = 2;
-    while (K < Kmax && (int64_t)K * K < (int64_t)num * nb) ++K;         // K = ceil(sqrt(5 nb))
-    const int64_t nw0 = (nb + K - 1) / K;                              // equal windows: ceil(nb / nw0) batches each
-    return (int)((nb + nw0 - 1) / nw0);
 }
 
 // what a plan left in the workspace was built for (tpnet_plan_tag::built, opaque to the caller)
 struct PlanBuilt {
-    uint64_t valid;
+    uint64_t valid;             // 1: a windowed plan, 2: a per-batch one
     const void *src, *dst, *t, *ws;
     int64_t E, batch, N;
     uint64_t ws_bytes;
@@ -170,166 +137,144 @@ struct PlanBuilt {
 };
 static_assert(sizeof(PlanBuilt) <= sizeof(((tpnet_plan_tag*)nullptr)->built), "tpnet_plan_tag::built too small");
 
-static int run_stream_windowed(const tpnet_state& st, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                               const double* t, int64_t E, int64_t batch, double now_time, double lambda,
-                               uint32_t launch_id_base, uint32_t flags, float* out_pos, float* out_neg, void* ws,
-                               size_t ws_bytes, int64_t chunk, int Kmax, hipStream_t s, StepTimer* timer,
-                               tpnet_plan_tag* tag, size_t region) {
-    const int NN = 2 * st.L + 2;
-    const int NG = (flags & TPNET_FLAG_PACKED) ? NN * (NN + 1) / 2 : NN * NN;
-    uint32_t lid = launch_id_base;
-    const bool have_readout = out_pos || out_neg;
+// one tpnet_run_stream call
+struct StreamCall {
+    const tpnet_state& st;
+    const int64_t *src, *dst, *neg;
+    const double* t;
+    int64_t E, batch;
+    double now_time, lambda;
+    uint32_t launch_id_base, flags;
+    float *out_pos, *out_neg;
+    void* ws;
+    size_t ws_bytes;
+    hipStream_t s;
+    StepTimer* timer;
+    tpnet_plan_tag* tag;
+    StreamArgs args_at(int64_t c0) const {
+        const int NN = 2 * st.L + 2;            // floats per feature row of the outputs: NN x NN, or its upper triangle
+        return stream_args_at(src, dst, neg, t, out_pos, out_neg, c0, (flags & TPNET_FLAG_PACKED) ? NN * (NN + 1) / 2 : NN * NN);
+    }
+};
+
+// The caller's tag for one call: may the plan in the workspace be replayed (`possible`: the schedule can do so at all, if the caller
+// vouches for the stream and, with_table, for the table's per-node state), and the record -- a byte image -- of what this call leaves there
+struct PlanReplay {
+    tpnet_plan_tag* const tag;
+    PlanBuilt now;
+    bool replay = false;
+    PlanReplay(const StreamCall& c, bool possible, uint64_t valid, bool with_table, int K, uint32_t flags, bool have_readout,
+               int64_t chunk, size_t region) : tag(c.tag) {
+        memset(&now, 0, sizeof(now));
+        if (!tag) return;
+        if (possible && tag->stream_sig && (!with_table || tag->table_sig)) {
+            now.valid = valid; now.src = c.src; now.dst = c.dst; now.t = c.t; now.ws = c.ws; now.E = c.E; now.batch = c.batch;
+            now.N = c.st.N; now.ws_bytes = c.ws_bytes; now.now_time = c.now_time; now.lambda = c.lambda; now.d = c.st.d; now.L = c.st.L;
+            now.K = K; now.flags = flags; now.table_sig = with_table ? tag->table_sig : 0; now.stream_sig = tag->stream_sig;
+            now.have_readout = have_readout ? 1 : 0; now.chunk = chunk; now.region = region;
+            replay = memcmp(&now, tag->built, sizeof(PlanBuilt)) == 0;
+        }
+        memset(tag->built, 0, sizeof(tag->built));                   // (invalid unless this call completes: commit)
+        tag->replayed = replay ? 1 : 0;
+    }
+    // the call completed; all_kept: every chunk's plan is still in the workspace (planned by a planner that keeps it)
+    void commit(bool all_kept) { if (now.valid && all_kept) memcpy(tag->built, &now, sizeof(PlanBuilt)); }
+};
+
+static int run_stream_windowed(const StreamCall& c, int64_t chunk, int Kmax, size_t region) {
+    const tpnet_state& st = c.st;
+    const int64_t E = c.E, batch = c.batch;
+    hipStream_t s = c.s;
+    uint32_t lid = c.launch_id_base;
+    const bool have_readout = c.out_pos || c.out_neg;
     // a plan may be replayed when the caller vouches (tag) that the stream arrays and the table's per-node state are what the
     // plan in this workspace was built for, and the workspace still holds the plan of EVERY chunk: the stream is one chunk, or
     // its chunks' plans lie side by side (`region` bytes each, window_chunk) in front of the one version log they share -- the
     // table state a later chunk's plan was built on follows from the first one's and the stream
-    char* const arena = reinterpret_cast<char*>((reinterpret_cast<size_t>(ws) + 255) / 256 * 256);
+    char* const arena = reinterpret_cast<char*>((reinterpret_cast<size_t>(c.ws) + 255) / 256 * 256);
     const int64_t n_chunks = (E + chunk - 1) / chunk;
     float* const shared_log = region ? reinterpret_cast<float*>(arena + (size_t)n_chunks * region) : nullptr;
-    PlanBuilt now{};
-    bool replay = false, all_planned_here = true;
-    if (tag && (n_chunks == 1 || region) && tag->table_sig && tag->stream_sig) {
-        now.valid = 1; now.src = src; now.dst = dst; now.t = t; now.ws = ws; now.E = E; now.batch = batch; now.N = st.N;
-        now.ws_bytes = ws_bytes; now.now_time = now_time; now.lambda = lambda; now.d = st.d; now.L = st.L;
-        now.K = window_batches_for(((E < chunk ? E : chunk) + batch - 1) / batch, Kmax);
-        now.flags = flags & ~(uint32_t)TPNET_FLAG_SCHED_WINDOWED;
-        now.table_sig = tag->table_sig; now.stream_sig = tag->stream_sig; now.have_readout = have_readout ? 1 : 0;
-        now.chunk = chunk; now.region = region;
-        replay = memcmp(&now, tag->built, sizeof(PlanBuilt)) == 0;
-    }
-    if (tag) {
-        memset(tag->built, 0, sizeof(tag->built));                  // (invalid unless this call completes every chunk's plan)
-        tag->replayed = replay ? 1 : 0;
-    }
+    PlanReplay tag(c, n_chunks == 1 || region, 1, true, window_batches_for(((E < chunk ? E : chunk) + batch - 1) / batch, Kmax),
+                   c.flags & ~(uint32_t)TPNET_FLAG_SCHED_WINDOWED, have_readout, chunk, region);
+    bool all_kept = true;
     for (int64_t c0 = 0, ci = 0; c0 < E; c0 += chunk, ++lid, ++ci) {
         const int64_t Ec = (E - c0 < chunk) ? (E - c0) : chunk;
         const int64_t nb = (Ec + batch - 1) / batch;
         const int K = window_batches_for(nb, Kmax);
         WPlan p{};
         int rc = region ? wplan_carve(arena + (size_t)ci * region, region, Ec, batch, st.N, st.d, st.L, K, &p, shared_log)
-                        : wplan_carve(ws, ws_bytes, Ec, batch, st.N, st.d, st.L, K, &p);
+                        : wplan_carve(c.ws, c.ws_bytes, Ec, batch, st.N, st.d, st.L, K, &p);
         if (rc) return rc;
-        static const int no3 = TPNET_DEV_INT(NO_PLAN3, 0);
-        // the hashed planner costs ~45 us + 0.76 us per batch, the sorted one ~200 us + 0.63 us per batch (C2, profiles/r03_C2.md):
-        // 4 % of a long stream's time, paid for having one set of plan kernels (see window_chunk)
-        static const int max3 = TPNET_DEV_INT(PLAN3_MAX_BATCHES, 1 << 30);
-        const bool dense = !(flags & (TPNET_FLAG_PLAN_SORTED | TPNET_FLAG_PLAN_HASHED)) && wplan_dense_applies(st, p, Ec, batch, K);
-        const bool plan3 = !dense && !no3 && !(flags & TPNET_FLAG_PLAN_SORTED) && nb <= max3 && wplan3_applies(st, Ec, batch, K);
         // (the sorted planner keeps nothing to replay: a stream with such a chunk is planned again every time; a recorded plan had
         // none, and the same sizes choose the same planners)
-        if (!(plan3 || dense)) all_planned_here = false;
-        if (dense)
-            rc = wplan_dense_build(st, p, src + c0, dst + c0, neg ? neg + c0 : nullptr, t + c0, Ec, batch, now_time,
-                                   c0 > 0 ? t + c0 - 1 : nullptr, lambda, have_readout, replay, s);
-        else if (plan3)
-            rc = wplan3_build(st, p, src + c0, dst + c0, neg ? neg + c0 : nullptr, t + c0, Ec, batch, now_time,
-                              c0 > 0 ? t + c0 - 1 : nullptr, lambda, have_readout, replay, s);
-        else
-            rc = wplan_build(st, p, src + c0, dst + c0, neg ? neg + c0 : nullptr, t + c0, Ec, batch, now_time,
-                             c0 > 0 ? t + c0 - 1 : nullptr, lambda, have_readout, s);
+        const WPlanner planner = choose_wplanner(st, &p, Ec, batch, K, c.flags);
+        all_kept &= planner.replayable;
+        const StreamArgs a = c.args_at(c0);
+        const WPlanArgs pa{a.src, a.dst, a.neg, a.t, Ec, batch, c.now_time, c0 > 0 ? c.t + c0 - 1 : nullptr, c.lambda, have_readout,
+                           tag.replay};
+        rc = planner.build(st, p, pa, s);
         if (rc) return rc;
-        StreamArgs a;
-        a.src = src + c0;
-        a.dst = dst + c0;
-        a.neg = neg ? neg + c0 : nullptr;
-        a.t = t + c0;
-        a.out_pos = out_pos ? out_pos + c0 * NG : nullptr;
-        a.out_neg = out_neg ? out_neg + c0 * NG : nullptr;
-        a.own_mod = 1;
-        a.own_rem = 0;
         const int64_t nw = (Ec + p.Ew - 1) / p.Ew;
         const int64_t nsteps = nw + (have_readout ? st.L : st.L - 1);
-        const bool timed = timer && timer->n < timer->cap;
-        if (timed) (void)hipEventRecord(timer->ev[2 * timer->n], s);
+        const bool timed = c.timer && c.timer->begin(s);
         for (int64_t j = 0; j < nsteps; ++j) {
-            rc = launch_wstep(st, a, p, j, Ec, batch, lambda, flags, s);
+            rc = launch_wstep(st, a, p, j, Ec, batch, c.lambda, c.flags, s);
             if (rc) return rc;
         }
-        if (timed) {
-            (void)hipEventRecord(timer->ev[2 * timer->n + 1], s);
-            ++timer->n;
-            timer->launches += nsteps;
-            timer->batches += nb;
-            timer->edges += Ec;
-        }
-        // the write-back: node by node where the hashed planner planned the chunk (wplan3.hip: 9 us for the 158-batch epoch), else
-        // the scan of the sorted positions for the last-run flag (wstep.hip: 25 us).  (Measured and not kept, round 3: the
+        if (timed) c.timer->end(s, nsteps, Ec);
+        // the write-back: node by node where the dense or the hashed planner planned the chunk (wplan3.hip: 9 us for the 158-batch
+        // epoch), else the scan of the sorted positions for the last-run flag (wstep.hip: 25 us).  (Measured and not kept, round 3: the
         // write-back as extra blocks of the chunk's last pipeline step -- readouts only, nothing it reads is written -- grew that
         // step by what the write-back takes alone, leading the grid or not, and every other step by ~2 us: 634 against 635 us for
         // the epoch; a write-back driven by chain records that carry (last chain of the node, table copy, last clock): 30 us.)
-        if (!(dense ? wplan_dense_writeback(st, p, Ec, batch, lid, s) : (plan3 && wplan3_writeback(st, p, Ec, batch, lid, s)))) {
-            rc = launch_wwriteback(st, p, Ec, lid, s);
-            if (rc) return rc;
-        }
+        rc = planner.writeback(st, p, Ec, batch, lid, s, -1);
+        if (rc) return rc;
     }
-    if (now.valid && all_planned_here) memcpy(tag->built, &now, sizeof(PlanBuilt));
+    tag.commit(all_kept);
     return TPNET_OK;
 }
 
-static int run_stream_impl(const tpnet_state& st, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                           const double* t, int64_t E, int64_t batch, double now_time, double lambda,
-                           uint32_t launch_id_base, uint32_t flags, float* out_pos, float* out_neg, void* ws,
-                           size_t ws_bytes, hipStream_t s, StepTimer* timer, tpnet_plan_tag* tag = nullptr) {
+static int run_stream_impl(const StreamCall& c) {
+    const tpnet_state& st = c.st;
+    const int64_t E = c.E, batch = c.batch;
+    const double lambda = c.lambda;
+    const uint32_t flags = c.flags;
+    hipStream_t s = c.s;
     if (E == 0) return TPNET_OK;
-    {
-        int Kw = 0;
-        size_t region = 0;
-        const int64_t wchunk = window_chunk(st, ws_bytes, E, batch, flags, &Kw, tag ? &region : nullptr);
-        if (wchunk > 0)
-            return run_stream_windowed(st, src, dst, neg, t, E, batch, now_time, lambda, launch_id_base, flags, out_pos,
-                                       out_neg, ws, ws_bytes, wchunk, Kw, s, timer, tag, region);
-    }
-    const int64_t chunk = max_chunk(ws_bytes, E, batch);
+    int Kw = 0;
+    size_t region = 0;
+    const int64_t wchunk = window_chunk(st, c.ws_bytes, E, batch, flags, &Kw, c.tag ? &region : nullptr);
+    if (wchunk > 0) return run_stream_windowed(c, wchunk, Kw, region);
+    const int64_t chunk = max_chunk(c.ws_bytes, E, batch);
     // the per-batch plan of a stream (item lists, coefficients, batch descriptors: plan.hip) is a function of src / dst / t, the
     // clock at entry and the flags alone -- not of the table -- and the step kernels only read it: a stream that is ONE chunk (up
     // to ~2 M edges: every dataset of the reference at any batch size) replays it when the caller vouches for the arrays
-    // (tag->stream_sig; table_sig is not looked at).  valid = 2 tells such a plan from a windowed one (valid = 1).
-    PlanBuilt now{};
-    bool replay = false;
-    if (tag && chunk >= E && tag->stream_sig) {
-        now.valid = 2; now.src = src; now.dst = dst; now.t = t; now.ws = ws; now.E = E; now.batch = batch; now.N = st.N;
-        now.ws_bytes = ws_bytes; now.now_time = now_time; now.lambda = lambda; now.d = st.d; now.L = st.L; now.K = 0;
-        now.flags = flags; now.table_sig = 0; now.stream_sig = tag->stream_sig;
-        now.have_readout = out_pos ? 1 : 0;                     // (the edge-fused update's lists exist for a (src, dst) readout only)
-        now.chunk = chunk; now.region = 0;
-        replay = memcmp(&now, tag->built, sizeof(PlanBuilt)) == 0;
-    }
-    if (tag) { memset(tag->built, 0, sizeof(tag->built)); tag->replayed = replay ? 1 : 0; }   // (invalid unless the call completes)
+    // (tag->stream_sig; table_sig is not looked at).  (have_readout: the edge-fused update's lists exist for a (src, dst) readout only)
+    PlanReplay tag(c, chunk >= E, 2, false, 0, flags, c.out_pos != nullptr, chunk, 0);
     if (chunk < 1) return TPNET_ERR_WORKSPACE;
-    const int NN = 2 * st.L + 2;
-    const int NG = (flags & TPNET_FLAG_PACKED) ? NN * (NN + 1) / 2 : NN * NN;   // floats per feature row of a chunk's outputs
-    uint32_t lid = launch_id_base;
+    uint32_t lid = c.launch_id_base;
     for (int64_t c0 = 0; c0 < E; c0 += chunk) {
         const int64_t Ec = (E - c0 < chunk) ? (E - c0) : chunk;
         Plan p{};
-        int rc = plan_carve(ws, ws_bytes, Ec, batch, &p);
+        int rc = plan_carve(c.ws, c.ws_bytes, Ec, batch, &p);
         if (rc) return rc;
         // edge-fused updates: every launch of this chunk must run BOTH roles with the (src,dst) readout on, and the sums
         // must not be order-sensitive by contract; worth it where the batch is bound by bytes, not by its longest chain
         static const int fuse_env = TPNET_DEV_INT(FUSE, -1);       // developer override: 0 / 1
-        static const int role_mask0 = TPNET_DEV_INT(ROLE_MASK, 3);
-        const bool fuse = out_pos && p.fuse_src && role_mask0 == 3 &&
+        static const int role_mask = TPNET_DEV_INT(ROLE_MASK, 3);   // developer override: 1 / 2 / 3 = readout only / update only / both
+        const bool fuse = c.out_pos && p.fuse_src && role_mask == 3 &&
                           !(flags & (TPNET_FLAG_EAGER_DECAY | TPNET_FLAG_SEQUENTIAL)) &&
                           (fuse_env >= 0 ? fuse_env == 1 : batch > 1024);
+        const StreamArgs a = c.args_at(c0);
         // the clock before a later chunk is t[c0-1], read on device (no host copy of the timestamps is needed)
-        if (!replay) {
-            rc = plan_build(st, p, src + c0, dst + c0, t + c0, Ec, batch, now_time, c0 > 0 ? t + c0 - 1 : nullptr, lambda,
+        if (!tag.replay) {
+            rc = plan_build(st, p, a.src, a.dst, a.t, Ec, batch, c.now_time, c0 > 0 ? c.t + c0 - 1 : nullptr, lambda,
                             flags | (fuse ? PLAN_FUSE : 0u), s);
             if (rc) return rc;
         }
-        StreamArgs a;
-        a.src = src + c0;
-        a.dst = dst + c0;
-        a.neg = neg ? neg + c0 : nullptr;
-        a.t = t + c0;
-        a.out_pos = out_pos ? out_pos + c0 * NG : nullptr;
-        a.out_neg = out_neg ? out_neg + c0 * NG : nullptr;
-        a.own_mod = 1;
-        a.own_rem = 0;
         const int64_t nb = (Ec + batch - 1) / batch;
         const bool have_readout = a.out_pos || a.out_neg;
-        const bool timed = timer && timer->n < timer->cap && !(flags & TPNET_FLAG_EAGER_DECAY);
-        if (timed) (void)hipEventRecord(timer->ev[2 * timer->n], s);
+        const bool timed = c.timer && !(flags & TPNET_FLAG_EAGER_DECAY) && c.timer->begin(s);
         for (int64_t b = 0; b < nb; ++b, ++lid) {
             const int32_t ne = (int32_t)((Ec - b * batch < batch) ? (Ec - b * batch) : batch);
             if (flags & TPNET_FLAG_EAGER_DECAY) {
@@ -343,22 +288,15 @@ static int run_stream_impl(const tpnet_state& st, const int64_t* src, const int6
                 rc = launch_step(st, a, p, b, batch, ne, lambda, lid, flags | ROLE_UPDATE, s);
                 if (rc) return rc;
             } else {
-                static const int role_mask = TPNET_DEV_INT(ROLE_MASK, 3);
                 const uint32_t roles = ((role_mask & 2) ? ROLE_UPDATE : 0u) |
                                        ((have_readout && (role_mask & 1)) ? ROLE_READOUT : 0u);
                 rc = launch_step(st, a, p, b, batch, ne, lambda, lid, flags | roles | (fuse ? STEP_FUSE : 0u), s);
                 if (rc) return rc;
             }
         }
-        if (timed) {
-            (void)hipEventRecord(timer->ev[2 * timer->n + 1], s);
-            ++timer->n;
-            timer->launches += nb;
-            timer->batches += nb;
-            timer->edges += Ec;
-        }
+        if (timed) c.timer->end(s, nb, Ec);
     }
-    if (now.valid) memcpy(tag->built, &now, sizeof(PlanBuilt));
+    tag.commit(true);
     return TPNET_OK;
 }
 
@@ -489,7 +427,9 @@ size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch) { return plan_byt
 static size_t windowed_workspace_bytes(int64_t N, int d, int L, int64_t max_edges, int64_t batch, int64_t chunk_cap) {
     int K = 0;
     int64_t Ew = 0;
-    int64_t lim = window_chunk_limit(N, d, L, max_edges, batch, 0u, &K, &Ew);
+    tpnet_state st{};
+    st.N = N; st.d = d; st.L = L;
+    int64_t lim = window_chunk_limit(st, max_edges, batch, 0u, &K, &Ew);
     if (lim == 0) return 0;
     if (chunk_cap > 0 && lim > chunk_cap) lim = chunk_cap;
     const size_t one = wplan_bytes(lim, batch, N, d, L);
@@ -503,30 +443,26 @@ static size_t windowed_workspace_bytes(int64_t N, int d, int L, int64_t max_edge
     return all > one ? all : one;
 }
 
-size_t tpnet_stream_workspace_bytes(int64_t N, int32_t d, int32_t L, int64_t max_edges, int64_t batch) {
+size_t tpnet_stream_workspace_bytes_capped(int64_t N, int32_t d, int32_t L, int64_t max_edges, int64_t batch,
+                                           size_t log_cap_bytes) {
     if (max_edges < 1) max_edges = 1;
     if (batch < 1) batch = 1;
+    int64_t e = 0;                                         // the most edges the caller's version log lets a chunk cover (0: no cap)
+    if (log_cap_bytes > 0 && L >= 1 && d >= 1) {
+        e = (int64_t)(log_cap_bytes / (2 * (size_t)L * (size_t)d * 4)) / batch * batch;
+        if (e < 4 * batch) e = 4 * batch;                  // (the windowed schedule needs at least four batches per chunk)
+    }
     // a plan never covers more than a chunk: ~2 M edges on the per-batch schedule, what the version log allows on the
     // windowed one; longer streams are walked chunk by chunk
     const int64_t cap_a = (2000000 / batch > 0 ? 2000000 / batch : 1) * batch;
-    const size_t a = plan_bytes(max_edges < cap_a ? max_edges : cap_a, batch);
-    const size_t b = windowed_workspace_bytes(N, d, L, max_edges, batch, 0);
-    return a > b ? a : b;
-}
-
-size_t tpnet_stream_workspace_bytes_capped(int64_t N, int32_t d, int32_t L, int64_t max_edges, int64_t batch,
-                                           size_t log_cap_bytes) {
-    if (log_cap_bytes == 0 || L < 1 || d < 1) return tpnet_stream_workspace_bytes(N, d, L, max_edges, batch);
-    if (max_edges < 1) max_edges = 1;
-    if (batch < 1) batch = 1;
-    int64_t e = (int64_t)(log_cap_bytes / (2 * (size_t)L * (size_t)d * 4));
-    e = e / batch * batch;
-    if (e < 4 * batch) e = 4 * batch;                      // (the windowed schedule needs at least four batches per chunk)
-    const int64_t cap_a = (2000000 / batch > 0 ? 2000000 / batch : 1) * batch;
-    const int64_t ea = max_edges < e ? max_edges : e;
+    const int64_t ea = (e > 0 && e < max_edges) ? e : max_edges;
     const size_t a = plan_bytes(ea < cap_a ? ea : cap_a, batch);
     const size_t b = windowed_workspace_bytes(N, d, L, max_edges, batch, e);
     return a > b ? a : b;
+}
+
+size_t tpnet_stream_workspace_bytes(int64_t N, int32_t d, int32_t L, int64_t max_edges, int64_t batch) {
+    return tpnet_stream_workspace_bytes_capped(N, d, L, max_edges, batch, 0);
 }
 
 int tpnet_stream_schedule(int64_t N, int32_t d, int32_t L, int64_t E, int64_t batch, uint32_t flags, size_t ws_bytes) {
@@ -558,32 +494,10 @@ int tpnet_update(const tpnet_state* st, const int64_t* src, const int64_t* dst, 
             rc = launch_decay_desc(*st, p, 0, s);
             if (rc) return rc;
         }
-        StreamArgs a{};
-        a.own_mod = 1;
-        return launch_step(*st, a, p, 0, B, (int32_t)B, lambda, launch_id, flags | ROLE_UPDATE, s);
+        return launch_step(*st, StreamArgs{}, p, 0, B, (int32_t)B, lambda, launch_id, flags | ROLE_UPDATE, s);
     }
-    return run_stream_impl(*st, src, dst, nullptr, t, B, B, now_time, lambda, launch_id, flags, nullptr, nullptr,
-                           workspace, ws_bytes, (hipStream_t)stream, nullptr);
-}
-
-int tpnet_run_stream(const tpnet_state* st, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                     const double* t, int64_t E, int64_t batch, double now_time, double lambda,
-                     uint32_t launch_id_base, uint32_t flags, float* out_pos, float* out_neg, void* workspace,
-                     size_t ws_bytes, double* t_end_out, void* stream) {
-    int rc = check_state(st);
-    if (rc) return rc;
-    if (E < 0 || batch < 1 || (E > 0 && (!src || !dst || !t))) return TPNET_ERR_BAD_ARG;
-    if (out_neg && !neg) return TPNET_ERR_BAD_ARG;
-    const int64_t nb = (E + batch - 1) / batch;
-    if (launch_id_base == 0 || (uint64_t)launch_id_base + (uint64_t)nb >= 0x7FFFFFFFull) return TPNET_ERR_BAD_ARG;
-    rc = run_stream_impl(*st, src, dst, neg, t, E, batch, now_time, lambda, launch_id_base, flags, out_pos, out_neg,
-                         workspace, ws_bytes, (hipStream_t)stream, nullptr);
-    if (rc) return rc;
-    if (t_end_out && E > 0) {
-        TPNET_HIP_TRY(hipMemcpyAsync(t_end_out, t + E - 1, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        TPNET_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    }
-    return TPNET_OK;
+    return run_stream_impl({*st, src, dst, nullptr, t, B, B, now_time, lambda, launch_id, flags, nullptr, nullptr, workspace, ws_bytes,
+                            (hipStream_t)stream, nullptr, nullptr});
 }
 
 int tpnet_run_stream_tagged(const tpnet_state* st, const int64_t* src, const int64_t* dst, const int64_t* neg,
@@ -596,14 +510,22 @@ int tpnet_run_stream_tagged(const tpnet_state* st, const int64_t* src, const int
     if (out_neg && !neg) return TPNET_ERR_BAD_ARG;
     const int64_t nb = (E + batch - 1) / batch;
     if (launch_id_base == 0 || (uint64_t)launch_id_base + (uint64_t)nb >= 0x7FFFFFFFull) return TPNET_ERR_BAD_ARG;
-    rc = run_stream_impl(*st, src, dst, neg, t, E, batch, now_time, lambda, launch_id_base, flags, out_pos, out_neg,
-                         workspace, ws_bytes, (hipStream_t)stream, nullptr, tag);
+    rc = run_stream_impl({*st, src, dst, neg, t, E, batch, now_time, lambda, launch_id_base, flags, out_pos, out_neg, workspace,
+                          ws_bytes, (hipStream_t)stream, nullptr, tag});
     if (rc) return rc;
     if (t_end_out && E > 0) {
         TPNET_HIP_TRY(hipMemcpyAsync(t_end_out, t + E - 1, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
         TPNET_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     }
     return TPNET_OK;
+}
+
+int tpnet_run_stream(const tpnet_state* st, const int64_t* src, const int64_t* dst, const int64_t* neg,
+                     const double* t, int64_t E, int64_t batch, double now_time, double lambda,
+                     uint32_t launch_id_base, uint32_t flags, float* out_pos, float* out_neg, void* workspace,
+                     size_t ws_bytes, double* t_end_out, void* stream) {
+    return tpnet_run_stream_tagged(st, src, dst, neg, t, E, batch, now_time, lambda, launch_id_base, flags, out_pos, out_neg, workspace,
+                                   ws_bytes, t_end_out, stream, nullptr);
 }
 
 // a kernel that keeps its queue busy for `ticks` of the 100 MHz wall clock, and one that does nothing
@@ -653,10 +575,7 @@ int tpnet_step_batch(const tpnet_state* st, const int64_t* src, const int64_t* d
     Plan p{};
     rc = plan_carve(workspace, ws_bytes, E, batch, &p);
     if (rc) return rc;
-    StreamArgs a;
-    a.src = src; a.dst = dst; a.neg = neg; a.t = t;
-    a.out_pos = out_pos; a.out_neg = out_neg;
-    a.own_mod = own_mod; a.own_rem = own_rem;
+    const StreamArgs a = stream_args_at(src, dst, neg, t, out_pos, out_neg, 0, 0, own_mod, own_rem);
     const int32_t ne = (int32_t)((E - b * batch < batch) ? (E - b * batch) : batch);
     const bool have_readout = out_pos || out_neg;
     return launch_step(*st, a, p, b, batch, ne, lambda, launch_id,
@@ -730,27 +649,25 @@ int tpnet_time_stream(const tpnet_state* st, const int64_t* src, const int64_t* 
                       const double* t, int64_t E, int64_t batch, double now_time, double lambda,
                       uint32_t launch_id_base, uint32_t flags, float* out_pos, float* out_neg, void* workspace,
                       size_t ws_bytes, int reps, float* total_ms_out, float* kernel_ms_out, int64_t* launches_out,
-                      int64_t* edges_out, void* stream) {
+                      int64_t* edges_out, void* stream) try {
     int rc = check_state(st);
     if (rc) return rc;
     if (reps < 1 || E < 1 || batch < 1) return TPNET_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t nb = (E + batch - 1) / batch;
     if ((uint64_t)launch_id_base + (uint64_t)nb * (uint64_t)(reps + 1) >= 0x7FFFFFFFull) return TPNET_ERR_BAD_ARG;
-    hipEvent_t e0, e1;
-    TPNET_HIP_TRY(hipEventCreate(&e0));
-    TPNET_HIP_TRY(hipEventCreate(&e1));
-    // event pairs around the step-launch loop of every chunk of the LAST rep (at most 64 chunks)
+    // event pairs around the step-launch loop of every chunk of the LAST rep (at most 64 chunks), then the pair around the reps
     StepTimer tm;
     tm.cap = 256;
-    std::vector<hipEvent_t> evs((size_t)(2 * tm.cap));
-    for (auto& e : evs) TPNET_HIP_TRY(hipEventCreate(&e));
+    EventSet evs((size_t)(2 * tm.cap) + 2);
+    TPNET_HIP_TRY(evs.error());
     tm.ev = evs.data();
+    const hipEvent_t e0 = evs[2 * tm.cap], e1 = evs[2 * tm.cap + 1];
     uint32_t lid = launch_id_base;
     TPNET_HIP_TRY(hipEventRecord(e0, s));
     for (int r = 0; r < reps; ++r) {
-        rc = run_stream_impl(*st, src, dst, neg, t, E, batch, now_time, lambda, lid, flags, out_pos, out_neg, workspace,
-                             ws_bytes, s, (kernel_ms_out && r == reps - 1) ? &tm : nullptr);
+        rc = run_stream_impl({*st, src, dst, neg, t, E, batch, now_time, lambda, lid, flags, out_pos, out_neg, workspace, ws_bytes, s,
+                              (kernel_ms_out && r == reps - 1) ? &tm : nullptr, nullptr});
         if (rc) return rc;
         lid += (uint32_t)nb;
     }
@@ -770,10 +687,7 @@ int tpnet_time_stream(const tpnet_state* st, const int64_t* src, const int64_t* 
     }
     if (launches_out) *launches_out = tm.launches;
     if (edges_out) *edges_out = tm.edges;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    for (auto& e : evs) (void)hipEventDestroy(e);
     return TPNET_OK;
-}
+} TPNET_CATCH_BAD_ALLOC
 
 }  // extern "C"

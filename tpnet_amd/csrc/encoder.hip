@@ -35,7 +35,7 @@ int tpnet_encoder_fused_supported(const tpnet_state* st, int64_t n_rows, int32_t
 int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                             int32_t K, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram,
                             float* out, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L != 3) return TPNET_ERR_BAD_ARG;
+    if (check_state(st) || st->L != 3) return TPNET_ERR_BAD_ARG;
     if (n_rows < 0 || K < 0 || (n_rows > 0 && K > 0 && (!neigh || !a1 || !a2 || !out || !mlp))) return TPNET_ERR_BAD_ARG;
     if (n_rows == 0 || K == 0) return TPNET_OK;
     if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;

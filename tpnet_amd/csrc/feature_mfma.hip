@@ -353,7 +353,7 @@ extern "C" int tpnet_mlp_prepare(const float* w1, const float* w2, int32_t F, in
 extern "C" int tpnet_pair_feature_bf16(const tpnet_state* st, const int64_t* u, const int64_t* v, int64_t n, double now_time,
                                        double lambda, uint32_t flags, const void* w1_bf16, const float* b1,
                                        const void* w2p_bf16, const float* b2, float* out_gram, float* out, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1) return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (n < 0 || (n > 0 && (!u || !v || !out || !w1_bf16 || !b1 || !w2p_bf16 || !b2))) return TPNET_ERR_BAD_ARG;
     return launch_pair_feature_bf16(*st, u, v, n, now_time, lambda, flags, w1_bf16, b1, w2p_bf16, b2, out_gram, out,
                                     (hipStream_t)stream, 0, nullptr);

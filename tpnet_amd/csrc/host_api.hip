@@ -165,8 +165,7 @@ int64_t tpnet_stage_max_batch(const tpnet_stage* sg) {
 
 int tpnet_pair_feature(const tpnet_state* st, const int64_t* u, const int64_t* v, int64_t n, double now_time,
                        double lambda, uint32_t flags, const tpnet_mlp* mlp, float* out_gram, float* out, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS)
-        return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (n < 0 || !mlp || (n > 0 && (!u || !v || !out))) return TPNET_ERR_BAD_ARG;
     return launch_pair_feature(*st, u, v, n, now_time, lambda, flags, *mlp, out_gram, out, (hipStream_t)stream);
 }
@@ -174,8 +173,7 @@ int tpnet_pair_feature(const tpnet_state* st, const int64_t* u, const int64_t* v
 int tpnet_host_pair_feature(const tpnet_state* st, tpnet_stage* stage, const int64_t* h_u, const int64_t* h_v, int64_t n,
                             double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* out_gram,
                             float* out, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS)
-        return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (n < 0 || (n > 0 && (!h_u || !h_v || !out)) || !stage) return TPNET_ERR_BAD_ARG;
     if (n == 0) return TPNET_OK;
     char *host = nullptr, *dev = nullptr;
@@ -197,28 +195,34 @@ int tpnet_host_pair_feature(const tpnet_state* st, tpnet_stage* stage, const int
 int tpnet_host_update(const tpnet_state* st, tpnet_stage* stage, const int64_t* h_src, const int64_t* h_dst,
                       const double* h_t, int64_t B, double now_time, double lambda, uint32_t launch_id, uint32_t flags,
                       void* workspace, size_t ws_bytes, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS)
-        return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (B < 1 || !h_src || !h_dst || !h_t || !stage) return TPNET_ERR_BAD_ARG;
     if (launch_id == 0 || launch_id >= 0x7FFFFFFFu) return TPNET_ERR_BAD_ARG;
     if (flags & TPNET_FLAG_EAGER_DECAY) return TPNET_ERR_BAD_ARG;     // (the exact mode's dense decay is tpnet_decay, before this call)
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)B * 24;                              // src, dst, t: one block of the slot
+    char *host = nullptr, *dev = nullptr;
+    // ids checked and copied with the clocks into the ring; the caller's launches then read them at `dev`
+    auto staged = [&]() {
+        const int rc = stage_acquire(stage, bytes, s, &host, &dev);
+        if (rc) return rc;
+        int64_t* hs = reinterpret_cast<int64_t*>(host);
+        if (!copy_ids(hs, h_src, B, st->N) || !copy_ids(hs + B, h_dst, B, st->N)) return (int)TPNET_ERR_INDEX;
+        memcpy(hs + 2 * B, h_t, (size_t)B * 8);
+        stage_written(stage);
+        return (int)TPNET_OK;
+    };
     if (B > tpnet_stage_max_batch(stage)) {
         // a batch too large for the single-workgroup plan: the staged arrays are copied to the tail of the workspace (the
         // chunk planner gathers from them at random: not something to do over PCIe) and the per-batch path plans + steps
-        if ((size_t)B * 24 > stage->slot_bytes) return TPNET_ERR_BAD_ARG;
+        if (bytes > stage->slot_bytes) return TPNET_ERR_BAD_ARG;
         const size_t pb = (plan_bytes(B, B) + 255) / 256 * 256;
-        if (!workspace || pb + (size_t)B * 24 > ws_bytes) return TPNET_ERR_WORKSPACE;
-        char *host = nullptr, *dev = nullptr;
-        hipStream_t s = (hipStream_t)stream;
-        int rc = stage_acquire(stage, (size_t)B * 24, s, &host, &dev);
+        if (!workspace || pb + bytes > ws_bytes) return TPNET_ERR_WORKSPACE;
+        int rc = staged();
         if (rc) return rc;
-        int64_t* hs = reinterpret_cast<int64_t*>(host);
-        if (!copy_ids(hs, h_src, B, st->N) || !copy_ids(hs + B, h_dst, B, st->N)) return TPNET_ERR_INDEX;
-        memcpy(hs + 2 * B, h_t, (size_t)B * 8);
-        stage_written(stage);
         int64_t* d = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + pb);
-        TPNET_HIP_TRY(hipMemcpyAsync(d, host, (size_t)B * 24, hipMemcpyHostToDevice, s));
-        rc = stage_release(stage, (size_t)B * 24, s);
+        TPNET_HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyDefault, s));      // (the ring is pinned host memory or device memory)
+        rc = stage_release(stage, bytes, s);
         if (rc) return rc;
         return tpnet_update(st, d, d + B, reinterpret_cast<const double*>(d + 2 * B), B, now_time, lambda, launch_id, flags,
                             workspace, pb, stream);
@@ -226,22 +230,14 @@ int tpnet_host_update(const tpnet_state* st, tpnet_stage* stage, const int64_t* 
     Plan p{};
     int rc = plan_carve(workspace, ws_bytes, B, B, &p);
     if (rc) return rc;
-    char *host = nullptr, *dev = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    rc = stage_acquire(stage, (size_t)B * 24, s, &host, &dev);
+    rc = staged();
     if (rc) return rc;
-    int64_t* hs = reinterpret_cast<int64_t*>(host);
-    if (!copy_ids(hs, h_src, B, st->N) || !copy_ids(hs + B, h_dst, B, st->N)) return TPNET_ERR_INDEX;
-    memcpy(hs + 2 * B, h_t, (size_t)B * 8);
-    stage_written(stage);
     const int64_t* ds = reinterpret_cast<const int64_t*>(dev);
     rc = plan_one(*st, p, ds, ds + B, reinterpret_cast<const double*>(ds + 2 * B), B, now_time, lambda, flags, s);
     if (rc) return rc;
-    rc = stage_release(stage, (size_t)B * 24, s);                      // the plan kernel is the only reader of the slot
+    rc = stage_release(stage, bytes, s);                              // the plan kernel is the only reader of the slot
     if (rc) return rc;
-    StreamArgs a{};
-    a.own_mod = 1;
-    return launch_step(*st, a, p, 0, B, (int32_t)B, lambda, launch_id, flags | ROLE_UPDATE, s);
+    return launch_step(*st, StreamArgs{}, p, 0, B, (int32_t)B, lambda, launch_id, flags | ROLE_UPDATE, s);
 }
 
 // The encoder's whole readout for one (src, other) batch (tpnet_encoder_features) with the BATCH's arrays on the host -- what the

@@ -916,6 +916,39 @@ int wplan_window_batches(int64_t batch, int d, int L) {
     return K >= 2 ? (int)K : 0;
 }
 
+// Batches per window of a chunk of nb batches.  A pipeline of nw windows is nw + L dependent launches, each a fixed floor
+// (~10 us: kernel boundary + the dependent loads of its longest unit) plus its share of the bandwidth work (~2.5 us per batch
+// at C2): few long windows for short streams.  Measured (tools/short_trace.sh, sum of the pipeline launches): 20 batches as
+// 1 / 2 / 4 windows 127 / 85 / 110 us; 158 batches at 12 / 16 / 24 per window 493 / 472 / 450 us; long streams: the cap of 24
+// (tools/degree_sensitivity.py).
+int window_batches_for(int64_t nb, int Kmax) {
+    static const int fixed = TPNET_DEV_INT(WINDOW_FIXED, 0);
+    if (fixed > 0) return fixed < Kmax ? fixed : Kmax;
+    static const int num = TPNET_DEV_INT(WINDOW_SQ, 5);
+    int K = 2;
+    while (K < Kmax && (int64_t)K * K < (int64_t)num * nb) ++K;         // K = ceil(sqrt(5 nb))
+    const int64_t nw0 = (nb + K - 1) / K;                              // equal windows: ceil(nb / nw0) batches each
+    return (int)((nb + nw0 - 1) / nw0);
+}
+
+// Dense where the caller's flags leave the choice open and it serves; else hashed; else sorted.  The hashed planner costs ~45 us +
+// 0.76 us per batch, the sorted one ~200 us + 0.63 us per batch (C2, profiles/r03_C2.md): 4 % of a long stream's time, paid for
+// having ONE set of plan kernels whatever the stream's length (a chunk that falls to the sorted planner meets rocPRIM's large-size
+// sort kernels for the first time in the middle of a long call: HIP resolves a kernel at its first launch, ~0.3 ms each) -- so
+// streams of batches that fit one workgroup's LDS are cut into chunks of at most 64 (dense: 256) windows.
+WPlanner choose_wplanner(const tpnet_state& st, const WPlan* p, int64_t Ec, int64_t batch, int K, uint32_t flags) {
+    static const int no3 = TPNET_DEV_INT(NO_PLAN3, 0);
+    static const int max3 = TPNET_DEV_INT(PLAN3_MAX_BATCHES, 1 << 30);
+    const bool small = batch <= PLAN_ONE_MAX;
+    if (!(flags & (TPNET_FLAG_PLAN_SORTED | TPNET_FLAG_PLAN_HASHED)) &&
+        (p ? wplan_dense_applies(st, *p, Ec, batch, K) : small && wplan_dense_eligible(st.N, st.d, st.L, batch)))
+        return {wplan_dense_build, wplan_dense_writeback, true, 256};
+    if (!(flags & TPNET_FLAG_PLAN_SORTED) &&
+        (p ? !no3 && (Ec + batch - 1) / batch <= max3 && wplan3_applies(st, Ec, batch, K) : small))
+        return {wplan3_build, wplan3_writeback, true, WIN_MAX_WINDOWS};
+    return {wplan_build, launch_wwriteback, false, 0};
+}
+
 // Contributions per (node, window) above which a workgroup per column part walks the chain instead of one lane group: a lane
 // group keeps 8 rows in flight, so a chain of n contributions is n / 8 dependent memory round trips -- the latency floor of a
 // launch, which has to stay below the launch's bandwidth time, i.e. scale with the bytes of a window (batches x edges x row
@@ -1370,9 +1403,10 @@ __global__ void k_plan_w(WPlan p, const K* __restrict__ keys, const int64_t* __r
         edge_refs<K>(blockIdx.x - fgrid, gridDim.x - fgrid, p, keys, src, dst, neg, Ec, B, N, batch_bits, lambda, meta);
 }
 
-int wplan_build(const tpnet_state& st, const WPlan& p, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                const double* t, int64_t Ec, int64_t batch, double now_time, const double* t_prev_dev, double lambda,
-                bool want_readout, hipStream_t s) {
+int wplan_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipStream_t s) {
+    const int64_t *src = a.src, *dst = a.dst, *neg = a.neg, Ec = a.Ec, batch = a.batch;
+    const double *t = a.t, *t_prev_dev = a.t_prev_dev, now_time = a.now_time, lambda = a.lambda;
+    const bool want_readout = a.want_readout;
     const int64_t nb = (Ec + batch - 1) / batch;
     const int64_t nc = 2 * Ec;
     const int64_t nw = (Ec + p.Ew - 1) / p.Ew;

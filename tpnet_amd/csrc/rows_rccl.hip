@@ -9,7 +9,6 @@
 
 #include <dlfcn.h>
 #include <cstring>
-#include <vector>
 
 namespace tpnet {
 
@@ -112,8 +111,7 @@ int tpnet_rows_step(const tpnet_state* st, void* comm, const int64_t* pack_ids, 
                     double now_time, const int64_t* src, const int64_t* dst, const int64_t* neg, const double* t, int64_t E,
                     int64_t batch, int64_t b, double lambda, uint32_t launch_id, uint32_t flags, int32_t n_owned,
                     float* out_pos, float* out_neg, void* workspace, size_t ws_bytes, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS)
-        return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (G < 1 || maxc < 0 || n_pack < 0 || n_pack > maxc || n_unpack < 0) return TPNET_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     int rc;
@@ -133,8 +131,7 @@ int tpnet_rows_step(const tpnet_state* st, void* comm, const int64_t* pack_ids, 
 
 int tpnet_pack_split(const tpnet_state* st, const int64_t* ids, int64_t n, double now_time, double lambda, float* out_p0,
                      float* out_q, int64_t halo0, int64_t n_halo, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS)
-        return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (n < 0 || n_halo < 0 || halo0 < 0 || halo0 + n_halo > st->N || (n > 0 && (!ids || !out_p0 || !out_q))) return TPNET_ERR_BAD_ARG;
     return launch_pack_split(*st, ids, n, now_time, lambda, out_p0, out_q, halo0, n_halo, (hipStream_t)stream);
 }
@@ -184,8 +181,7 @@ int tpnet_rows_step_targeted(const tpnet_state* st, void* comm, const int64_t* p
                              const int64_t* src, const int64_t* dst, const int64_t* neg, const double* t, int64_t E,
                              int64_t batch, int64_t b, double lambda, uint32_t launch_id, uint32_t flags, int32_t n_owned,
                              float* out_pos, float* out_neg, void* workspace, size_t ws_bytes, void* stream) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS)
-        return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (G < 1 || me < 0 || me >= G || n_owned < 0 || n_owned > st->N) return TPNET_ERR_BAD_ARG;
     const int rc = rows_exchange_targeted(st, comm, pack_ids, send_p0, send_q, send_cnt, recv_cnt, G, me, now_time, lambda, n_owned,
                                           (hipStream_t)stream);
@@ -204,8 +200,7 @@ static int rows_stream_loop(const tpnet_state* st, void* comm, const int64_t* pa
     const int64_t nb = batch > 0 ? (E + batch - 1) / batch : 0;
     if (batch < 1 || b0 < 0 || b1 > nb || b0 > b1 || !t_last || !send_cnt || !recv_cnt || !pack_start || G < 1) return TPNET_ERR_BAD_ARG;
     if (launch_id_base == 0 || (uint64_t)launch_id_base + (uint64_t)nb >= 0x7FFFFFFFull) return TPNET_ERR_BAD_ARG;
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || st->N < 1 || st->d < 1 || st->L < 1 || st->L > TPNET_MAX_LAYERS)
-        return TPNET_ERR_BAD_ARG;
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (me < 0 || me >= G || n_owned < 0 || n_owned > st->N) return TPNET_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     for (int64_t b = b0; b < b1; ++b) {
@@ -243,11 +238,11 @@ int tpnet_time_rows_stream_targeted(const tpnet_state* st, void* comm, const int
                                     const int64_t* neg, const double* t, int64_t E, int64_t batch, int64_t b0, int64_t b1,
                                     double lambda, uint32_t launch_id_base, uint32_t flags, int32_t n_owned, float* out_pos,
                                     float* out_neg, void* workspace, size_t ws_bytes, void* stream, float* total_ms_out,
-                                    float* step_ms_out, float* exchange_ms_out) {
+                                    float* step_ms_out, float* exchange_ms_out) try {
     if (b1 <= b0 || b1 - b0 > 4096) return TPNET_ERR_BAD_ARG;
     const size_t n = (size_t)(b1 - b0);
-    std::vector<hipEvent_t> ev(3 * n);
-    for (auto& e : ev) TPNET_HIP_TRY(hipEventCreate(&e));
+    EventSet ev(3 * n);
+    TPNET_HIP_TRY(ev.error());
     int rc = rows_stream_loop(st, comm, pack_ids, pack_start, send_p0, send_q, send_cnt, recv_cnt, G, me, now_time, t_last, src, dst,
                               neg, t, E, batch, b0, b1, lambda, launch_id_base, flags, n_owned, out_pos, out_neg, workspace, ws_bytes,
                               stream, ev.data());
@@ -266,8 +261,7 @@ int tpnet_time_rows_stream_targeted(const tpnet_state* st, void* comm, const int
         if (step_ms_out) *step_ms_out = (float)(step / (double)n);
         if (exchange_ms_out) *exchange_ms_out = (float)(xch / (double)n);
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
     return rc;
-}
+} TPNET_CATCH_BAD_ALLOC
 
 }  // extern "C"

@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <new>
 #include "../../include/tpnet_hip.h"
 #include "tpnet_dev.h"
+#include "event_set.hpp"
 
 // Developer knobs (window length, thresholds, roles switched off for timing experiments ...) exist only in builds made with
 // -DTPNET_DEV (make VARIANT=dev VARFLAGS=-DTPNET_DEV -> libtpnet_hip_dev.so, loaded through TPNET_DEV_LIB by tools/): the product
@@ -83,20 +85,31 @@ struct Plan {
 };
 static constexpr size_t TPNET_DBG_BYTES = 1u << 20;   // (diagnostic builds: 512 KB of per-wave stamps + 512 KB of per-block stamps)
 
-struct StreamArgs {
-    const int64_t* src;
-    const int64_t* dst;
-    const int64_t* neg;
-    const double* t;
-    float* out_pos;
-    float* out_neg;
-    int32_t own_mod;   // row sharding: this rank computes targets / pairs (by their src node) with id % own_mod == own_rem
-    int32_t own_rem;   // (own_mod = 1: everything; own_mod = 0: compact local table, the rank owns ids < own_rem)
+struct StreamArgs {         // (as constructed: no arrays -- a launch that reads none -- and every row owned)
+    const int64_t* src = nullptr;
+    const int64_t* dst = nullptr;
+    const int64_t* neg = nullptr;
+    const double* t = nullptr;
+    float* out_pos = nullptr;
+    float* out_neg = nullptr;
+    int32_t own_mod = 1;   // row sharding: this rank computes targets / pairs (by their src node) with id % own_mod == own_rem
+    int32_t own_rem = 0;   // (own_mod = 1: everything; own_mod = 0: compact local table, the rank owns ids < own_rem)
     // the windowed pipeline of a row shard (wshard.hip): the edges whose src node this rank owns, window by window (ascending): the
     // readout role of window w walks own_list[own_start[w] .. own_start[w + 1]) instead of every edge of the window
     const uint32_t* own_list = nullptr;
     const uint32_t* own_start = nullptr;
 };
+// the chunk at edge c0 of a stream whose outputs are rows of `row` floats; every row owned, or a row shard's view (own_mod, own_rem)
+inline StreamArgs stream_args_at(const int64_t* src, const int64_t* dst, const int64_t* neg, const double* t, float* out_pos,
+                                 float* out_neg, int64_t c0, int64_t row, int32_t own_mod = 1, int32_t own_rem = 0) {
+    StreamArgs a;
+    a.src = src + c0; a.dst = dst + c0; a.t = t + c0;
+    a.neg = neg ? neg + c0 : nullptr;
+    a.out_pos = out_pos ? out_pos + c0 * row : nullptr;
+    a.out_neg = out_neg ? out_neg + c0 * row : nullptr;
+    a.own_mod = own_mod; a.own_rem = own_rem;
+    return a;
+}
 
 // Launch geometry of the fast paths: LPP lanes cooperate on one row (one pair / one target), each lane owning VPL
 // vectors of W floats per column chunk.
@@ -306,48 +319,65 @@ struct WPlan {
 
 size_t wplan_bytes(int64_t max_edges, int64_t batch, int64_t N, int d, int L);
 int wplan_window_batches(int64_t batch, int d, int L);                 // 0 = the windowed path does not apply
+int window_batches_for(int64_t nb, int Kmax);                          // batches per window of a chunk of nb batches (<= Kmax)
 int64_t wplan_max_chunk_edges(int64_t batch, int d, int L);            // edges one plan (and its log) may cover
 int wplan_carve(void* ws, size_t ws_bytes, int64_t Ec, int64_t batch, int64_t N, int d, int L, int K, WPlan* out,
                 float* shared_log = nullptr, bool shard = false);   // K <= wplan_window_batches (shard: chosen by the caller); shared_log: the version log lives outside the region
 size_t wplan_bytes_shard(int64_t max_edges, int64_t batch, int64_t N, int d, int L);   // workspace of a row shard's chunk (wshard.hip)
 size_t wplan_log_bytes(int64_t max_edges, int d, int L);       // the version log's share of wplan_bytes
-int wplan_build(const tpnet_state& st, const WPlan& p, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                const double* t, int64_t Ec, int64_t batch, double now_time, const double* t_prev_dev, double lambda,
-                bool want_readout, hipStream_t s);
-// the same plan without a device-wide sort (wplan3.hip: one fill + three kernels) for batches that fit one workgroup's LDS and chunks of <= 64 windows;
-// replay = the workspace still holds this plan of the SAME stream on the SAME table state: only the negatives' readout
-// references are formed again
+// Three planners fill the same WPlan with the same arithmetic per run (bit-identical results): sorted (plan.hip: two device-wide
+// sorts, any chunk, keeps nothing to replay), hashed (wplan3.hip: one fill + three kernels, for batches that fit one workgroup's LDS
+// and chunks of <= 64 windows) and dense (wplan_dense.hip: ONE launch through a dense (batch x node) matrix of run lengths, where the
+// table is small against the stream -- wplan_dense_eligible: every dataset of the reference; up to 256 windows; also a row shard's).
+struct WPlanArgs {        // what a chunk is planned from
+    const int64_t *src, *dst, *neg;
+    const double* t;
+    int64_t Ec, batch;
+    double now_time;
+    const double* t_prev_dev;   // the clock before a later chunk: t[c0 - 1], read on the device (nullptr: now_time)
+    double lambda;
+    bool want_readout;
+    bool replay;          // the workspace still holds this plan of the SAME stream on the SAME table state: only the negatives' readout
+                          // references are formed again (the sorted planner plans anew)
+    // own (row shard, wshard.hip, dense planner; -1: everything): the stream holds LOCAL ids, rows < own are this rank's, the rows behind
+    // them halo rows of other ranks' nodes -- only contributions to owned targets are planned (a halo node's run is ONE log slot, filled
+    // by the exchange), only owned nodes are written back; status (shard): [0] += batches whose owned contributions exceeded the sort
+    int64_t own = -1;
+    uint32_t* status = nullptr;
+};
+int wplan_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipStream_t s);
+int wplan3_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipStream_t s);
+int wplan_dense_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipStream_t s);
+// end of the chunk: every touched node's last version -> the table's other copy, meta published under launch_id: the scan of the sorted
+// positions for the last-run flag (wstep.hip); node by node (a table much larger than the chunk goes to the scan)
+int launch_wwriteback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s, int64_t own = -1);
+int wplan3_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s, int64_t own = -1);
+int wplan_dense_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s, int64_t own = -1);
 bool wplan3_applies(const tpnet_state& st, int64_t Ec, int64_t batch, int K);
 size_t wplan3_table_bytes(int64_t Ec, int64_t batch);
 size_t wplan3_blk_bytes(int64_t Ec, int64_t batch);
-int wplan3_build(const tpnet_state& st, const WPlan& p, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                 const double* t, int64_t Ec, int64_t batch, double now_time, const double* t_prev_dev, double lambda,
-                 bool want_readout, bool replay, hipStream_t s);
-// the same plan in ONE launch through a dense (batch x node) matrix of run lengths (wplan_dense.hip), where the table is small
-// against the stream (wplan_dense_eligible: every dataset of the reference); any number of windows up to 256
 bool wplan_dense_eligible(int64_t N, int d, int L, int64_t batch);
 size_t wplan_dense_bytes(int64_t Ec, int64_t batch, int64_t N, int d, int L);          // 0: not eligible
 bool wplan_dense_applies(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, int K);
-// own (row shard, wshard.hip; -1: everything): the stream holds LOCAL ids, rows < own are this rank's, the rows behind them halo
-// rows of other ranks' nodes -- only contributions to owned targets are planned (a halo node's run is ONE log slot, filled by the
-// exchange), only owned nodes are written back; status (shard): [0] += batches whose owned contributions exceeded the sort
-int wplan_dense_build(const tpnet_state& st, const WPlan& p, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                      const double* t, int64_t Ec, int64_t batch, double now_time, const double* t_prev_dev, double lambda,
-                      bool want_readout, bool replay, hipStream_t s, int64_t own = -1, uint32_t* status = nullptr);
-bool wplan_dense_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s,
-                           int64_t own = -1);
 bool wplan_dense_applies_shard(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, int K);
 
+// THE choice of a chunk's planner (plan.hip), from the caller's flags and what each planner serves.  p: the chunk's carved plan, with
+// Ec and K -- or nullptr (Ec, K ignored): the planner a stream of such batches is laid out for, before any chunk exists
+struct WPlanner {
+    decltype(&wplan_build) build;
+    decltype(&launch_wwriteback) writeback;
+    bool replayable;      // its plan can be kept in the workspace and replayed (WPlanArgs::replay)
+    int max_windows;      // windows per chunk it serves (0: no bound of its own)
+};
+WPlanner choose_wplanner(const tpnet_state& st, const WPlan* p, int64_t Ec, int64_t batch, int K, uint32_t flags);
 uint32_t wplan_heavy_threshold(int K, int64_t batch, int d);
 bool wplan_medium_chains(int d);          // rows that are exactly one chunk of their geometry: chain_medium serves (wstep.hip)
 // pipeline step j of a chunk of nw windows: layer i of window j-i+1 (i = 1..L) and the readout of window j-L, whichever
 // exist, in ONE launch; j = 0 .. nw+L-1.
 int launch_wstep(const tpnet_state& st, const StreamArgs& a, const WPlan& p, int64_t j, int64_t Ec, int64_t batch,
                  double lambda, uint32_t flags, hipStream_t s);
-// end of the chunk: every touched node's last version -> the table's other copy, meta published under launch_id
-int launch_wwriteback(const tpnet_state& st, const WPlan& p, int64_t Ec, uint32_t launch_id, hipStream_t s);
-// the same for a chunk the hashed planner planned, node by node (false: not served, take launch_wwriteback)
-bool wplan3_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s);
+// every pointer of the state set, 1 <= N < 2^31, d >= 1, 1 <= L <= TPNET_MAX_LAYERS: what every entry point asks of its tpnet_state
+int check_state(const tpnet_state* st);
 
 extern thread_local int g_last_hip_error;
 #define TPNET_HIP_TRY(expr)                                   \
@@ -358,5 +388,9 @@ extern thread_local int g_last_hip_error;
             return TPNET_ERR_HIP;                             \
         }                                                     \
     } while (0)
+// closes the function-try-block of an extern "C" entry point that allocates on the host (std::vector, new): an exception must not
+// cross the C ABI -- TPNET_ERR_HIP with tpnet_last_hip_error() = hipErrorOutOfMemory
+#define TPNET_CATCH_BAD_ALLOC \
+    catch (const std::bad_alloc&) { tpnet::g_last_hip_error = (int)hipErrorOutOfMemory; return TPNET_ERR_HIP; }
 
 }  // namespace tpnet

@@ -425,15 +425,16 @@ __global__ __launch_bounds__(256) void k_wwriteback_nodes(tpnet_state S, WPlan p
     }
 }
 
-// (false: the caller takes the position scan -- rows that are not 16-byte vectors, or a table much larger than the chunk)
-bool wplan3_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s) {
+// (a table much larger than the chunk: the position scan)
+int wplan3_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s, int64_t own) {
     static const int off = TPNET_DEV_INT(NO_WB_NODES, 0);
-    if (off || (st.L * st.d) % 4 != 0 || st.N > 8 * Ec) return false;
+    if (off || (st.L * st.d) % 4 != 0 || st.N > 8 * Ec) return launch_wwriteback(st, p, Ec, batch, launch_id, s, own);
     const WTmp q = wtmp_full(st, p, Ec, batch);
     int64_t grid = (st.N + 7) / 8;
     if (grid > 16384) grid = 16384;
     hipLaunchKernelGGL(k_wwriteback_nodes, dim3((unsigned)grid), dim3(256), 0, s, st, p, q, batch, launch_id);
-    return hipGetLastError() == hipSuccess;
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
 }
 
 bool wplan3_applies(const tpnet_state& st, int64_t Ec, int64_t batch, int K) {
@@ -446,9 +447,10 @@ bool wplan3_applies(const tpnet_state& st, int64_t Ec, int64_t batch, int K) {
            2 * Ec < (int64_t)WREF_SLOT_MASK;
 }
 
-int wplan3_build(const tpnet_state& st, const WPlan& p, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                 const double* t, int64_t Ec, int64_t batch, double now_time, const double* t_prev_dev, double lambda,
-                 bool want_readout, bool replay, hipStream_t s) {
+int wplan3_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipStream_t s) {
+    const int64_t *src = a.src, *dst = a.dst, *neg = a.neg, Ec = a.Ec, batch = a.batch;
+    const double *t = a.t, *t_prev_dev = a.t_prev_dev, now_time = a.now_time, lambda = a.lambda;
+    const bool want_readout = a.want_readout, replay = a.replay;
     if (!wplan3_applies(st, Ec, batch, p.K) || !p.wmask || !p.wcls || !p.wtab || !p.wblk) return TPNET_ERR_BAD_ARG;
     const int64_t nb = (Ec + batch - 1) / batch;
     WTmp q = wtmp_full(st, p, Ec, batch);

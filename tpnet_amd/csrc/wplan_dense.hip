@@ -782,10 +782,10 @@ bool wplan_dense_applies_shard(const tpnet_state& st, const WPlan& p, int64_t Ec
     return nw <= DENSE_MAX_WINDOWS && nw <= (nb + 1) / 2 + 1 && nb < 65535 && node_bits <= 31 && 2 * Ec < (int64_t)WREF_SLOT_MASK;
 }
 
-int wplan_dense_build(const tpnet_state& st, const WPlan& p, const int64_t* src, const int64_t* dst, const int64_t* neg,
-                      const double* t, int64_t Ec, int64_t batch, double now_time, const double* t_prev_dev, double lambda,
-                      bool want_readout, bool replay, hipStream_t s, int64_t own, uint32_t* status) {
-    if (own < 0 || own > st.N) own = st.N;
+int wplan_dense_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& pa, hipStream_t s) {
+    const int64_t Ec = pa.Ec, batch = pa.batch;
+    const bool replay = pa.replay;
+    const int64_t own = (pa.own < 0 || pa.own > st.N) ? st.N : pa.own;
     const bool shard = own < st.N;
     if (!(shard ? wplan_dense_applies_shard(st, p, Ec, batch, p.K) : wplan_dense_applies(st, p, Ec, batch, p.K))) return TPNET_ERR_BAD_ARG;
     if (shard && replay) return TPNET_ERR_BAD_ARG;                      // (a shard's plan is kept by its runner, not replayed here)
@@ -793,19 +793,19 @@ int wplan_dense_build(const tpnet_state& st, const WPlan& p, const int64_t* src,
     const WTmp q = wtmp_of(p, (size_t)(2 * Ec));
     const DView D = dview_of(p, Ec, batch, st.N);
     DArgs a;
-    a.src = src; a.dst = dst; a.neg = neg; a.t = t; a.t_prev = t_prev_dev;
+    a.src = pa.src; a.dst = pa.dst; a.neg = pa.neg; a.t = pa.t; a.t_prev = pa.t_prev_dev;
     a.meta = reinterpret_cast<const NodeMeta*>(st.meta);
     a.err = st.err;
     a.Ec = Ec; a.Bfull = batch; a.N = st.N; a.nb = nb; a.nw = (nb + p.K - 1) / p.K;
-    a.now_time = now_time; a.lambda = lambda;
+    a.now_time = pa.now_time; a.lambda = pa.lambda;
     int node_bits = 1;
     while (node_bits < 31 && (1ll << node_bits) < st.N) ++node_bits;
     a.node_bits = node_bits;
     a.L = st.L;
-    a.nwhich = want_readout ? (neg ? 3 : 2) : 0;
+    a.nwhich = pa.want_readout ? (pa.neg ? 3 : 2) : 0;
     a.nchunks = (int32_t)((st.N + DCH - 1) / DCH);
     a.own = own;
-    a.status = status;
+    a.status = pa.status;
     if (replay) {
         if (a.nwhich == 3) {
             int g = (int)((Ec + 255) / 256);
@@ -836,16 +836,17 @@ int wplan_dense_build(const tpnet_state& st, const WPlan& p, const int64_t* src,
     return TPNET_OK;
 }
 
-bool wplan_dense_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s,
-                           int64_t own) {
-    if ((st.L * st.d) % 4 != 0) return false;
+int wplan_dense_writeback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t batch, uint32_t launch_id, hipStream_t s,
+                          int64_t own) {
+    if ((st.L * st.d) % 4 != 0) return TPNET_ERR_BAD_ARG;                  // (the pipeline's rows are 16-byte vectors: launch_wstep)
     if (own < 0 || own > st.N) own = st.N;
     const DView D = dview_of(p, Ec, batch, st.N);
     int64_t grid = (own + 7) / 8;
     if (grid > 16384) grid = 16384;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(k_wwriteback_dense, dim3((unsigned)grid), dim3(256), 0, s, st, p, D, launch_id, own);
-    return hipGetLastError() == hipSuccess;
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
 }
 
 }  // namespace tpnet

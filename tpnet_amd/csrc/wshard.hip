@@ -394,8 +394,10 @@ void tpnet_wshard_destroy(tpnet_wshard* w) { delete w; }
 int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* dst, const int64_t* neg, const double* t, int64_t E,
                       int64_t batch, int64_t N_global, int32_t G, int32_t me, int32_t n_owned, double now_time, double lambda,
                       uint32_t flags, int32_t want_pos, int32_t want_neg, void* workspace, size_t ws_bytes, void* stream,
-                      tpnet_wshard** out) {
-    if (!st || !st->p0 || !st->q || !st->meta || !st->err || !src || !dst || !t || !out || !workspace) return TPNET_ERR_BAD_ARG;
+                      tpnet_wshard** out) try {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (!src || !dst || !t || !out || !workspace) return TPNET_ERR_BAD_ARG;
     if (E < 1 || batch < 1 || G < 1 || G > WS_MAXG || me < 0 || me >= G || n_owned < 1 || n_owned >= st->N) return TPNET_ERR_BAD_ARG;
     if (N_global < 1 || (N_global + G - 1) / G != n_owned) return TPNET_ERR_BAD_ARG;
     *out = nullptr;
@@ -409,10 +411,7 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
     int64_t Kmax = 24576 * (int64_t)G / batch;
     if (Kmax > WIN_MAX_BATCHES) Kmax = WIN_MAX_BATCHES;
     if (Kmax < 2) return 1;
-    int K = 2;
-    while (K < Kmax && (int64_t)K * K < 5 * nb) ++K;                      // ceil(sqrt(5 nb)), as api.hip's window_batches_for
-    const int64_t nw0 = (nb + K - 1) / K;
-    K = (int)((nb + nw0 - 1) / nw0);
+    const int K = window_batches_for(nb, (int)Kmax);
     const int64_t nw = (nb + K - 1) / K;
     if (nw >= (1 << WS_WIN_BITS) || nw > 256) return 1;
     hipStream_t s = (hipStream_t)stream;
@@ -425,7 +424,7 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
     auto fail = [&](int rc) { return rc; };
     const size_t plan_b = ws_al(wplan_bytes_shard(E, batch, st->N, d, L));
     char* base = reinterpret_cast<char*>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
-    int rc = wplan_carve(base, plan_b, E, batch, st->N, d, L, K, &w->p, nullptr, true);
+    rc = wplan_carve(base, plan_b, E, batch, st->N, d, L, K, &w->p, nullptr, true);
     if (rc) return fail(rc == TPNET_ERR_BAD_ARG ? 1 : rc);
     if (!wplan_dense_applies_shard(*st, w->p, E, batch, K)) return fail(1);
     char* c = base + plan_b;
@@ -491,13 +490,10 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
     rc = launch_pack_split(*st, nullptr, 0, now_time, lambda, nullptr, nullptr, n_owned, w->hstart[G], s);
     if (rc) return fail(rc);
     // ---- the plan of the pipeline on the local ids, owned targets only
-    rc = wplan_dense_build(*st, w->p, lsrc, ldst, neg ? lneg : nullptr, t, E, batch, now_time, nullptr, lambda, w->have_readout, false, s,
-                           n_owned, status + 1);
-    if (rc) return fail(rc);
     StreamArgs& a = w->a;
-    a.src = lsrc; a.dst = ldst; a.neg = neg ? lneg : nullptr; a.t = t;
-    a.out_pos = nullptr; a.out_neg = nullptr;
-    a.own_mod = 0; a.own_rem = n_owned;
+    a = stream_args_at(lsrc, ldst, neg ? lneg : nullptr, t, nullptr, nullptr, 0, 0, 0, n_owned);      // (local ids: the rank owns those < n_owned)
+    rc = wplan_dense_build(*st, w->p, {a.src, a.dst, a.neg, t, E, batch, now_time, nullptr, lambda, w->have_readout, false, n_owned, status + 1}, s);
+    if (rc) return fail(rc);
     {
         // the rank's own edges (src node owned), in order, and every window's slice of them
         size_t tb = tmp_bytes;
@@ -595,7 +591,7 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
     TPNET_HIP_TRY(hipGetLastError());
     *out = holder.release();
     return TPNET_OK;
-}
+} TPNET_CATCH_BAD_ALLOC
 
 /* sizes the caller needs: steps of the pipeline, halo rows in use, rows of the largest step's messages, the chunk's row counts per
  * owner [G], rows per (step, peer) [nsteps][G] */
@@ -713,8 +709,7 @@ int tpnet_wshard_step(tpnet_wshard* w, void* comm, int64_t j, uint32_t phases, f
 /* the write-back of the owned nodes (the halo rows are scratch of the chunk) */
 int tpnet_wshard_finish(tpnet_wshard* w, uint32_t launch_id, void* stream) {
     if (!w || launch_id == 0 || launch_id >= 0x7FFFFFFFu) return TPNET_ERR_BAD_ARG;
-    if (!wplan_dense_writeback(w->st, w->p, w->E, w->batch, launch_id, (hipStream_t)stream, w->n_owned)) return TPNET_ERR_HIP;
-    return TPNET_OK;
+    return wplan_dense_writeback(w->st, w->p, w->E, w->batch, launch_id, (hipStream_t)stream, w->n_owned);
 }
 
 /* begin + every step + finish in ONE call (comm: an RCCL communicator of tpnet_rccl_comm_create; NULL with one rank) */
@@ -733,13 +728,13 @@ int tpnet_wshard_run(tpnet_wshard* w, void* comm, float* out_pos, float* out_neg
 /* measurement aid (tpnet_dev.h): tpnet_wshard_run with HIP events on `stream` around every step's launch and around its pack +
  * exchange + unpack; one synchronise at the end.  launch_ms_out / exchange_ms_out: averages per step. */
 int tpnet_time_wshard_run(tpnet_wshard* w, void* comm, float* out_pos, float* out_neg, uint32_t launch_id, void* stream,
-                          float* total_ms_out, float* launch_ms_out, float* exchange_ms_out) {
+                          float* total_ms_out, float* launch_ms_out, float* exchange_ms_out) try {
     if (!w) return TPNET_ERR_BAD_ARG;
     if (w->G > 1 && !comm) return TPNET_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)w->nsteps;
-    std::vector<hipEvent_t> ev(3 * n + 1);
-    for (auto& e : ev) TPNET_HIP_TRY(hipEventCreate(&e));
+    EventSet ev(3 * n + 1);
+    TPNET_HIP_TRY(ev.error());
     (void)hipEventRecord(ev[3 * n], s);
     int rc = tpnet_wshard_begin(w, comm, WS_PH_PACK | WS_PH_EXCHANGE, stream);
     for (size_t j = 0; j < n && rc == TPNET_OK; ++j) {
@@ -765,8 +760,7 @@ int tpnet_time_wshard_run(tpnet_wshard* w, void* comm, float* out_pos, float* ou
         if (launch_ms_out) *launch_ms_out = (float)(la / (double)n);
         if (exchange_ms_out) *exchange_ms_out = (float)(xc / (double)n);
     }
-    for (auto& e : ev) (void)hipEventDestroy(e);
     return rc;
-}
+} TPNET_CATCH_BAD_ALLOC
 
 }  // extern "C"

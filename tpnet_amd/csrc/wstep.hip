@@ -981,7 +981,7 @@ __global__ __launch_bounds__(WB) void k_wwriteback(tpnet_state S, WPlan P, int64
     }
 }
 
-int launch_wwriteback(const tpnet_state& st, const WPlan& p, int64_t Ec, uint32_t launch_id, hipStream_t s) {
+int launch_wwriteback(const tpnet_state& st, const WPlan& p, int64_t Ec, int64_t, uint32_t launch_id, hipStream_t s, int64_t) {
     const int64_t nc = 2 * Ec;
     int64_t grid = (nc + WBS - 1) / WBS;
     if (grid > 16384) grid = 16384;
