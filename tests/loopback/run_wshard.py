@@ -105,7 +105,7 @@ def run_copy(runs, D, B, lib):
         _lib.check(lib.tpnet_wshard_finish(plans[r]["handle"], runs[r].rp._next_launch_ids(1), runs[r].rp._stream()), "finish")
         lib.tpnet_wshard_destroy(plans[r]["handle"])
         rp = runs[r].rp
-        rp._now_host = float(dt[-1].item()); rp._params_valid = False; rp._now_dirty = True; rp._table_written()
+        rp._advanced(float(dt[-1].item()))
     torch.cuda.synchronize()
     return outs, moved, plans[0]["nsteps"]
 

@@ -1339,7 +1339,7 @@ def test_every_optional_pointer_null_on_both_schedules(d, L, N, B, nb, schedule)
         rc = lib.tpnet_run_stream_tagged(*args, C.byref(tag) if tagged else None) if tagged is not None else lib.tpnet_run_stream(*args)
         if rc == 0:
             torch.cuda.synchronize()
-            rp._now_host = float(t[-1]); rp._params_valid = False; rp._now_dirty = True; rp._table_written()
+            rp._advanced(float(t[-1]))
             if t_out:
                 assert tv.value == float(t[-1])
             rp.check_device_errors()

@@ -1,0 +1,244 @@
+#!/usr/bin/env python3
+"""Developer tool: a census of the module's routes.  One call per case through PUBLIC methods only, seeded inputs, every result
+saved with np.save under the directory given as the first argument (default: feature_paths_out); a case that raises saves the
+exception's type and text instead.  Two trees compute the same thing by the same kernels if their directories compare equal
+file by file (`cmp`): the paths differ in summation order, so equal bytes pin the route.  With rocprofv3 --kernel-trace --stats
+around it, the kernel names and call counts close the gap.
+
+    python tools/feature_paths.py OUT_DIR
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tpnet_amd
+from tpnet_amd.matrix_memory import MatrixMemory
+from tpnet_amd.sampler import GpuRecentNeighborSampler
+
+OUT = sys.argv[1] if len(sys.argv) > 1 else "feature_paths_out"
+os.makedirs(OUT, exist_ok=True)
+DEV = "cuda:0"
+N = 5000
+SAVED = []
+
+
+def save(name, val):
+    if isinstance(val, torch.Tensor):
+        val = val.detach().cpu().numpy()
+    if isinstance(val, (tuple, list)):
+        for i, v in enumerate(val):
+            save(f"{name}.{i}", v)
+        return
+    np.save(os.path.join(OUT, name + ".npy"), np.asarray(val))
+    SAVED.append(name)
+
+
+def case(name, fn):
+    try:
+        val = fn()
+    except Exception as e:                              # the cases that must raise: type and text are the result
+        val = np.array([type(e).__name__, str(e)])
+    torch.cuda.synchronize()
+    save(name, val)
+
+
+def make(d, L=3, n_nodes=N, seed=0, batches=3, **kw):
+    """A module with a few batches of history (so that layers 1..L are not zero)."""
+    torch.manual_seed(seed)
+    args = dict(node_num=n_nodes, edge_num=40000, dim_factor=10, num_layer=L, time_decay_weight=1e-6, device=DEV, use_matrix=False,
+                beginning_time=np.float64(0.0), not_scale=False, enforce_dim=d)
+    args.update(kw)
+    rp = tpnet_amd.RandomProjectionModule(**args).to(DEV)
+    rng = np.random.RandomState(seed + 1)
+    t0 = 0.0
+    for _ in range(batches):
+        t = np.sort(rng.uniform(t0, t0 + 1e5, 300))
+        rp.update(rng.randint(0, n_nodes, 300), rng.randint(0, n_nodes, 300), t)
+        t0 = t[-1]
+    return rp
+
+
+def with_grads(rp, fn):
+    """fn() with gradients recorded: (out, the four weight gradients of self.mlp after out.sum().backward())."""
+    rp.mlp.zero_grad(set_to_none=True)
+    out = fn()
+    out.sum().backward()
+    return [out] + [p.grad for p in rp.mlp.parameters()]
+
+
+def ids(rng, n, n_nodes=N):
+    return rng.randint(0, n_nodes, n).astype(np.int64)
+
+
+def encoder_call(rng, rows, K, n_nodes=N, repeated=True):
+    """The reference encoder's arrays: src = tile(neighbours, 2), dst = concat(repeat(a1, K), repeat(a2, K))."""
+    neigh = ids(rng, rows * K, n_nodes)
+    if repeated:
+        v = np.concatenate([np.repeat(ids(rng, rows, n_nodes), K), np.repeat(ids(rng, rows, n_nodes), K)])
+    else:
+        v = ids(rng, 2 * rows * K, n_nodes)
+    return np.tile(neigh, 2), v
+
+
+def dev(x, dt=torch.int64):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV, dt)
+
+
+def main():
+    rng = np.random.RandomState(7)
+    # ---- the decoder's calls from host arrays -----------------------------------------------------------------------------
+    rp128 = make(128)
+    for n in (200, 1000):
+        u, v = ids(rng, n), ids(rng, n)
+        with torch.no_grad():
+            case(f"decoder_n{n}_nograd", lambda: rp128.get_pair_wise_feature(u, v))
+        case(f"decoder_n{n}_grad", lambda: with_grads(rp128, lambda: rp128.get_pair_wise_feature(u, v)))
+    # ---- around the staging ring's and the one-launch kernel's limits (16 386 = the ring's 16 384 pairs + 2) ---------------
+    rp172 = make(172)
+    for rp, d in ((rp128, 128), (rp172, 172)):
+        for n in (8192, 8194, 16384, 16386):
+            half = ids(rng, n // 2)
+            v = ids(rng, n)
+            w = ids(rng, n)
+            with torch.no_grad():
+                case(f"d{d}_n{n}_tiled", lambda: rp.get_pair_wise_feature(np.tile(half, 2), v))
+                case(f"d{d}_n{n}_plain", lambda: rp.get_pair_wise_feature(w, v))
+    # ---- the encoder's tile / repeat call, 80 000 pairs --------------------------------------------------------------------
+    K = 20
+    u, v = encoder_call(rng, 2000, K)
+    mods = {128: rp128, 172: rp172}
+    for d in (64, 128, 140, 172, 256, 512):
+        rp = mods.get(d) or make(d)
+        mods[d] = rp
+        with torch.no_grad():
+            case(f"encoder_d{d}_nograd", lambda: rp.get_pair_wise_feature(u, v))
+        case(f"encoder_d{d}_grad", lambda: with_grads(rp, lambda: rp.get_pair_wise_feature(u, v)))
+    rp_l2 = make(172, L=2)
+    with torch.no_grad():
+        case("encoder_d172_L2_nograd", lambda: rp_l2.get_pair_wise_feature(u, v))
+    case("encoder_d172_L2_grad", lambda: with_grads(rp_l2, lambda: rp_l2.get_pair_wise_feature(u, v)))
+    u2, v2 = encoder_call(rng, 2000, K, repeated=False)
+    w2 = ids(rng, 80000)
+    with torch.no_grad():
+        case("tiled_not_repeated_d172", lambda: rp172.get_pair_wise_feature(u2, v2))
+        case("not_tiled_d172", lambda: rp172.get_pair_wise_feature(w2, v2))
+        case("not_tiled_d128", lambda: rp128.get_pair_wise_feature(w2, v2))
+    case("not_tiled_d172_grad", lambda: with_grads(rp172, lambda: rp172.get_pair_wise_feature(w2, v2)))
+    # ---- kinds of ids -----------------------------------------------------------------------------------------------------
+    a, b = ids(rng, 500), ids(rng, 500)
+    with torch.no_grad():
+        case("src_device", lambda: rp128.get_pair_wise_feature(dev(a), dev(b)))
+        case("src_device_dst_host", lambda: rp128.get_pair_wise_feature(dev(a), b))
+        case("dst_device", lambda: rp128.get_pair_wise_feature(a, dev(b)))
+        case("dst_device_d172_tiled", lambda: rp172.get_pair_wise_feature(np.tile(a, 2), dev(np.tile(b, 2))))
+        case("ids_int32", lambda: rp128.get_pair_wise_feature(a.astype(np.int32), b.astype(np.int32)))
+        case("ids_list", lambda: rp128.get_pair_wise_feature(a.tolist(), b.tolist()))
+        case("ids_strided", lambda: rp128.get_pair_wise_feature(np.tile(a, 2)[::2], np.tile(b, 2)[::2]))
+        case("ids_negative", lambda: rp128.get_pair_wise_feature(a - N, b))
+        case("ids_negative_long", lambda: rp128.get_pair_wise_feature(np.tile(a - N, 40), np.tile(b, 40)))
+        case("ids_negative_pair_gram", lambda: rp128.pair_gram(a - N, b - N))
+        case("ids_out_of_range", lambda: rp128.get_pair_wise_feature(np.where(a == a[3], N, a), b))
+        case("ids_below_minus_n", lambda: rp128.get_pair_wise_feature(np.where(a == a[3], -N - 1, a), b))
+        case("ids_2d", lambda: rp128.get_pair_wise_feature(a.reshape(2, -1), b.reshape(2, -1)))
+        case("ids_length_mismatch", lambda: rp128.get_pair_wise_feature(a, b[:-1]))
+        case("ids_empty", lambda: rp128.get_pair_wise_feature(a[:0], b[:0]))
+    # ---- self.mlp variants ------------------------------------------------------------------------------------------------
+    for d in (128, 256):
+        rp = make(d, seed=3)
+        rp.fused_mlp = True
+        with torch.no_grad():
+            case(f"fused_mlp_d{d}_short", lambda: rp.get_pair_wise_feature(a, b))
+            case(f"fused_mlp_d{d}_encoder", lambda: rp.get_pair_wise_feature(u, v))
+        case(f"fused_mlp_d{d}_short_grad", lambda: with_grads(rp, lambda: rp.get_pair_wise_feature(a, b)))
+    rp_id = make(128, seed=4)
+    rp_id.mlp = nn.Identity()
+    with torch.no_grad():
+        case("mlp_identity_short", lambda: rp_id.get_pair_wise_feature(a, b))
+        case("mlp_identity_encoder", lambda: rp_id.get_pair_wise_feature(u, v))
+    rp_m = make(0, n_nodes=64, use_matrix=True, enforce_dim=-1)
+    am, bm = ids(rng, 100, 64), ids(rng, 100, 64)
+    with torch.no_grad():
+        case("use_matrix", lambda: rp_m.get_pair_wise_feature(am, bm))
+        case("use_matrix_rows", lambda: rp_m.get_random_projections(am))
+    # ---- the readouts before self.mlp -------------------------------------------------------------------------------------
+    big_a, big_b = ids(rng, 20000), ids(rng, 20000)
+    neigh = ids(rng, 50 * K).reshape(50, K)
+    a1, a2 = ids(rng, 50), ids(rng, 50)
+    with torch.no_grad():
+        for tag, kw in (("plain", {}), ("raw", dict(raw=True)), ("packed", dict(packed=True))):
+            case(f"pair_gram_{tag}", lambda: rp128.pair_gram(a, b, **kw))
+            case(f"pair_gram_{tag}_long", lambda: rp128.pair_gram(big_a, big_b, **kw))
+        case("pair_gram_device", lambda: rp128.pair_gram(dev(a), dev(b)))
+        case("pair_gram_shared", lambda: rp172.pair_gram_shared(a, b, ids(np.random.RandomState(9), 500)))
+        case("feature_shared", lambda: rp172.get_pair_wise_feature_shared(a, b, ids(np.random.RandomState(9), 500)))
+        case("pair_gram_anchored", lambda: rp128.pair_gram_anchored(neigh, a1, a2))
+        case("pair_gram_anchored_no_mfma", lambda: rp128.pair_gram_anchored(neigh, a1, a2, matrix_cores=False))
+        case("pair_gram_anchored_d172", lambda: rp172.pair_gram_anchored(dev(neigh), a1, a2))
+        case("feature_anchored_device", lambda: rp128.get_pair_wise_feature_anchored(dev(neigh), dev(a1), dev(a2)))
+        case("feature_anchored_device_d172", lambda: rp172.get_pair_wise_feature_anchored(dev(neigh), a1, a2))
+        case("feature_anchored_host", lambda: rp128.get_pair_wise_feature_anchored(neigh, a1, a2))
+    case("feature_anchored_device_grad",
+         lambda: with_grads(rp128, lambda: rp128.get_pair_wise_feature_anchored(dev(neigh), dev(a1), dev(a2))))
+    # ---- the encoder's whole readout with the device-side sampler ----------------------------------------------------------
+    E = 30000
+    es, ed, et = ids(rng, E), ids(rng, E), np.sort(rng.uniform(0, 2e5, E))
+    sampler = GpuRecentNeighborSampler(es, ed, et, device=DEV, num_nodes=N)
+    for rp, d in ((rp128, 128), (rp172, 172), (rp_l2, "172_L2")):
+        for B, Kq in ((200, 20), (11000, 4)):              # (11 000: above the staging ring's largest host batch)
+            s, o, tq = es[-B:], ed[-B:], et[-B:] + 1.0
+            with torch.no_grad():
+                case(f"encoder_features_d{d}_B{B}_host", lambda: rp.encoder_pair_features(sampler, s, o, tq, Kq))
+                case(f"encoder_features_d{d}_B{B}_device",
+                     lambda: rp.encoder_pair_features(sampler, dev(s), dev(o), dev(tq, torch.float64), Kq))
+    sB, oB, tB = es[-200:], ed[-200:], et[-200:] + 1.0
+    case("encoder_features_grad", lambda: with_grads(rp128, lambda: rp128.encoder_pair_features(sampler, sB, oB, tB, 20)[0]))
+    case("encoder_features_bad_length", lambda: rp128.encoder_pair_features(sampler, sB, oB[:-1], tB, 20))
+    # ---- update -----------------------------------------------------------------------------------------------------------
+    for exact in (False, True):
+        rp = make(128, seed=5, exact=exact)
+        tag = "exact" if exact else "lazy"
+        t0 = 4e5
+        for B in (200, 2049, 20000):                        # (one workgroup's plan / staged + chunk planner / device copies)
+            tt = np.sort(rng.uniform(t0, t0 + 1e4, B))
+            t0 = tt[-1]
+            uu, vv = ids(rng, B), ids(rng, B)
+            case(f"update_{tag}_B{B}", lambda: (rp.update(uu, vv, tt), rp.get_random_projections(a))[1])
+        tt = np.sort(rng.uniform(t0, t0 + 1e4, 200))
+        t0 = tt[-1]
+        case(f"update_{tag}_device", lambda: (rp.update(dev(a[:200]), dev(b[:200]), tt), rp.get_random_projections(b))[1])
+        case(f"update_{tag}_negative", lambda: (rp.update(a[:200] - N, b[:200].tolist(), tt + 1e4), rp.get_random_projections(b))[1])
+        t0 += 1e4
+        before = rp.backup_random_projections()
+        bad = a[:200].copy()
+        bad[17] = N
+        case(f"update_{tag}_out_of_range", lambda: rp.update(bad, b[:200], tt + 2e4))
+        case(f"update_{tag}_out_of_range_dst", lambda: rp.update(b[:200], bad - 2 * N - 1, tt + 2e4))
+        case(f"update_{tag}_empty", lambda: rp.update(a[:0], b[:0], tt[:0]))
+        case(f"update_{tag}_length_mismatch", lambda: rp.update(a[:200], b[:199], tt))
+        after = rp.backup_random_projections()
+        save(f"update_{tag}_state_before", [before[0]] + before[1])
+        save(f"update_{tag}_state_after", [after[0]] + after[1])
+        case(f"update_{tag}_rows", lambda: rp.get_random_projections(np.arange(0, N, 7)))
+        case(f"update_{tag}_rows_list", lambda: rp.get_random_projections([1, 2, -3]))
+        case(f"update_{tag}_now_time", lambda: rp.now_time.detach().clone())
+        with torch.no_grad():
+            case(f"update_{tag}_feature", lambda: rp.get_pair_wise_feature(a, b))
+    # ---- MatrixMemory -----------------------------------------------------------------------------------------------------
+    mm = MatrixMemory(num_node=60, num_hop=2, device=DEV).to(DEV)
+    for k in range(3):
+        mm.update(ids(rng, 40, 60), ids(rng, 40, 60))
+    case("matrix_memory_get", lambda: mm.get_memory(ids(np.random.RandomState(11), 80, 60), ids(np.random.RandomState(12), 80, 60)))
+    case("matrix_memory_backup", lambda: mm.backup_memory())
+    case("matrix_memory_out_of_range", lambda: mm.update(np.array([1, 60]), np.array([2, 3])))
+    case("matrix_memory_after", lambda: mm.backup_memory())
+    with open(os.path.join(OUT, "cases.txt"), "w") as f:
+        f.write("\n".join(SAVED) + "\n")
+    print(f"{len(SAVED)} files in {OUT}")
+
+
+if __name__ == "__main__":
+    main()

@@ -40,9 +40,8 @@ T("_lib.fast", _lib.fast)
 T("_raw_stream", lambda: R._raw_stream(rp._eng["dev_index"]))
 T("6 data_ptr", lambda: (s_.data_ptr(), d_.data_ptr(), n_.data_ptr(), t_.data_ptr(), o_p.data_ptr(), o_n.data_ptr()))
 T("float(twd)", lambda: float(rp.time_decay_weight))
-T("_table_written", rp._table_written)
-def sets():
-    rp.last_stream_replayed = False; rp._now_host = 1.0; rp._params_valid = False; rp._now_dirty = True
-T("4 setattr", sets)
+def epilogue():
+    rp.last_stream_replayed = False; rp._advanced(1.0)
+T("epilogue (_advanced)", epilogue)
 T("slice x6 + float", lambda: (s_[0:E], d_[0:E], n_[0:E], t_[0:E], o_p[:E], o_n[:E], float(t[E - 1])))
 T("c_double", lambda: C.c_double(0.0))

@@ -97,7 +97,7 @@ def run(G, reps=4):
         for r in range(G):
             lib.tpnet_wshard_destroy(plans[r]["handle"])
             rp = runs[r].rp
-            rp._now_host = float(t[-1]); rp._params_valid = False; rp._now_dirty = True; rp._table_written()
+            rp._advanced(float(t[-1]))
         if rep >= 1:
             res.append((np.max(plan_us), k_us.sum(axis=1).max(), x_us.sum(axis=1).max(), nst, sent.max(), halo.max(), k_us.max(axis=0)))
     med = lambda i: float(np.median([x[i] for x in res]))

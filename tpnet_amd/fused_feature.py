@@ -7,13 +7,27 @@ layers' gradients (the projections carry no gradient: requires_grad=False in the
 Differs from the torch layers in f32 summation order only, so it is the DEFAULT for the decoder's short pair lists."""
 import ctypes as C
 import os
+import warnings
 import weakref
+from typing import NamedTuple
 
 import torch
 
 from . import _lib
 
-_PREPARED = weakref.WeakKeyDictionary()     # mlp module -> cache entry (kept off the module: ctypes objects do not deepcopy)
+_PREPARED = weakref.WeakKeyDictionary()     # mlp module -> Prepared (kept off the module: ctypes objects do not deepcopy)
+
+
+class Prepared(NamedTuple):
+    """What prepared() returns: self.mlp's weights in the layouts the kernels read."""
+    key: tuple          # (data_ptr, _version) of w1, b1, w2, b2 when the derived buffers were last written
+    st: object          # the tpnet_mlp struct (_lib.Mlp)
+    ref: object         # its byref: what the C calls take
+    derived: tuple      # (w1t, w2t, w2f or None, weight image or None): the buffers the struct points into
+    params: tuple       # the Parameters (w1, b1, w2, b2)
+    storage: tuple      # their data_ptr()s: the same storage keeps the derived buffers and the struct
+
+
 # longer lists: the readout kernels + the dense layers as GEMMs (torch, or the bf16 kernel if opted in)
 MAX_PAIRS = int(os.environ.get("TPNET_DEV_FUSED_MAX_PAIRS", "8192"))
 
@@ -73,15 +87,15 @@ def weight_grads_f32(x, gy, w1, b1, w2, prep, mode=None):
     mode: "mfma" | "torch" (None: the module-level `mlp_backward`)."""
     mode = mode or mlp_backward
     n = int(x.shape[0])
-    if (mode == "mfma" and prep is not None and x.is_cuda and n >= MFMA_BWD_FROM and x.dtype == torch.float32 and prep[1].w1 and prep[1].w2t
-            and prep[0][:6] == (w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version)):
+    if (mode == "mfma" and prep is not None and x.is_cuda and n >= MFMA_BWD_FROM and x.dtype == torch.float32 and prep.st.w1 and prep.st.w2t
+            and prep.key[:6] == (w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version)):
         lib = _lib.load()
         x = x.contiguous()
         gy = gy.contiguous().float()
         pf = int(lib.tpnet_mlp64_bwd_partial_floats())
         nblk = min(256, (n + 31) // 32)
         part = torch.empty((nblk, pf), dtype=torch.float32, device=x.device)
-        rc = lib.tpnet_mlp64_bwd_f32(x.data_ptr(), gy.data_ptr(), n, prep[2], part.data_ptr(), nblk,
+        rc = lib.tpnet_mlp64_bwd_f32(x.data_ptr(), gy.data_ptr(), n, prep.ref, part.data_ptr(), nblk,
                                      C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
         if rc > 0:
             tot = part[:rc].sum(0)
@@ -89,7 +103,6 @@ def weight_grads_f32(x, gy, w1, b1, w2, prep, mode=None):
             return tot[:H * F].view(H, F), tot[2 * H * F:2 * H * F + H], tot[H * F:2 * H * F].view(F, H), gy.sum(0)
         if rc not in _declined_once:                    # (said once per code: the torch expressions below serve the call)
             _declined_once.add(rc)
-            import warnings
             warnings.warn(f"tpnet_mlp64_bwd_f32 declined a call of {n} rows (rc {rc}): weight gradients by the fp32 torch expressions")
     pre = torch.addmm(b1, x, w1.t())                 # fp32 recompute of the hidden layer
     hid = torch.relu(pre)
@@ -131,11 +144,11 @@ def mlp_f32(mlp, x):
     if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.shape[1] != 64:
         return None
     prep = prepared(mlp, 64)
-    if prep is None or not prep[1].w1:
+    if prep is None or not prep.st.w1:
         return None
-    if needs_grad(prep[4]):
-        return _MlpF32.apply(x, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, prep[2], prep, getattr(mlp, "mlp_backward", None))
-    return _MlpF32.forward(_NoCtx(), x, None, None, None, None, prep[2])
+    if needs_grad(prep.params):
+        return _MlpF32.apply(x, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, prep.ref, prep, getattr(mlp, "mlp_backward", None))
+    return _MlpF32.forward(_NoCtx(), x, None, None, None, None, prep.ref)
 
 
 class _NoCtx:
@@ -155,7 +168,7 @@ def invalidate(mlp=None):
 
 
 def prepared(mlp, F):
-    """(key, tpnet_mlp struct, its byref, keep-alive tensors) or None if `mlp` is not the reference's Linear-ReLU-Linear on
+    """A Prepared record, or None if `mlp` is not the reference's Linear-ReLU-Linear on
     a GPU: transposed f32 copies of the weights, rebuilt only when a parameter changed (optimizer step, load_state_dict,
     .to()): keyed on (data_ptr, _version) of the four tensors.
     CONTRACT: the Parameters are updated through versioned ops (optimizer steps, copy_(), load_state_dict, .to()).  b1, b2 and
@@ -173,15 +186,15 @@ def prepared(mlp, F):
         return None
     key = (w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version, b2.data_ptr(), b2._version)
     cache = _PREPARED.get(mlp)
-    if cache is None or cache[0] != key:
+    if cache is None or cache.key != key:
         if not supported(mlp, F) or not (w1.is_contiguous() and w2.is_contiguous() and b1.is_contiguous() and b2.is_contiguous()):
             return None
         # the derived layouts (w1t, w2t and, for F = 64, the gathered w2f) live in buffers that stay with the module and are
         # rewritten by ONE launch (tpnet_mlp_prepare) when a parameter changed; b1, b2 and tpnet_mlp::w1 are the Parameters' own
         # storage.  (As torch expressions -- two transposes, a copy, an index gather -- this was ~100 us of every training step.)
-        same_store = cache is not None and cache[5] == (w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr())
-        if same_store:
-            keep, st = cache[3], cache[1]
+        storage = (w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr())
+        if cache is not None and cache.storage == storage:
+            keep, st = cache.derived, cache.st
         else:
             H = w1.shape[0]
             x64 = F == 64 and H == 256
@@ -199,7 +212,7 @@ def prepared(mlp, F):
         if keep[3] is not None:
             _lib.check(_lib.load().tpnet_mlp_prepare_image(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), keep[3].data_ptr(),
                                                            C.c_void_p(torch.cuda.current_stream(w1.device).cuda_stream)), "mlp_prepare_image")
-        cache = (key, st, C.byref(st), keep, (w1, b1, w2, b2), (w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()))
+        cache = Prepared(key, st, C.byref(st), keep, (w1, b1, w2, b2), storage)
         _PREPARED[mlp] = cache
     return cache
 

@@ -138,7 +138,7 @@ def fused_readout_mlp(rp, u_dev: torch.Tensor, v_dev: torch.Tensor) -> torch.Ten
     w1b, b1c, w2p, b2c = prep[:4]
     n = int(u_dev.numel())
     lib = _lib.load()
-    flags = _lib.FLAG_NOT_SCALE if rp.not_scale else 0
+    flags = rp._readout_flags()
 
     def launch(gram):
         y = torch.empty((n, F), dtype=torch.float32, device=u_dev.device)

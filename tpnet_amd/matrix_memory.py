@@ -135,7 +135,7 @@ class MatrixMemory(nn.Module):
         self._ensure_engine()
         rp = self.__dict__["_rp"]
         rp._ensure_engine()
-        u, v = rp._to_device(rp._check_ids(src_node_ids, "src_node_ids"), rp._check_ids(dst_node_ids, "dst_node_ids"))
+        u, v = rp._to_device(rp._ids(src_node_ids, "src_node_ids"), rp._ids(dst_node_ids, "dst_node_ids"))
         n = u.numel()
         out = torch.empty((n, self.num_hop + 1), dtype=torch.float32, device=rp._dev())
         st = rp._state()
@@ -173,10 +173,5 @@ def _bare_table(rp: RandomProjectionModule, N: int, H: int, device):
         [nn.Parameter(torch.zeros((1, 1), device=device), requires_grad=False) for _ in range(H + 1)])
     rp.pair_wise_feature_dim = (2 * H + 2) ** 2
     rp.mlp = nn.Identity()
-    rp._eng = None
-    rp._engine_valid = False
-    rp._params_valid = True
-    rp._param_sig = None
-    rp._now_host = 0.0
-    rp._launch_id = 1
+    rp._init_engine_side(0.0)
     rp.to(device)

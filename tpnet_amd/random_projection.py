@@ -14,10 +14,14 @@ How the state is held:
     (attribute access, state_dict(), backup, .to()), and imported back when somebody writes them
     (reload, load_state_dict, .to(), direct `.data` assignment -- detected through data_ptr/_version).
 """
+import copy
 import ctypes as C
+import functools
 import itertools
 import math
+import struct
 import weakref
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -25,11 +29,9 @@ import torch.nn as nn
 
 from . import _lib
 from . import fused_feature as _ff
+from . import fused_mlp as _fm
 
 _MAX_LAUNCH_ID = 0x7FFFFFFF - (1 << 24)
-
-
-# the current stream's raw handle without building a torch.cuda.Stream object (the hot methods need it every call)
 _BIG_SLOT_BYTES = 1 << 20      # one encoder call from host arrays: up to 100 000 neighbour ids + their anchors
 # where the per-batch staging ring of the host-array calls lives (tpnet_stage_create_ex): -1 = device memory written through the
 # large BAR where the device has one (the kernels' first loads are local: ~1.5 us less at the head of each of a batch's three
@@ -41,6 +43,7 @@ def _ptr_or_null(t):
     return t.data_ptr() if t is not None else None
 
 
+# the current stream's raw handle without building a torch.cuda.Stream object (the hot methods need it every call)
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i: torch.cuda.current_stream(i).cuda_stream)
 
 
@@ -96,6 +99,33 @@ class _LazyLayers(nn.ParameterList):
         return super().__iter__()
 
 
+class _StateRef(NamedTuple):
+    """The cached tpnet_state struct of a module (_st_ref) and what it was built from."""
+    p0: int             # data_ptr of P[0] when the struct was built
+    eng: dict           # the engine buffers it points into
+    st: object          # the struct (_lib.State)
+    ref: object         # its byref: what the ctypes calls take
+    addr: int           # its address: what the C extension's calls take
+
+
+def _pack8(buf, arrays):
+    """Lay host arrays of 8-byte items (int64 ids, float64 times; any lengths) end to end into `buf`, an int64 host tensor."""
+    hv, o = buf.numpy(), 0
+    for a in arrays:
+        hv[o:o + a.size] = a.reshape(-1).view(np.int64)
+        o += a.size
+
+
+def _unpack8(buf, arrays):
+    """One view of `buf` (_pack8's layout, on any device) per array, with the array's length and item type."""
+    res, o = [], 0
+    for a in arrays:
+        v = buf[o:o + a.size]
+        res.append(v if a.dtype == np.int64 else v.view(torch.float64))
+        o += a.size
+    return res
+
+
 class _Stage:
     """The pinned, device-mapped staging ring of the host-array entry points (tpnet_stage_*): 8 slots of 256 KB, i.e. up to
     16 384 pairs or one batch of up to 2 048 edges per call.  The only thing the C library allocates; freed with the engine."""
@@ -138,13 +168,9 @@ class PreparedStream:
 
 
 class RandomProjectionModule(nn.Module):
-    # plan-replay bookkeeping (class-level defaults: tpnet_amd/matrix_memory.py builds instances without this constructor)
-    _table_sig = 0
     # bound on the windowed schedule's version log per chunk when run_stream sizes its workspace (None: the library's 16 GiB); a
     # workspace that is already larger keeps its chunk length -- the C side takes the longest chunk the workspace holds
     stream_log_cap_bytes = None
-    _sig_counter = 1
-    _plan_tag = None
 
     def __init__(self, node_num: int, edge_num: int, dim_factor: int, num_layer: int, time_decay_weight: float,
                  device: str, use_matrix: bool, beginning_time: np.float64, not_scale: bool, enforce_dim: int,
@@ -196,22 +222,27 @@ class RandomProjectionModule(nn.Module):
         self.pair_wise_feature_dim = (2 * self.num_layer + 2) ** 2
         self.mlp = nn.Sequential(nn.Linear(self.pair_wise_feature_dim, self.pair_wise_feature_dim * 4), nn.ReLU(),
                                  nn.Linear(self.pair_wise_feature_dim * 4, self.pair_wise_feature_dim))
-        # ---- engine side (plain attributes: not parameters/buffers, so the state-dict keys match the reference)
-        self._eng = None                      # dict of device tensors, allocated on first use
-        self._engine_valid = False            # engine holds the truth for layers 1..L
-        self._params_valid = True             # the Parameters hold the truth for layers 1..L
-        self._param_sig = None                # (data_ptr, _version) of the layer Parameters at the last sync
-        self._now_host = float(beginning_time)
-        self._launch_id = 1
-        self._now_dirty = False
-        self._params_exposed = False          # the ParameterList was handed out since the last import (see __getattr__)
-        self._table_sig = 0                   # identifies the table's per-node (copy, reference time) state (plan replay)
-        self._sig_counter = 1
-        self._plan_tag = None                 # _lib.PlanTag of the plan the stream workspace holds
+        self._init_engine_side(beginning_time)
 
     # ------------------------------------------------------------------------------------------------------
     # plumbing
     # ------------------------------------------------------------------------------------------------------
+    def _init_engine_side(self, now):
+        """The engine-side fields of a new instance (plain attributes: not parameters / buffers, so the state-dict keys match the
+        reference); whoever builds an instance without the constructor (matrix_memory._bare_table) calls this."""
+        self.__dict__.update(
+            _eng=None,                        # dict of device tensors, allocated on first use
+            _engine_valid=False,              # engine holds the truth for layers 1..L
+            _params_valid=True,               # the Parameters hold the truth for layers 1..L
+            _param_sig=None,                  # (data_ptr, _version) of the layer Parameters at the last sync
+            _now_host=float(now),
+            _launch_id=1,
+            _now_dirty=False,
+            _params_exposed=False,            # the ParameterList was handed out since the last import (see __getattr__)
+            _table_sig=0,                     # identifies the table's per-node (copy, reference time) state (plan replay)
+            _sig_counter=1,
+            _plan_tag=None)                   # _lib.PlanTag of the plan the stream workspace holds
+
     def _plist(self):
         # the Parameter OBJECTS of the list are stable (`.data = ...`, `.to()`, load_state_dict keep them), so they are
         # looked up once: nn.ParameterList.__getitem__ costs microseconds and the hot methods need them every call
@@ -242,8 +273,8 @@ class RandomProjectionModule(nn.Module):
                 _OWNERS[id(self)] = self
             else:                                    # (a plain list put there by somebody else: the eager behaviour)
                 self._layers_read()
-        elif name == "now_time" and self.__dict__.get("_now_dirty", False):
-            self._sync_now_time()
+        elif name == "now_time" and self.__dict__.get("_now_dirty", False):     # (.get: nn.Module.__init__ and the constructor
+            self._sync_now_time()                                               #  read attributes before _init_engine_side has run)
         return super().__getattr__(name)
 
     def _layers_read(self):
@@ -307,25 +338,39 @@ class RandomProjectionModule(nn.Module):
         """byref of the tpnet_state struct, rebuilt only when P[0]'s storage or the engine buffers changed."""
         ptr = self._plist()[0].data_ptr()
         c = self.__dict__.get("_st_cache")
-        if c is None or c[0] != ptr or c[1] is not self._eng:
+        if c is None or c.p0 != ptr or c.eng is not self._eng:
             st = self._state()
-            c = (ptr, self._eng, st, C.byref(st), C.addressof(st))
-            self.__dict__["_st_cache"] = c
-        return c[3]
+            c = self.__dict__["_st_cache"] = _StateRef(ptr, self._eng, st, C.byref(st), C.addressof(st))
+        return c.ref
 
-    @staticmethod
-    def _host_ids(ids, what):
-        """Host ids as a contiguous one-dimensional int64 numpy array (no copy when they already are: the reference's callers
-        pass exactly that), or None for a torch tensor.  The range check happens in the C call that stages them."""
+    def _ids(self, ids, what, staged=False):
+        """Node ids in the form a call needs.  `staged` (the C calls that stage host ids themselves, and check their range and wrap
+        negative ones while they do): a contiguous one-dimensional int64 numpy array (no copy when they already are: the
+        reference's callers pass exactly that), or None for a torch tensor.  Otherwise, for upload (_to_device): a device tensor
+        as it is -- an extension: ids already on the device (e.g. from the device-side sampler) are used in place, the kernels
+        check the range themselves (bad ids are skipped, counted, and give NaN features) -- or the host array with its range
+        checked and python-style negative ids wrapped, as ATen indexing does."""
         if type(ids) is not np.ndarray:
             if isinstance(ids, torch.Tensor):
-                return None
+                if staged:
+                    return None
+                if ids.is_cuda:
+                    if ids.dtype != torch.int64 or ids.dim() != 1:
+                        raise ValueError(f"{what}: device ids must be a one-dimensional int64 tensor")
+                    return ids.contiguous()
             ids = np.asarray(ids)
         if ids.dtype != np.int64 or not ids.flags.c_contiguous:
             ids = np.ascontiguousarray(ids, dtype=np.int64)
         if ids.ndim != 1:
-            raise ValueError(f"{what} must be one-dimensional")
-        return ids
+            if ids.ndim or staged:
+                raise ValueError(f"{what} must be one-dimensional")
+            ids = ids.reshape(1)                                      # (for upload, a scalar is an array of one id)
+        if staged or not ids.size:
+            return ids
+        lo = ids.min()
+        if lo < -self.node_num or ids.max() >= self.node_num:
+            raise IndexError(f"{what}: index out of range for {self.node_num} nodes")
+        return np.where(ids < 0, ids + self.node_num, ids) if lo < 0 else ids
 
     def _host_readout(self, u, v, n, flags, width, mlp_ref=None, out_gram=None):
         """One FFI call: ids checked + staged on the host, ONE kernel (readout, or readout + self.mlp when mlp_ref)."""
@@ -335,7 +380,7 @@ class RandomProjectionModule(nn.Module):
             fast = _lib.fast()
             if fast is not None:
                 self._st_ref()
-                rc = fast.pair_feature(self.__dict__["_st_cache"][4], eng["stage"].handle.value, u, v, self._now_host,
+                rc = fast.pair_feature(self.__dict__["_st_cache"].addr, eng["stage"].handle.value, u, v, self._now_host,
                                        float(self.time_decay_weight), flags, C.addressof(mlp_ref._obj) if mlp_ref is not None else 0,
                                        out_gram.data_ptr() if out_gram is not None else 0, out.data_ptr(),
                                        _raw_stream(eng["dev_index"]))
@@ -405,16 +450,25 @@ class RandomProjectionModule(nn.Module):
     # plan replay (tpnet_run_stream_tagged): the table signature names the per-node (current copy, reference time) state --
     # uniform (copy 0, one reference time) right after a reset or an import, unique after anything else wrote the state
     def _table_uniform(self, tref: float):
-        import struct
         self._table_sig = (struct.unpack("<Q", struct.pack("<d", float(tref)))[0] ^ 0x9E3779B97F4A7C15) | 1
 
     def _table_written(self):
-        self._sig_counter += 1
-        self._table_sig = (self._sig_counter << 1) & 0x7FFFFFFFFFFFFFFE or 2      # even: never equals a uniform signature
+        d = self.__dict__                                  # (plain stores, as in _advanced: once per update() call)
+        n = d["_sig_counter"] = d["_sig_counter"] + 1
+        d["_table_sig"] = (n << 1) & 0x7FFFFFFFFFFFFFFE or 2                       # even: never equals a uniform signature
+
+    def _advanced(self, now: float):
+        """The table was advanced to `now` by an update or a stream: the clock and the layer Parameters are stale, and no plan made
+        for the earlier per-node state may be replayed.  (Plain stores: not through nn.Module.__setattr__.)"""
+        d = self.__dict__
+        d["_now_host"] = now
+        d["_params_valid"] = False
+        d["_now_dirty"] = True
+        self._table_written()
 
     def _drop_plan(self):
         """The stream workspace is about to be used by something else (or was reallocated): no plan to replay."""
-        tag = self.__dict__.get("_plan_tag")
+        tag = self._plan_tag
         if tag is not None:
             C.memset(C.byref(tag), 0, C.sizeof(tag))
         self.__dict__["_rows_plan_sig"] = None          # (the row-sharded runner's per-batch plan of a stream: tpnet_amd/sharded.py)
@@ -471,86 +525,35 @@ class RandomProjectionModule(nn.Module):
         self._launch_id += n
         return first
 
-    def _check_ids(self, ids, what):
-        if isinstance(ids, torch.Tensor) and ids.is_cuda:
-            # extension: ids already on the device (e.g. from the device-side sampler) are used in place; the kernels
-            # check the range themselves (bad ids are skipped, counted, and give NaN features)
-            if ids.dtype != torch.int64 or ids.dim() != 1:
-                raise ValueError(f"{what}: device ids must be a one-dimensional int64 tensor")
-            return ids.contiguous()
-        ids = np.ascontiguousarray(np.asarray(ids), dtype=np.int64)
-        if ids.ndim != 1:
-            raise ValueError(f"{what} must be one-dimensional")
-        if ids.size and (ids.min() < -self.node_num or ids.max() >= self.node_num):
-            raise IndexError(f"{what}: index out of range for {self.node_num} nodes")
-        if ids.size and ids.min() < 0:
-            ids = np.where(ids < 0, ids + self.node_num, ids)     # python-style negative ids, as ATen indexing
-        return ids
+    def _pin_slot(self, items: int):
+        """The next buffer of the ring of pinned upload buffers, at least `items` int64 long and no longer in use by the copy that
+        last read it: [pinned tensor, event of its last copy]."""
+        ring = self.__dict__.setdefault("_pin_ring", {"bufs": [[None, None] for _ in range(8)], "pos": 0})
+        slot = ring["bufs"][ring["pos"]]
+        ring["pos"] = (ring["pos"] + 1) % len(ring["bufs"])
+        if slot[1] is None:
+            slot[1] = torch.cuda.Event()
+        else:
+            slot[1].synchronize()                                     # the copy that last used this buffer is done
+        if slot[0] is None or slot[0].numel() < items:
+            slot[0] = torch.empty(max(items, 4096), dtype=torch.int64).pin_memory()
+        return slot
 
     def _to_device(self, *arrays):
-        """ONE asynchronous host->device copy for several equally long 8-byte arrays (int64 ids, float64 times)
-        through a small ring of pinned staging buffers.  The reference issues one pageable (blocking) copy per array
-        (TPNet.py:74-77); here the host only memcpy's into pinned memory and moves on."""
+        """ONE asynchronous host->device copy for several host arrays of 8-byte items (int64 ids, float64 times), of any lengths,
+        through a small ring of pinned buffers: a device view per array.  The reference issues one pageable (blocking) copy per
+        array (TPNet.py:74-77); here the host only memcpy's into pinned memory and moves on.  All tensors: returned as they are
+        (already resident); some: those are brought to the host first."""
         if all(isinstance(a, torch.Tensor) for a in arrays):
-            return list(arrays)                                       # already resident
-        if any(isinstance(a, torch.Tensor) for a in arrays):
-            arrays = [a.cpu().numpy() if isinstance(a, torch.Tensor) else a for a in arrays]
-        n = arrays[0].size
-        k = len(arrays)
+            return list(arrays)
+        arrays = [a.cpu().numpy() if isinstance(a, torch.Tensor) else a for a in arrays]
         dev = self._dev()
-        ring = self.__dict__.setdefault("_pin_ring", {"bufs": [], "pos": 0})
-        if not ring["bufs"]:
-            ring["bufs"] = [[None, None] for _ in range(8)]          # [pinned tensor, event of its last copy]
-        slot = ring["bufs"][ring["pos"]]
-        ring["pos"] = (ring["pos"] + 1) % len(ring["bufs"])
-        if slot[1] is not None:
-            slot[1].synchronize()                                     # the copy that last used this buffer is done
-        if slot[0] is None or slot[0].numel() < k * n:
-            slot[0] = torch.empty(max(k * n, 4096), dtype=torch.int64).pin_memory()
-        host = slot[0][: k * n].view(k, n)
-        hv = host.numpy()
-        for i, a in enumerate(arrays):
-            hv[i] = a.view(np.int64)
-        out = host.to(dev, non_blocking=True)
-        if slot[1] is None:
-            slot[1] = torch.cuda.Event()
-        slot[1].record(torch.cuda.current_stream(dev))
-        return [out[i] if arrays[i].dtype == np.int64 else out[i].view(torch.float64) for i in range(k)]
-
-    def _to_device_multi(self, *arrays):
-        """_to_device for host arrays of DIFFERENT lengths (8-byte items): one pinned buffer, one asynchronous copy, a device view
-        per array."""
-        sizes = [int(a.size) for a in arrays]
-        tot = sum(sizes)
-        dev = self._dev()
-        ring = self.__dict__.setdefault("_pin_ring", {"bufs": [], "pos": 0})
-        if not ring["bufs"]:
-            ring["bufs"] = [[None, None] for _ in range(8)]
-        slot = ring["bufs"][ring["pos"]]
-        ring["pos"] = (ring["pos"] + 1) % len(ring["bufs"])
-        if slot[1] is not None:
-            slot[1].synchronize()
-        if slot[0] is None or slot[0].numel() < tot:
-            slot[0] = torch.empty(max(tot, 4096), dtype=torch.int64).pin_memory()
-        host = slot[0][:tot]
-        hv = host.numpy()
-        o = 0
-        for a, k in zip(arrays, sizes):
-            hv[o:o + k] = a.reshape(-1).view(np.int64)
-            o += k
-        out = host.to(dev, non_blocking=True)
-        if slot[1] is None:
-            slot[1] = torch.cuda.Event()
-        slot[1].record(torch.cuda.current_stream(dev))
-        res, o = [], 0
-        for a, k in zip(arrays, sizes):
-            v = out[o:o + k]
-            res.append(v if a.dtype == np.int64 else v.view(torch.float64))
-            o += k
-        return res
-
-    def _ids_to_device(self, ids, what):
-        return self._to_device(self._check_ids(ids, what))[0]
+        tot = sum(a.size for a in arrays)
+        buf, event = self._pin_slot(tot)
+        _pack8(buf[:tot], arrays)
+        out = buf[:tot].to(dev, non_blocking=True)
+        event.record(torch.cuda.current_stream(dev))
+        return _unpack8(out, arrays)
 
     # copy / pickle: the engine buffers, pinned staging ring and cached refs are per-process plumbing, not state ------
     def __getstate__(self):
@@ -569,7 +572,6 @@ class RandomProjectionModule(nn.Module):
         self.__dict__.update(d)
 
     def __deepcopy__(self, memo):
-        import copy
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         new.__dict__.update(copy.deepcopy(self.__getstate__(), memo))
@@ -611,23 +613,23 @@ class RandomProjectionModule(nn.Module):
         B = int(t.size)
         lam = float(self.time_decay_weight)
         flags = 0
-        src_h, dst_h = self._host_ids(src_node_ids, "src_node_ids"), self._host_ids(dst_node_ids, "dst_node_ids")
+        src_h, dst_h = self._ids(src_node_ids, "src_node_ids", True), self._ids(dst_node_ids, "dst_node_ids", True)
         stage = self._eng["stage"]
         host = src_h is not None and dst_h is not None and B <= stage.max_host_batch
         if host and self.exact:
             # range check BEFORE anything is enqueued (the exact mode's decay below is a state change; otherwise the C call
             # checks the ids on the host before it launches anything)
-            for ids, what in ((src_h, "src_node_ids"), (dst_h, "dst_node_ids")):
-                if ids.min() < -self.node_num or ids.max() >= self.node_num:
-                    raise IndexError(f"{what}: index out of range for {self.node_num} nodes")
+            self._ids(src_h, "src_node_ids")
+            self._ids(dst_h, "dst_node_ids")
         elif not host:
-            src, dst, t_dev = self._to_device(self._check_ids(src_node_ids, "src_node_ids"),
-                                              self._check_ids(dst_node_ids, "dst_node_ids"), t)
+            src, dst, t_dev = self._to_device(self._ids(src_node_ids, "src_node_ids"),
+                                              self._ids(dst_node_ids, "dst_node_ids"), t)
+        stream = _raw_stream(self._eng["dev_index"])
         if self.exact:
             # the factor exactly as the reference forms it: f64 numpy, rounded to f32 once (TPNet.py:84-85)
             g = np.exp(-self.time_decay_weight * (np.float64(next_time) - np.float64(self._now_host)))
             fac = (C.c_float * self.num_layer)(*[np.float32(np.power(g, i)) for i in range(1, self.num_layer + 1)])
-            _lib.check(lib.tpnet_decay(self._st_ref(), fac, next_time, self._stream()), "decay")
+            _lib.check(lib.tpnet_decay(self._st_ref(), fac, next_time, stream), "decay")
             flags |= _lib.FLAG_SEQUENTIAL
         ws = self._workspace(B, B, tail=24 * B + 512 if (host and B > stage.max_batch) else 0)
         lid = self._next_launch_ids(1)
@@ -637,27 +639,22 @@ class RandomProjectionModule(nn.Module):
             fast = _lib.fast()
             if fast is not None:
                 self._st_ref()
-                rc = fast.update(self.__dict__["_st_cache"][4], self._eng["stage"].handle.value, src_h, dst_h, t, self._now_host,
-                                 lam, lid, flags, ws.data_ptr(), ws.numel(), _raw_stream(self._eng["dev_index"]))
+                rc = fast.update(self.__dict__["_st_cache"].addr, stage.handle.value, src_h, dst_h, t, self._now_host,
+                                 lam, lid, flags, ws.data_ptr(), ws.numel(), stream)
             else:
-                rc = lib.tpnet_host_update(self._st_ref(), self._eng["stage"].handle, src_h.ctypes.data, dst_h.ctypes.data,
-                                           t.ctypes.data, B, self._now_host, lam, lid, flags, ws.data_ptr(), ws.numel(),
-                                           _raw_stream(self._eng["dev_index"]))
+                rc = lib.tpnet_host_update(self._st_ref(), stage.handle, src_h.ctypes.data, dst_h.ctypes.data,
+                                           t.ctypes.data, B, self._now_host, lam, lid, flags, ws.data_ptr(), ws.numel(), stream)
             if rc:
                 _lib.check(rc, "host_update")
         else:
             _lib.check(lib.tpnet_update(self._st_ref(), src.data_ptr(), dst.data_ptr(), t_dev.data_ptr(), B, self._now_host,
-                                        lam, lid, flags, ws.data_ptr(), ws.numel(), self._stream()),
-                       "update")
-        self._now_host = next_time
-        self._params_valid = False
-        self._now_dirty = True
-        self._table_written()
+                                        lam, lid, flags, ws.data_ptr(), ws.numel(), stream), "update")
+        self._advanced(next_time)
 
     def get_random_projections(self, node_ids: np.ndarray):
         """models/TPNet.py:101-110: [P[i][node_ids] for i in 0..L]."""
         self._ensure_engine()
-        ids = self._ids_to_device(node_ids, "node_ids")
+        ids = self._to_device(self._ids(node_ids, "node_ids"))[0]
         n = ids.numel()
         out = torch.empty((self.num_layer + 1, n, self.dim), dtype=torch.float32, device=self._dev())
         st = self._state()
@@ -665,6 +662,14 @@ class RandomProjectionModule(nn.Module):
                                                  float(self.time_decay_weight), out.data_ptr(), self._stream()),
                    "gather_rows")
         return [out[i] for i in range(self.num_layer + 1)]
+
+    def _readout_flags(self, raw: bool = False, packed: bool = False, matrix_cores: bool = True) -> int:
+        """The TPNET_FLAG_* word of a readout: `raw` / `packed` as in pair_gram (both leave out the log tail, as not_scale does),
+        `matrix_cores=False` keeps the anchored readout off the matrix cores."""
+        flags = _lib.FLAG_NOT_SCALE if (self.not_scale or raw or packed) else 0
+        if packed:
+            flags |= _lib.FLAG_PACKED
+        return flags if matrix_cores else flags | _lib.FLAG_NO_MFMA_READOUT
 
     @property
     def packed_feature_dim(self) -> int:
@@ -680,22 +685,16 @@ class RandomProjectionModule(nn.Module):
         self._ensure_engine()
         if len(src_node_ids) != len(dst_node_ids):
             raise ValueError("src_node_ids and dst_node_ids must have the same length")
-        uh, vh = self._host_ids(src_node_ids, "src_node_ids"), self._host_ids(dst_node_ids, "dst_node_ids")
+        uh, vh = self._ids(src_node_ids, "src_node_ids", True), self._ids(dst_node_ids, "dst_node_ids", True)
+        flags = self._readout_flags(raw, packed)
+        width = self.packed_feature_dim if packed else self.pair_wise_feature_dim
         if uh is not None and vh is not None and uh.size <= self._eng["stage"].max_pairs:
-            flags = _lib.FLAG_NOT_SCALE if (self.not_scale or raw or packed) else 0
-            if packed:
-                flags |= _lib.FLAG_PACKED
-            return self._host_readout(uh, vh, uh.size, flags,
-                                      self.packed_feature_dim if packed else self.pair_wise_feature_dim)
-        u, v = self._to_device(self._check_ids(src_node_ids, "src_node_ids"),
-                               self._check_ids(dst_node_ids, "dst_node_ids"))
+            return self._host_readout(uh, vh, uh.size, flags, width)
+        u, v = self._to_device(self._ids(src_node_ids, "src_node_ids"),
+                               self._ids(dst_node_ids, "dst_node_ids"))
         n = u.numel()
-        out = torch.empty((n, self.packed_feature_dim if packed else self.pair_wise_feature_dim),
-                          dtype=torch.float32, device=self._dev())
+        out = torch.empty((n, width), dtype=torch.float32, device=self._dev())
         st = self._state()
-        flags = _lib.FLAG_NOT_SCALE if (self.not_scale or raw or packed) else 0
-        if packed:
-            flags |= _lib.FLAG_PACKED
         _lib.check(_lib.load().tpnet_pair_gram(C.byref(st), u.data_ptr(), v.data_ptr(), n, self._now_host,
                                                float(self.time_decay_weight), flags, out.data_ptr(), self._stream()),
                    "pair_gram")
@@ -707,14 +706,13 @@ class RandomProjectionModule(nn.Module):
         self._ensure_engine()
         if not (len(node_ids) == len(first_ids) == len(second_ids)):
             raise ValueError("node_ids, first_ids and second_ids must have the same length")
-        u, v1, v2 = self._to_device(self._check_ids(node_ids, "node_ids"), self._check_ids(first_ids, "first_ids"),
-                                    self._check_ids(second_ids, "second_ids"))
+        u, v1, v2 = self._to_device(self._ids(node_ids, "node_ids"), self._ids(first_ids, "first_ids"),
+                                    self._ids(second_ids, "second_ids"))
         n = u.numel()
         out = torch.empty((2, n, self.pair_wise_feature_dim), dtype=torch.float32, device=self._dev())
         st = self._state()
-        flags = _lib.FLAG_NOT_SCALE if self.not_scale else 0
         _lib.check(_lib.load().tpnet_pair_gram_shared(C.byref(st), u.data_ptr(), v1.data_ptr(), v2.data_ptr(), n,
-                                                      self._now_host, float(self.time_decay_weight), flags,
+                                                      self._now_host, float(self.time_decay_weight), self._readout_flags(),
                                                       out[0].data_ptr(), out[1].data_ptr(), self._stream()),
                    "pair_gram_shared")
         return out[0], out[1]
@@ -723,44 +721,71 @@ class RandomProjectionModule(nn.Module):
         """models/TPNet.py:112-129.  No gradient flows into the projections (requires_grad=False in the
         reference, :49-62); self.mlp stays a trainable torch module.
         The encoder calls this with src_node_ids = tile(neighbours, 2) (models/TPNet.py:313-316): when the two halves
-        of src_node_ids are equal, each neighbour's rows are fetched once for both of its pairs."""
-        if self.fused_mlp and self._plist()[0].device.type == "cuda":
-            # opt-in: self.mlp on the bf16 matrix cores INSIDE the readout kernel (the features never leave the chip)
-            from . import fused_mlp as fm
-            # (rows of < 256 floats on long lists: the 512-thread workgroups of the one-kernel version cost the readout its
-            # occupancy -- 80 000 pairs at d=128: 89 us against 69 us for readout kernel + mlp kernel -- tools/feature_rate.py)
-            if fm.readout_supported(self) and (self.dim >= 256 or len(src_node_ids) <= 16384):
-                if len(src_node_ids) != len(dst_node_ids):
-                    raise ValueError("src_node_ids and dst_node_ids must have the same length")
-                self._ensure_engine()
-                u, v = self._to_device(self._check_ids(src_node_ids, "src_node_ids"),
-                                       self._check_ids(dst_node_ids, "dst_node_ids"))
-                return fm.fused_readout_mlp(self, u, v)
+        of src_node_ids are equal, each neighbour's rows are fetched once for both of its pairs.
+        The routes are numbered below in the order in which they are tried; one that declines leaves the call to the next."""
+        cuda = self._plist()[0].device.type == "cuda"
+        NG = self.pair_wise_feature_dim
+        # 1. opt-in (fused_mlp): self.mlp on the bf16 matrix cores INSIDE the readout kernel (the features never leave the chip).
+        #    Not for rows of < 256 floats on long lists: the 512-thread workgroups of the one-kernel version cost the readout its
+        #    occupancy -- 80 000 pairs at d=128: 87..89 us against 42 + 34 us for readout kernel + dense-layer kernel
+        #    (tools/feature_rate.py); the same holds for the fp32 kernel of route 4
+        if self.fused_mlp and cuda and _fm.readout_supported(self) and (self.dim >= 256 or len(src_node_ids) <= 16384):
+            if len(src_node_ids) != len(dst_node_ids):
+                raise ValueError("src_node_ids and dst_node_ids must have the same length")
+            self._ensure_engine()
+            u, v = self._to_device(self._ids(src_node_ids, "src_node_ids"), self._ids(dst_node_ids, "dst_node_ids"))
+            return _fm.fused_readout_mlp(self, u, v)
+        # 2. src on the device: the readout from device ids, then self.mlp
         if isinstance(src_node_ids, torch.Tensor):
             return self._apply_mlp(self.pair_gram(src_node_ids, dst_node_ids))
         src = np.asarray(src_node_ids)
         n = len(src)
+        prep = mfma = None
         if not self.fused_mlp and not isinstance(dst_node_ids, torch.Tensor):
-            # readout AND self.mlp in one launch, fp32: the decoder's call (models/modules.py:112: n = batch size) and, where the
-            # fp32 matrix-core kernel serves the shape (L = 3, rows of >= 36 floats in 16-byte vectors), lists of any length
-            fused = self._fused_feature(src, dst_node_ids, n)
-            if fused is not None:
-                return fused
-        if n > 8192 and n % 2 == 0 and not self.fused_mlp and self._plist()[0].device.type == "cuda":
-            # the encoder's call as the reference issues it (models/TPNet.py:311-316: src = tile(neigh, 2), dst = concat(repeat(a1, K),
-            # repeat(a2, K)) on the host): recognised in one pass over the two arrays in C; n / 2 neighbour ids + 2 n / (2 K) anchors
-            # go up instead of 2 n ids, the anchored readout and the dense layers run as one call (dim % 4 == 0, 36 <= dim <= 512;
-            # one launch on the matrix cores up to dim = 160)
+            if len(dst_node_ids) != n:
+                raise ValueError("src_node_ids and dst_node_ids must have the same length")
+            mlp = self._modules.get("mlp")              # (self.mlp without nn.Module.__getattr__)
+            if mlp is None:
+                mlp = self.mlp
+            prep = _ff.prepared(mlp, NG) if cuda else None       # (None: not the reference's Linear-ReLU-Linear on this GPU)
+        if prep is not None:
+            self._ensure_engine()
+            # (the fp32 matrix-core kernel serves L = 3 and rows of >= 36 floats in 16-byte vectors: lists up to the staging ring's
+            # length; the plain one up to _ff.MAX_PAIRS)
+            mfma = bool(prep.st.w1) and self.dim % 4 == 0 and self.dim >= 36 and not self.use_matrix
+            if n <= (self._eng["stage"].max_pairs if mfma else _ff.MAX_PAIRS):
+                # 3. the decoder's call (models/modules.py:112: n = batch size) from host arrays: ids checked and staged, readout
+                #    AND self.mlp in one launch (tpnet_host_pair_feature), fp32.  (Flags and the no-grad branch are
+                #    _readout_flags() and _feature_call() inline: this call is host-bound, a frame is 0.1 us of 35 per batch.)
+                uh, vh = self._ids(src, "src_node_ids", True), self._ids(dst_node_ids, "dst_node_ids", True)
+                flags = _lib.FLAG_NOT_SCALE if self.not_scale else 0
+                if not _ff.needs_grad(prep.params):
+                    return self._host_readout(uh, vh, n, flags, NG, prep.ref)
+                return self._feature_call(prep, n, functools.partial(self._host_readout, uh, vh, n, flags, NG, prep.ref))
+        # ---- long lists (and whatever the routes above do not serve).  `tiled`: src = tile(x, 2) on rows wide enough for fetching
+        # x's rows once to pay (_tiled) -- one pass over the ids, made when the first route asks and at most once
+        tiled = None
+        if mfma and self.dim > 128:
+            tiled = self._tiled(src, n)
+            if not tiled:
+                # 4. wide rows, not the encoder's pattern: still one launch on the fp32 matrix cores, from a device copy of the ids
+                u, v = self._to_device(self._ids(src, "src_node_ids"), self._ids(dst_node_ids, "dst_node_ids"))
+                return self._feature_call(prep, n, self._pair_feature_launch(u, v, prep))
+        if n > 8192 and n % 2 == 0 and not self.fused_mlp and cuda:
+            # 5. the encoder's call as the reference issues it (models/TPNet.py:311-316: src = tile(neigh, 2), dst = concat(repeat(a1,
+            #    K), repeat(a2, K)) on the host): recognised in one pass over the two arrays in C; n / 2 neighbour ids + 2 n / (2 K)
+            #    anchors go up instead of 2 n ids, the anchored readout and the dense layers run as one call (dim % 4 == 0,
+            #    36 <= dim <= 512; one launch on the matrix cores up to dim = 160)
             feats = self._encoder_pattern_features(src, dst_node_ids, n)
             if feats is not None:
                 return feats
-        # (rows of <= 128 floats: the generic kernel's 16-lane geometry is as fast on long lists; measured)
-        if self.dim > 128 and n >= 4 and n % 2 == 0 and n > 8192 and np.array_equal(src[: n // 2], src[n // 2:]):
-            # the encoder's pattern: neighbours tiled twice, each half of dst a np.repeat of the row's anchor
-            # (models/TPNet.py:313-316): one lane group per row with the anchors in registers (rows of <= 128 floats: the
-            # generic kernel is as fast on long lists -- measured, tools/encoder_readout.py)
+        if tiled is None:
+            tiled = self._tiled(src, n)
+        if n > 8192 and tiled:
+            # 6. the same pattern where route 5 does not apply (L != 3, another self.mlp, ids that are not int64 arrays): the runs
+            #    of anchors found with numpy, one lane group per row with the anchors in registers, then self.mlp
             dst = np.asarray(dst_node_ids)
-            if self._plist()[0].device.type == "cuda":
+            if cuda:
                 self._ensure_engine()
                 r1 = self._anchor_runs(dst[: n // 2])
                 r2 = self._anchor_runs(dst[n // 2:]) if r1 is not None else None
@@ -769,12 +794,60 @@ class RandomProjectionModule(nn.Module):
                     if K >= 4:
                         m = (n // 2) // K
                         g = self.pair_gram_anchored(src[: n // 2].reshape(m, K), dst[: n // 2: K], dst[n // 2:: K])
-                        return self._apply_mlp(g.view(-1, self.pair_wise_feature_dim))
-        if self.dim > 128 and n >= 2 and n % 2 == 0 and np.array_equal(src[: n // 2], src[n // 2:]):
+                        return self._apply_mlp(g.view(-1, NG))
+        if tiled:
+            # 7. tiled src, any dst: each node's rows fetched once for its two pairs, then self.mlp
             dst = np.asarray(dst_node_ids)
-            g1, g2 = self.pair_gram_shared(src[: n // 2], dst[: n // 2], dst[n // 2:])
-            return self._apply_mlp(torch.cat([g1, g2], dim=0))
+            return self.get_pair_wise_feature_shared(src[: n // 2], dst[: n // 2], dst[n // 2:])
+        # 8. the generic readout, then self.mlp
         return self._apply_mlp(self.pair_gram(src_node_ids, dst_node_ids))
+
+    def _tiled(self, src, n) -> bool:
+        """src = tile(x, 2), on rows of more than 128 floats.  (Rows of <= 128 floats: the generic kernel's 16-lane geometry is as
+        fast on long lists as the kernels that fetch x's rows once -- measured, tools/encoder_readout.py.)"""
+        return self.dim > 128 and n >= 2 and n % 2 == 0 and np.array_equal(src[: n // 2], src[n // 2:])
+
+    def _feature_call(self, prep, n, launch, rows_k=None):
+        """A readout + self.mlp call, `launch(gram)` -> the [n, (2L+2)^2] features, `gram` = where the kernel leaves the pre-mlp
+        features (None: nowhere).  With gradients recorded, the autograd node allocates that buffer and keeps it for the backward
+        pass.  Without: no buffer -- for the encoder's calls (`rows_k` = their (rows, K)) only where readout and dense layers are
+        ONE launch (tpnet_encoder_fused_supported: rows of 36..160 floats, dim % 4 == 0, K >= 4), else a scratch tensor between
+        the two launches; and if the runtime refuses the one launch after all (TPNET_ERR_NEED_GRAM), once more with a scratch."""
+        NG = self.pair_wise_feature_dim
+        if _ff.needs_grad(prep.params):
+            return _ff.apply_with_grad(self.mlp, launch, n, NG)
+        gram = None
+        if rows_k is not None and not _lib.load().tpnet_encoder_fused_supported(self._st_ref(), rows_k[0], rows_k[1], prep.ref):
+            gram = torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
+        try:
+            return launch(gram)
+        except _lib.NeedGramBuffer:
+            return launch(torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"]))
+
+    def _pair_feature_launch(self, u, v, prep):
+        """The launch (for _feature_call) of tpnet_pair_feature: readout of the pairs (u, v) (device ids) and self.mlp in one kernel."""
+        n, flags = u.numel(), self._readout_flags()
+
+        def launch(gram):
+            out = torch.empty((n, self.pair_wise_feature_dim), dtype=torch.float32, device=self._eng["dev"])
+            _lib.check(_lib.load().tpnet_pair_feature(self._st_ref(), u.data_ptr(), v.data_ptr(), n, self._now_host,
+                                                      float(self.time_decay_weight), flags, prep.ref, _ptr_or_null(gram),
+                                                      out.data_ptr(), self._stream()), "pair_feature")
+            return out
+        return launch
+
+    def _anchored_launch(self, wd, a1, a2, rows, K, prep):
+        """The launch (for _feature_call) of tpnet_anchored_features: `rows` x K neighbour ids `wd` and two anchors per row, all on
+        the device -> [2 * rows * K, (2L+2)^2] features, self.mlp applied."""
+        lib, flags, dev = _lib.load(), self._readout_flags(), self._eng["dev"]
+
+        def launch(gram):
+            out = torch.empty((2 * rows * K, self.pair_wise_feature_dim), dtype=torch.float32, device=dev)
+            _lib.check(lib.tpnet_anchored_features(self._st_ref(), wd.data_ptr(), a1.data_ptr(), a2.data_ptr(), rows, K, self._now_host,
+                                                   float(self.time_decay_weight), flags, prep.ref, _ptr_or_null(gram), out.data_ptr(),
+                                                   _raw_stream(self._eng["dev_index"])), "anchored_features")
+            return out
+        return launch
 
     def _encoder_pattern_features(self, src, dst, n):
         """get_pair_wise_feature for the encoder's tile / repeat pattern on host arrays (None: not that pattern, or a shape the
@@ -791,10 +864,7 @@ class RandomProjectionModule(nn.Module):
         lib = _lib.load()
         if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
             return None
-        NG = self.pair_wise_feature_dim
-        flags = _lib.FLAG_NOT_SCALE if self.not_scale else 0
-        grad = _ff.needs_grad(prep[4])
-        if grad and int(lib.tpnet_host_encoder_pattern(src.ctypes.data, dst.ctypes.data, n, self.node_num)) < 4:
+        if _ff.needs_grad(prep.params) and int(lib.tpnet_host_encoder_pattern(src.ctypes.data, dst.ctypes.data, n, self.node_num)) < 4:
             # (training: the cheap host check FIRST -- a declined call would already have allocated an n x 64 feature buffer and an
             # autograd node over it, for the general path to do the same work again)
             return None
@@ -807,38 +877,26 @@ class RandomProjectionModule(nn.Module):
             if eng.get("stage_big") is None:
                 eng["stage_big"] = _Stage(lib, eng["dev"], slots=4, slot_bytes=_BIG_SLOT_BYTES)
             served = C.c_int32(0)
+            flags = self._readout_flags()
 
             def launch_host(gram):
-                out = torch.empty((n, NG), dtype=torch.float32, device=eng["dev"])
+                out = torch.empty((n, self.pair_wise_feature_dim), dtype=torch.float32, device=eng["dev"])
                 _lib.check(lib.tpnet_host_anchored_features(self._st_ref(), eng["stage_big"].handle, src.ctypes.data, dst.ctypes.data, n,
-                                                            self._now_host, float(self.time_decay_weight), flags, prep[2],
+                                                            self._now_host, float(self.time_decay_weight), flags, prep.ref,
                                                             _ptr_or_null(gram), out.data_ptr(), C.byref(served),
                                                             _raw_stream(eng["dev_index"])), "host_anchored_features")
                 return out
             # (no backward pass: no feature buffer; the call declines -- served stays 0 -- where readout and dense layers are two
             # launches, and where the arrays are not the pattern or hold an id out of range: the path below then answers)
-            try:
-                res = _ff.apply_with_grad(self.mlp, launch_host, n, NG) if grad else launch_host(None)
-            except _lib.NeedGramBuffer:
-                res = launch_host(torch.empty((n, NG), dtype=torch.float32, device=eng["dev"]))
+            res = self._feature_call(prep, n, launch_host)
             if served.value >= 4:
                 return res
         K = int(lib.tpnet_host_encoder_pattern(src.ctypes.data, dst.ctypes.data, n, self.node_num))
         if K < 4:
             return None
         h = n // 2
-        m = h // K
-        wd, a1, a2 = self._to_device_multi(src[:h], np.ascontiguousarray(dst[:h:K]), np.ascontiguousarray(dst[h::K]))
-
-        def launch(gram):
-            out = torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
-            _lib.check(lib.tpnet_anchored_features(self._st_ref(), wd.data_ptr(), a1.data_ptr(), a2.data_ptr(), m, K, self._now_host,
-                                                   float(self.time_decay_weight), flags, prep[2], _ptr_or_null(gram), out.data_ptr(),
-                                                   _raw_stream(self._eng["dev_index"])), "anchored_features")
-            return out
-        if grad:
-            return _ff.apply_with_grad(self.mlp, launch, n, NG)
-        return self._launch_no_grad(launch, m, K, prep, n, NG)
+        wd, a1, a2 = self._to_device(src[:h], np.ascontiguousarray(dst[:h:K]), np.ascontiguousarray(dst[h::K]))
+        return self._feature_call(prep, n, self._anchored_launch(wd, a1, a2, h // K, K, prep), (h // K, K))
 
     def pair_gram_anchored(self, neighbor_ids, first_anchor_ids, second_anchor_ids, matrix_cores=True):
         """The encoder's readout before self.mlp (models/TPNet.py:311-324): neighbor_ids [n, K] (the sampled neighbours of n
@@ -849,48 +907,26 @@ class RandomProjectionModule(nn.Module):
         vectors, dim % 4 == 0 and 36 <= dim <= 512 (the reference's default widths 120, 140, 160 among them); rows of 36..160
         floats with L = 3 and K >= 4 take the matrix cores (csrc/encoder_mfma.hip) unless matrix_cores=False."""
         self._ensure_engine()
-        if isinstance(neighbor_ids, torch.Tensor):
-            if neighbor_ids.dim() != 2:
-                raise ValueError("neighbor_ids must be [n, K]")
-            n, K = neighbor_ids.shape
-            w = neighbor_ids.reshape(-1)
-        else:
-            nb = np.asarray(neighbor_ids)
-            if nb.ndim != 2:
-                raise ValueError("neighbor_ids must be [n, K]")
-            n, K = nb.shape
-            w = nb.reshape(-1)
+        nb = neighbor_ids if isinstance(neighbor_ids, torch.Tensor) else np.asarray(neighbor_ids)
+        if nb.ndim != 2:
+            raise ValueError("neighbor_ids must be [n, K]")
+        n, K = nb.shape
+        w = nb.reshape(-1)
         if len(first_anchor_ids) != n or len(second_anchor_ids) != n:
             raise ValueError("one first and one second anchor per row of neighbor_ids")
         lib = _lib.load()
         if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
             raise _lib.TPNetHipError(f"pair_gram_anchored needs dim % 4 == 0 and 36 <= dim <= 512, not {self.dim}: "
                                      "use pair_gram_shared")
-        wd = self._to_device(self._check_ids(w, "neighbor_ids"))[0]
-        a1, a2 = self._to_device(self._check_ids(first_anchor_ids, "first_anchor_ids"),
-                                 self._check_ids(second_anchor_ids, "second_anchor_ids"))
+        wd = self._to_device(self._ids(w, "neighbor_ids"))[0]
+        a1, a2 = self._to_device(self._ids(first_anchor_ids, "first_anchor_ids"),
+                                 self._ids(second_anchor_ids, "second_anchor_ids"))
         out = torch.empty((2, n * K, self.pair_wise_feature_dim), dtype=torch.float32, device=self._dev())
-        flags = (_lib.FLAG_NOT_SCALE if self.not_scale else 0) | (0 if matrix_cores else _lib.FLAG_NO_MFMA_READOUT)
+        flags = self._readout_flags(matrix_cores=matrix_cores)
         _lib.check(lib.tpnet_pair_gram_anchored(self._st_ref(), wd.data_ptr(), a1.data_ptr(), a2.data_ptr(), n, K,
                                                 self._now_host, float(self.time_decay_weight), flags, out[0].data_ptr(),
                                                 out[1].data_ptr(), self._stream()), "pair_gram_anchored")
         return out
-
-    def _launch_no_grad(self, launch, n_rows, K, prep, n, NG):
-        """An encoder call without a backward pass: no feature buffer where readout and dense layers are one launch; if the runtime
-        refuses that launch after all (TPNET_ERR_NEED_GRAM), once more with a scratch buffer."""
-        try:
-            return launch(self._gram_buffer(n_rows, K, prep, n, NG))
-        except _lib.NeedGramBuffer:
-            return launch(torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"]))
-
-    def _gram_buffer(self, n_rows, K, prep, n, NG):
-        """Where the pre-mlp features of an encoder call go when no backward pass needs them: nowhere (None) if readout and dense
-        layers are ONE launch (tpnet_encoder_fused_supported: rows of 36..160 floats, dim % 4 == 0, K >= 4), else a scratch tensor
-        between the two launches."""
-        if _lib.load().tpnet_encoder_fused_supported(self._st_ref(), n_rows, K, prep[2]):
-            return None
-        return torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
 
     def _overlapped_mlp(self):
         """The prepared fp32 weights of self.mlp if the encoder's one-call path applies (readout chunks and their dense layers side
@@ -898,7 +934,7 @@ class RandomProjectionModule(nn.Module):
         if self.fused_mlp or self.num_layer != 3:
             return None
         prep = _ff.prepared(self.mlp, self.pair_wise_feature_dim)
-        return prep if (prep is not None and prep[1].w1) else None
+        return prep if (prep is not None and prep.st.w1) else None
 
     def get_pair_wise_feature_anchored(self, neighbor_ids, first_anchor_ids, second_anchor_ids):
         """Extension: the encoder's call (models/TPNet.py:313-316) from its natural arguments; [2*n*K, (2L+2)^2] in the
@@ -909,22 +945,10 @@ class RandomProjectionModule(nn.Module):
             lib = _lib.load()
             if lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
                 n, K = neighbor_ids.shape
-                wd = self._check_ids(neighbor_ids.reshape(-1), "neighbor_ids")
-                a1, a2 = self._to_device(self._check_ids(first_anchor_ids, "first_anchor_ids"),
-                                         self._check_ids(second_anchor_ids, "second_anchor_ids"))
-                NG = self.pair_wise_feature_dim
-                flags = _lib.FLAG_NOT_SCALE if self.not_scale else 0
-
-                def launch(gram):
-                    out = torch.empty((2 * n * K, NG), dtype=torch.float32, device=self._eng["dev"])
-                    _lib.check(lib.tpnet_anchored_features(self._st_ref(), wd.data_ptr(), a1.data_ptr(), a2.data_ptr(), n, K,
-                                                           self._now_host, float(self.time_decay_weight), flags, prep[2],
-                                                           _ptr_or_null(gram), out.data_ptr(), _raw_stream(self._eng["dev_index"])),
-                               "anchored_features")
-                    return out
-                if _ff.needs_grad(prep[4]):
-                    return _ff.apply_with_grad(self.mlp, launch, 2 * n * K, NG)
-                return self._launch_no_grad(launch, n, K, prep, 2 * n * K, NG)
+                wd = self._ids(neighbor_ids.reshape(-1), "neighbor_ids")
+                a1, a2 = self._to_device(self._ids(first_anchor_ids, "first_anchor_ids"),
+                                         self._ids(second_anchor_ids, "second_anchor_ids"))
+                return self._feature_call(prep, 2 * n * K, self._anchored_launch(wd, a1, a2, n, K, prep), (n, K))
         g = self.pair_gram_anchored(neighbor_ids, first_anchor_ids, second_anchor_ids)
         return self._apply_mlp(g.view(-1, self.pair_wise_feature_dim))
 
@@ -940,14 +964,14 @@ class RandomProjectionModule(nn.Module):
         if host:
             # the batch's arrays as the reference's loop holds them (numpy slices of the edge list): staged through the pinned ring
             # and read there by the row set-up kernel -- no copy is enqueued
-            src_ids = self._host_ids(src_ids, "src_ids")
-            other_ids = self._host_ids(other_ids, "other_ids")
+            src_ids = self._ids(src_ids, "src_ids", True)
+            other_ids = self._ids(other_ids, "other_ids", True)
             times = np.ascontiguousarray(np.asarray(times), dtype=np.float64)
             B, K = int(src_ids.size), int(num_neighbors)
             if other_ids is None or other_ids.size != B or times.size != B:
                 raise ValueError("encoder_pair_features: src_ids, other_ids and times must be host arrays of one length")
             if B > self._eng["stage"].max_host_batch:
-                s_d, o_d, t_d = self._to_device(self._check_ids(src_ids, "src_ids"), self._check_ids(other_ids, "other_ids"), times)
+                s_d, o_d, t_d = self._to_device(self._ids(src_ids, "src_ids"), self._ids(other_ids, "other_ids"), times)
                 return self.encoder_pair_features(sampler, s_d, o_d, t_d, num_neighbors)
         else:
             B, K = int(src_ids.numel()), int(num_neighbors)
@@ -958,7 +982,7 @@ class RandomProjectionModule(nn.Module):
         NG = self.pair_wise_feature_dim
         nbytes = lib.tpnet_encoder_scratch_bytes(B, K)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        flags = _lib.FLAG_NOT_SCALE if self.not_scale else 0
+        flags = self._readout_flags()
         off = (-scratch.data_ptr()) % 256 + 64 * B
         neigh = scratch[off: off + 16 * B * K].view(torch.int64).view(2 * B, K)
         prep = self._overlapped_mlp()
@@ -970,20 +994,18 @@ class RandomProjectionModule(nn.Module):
                     _lib.check(lib.tpnet_host_encoder_features(
                         self._st_ref(), self._eng["stage"].handle, sampler._buf.data_ptr(), sampler.E, sampler.num_nodes,
                         src_ids.ctypes.data, other_ids.ctypes.data, times.ctypes.data, B, K, self._now_host,
-                        float(self.time_decay_weight), flags, prep[2], scratch.data_ptr(), nbytes, _ptr_or_null(gram), out.data_ptr(),
+                        float(self.time_decay_weight), flags, prep.ref, scratch.data_ptr(), nbytes, _ptr_or_null(gram), out.data_ptr(),
                         _raw_stream(self._eng["dev_index"])), "host_encoder_features")
                     return out
                 _lib.check(lib.tpnet_encoder_features(self._st_ref(), sampler._buf.data_ptr(), sampler.E, sampler.num_nodes,
                                                       src_ids.data_ptr(), other_ids.data_ptr(), times.data_ptr(), B, K,
-                                                      self._now_host, float(self.time_decay_weight), flags, prep[2],
+                                                      self._now_host, float(self.time_decay_weight), flags, prep.ref,
                                                       scratch.data_ptr(), nbytes, _ptr_or_null(gram), out.data_ptr(),
                                                       _raw_stream(self._eng["dev_index"])), "encoder_features")
                 return out
-            if _ff.needs_grad(prep[4]):
-                return _ff.apply_with_grad(self.mlp, launch, 4 * B * K, NG), neigh
-            return self._launch_no_grad(launch, 2 * B, K, prep, 4 * B * K, NG), neigh
+            return self._feature_call(prep, 4 * B * K, launch, (2 * B, K)), neigh
         if host:
-            s_d, o_d, t_d = self._to_device(self._check_ids(src_ids, "src_ids"), self._check_ids(other_ids, "other_ids"), times)
+            s_d, o_d, t_d = self._to_device(self._ids(src_ids, "src_ids"), self._ids(other_ids, "other_ids"), times)
             return self.encoder_pair_features(sampler, s_d, o_d, t_d, num_neighbors)
         out = torch.empty((2, 2 * B * K, NG), dtype=torch.float32, device=dev)
         _lib.check(lib.tpnet_encoder_gram(self._st_ref(), sampler._buf.data_ptr(), sampler.E, sampler.num_nodes, src_ids.data_ptr(),
@@ -1012,50 +1034,9 @@ class RandomProjectionModule(nn.Module):
         g1, g2 = self.pair_gram_shared(node_ids, first_ids, second_ids)
         return self._apply_mlp(torch.cat([g1, g2], dim=0))
 
-    def _fused_feature(self, src, dst, n):
-        """tpnet_host_pair_feature with self.mlp (None if self.mlp is not the reference's Linear-ReLU-Linear on this GPU)."""
-        NG = self.pair_wise_feature_dim
-        mlp = self._modules.get("mlp")              # (self.mlp without nn.Module.__getattr__)
-        if mlp is None:
-            mlp = self.mlp
-        if len(dst) != n:
-            raise ValueError("src_node_ids and dst_node_ids must have the same length")
-        if self._plist()[0].device.type != "cuda":
-            return None
-        prep = _ff.prepared(mlp, NG)
-        if prep is None:
-            return None
-        self._ensure_engine()
-        mfma = bool(prep[1].w1) and self.dim % 4 == 0 and self.dim >= 36 and not self.use_matrix
-        if n > (self._eng["stage"].max_pairs if mfma else _ff.MAX_PAIRS):
-            # a long list: with the matrix-core kernel still one launch, from a device copy of the ids -- except the encoder's
-            # pattern on wide rows, which the caller below serves with the anchored readout + the matrix-core mlp
-            # (rows of <= 128 floats on long lists: the 512-thread workgroups of the one-kernel version cost the readout its
-            # occupancy -- 80 000 pairs at d=128: 87 us against 42 + 34 us for readout kernel + dense-layer kernel)
-            if not mfma or self.dim <= 128 or (n % 2 == 0 and np.array_equal(src[: n // 2], src[n // 2:])):
-                return None
-            u, v = self._to_device(self._check_ids(src, "src_node_ids"), self._check_ids(dst, "dst_node_ids"))
-            flags = _lib.FLAG_NOT_SCALE if self.not_scale else 0
-
-            def launch(gram):
-                out = torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
-                _lib.check(_lib.load().tpnet_pair_feature(self._st_ref(), u.data_ptr(), v.data_ptr(), n, self._now_host,
-                                                          float(self.time_decay_weight), flags, prep[2],
-                                                          gram.data_ptr() if gram is not None else None, out.data_ptr(),
-                                                          self._stream()), "pair_feature")
-                return out
-            return _ff.apply_with_grad(mlp, launch, n, NG) if _ff.needs_grad(prep[4]) else launch(None)
-        uh, vh = self._host_ids(src, "src_node_ids"), self._host_ids(dst, "dst_node_ids")
-        flags = _lib.FLAG_NOT_SCALE if self.not_scale else 0
-        if _ff.needs_grad(prep[4]):
-            return _ff.apply_with_grad(mlp, lambda gram: self._host_readout(uh, vh, n, flags, NG, prep[2], gram), n, NG)
-        return self._host_readout(uh, vh, n, flags, NG, prep[2])
-
     def _apply_mlp(self, feats: torch.Tensor) -> torch.Tensor:
-        if self.fused_mlp:
-            from . import fused_mlp as fm
-            if fm.supported(self.mlp):
-                return fm.fused_mlp(self.mlp, feats)
+        if self.fused_mlp and _fm.supported(self.mlp):
+            return _fm.fused_mlp(self.mlp, feats)
         y = _ff.mlp_f32(self.mlp, feats) if self.num_layer == 3 else None      # the fp32 matrix-core kernel where it applies
         return y if y is not None else self.mlp(feats)
 
@@ -1152,9 +1133,7 @@ class RandomProjectionModule(nn.Module):
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("run_stream: batch_size must be positive")
-        flags = (_lib.FLAG_NOT_SCALE if (self.not_scale or raw or packed) else 0)
-        if packed:
-            flags |= _lib.FLAG_PACKED
+        flags = self._readout_flags(raw, packed)
         if self.exact:
             flags |= _lib.FLAG_EAGER_DECAY | _lib.FLAG_SEQUENTIAL
         schedule = schedule or self.default_schedule
@@ -1193,7 +1172,7 @@ class RandomProjectionModule(nn.Module):
         if ws is None or ws.numel() < p.ws_need or p.ws_cap != self.stream_log_cap_bytes:   #  only if somebody replaced it since)
             ws = self._workspace(E, batch_size, stream=True, keep_plan=True)
         self._st_ref()                                   # (the cached tpnet_state struct: rebuilt only when a buffer moved)
-        st = self.__dict__["_st_cache"][2]
+        st = self.__dict__["_st_cache"].st
         lid = self._next_launch_ids(p.nb)
         flags = p.flags
         t_out = C.c_double(0.0)
@@ -1205,7 +1184,7 @@ class RandomProjectionModule(nn.Module):
         tag = None
         ps, pd, pn, pt, pop, pon = p.ptrs
         if p.replay is not False and self.plan_replay:
-            tag = self.__dict__.get("_plan_tag")
+            tag = self._plan_tag
             if tag is None:
                 tag = self.__dict__["_plan_tag"] = _lib.PlanTag()
             held = self.__dict__.get("_plan_held")
@@ -1217,23 +1196,21 @@ class RandomProjectionModule(nn.Module):
             self._drop_plan()
         self.__dict__["_rows_plan_sig"] = None          # (this call writes the workspace: the row shard's plan there is gone)
         t_end = p.t_end
+        stream = _raw_stream(self._eng["dev_index"])
         fast = _lib.fast()
         if fast is not None:
             rc, t_got = fast.run_stream(C.addressof(st), ps, pd, pn, pt, E, batch_size, self._now_host, float(self.time_decay_weight),
                                         lid, flags, pop, pon, ws.data_ptr(), ws.numel(), 0 if t_end is not None else 1,
-                                        _raw_stream(self._eng["dev_index"]), C.addressof(tag) if tag is not None else 0)
+                                        stream, C.addressof(tag) if tag is not None else 0)
             t_out.value = t_got
             _lib.check(rc, "run_stream")
         else:
             _lib.check(_lib.load().tpnet_run_stream_tagged(
                 C.byref(st), ps, pd, pn or None, pt, E, batch_size, self._now_host, float(self.time_decay_weight), lid, flags,
-                pop or None, pon or None, ws.data_ptr(), ws.numel(), None if t_end is not None else C.byref(t_out), self._stream(),
+                pop or None, pon or None, ws.data_ptr(), ws.numel(), None if t_end is not None else C.byref(t_out), stream,
                 C.byref(tag) if tag is not None else None), "run_stream")
         self.last_stream_replayed = bool(tag is not None and tag.replayed)
-        self._now_host = t_end if t_end is not None else float(t_out.value)
-        self._params_valid = False
-        self._now_dirty = True
-        self._table_written()
+        self._advanced(t_end if t_end is not None else float(t_out.value))
         return p.out_pos, p.out_neg
 
     def check_device_errors(self):

@@ -312,7 +312,7 @@ class ShardedStreamRunner:
         ws = rp._workspace(E, B)
         st = rp._state()
         stream = rp._stream()
-        flags = _lib.FLAG_NOT_SCALE if rp.not_scale else 0
+        flags = rp._readout_flags()
         ls, ld, ln = R["src"], R["dst"], R["neg"]
         _lib.check(lib.tpnet_plan_stream(C.byref(st), ls.data_ptr(), ld.data_ptr(), t.data_ptr(), E, B, rp._now_host,
                                          lam, flags, ws.data_ptr(), ws.numel(), stream), "plan_stream")
@@ -372,9 +372,7 @@ class ShardedStreamRunner:
             if rc:
                 _lib.check(rc, "step_batch")
             now = t_last_l[b]
-        rp._now_host = now
-        rp._params_valid = False
-        rp._now_dirty = True
+        rp._advanced(now)
         if G > 1 and merge_outputs:
             dist.all_reduce(out_pos, group=self.group)          # disjoint rows: the sum is a merge
             if out_neg is not None:
@@ -679,7 +677,7 @@ class ShardedStreamRunner:
             out_neg.zero_()
         send_p0, send_q = self._send_buffers(d, L, R["smax"], dev)
         ctx = dict(E=E, B=B, nb=nb, out_pos=out_pos, out_neg=out_neg, now=rp._now_host)
-        flags = _lib.FLAG_NOT_SCALE if rp.not_scale else 0
+        flags = rp._readout_flags()
         ls, ld, ln = R["src"], R["dst"], R["neg"]
         if comm == "auto":
             nccl = G > 1 and not self.detached and dist.get_backend(self.group) == "nccl"
@@ -747,10 +745,7 @@ class ShardedStreamRunner:
     def finish_targeted(self, ctx, merge_outputs: bool = True):
         rp = self.rp
         if ctx["E"] and not ctx.get("windowed"):
-            rp._now_host = float(ctx["t_last"][-1])
-            rp._params_valid = False
-            rp._now_dirty = True
-            rp._table_written()
+            rp._advanced(float(ctx["t_last"][-1]))
         out_pos, out_neg = ctx["out_pos"], ctx["out_neg"]
         if self.G > 1 and merge_outputs and not self.detached:
             dist.all_reduce(out_pos, group=self.group)
@@ -919,7 +914,7 @@ class ShardedStreamRunner:
         rp._drop_plan()                                   # (the workspace is this call's now)
         ws = eng["ws"]
         h = C.c_void_p()
-        flags = _lib.FLAG_NOT_SCALE if rp.not_scale else 0
+        flags = rp._readout_flags()
         want_neg = want_neg and neg is not None
         rc = lib.tpnet_wshard_plan(rp._st_ref(), src.data_ptr(), dst.data_ptr(), neg.data_ptr() if neg is not None else None, t.data_ptr(),
                                    E, B, self.N, G, me, self.n_cap, rp._now_host, float(rp.time_decay_weight), flags,
@@ -1004,10 +999,7 @@ class ShardedStreamRunner:
                 t_end = float(np.asarray(t_host_last, dtype=np.float64)[-1])
             else:
                 t_end = float(t[-1].item())
-            rp._now_host = t_end
-            rp._params_valid = False
-            rp._now_dirty = True
-            rp._table_written()
+            rp._advanced(t_end)
         finally:
             lib.tpnet_wshard_destroy(h)
         self.last_stream_windowed = True
@@ -1171,7 +1163,7 @@ class ColumnShardedRunner:
         """Summed packed rows -> full feature rows, with the element-wise tail (tpnet_gram_unpack)."""
         n = packed.shape[0]
         if n:
-            flags = _lib.FLAG_NOT_SCALE if self.rp.not_scale else 0
+            flags = self.rp._readout_flags()
             _lib.check(_lib.load().tpnet_gram_unpack(packed.data_ptr(), n, self.rp.num_layer, flags, out.data_ptr(),
                                                      self.rp._stream()), "gram_unpack")
         return out
