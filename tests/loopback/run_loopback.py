@@ -4,8 +4,8 @@ table in ONE process on one GPU, each with its own host thread and stream, drive
 communicator of the in-process stand-in tests/loopback/librccl_loopback.so -- the `comm && G > 1` branch of
 tpnet_rows_step_targeted (message offsets, halo placement, two messages per peer inside one group) executes, which no gloo test
 reaches.  Checks: (1) bit for bit against the same two shards with the rows moved by plain copies (the gloo transport's data
-path: tpnet_pack_split -> copies into the halo rows -> tpnet_step_batch); (2) against the single-GPU run with the tolerances of
-test_sharded_stream_equals_single_gpu.  Prints one line 'LOOPBACK OK ...' or raises."""
+path, through the runner's own phases: pack_batch -> place_batch into the halo rows -> step_batch); (2) against the single-GPU
+run with the tolerances of test_sharded_stream_equals_single_gpu.  Prints one line 'LOOPBACK OK ...' or raises."""
 import ctypes as C
 import os
 import sys
@@ -131,28 +131,16 @@ def main():
         # ---- (B) the same shards, rows moved by plain copies on one stream (the gloo transport's data path)
         runs_b = shards(N, d, L, E, B, lam, t[0], P0, dev)
         cb = [runs_b[r].prepare_targeted(ds, dd, dn, dt, B, comm=None) for r in range(2)]
+        sent = [(c["send_p0"], c["send_q"]) for c in cb]
         for b in range(nb):
-            now = cb[0]["now"] if b == 0 else float(cb[0]["t_last"][b - 1])
             for r in range(2):
-                c = cb[r]
-                _lib.check(lib.tpnet_pack_split(C.byref(c["st"]), c["R"]["pack_ids"].data_ptr() + 8 * int(c["sstart"][b]),
-                                                int(c["stot"][b]), now, c["lam"], c["send_p0"].data_ptr(), c["send_q"].data_ptr(),
-                                                runs_b[r].n_cap, int(c["rtot"][b]), c["stream"]), "pack_split")
+                runs_b[r].pack_batch(cb[r], b)
+            cnts = [c["R"]["send_cnt"][b] for c in cb]
             for r in range(2):                              # rank r receives what the other one packed for it
-                c, o = cb[r], cb[1 - r]
-                n = int(c["rcnt"][b][1 - r])
-                assert n == int(o["scnt"][b][r])
-                rp = runs_b[r].rp
-                n_cap = runs_b[r].n_cap
-                rp._plist()[0].data[n_cap:n_cap + n].copy_(o["send_p0"][:n])
-                rp._eng["q"].view(2, rp.node_num, L * d)[0, n_cap:n_cap + n].copy_(o["send_q"][:n])
+                assert int(cb[r]["R"]["recv_cnt"][b][1 - r]) == int(cnts[1 - r][r])
+                assert runs_b[r].place_batch(sent, cnts) == int(cb[r]["R"]["rtot"][b])
             for r in range(2):
-                c = cb[r]
-                ln, on = c["ln"], c["out_neg"]
-                _lib.check(lib.tpnet_step_batch(C.byref(c["st"]), c["ls"].data_ptr(), c["ld"].data_ptr(), ln.data_ptr(), c["t"].data_ptr(),
-                                                E, B, b, c["lam"], c["lid0"] + b, c["flags"], 0, runs_b[r].n_cap,
-                                                c["out_pos"].data_ptr(), on.data_ptr(), c["ws"].data_ptr(), c["ws"].numel(), c["stream"]),
-                           "step_batch")
+                runs_b[r].step_batch(cb[r], b)
         ob = [runs_b[r].finish_targeted(cb[r], merge_outputs=False) for r in range(2)]
         torch.cuda.synchronize()
         fpB, fnB = ob[0][0] + ob[1][0], ob[0][1] + ob[1][1]

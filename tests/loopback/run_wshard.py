@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """TEST DRIVER (run in a process of its own by tests/test_sharded.py::test_windowed_shard_*): G row shards of one table in ONE
 process on one GPU on the WINDOWED pipeline (csrc/wshard.hip).  Transports: "copy" = pack launches, plain copies between the
-shards' buffers, unpack launches (the phases of tpnet_wshard_begin / tpnet_wshard_step one by one); "loopback" = every shard a host
-thread with its own stream, tpnet_wshard_run with a communicator of the in-process RCCL stand-in (tests/loopback/
-librccl_loopback.so).  Checks: the shards' features and tables equal the SINGLE-GPU run on the windowed schedule BIT FOR BIT (a log
+shards' buffers, unpack launches (the runner's phase methods wshard_begin / wshard_step / wshard_place_* one by one);
+"loopback" = every shard a host thread with its own stream, tpnet_wshard_run with a communicator of the in-process RCCL
+stand-in (tests/loopback/librccl_loopback.so).  Checks: the shards' features and tables equal the SINGLE-GPU run on the windowed schedule BIT FOR BIT (a log
 slot travels as it is; the table starts from a reset, so the chunk's halo rows need no decay), and the two transports equal each
 other.  Prints 'WSHARD OK ...' or raises."""
 import ctypes as C
@@ -19,9 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 import tpnet_amd                                           # noqa: E402
 from tpnet_amd import _lib                                 # noqa: E402
-from tpnet_amd.sharded import ShardedStreamRunner          # noqa: E402
-
-PH_LAUNCH, PH_PACK, PH_EXCHANGE, PH_UNPACK = 1, 2, 4, 8
+from tpnet_amd.sharded import PH_LAUNCH, PH_PACK, PH_UNPACK, ShardedStreamRunner          # noqa: E402
 
 
 def stream_of(seed, N, E, hubs=True):
@@ -59,53 +57,33 @@ def full_layers(runs, N, L, d):
 
 
 def run_copy(runs, D, B, lib):
-    """All shards in one thread, the rows moved by plain copies."""
+    """All shards in one thread on the runner's own phases, the rows moved by plain copies between the shards' buffers."""
     G = len(runs)
     ds, dd, dn, dt = D
     plans = [runs[r].plan_windowed(ds, dd, dn, dt, B) for r in range(G)]
     assert all(p is not None for p in plans), "the windowed shard declined"
-    E = plans[0]["E"]
-    outs = []
+    E, NG = plans[0]["E"], runs[0].rp.pair_wise_feature_dim
+    outs = [(torch.zeros((E, NG), device=ds.device), torch.zeros((E, NG), device=ds.device)) for _ in range(G)]
     for r in range(G):
-        outs.append((torch.zeros((E, 64 if runs[r].rp.num_layer == 3 else (2 * runs[r].rp.num_layer + 2) ** 2), device=ds.device),
-                     torch.zeros((E, 64 if runs[r].rp.num_layer == 3 else (2 * runs[r].rp.num_layer + 2) ** 2), device=ds.device)))
-    L, d = runs[0].rp.num_layer, runs[0].rp.dim
-    for r in range(G):
-        _lib.check(lib.tpnet_wshard_begin(plans[r]["handle"], None, PH_PACK, runs[r].rp._stream()), "begin")
+        runs[r].wshard_begin(plans[r])
     for r in range(G):                                     # shard r's halo rows <- every owner's packed rows
-        rp = runs[r].rp
-        p0_t = rp._plist()[0].data
-        q_t = rp._eng["q"].view(2, rp.node_num, L * d)
-        for o in range(G):
-            c = int(plans[r]["chunk_cnt"][o])
-            assert c == int(plans[o]["chunk_cnt"][o])
-            if o != r and c:
-                a0 = runs[r].n_cap + int(plans[r]["hstart"][o])
-                p0_t[a0:a0 + c].copy_(plans[o]["bufs"]["send_p0"][:c])
-                q_t[0, a0:a0 + c].copy_(plans[o]["bufs"]["send_q"][:c])
+        assert all(int(plans[r]["chunk_cnt"][o]) == int(plans[o]["chunk_cnt"][o]) for o in range(G))
+        runs[r].wshard_place_halo(plans[r], [(p["bufs"]["send_p0"], p["bufs"]["send_q"]) for p in plans])
     moved = 0
+    sent = [(p["bufs"]["sendbuf"],) for p in plans]
     for j in range(plans[0]["nsteps"]):
         for r in range(G):
-            _lib.check(lib.tpnet_wshard_step(plans[r]["handle"], None, j, PH_LAUNCH | PH_PACK, outs[r][0].data_ptr(), outs[r][1].data_ptr(),
-                                             runs[r].rp._stream()), "step")
+            runs[r].wshard_step(plans[r], j, PH_LAUNCH | PH_PACK, *outs[r])
+        cnts = [p["send_cnt"][j] for p in plans]
         for r in range(G):
-            ro = 0
-            for o in range(G):
-                c = int(plans[r]["recv_cnt"][j][o])
-                assert c == int(plans[o]["send_cnt"][j][r]), (j, r, o, c, int(plans[o]["send_cnt"][j][r]))
-                if c:
-                    a0 = int(plans[o]["send_cnt"][j][:r].sum())
-                    plans[r]["bufs"]["recvbuf"][ro:ro + c].copy_(plans[o]["bufs"]["sendbuf"][a0:a0 + c])
-                    moved += c
-                ro += c
+            assert plans[r]["recv_cnt"][j].tolist() == [int(c[r]) for c in cnts], (j, r)
+            moved += runs[r].wshard_place_step(plans[r], sent, cnts)
         for r in range(G):
-            _lib.check(lib.tpnet_wshard_step(plans[r]["handle"], None, j, PH_UNPACK, outs[r][0].data_ptr(), outs[r][1].data_ptr(),
-                                             runs[r].rp._stream()), "step")
+            runs[r].wshard_step(plans[r], j, PH_UNPACK, *outs[r])
     for r in range(G):
-        _lib.check(lib.tpnet_wshard_finish(plans[r]["handle"], runs[r].rp._next_launch_ids(1), runs[r].rp._stream()), "finish")
+        runs[r].wshard_finish(plans[r])
         lib.tpnet_wshard_destroy(plans[r]["handle"])
-        rp = runs[r].rp
-        rp._advanced(float(dt[-1].item()))
+        runs[r].rp._advanced(float(dt[-1].item()))
     torch.cuda.synchronize()
     return outs, moved, plans[0]["nsteps"]
 

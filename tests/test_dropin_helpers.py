@@ -168,7 +168,7 @@ def test_bare_table_has_every_field_of_the_constructor():
     _bare_table(bare, 6, 2, "cpu")
     assert set(full.__dict__) <= set(bare.__dict__), set(full.__dict__) - set(bare.__dict__)
     engine_side = ("_eng", "_engine_valid", "_params_valid", "_param_sig", "_now_host", "_launch_id", "_now_dirty", "_params_exposed",
-                   "_table_sig", "_sig_counter", "_plan_tag")
+                   "_table_sig", "_sig_counter", "_plan_tag", "_rows_plan_sig")
     fresh = RandomProjectionModule.__new__(RandomProjectionModule)
     fresh._init_engine_side(0.0)
     assert set(fresh.__dict__) == set(engine_side)

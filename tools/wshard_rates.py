@@ -5,7 +5,6 @@ live in one process and run ONE AFTER THE OTHER, so every figure is what ONE ran
 rows a rank sends / receives per launch -- on the windowed shard (csrc/wshard.hip) and on the per-batch shard (csrc/rows_rccl.hip)
 for the same stream.  Rows move by plain copies between the shards' buffers (no wire time: that is the part a one-GPU box cannot
 measure).  usage: python tools/wshard_rates.py [batches] [config]"""
-import ctypes as C
 import os
 import sys
 import time
@@ -15,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from tpnet_amd import _lib
-from tpnet_amd.sharded import ShardedStreamRunner
+from tpnet_amd.sharded import PH_LAUNCH, PH_PACK, PH_UNPACK, ShardedStreamRunner
 from tpnet_amd.stream import CONFIGS, synthetic_stream, synthetic_negatives, bytes_per_edge
 
 nbt = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -23,8 +22,16 @@ cfg = CONFIGS[sys.argv[2] if len(sys.argv) > 2 else "C2"]
 B1, d, L = cfg["B"], cfg["d"], 3
 dev = torch.device("cuda:0")
 lib = _lib.load()
-PH_LAUNCH, PH_PACK, PH_UNPACK = 1, 2, 8
-ev = lambda: torch.cuda.Event(enable_timing=True)
+
+
+def timed_us(phase, *args):
+    """One phase of one shard between two events, waited for: its GPU time in us."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    phase(*args)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3
 
 
 def run(G, reps=4):
@@ -52,45 +59,20 @@ def run(G, reps=4):
         nst = plans[0]["nsteps"]
         k_us = np.zeros((G, nst)); x_us = np.zeros((G, nst))
         for r in range(G):
-            _lib.check(lib.tpnet_wshard_begin(plans[r]["handle"], None, PH_PACK, runs[r].rp._stream()), "begin")
+            runs[r].wshard_begin(plans[r])
         for r in range(G):
-            rp = runs[r].rp
-            p0_t = rp._plist()[0].data
-            q_t = rp._eng["q"].view(2, rp.node_num, L * d)
-            for o in range(G):
-                c = int(plans[r]["chunk_cnt"][o])
-                if o != r and c:
-                    a0 = runs[r].n_cap + int(plans[r]["hstart"][o])
-                    p0_t[a0:a0 + c].copy_(plans[o]["bufs"]["send_p0"][:c])
-                    q_t[0, a0:a0 + c].copy_(plans[o]["bufs"]["send_q"][:c])
+            runs[r].wshard_place_halo(plans[r], [(p["bufs"]["send_p0"], p["bufs"]["send_q"]) for p in plans])
+        sent_bufs = [(p["bufs"]["sendbuf"],) for p in plans]
         for j in range(nst):
             for r in range(G):
-                e0, e1, e2 = ev(), ev(), ev()
-                e0.record()
-                _lib.check(lib.tpnet_wshard_step(plans[r]["handle"], None, j, PH_LAUNCH, outs[r][0].data_ptr(), outs[r][1].data_ptr(), runs[r].rp._stream()), "step")
-                e1.record()
-                _lib.check(lib.tpnet_wshard_step(plans[r]["handle"], None, j, PH_PACK, outs[r][0].data_ptr(), outs[r][1].data_ptr(), runs[r].rp._stream()), "step")
-                e2.record()
-                torch.cuda.synchronize()
-                k_us[r, j] = e0.elapsed_time(e1) * 1e3
-                x_us[r, j] = e1.elapsed_time(e2) * 1e3
+                k_us[r, j] = timed_us(runs[r].wshard_step, plans[r], j, PH_LAUNCH, *outs[r])
+                x_us[r, j] = timed_us(runs[r].wshard_step, plans[r], j, PH_PACK, *outs[r])
             for r in range(G):
-                ro = 0
-                for o in range(G):
-                    c = int(plans[r]["recv_cnt"][j][o])
-                    if c:
-                        a0 = int(plans[o]["send_cnt"][j][:r].sum())
-                        plans[r]["bufs"]["recvbuf"][ro:ro + c].copy_(plans[o]["bufs"]["sendbuf"][a0:a0 + c])
-                    ro += c
+                runs[r].wshard_place_step(plans[r], sent_bufs, [p["send_cnt"][j] for p in plans])
             for r in range(G):
-                e0, e1 = ev(), ev()
-                e0.record()
-                _lib.check(lib.tpnet_wshard_step(plans[r]["handle"], None, j, PH_UNPACK, outs[r][0].data_ptr(), outs[r][1].data_ptr(), runs[r].rp._stream()), "step")
-                e1.record()
-                torch.cuda.synchronize()
-                x_us[r, j] += e0.elapsed_time(e1) * 1e3
+                x_us[r, j] += timed_us(runs[r].wshard_step, plans[r], j, PH_UNPACK, *outs[r])
         for r in range(G):
-            _lib.check(lib.tpnet_wshard_finish(plans[r]["handle"], runs[r].rp._next_launch_ids(1), runs[r].rp._stream()), "finish")
+            runs[r].wshard_finish(plans[r])
         torch.cuda.synchronize()
         sent = np.array([p["send_cnt"].sum() for p in plans], dtype=np.float64)
         halo = np.array([p["halo"] for p in plans], dtype=np.float64)
@@ -117,7 +99,7 @@ def run(G, reps=4):
 
 
 def run_batch(G, reps=4):
-    """The same stream on the PER-BATCH shard (tpnet_pack_split + tpnet_step_batch per batch, rows moved by plain copies): the plan
+    """The same stream on the PER-BATCH shard (pack_batch + step_batch per batch, rows moved by plain copies): the plan
     of a call (exchange plan + per-batch plan of the kernels, wall clock) and the launches, per rank."""
     Bg = B1 * G
     E = nbt * Bg
@@ -142,43 +124,17 @@ def run_batch(G, reps=4):
             plan_us.append((time.perf_counter() - t0) * 1e6)
             cb.append(c)
         k_us = np.zeros(G); x_us = np.zeros(G)
+        sent_bufs = [(c["send_p0"], c["send_q"]) for c in cb]
         for b in range(nb):
-            now = cb[0]["now"] if b == 0 else float(cb[0]["t_last"][b - 1])
             for r in range(G):
-                c = cb[r]
-                e0, e1 = ev(), ev()
-                e0.record()
-                _lib.check(lib.tpnet_pack_split(C.byref(c["st"]), c["R"]["pack_ids"].data_ptr() + 8 * int(c["sstart"][b]), int(c["stot"][b]), now,
-                                                c["lam"], c["send_p0"].data_ptr(), c["send_q"].data_ptr(), runs[r].n_cap, int(c["rtot"][b]),
-                                                c["stream"]), "pack_split")
-                e1.record()
-                torch.cuda.synchronize()
-                x_us[r] += e0.elapsed_time(e1) * 1e3
+                x_us[r] += timed_us(runs[r].pack_batch, cb[r], b)
             for r in range(G):
-                c = cb[r]
-                rp = runs[r].rp
-                n_cap = runs[r].n_cap
-                ro = 0
-                for o in range(G):
-                    n = int(c["rcnt"][b][o])
-                    if n:
-                        a0 = int(cb[o]["scnt"][b][:r].sum())
-                        rp._plist()[0].data[n_cap + ro:n_cap + ro + n].copy_(cb[o]["send_p0"][a0:a0 + n])
-                        rp._eng["q"].view(2, rp.node_num, L * d)[0, n_cap + ro:n_cap + ro + n].copy_(cb[o]["send_q"][a0:a0 + n])
-                    ro += n
+                runs[r].place_batch(sent_bufs, [c["R"]["send_cnt"][b] for c in cb])
             for r in range(G):
-                c = cb[r]
-                e0, e1 = ev(), ev()
-                e0.record()
-                _lib.check(lib.tpnet_step_batch(C.byref(c["st"]), c["ls"].data_ptr(), c["ld"].data_ptr(), c["ln"].data_ptr(), c["t"].data_ptr(),
-                                                E, Bg, b, c["lam"], c["lid0"] + b, c["flags"], 0, runs[r].n_cap, c["out_pos"].data_ptr(),
-                                                c["out_neg"].data_ptr(), c["ws"].data_ptr(), c["ws"].numel(), c["stream"]), "step_batch")
-                e1.record()
-                torch.cuda.synchronize()
-                k_us[r] += e0.elapsed_time(e1) * 1e3
+                k_us[r] += timed_us(runs[r].step_batch, cb[r], b)
         for r in range(G):
             runs[r].finish_targeted(cb[r], merge_outputs=False)
-        sent = max(float(c["stot"].sum()) for c in cb)
+        sent = max(float(c["R"]["stot"].sum()) for c in cb)
         if rep >= 1:
             res.append((max(plan_us), k_us.max(), x_us.max(), sent))
     med = lambda i: float(np.median([x[i] for x in res]))

@@ -241,7 +241,8 @@ class RandomProjectionModule(nn.Module):
             _params_exposed=False,            # the ParameterList was handed out since the last import (see __getattr__)
             _table_sig=0,                     # identifies the table's per-node (copy, reference time) state (plan replay)
             _sig_counter=1,
-            _plan_tag=None)                   # _lib.PlanTag of the plan the stream workspace holds
+            _plan_tag=None,                   # _lib.PlanTag of the plan the stream workspace holds
+            _rows_plan_sig=None)              # what the row shard's per-batch plan there was made from (tpnet_amd/sharded.py)
 
     def _plist(self):
         # the Parameter OBJECTS of the list are stable (`.data = ...`, `.to()`, load_state_dict keep them), so they are

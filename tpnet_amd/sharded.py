@@ -118,6 +118,91 @@ def exchange_rows(send: torch.Tensor, maxc: int, group=None):
     return recv
 
 
+PH_LAUNCH, PH_PACK, PH_EXCHANGE, PH_UNPACK = 1, 2, 4, 8    # phase bits of tpnet_wshard_begin / tpnet_wshard_step (csrc/wshard.hip)
+
+
+def batch_count(E: int, B: int) -> int:
+    return (E + B - 1) // B
+
+
+def batch_clocks(t, E: int, B: int, t_host_last=None, end_only: bool = False):
+    """The clock at the end of every batch, float64 [nb]: the caller's `t_host_last`, else ONE gather of t at the batches' last
+    edges.  end_only: the call's last clock alone, as a float (no gather: t[-1])."""
+    if t_host_last is not None:
+        t_last = np.ascontiguousarray(t_host_last, dtype=np.float64)
+        return float(t_last[-1]) if end_only else t_last
+    if end_only:
+        return float(t[-1].item())
+    last_idx = torch.clamp(torch.arange(1, batch_count(E, B) + 1, device=t.device) * B, max=E) - 1
+    return np.ascontiguousarray(t[last_idx].cpu().numpy(), dtype=np.float64)
+
+
+def bad_id(N: int):
+    return IndexError(f"node id out of range for {N} nodes")
+
+
+def check_ids(N: int, src, dst, neg=None):
+    """IndexError unless every endpoint is in [0, N) (the lists key on batch * N + node: a bad id would alias)."""
+    ends = [src, dst] + ([neg] if neg is not None else [])
+    if int(torch.stack([x.min() for x in ends]).min()) < 0 or int(torch.stack([x.max() for x in ends]).max()) >= N:
+        raise bad_id(N)
+
+
+def output_buffers(E: int, NG: int, dev, have_neg: bool, out_pos=None, out_neg=None, zero: bool = False, alloc=torch.zeros):
+    """(out_pos, out_neg) of a call: fresh [E, NG] buffers from `alloc`, or the caller's after a check -- zeroed if `zero` (a merge
+    follows: it sums disjoint rows over zeros), else left as they are.  out_neg is None without negatives."""
+    for name, o in (("out_pos", out_pos), ("out_neg", out_neg)):
+        if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or tuple(o.shape) != (E, NG)):
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({E}, {NG}) on {dev}")
+    outs = []
+    for o, wanted in ((out_pos, True), (out_neg, have_neg)):
+        if not wanted:
+            o = None
+        elif o is None:
+            o = alloc((E, NG), dtype=torch.float32, device=dev)
+        elif zero:
+            o.zero_()
+        outs.append(o)
+    return outs[0], outs[1]
+
+
+def place_rows(dst, row0: int, bufs, send_cnt, me: int, shared: bool = False) -> int:
+    """THE placement of rows that arrive without RCCL.  bufs[o]: owner o's send buffers (a tuple, one tensor per tensor of `dst`;
+    not looked at where o sends this rank nothing); send_cnt[o][r]: how many rows o packed for reader r in this step.  What o packed
+    for reader `me` sits behind what it packed for the readers < me (shared: every reader gets the same rows, from row 0 on); it
+    lands behind what the owners < o sent, from row `row0` of every tensor of `dst` on.  Returns the rows placed."""
+    row = row0
+    for o, cnt in enumerate(send_cnt):
+        c = int(cnt[me])
+        if c:
+            a0 = 0 if shared else int(np.sum(cnt[:me]))
+            for d_, s_ in zip(dst, bufs[o]):
+                d_[row:row + c].copy_(s_[a0:a0 + c])
+            row += c
+    return row - row0
+
+
+class _StepTimer:
+    """Three HIP events per step of a loop (measurement only; `timing` None: nothing is recorded): mark(j, 0..2) around the step's two
+    parts, report() -> timing's total_ms / batches and the two parts' averages under the names the loop gives them."""
+
+    def __init__(self, timing, steps: int, dev):
+        self.timing, self.cur = timing, torch.cuda.current_stream(dev) if timing is not None else None
+        self.evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(steps)] if timing is not None else []
+
+    def mark(self, j: int, k: int):
+        if self.evs:
+            self.evs[j][k].record(self.cur)
+
+    def report(self, first: str, second: str):
+        evs = self.evs
+        if evs:
+            evs[-1][2].synchronize()
+            self.timing.update({"total_ms": evs[0][0].elapsed_time(evs[-1][2]), "batches": len(evs),
+                                first: sum(e[0].elapsed_time(e[1]) for e in evs) / len(evs),
+                                second: sum(e[1].elapsed_time(e[2]) for e in evs) / len(evs)})
+
+
 class ShardedStreamRunner:
     """ROW shard of the table (BASELINE.json north_star: "shards row-wise ... all-gather only for cross-shard neighbour
     rows").  Rank `me` of G holds ONLY the rows n with n % G == me -- all L+1 layers, local row n // G -- in a compact
@@ -129,6 +214,17 @@ class ShardedStreamRunner:
 
     exchange = "allgather"     # "allgather" (v1: every touched row to every rank) | "targeted" (v2: each row only to the ranks
                                # that read it, received in place: run_stream_targeted); both with RCCL called from C
+
+    # State kept across calls: None until first used.  (Defaults on the class, not assignments in the constructor: tests and tools
+    # also make a bare runner with object.__new__ and set only what a planner reads.)
+    _comm = None               # the C-side RCCL communicator; False: asked for, not to be had (_c_comm)
+    _xplan_cache = None        # (stream signature, exchange plan R, _Held of its tensors) of the last stream (_exchange_plan)
+    _pending_status = None     # (pinned buffer, event, offset) of a one-rank exchange plan's status words still in flight
+    _pin = None                # _kept: the pinned host buffer + event of an exchange plan's read-back
+    _xplan_scratch = None      # _kept: device scratch of tpnet_xplan_targeted
+    _xplan_scratch_l = None    # _kept: device scratch of tpnet_xplan_targeted_large
+    _send_bufs = None          # _kept: the per-batch shard's two send buffers
+    _wshard_bufs = None        # _kept: the windowed shard's exchange buffers
 
     def __init__(self, rp_local, node_num: int, halo_rows: int, group=None, world=None, rank=None):
         self.rp = rp_local
@@ -198,9 +294,11 @@ class ShardedStreamRunner:
         unpack -> step is ONE FFI call (tpnet_rows_step) instead of three plus a torch.distributed collective.  The
         128-byte unique id travels over the existing process group.  None if the group is not on RCCL or RCCL cannot be
         resolved (the runner then issues the collective through torch.distributed)."""
-        if hasattr(self, "_comm"):
-            return self._comm
-        self._comm = None
+        if self._comm is None:
+            self._comm = self._make_c_comm() or False
+        return self._comm or None
+
+    def _make_c_comm(self):
         if os.environ.get("TPNET_ROWS_C_LOOP", "1") == "0" or dist.get_backend(self.group) != "nccl":
             return None
         lib = _lib.load()
@@ -224,15 +322,15 @@ class ShardedStreamRunner:
         good = torch.tensor([1 if rc == 0 else 0], dtype=torch.int32, device=dev)
         dist.all_reduce(good, op=dist.ReduceOp.MIN, group=self.group)      # all ranks take the same path
         if int(good.item()) == 1:
-            self._comm = h
-        elif rc == 0:
+            return h
+        if rc == 0:
             lib.tpnet_rccl_comm_destroy(h)
-        return self._comm
+        return None
 
     def close(self):
-        if getattr(self, "_comm", None):
+        if self._comm:
             _lib.load().tpnet_rccl_comm_destroy(self._comm)
-            self._comm = None
+            self._comm = False
 
     def __enter__(self):
         return self
@@ -246,13 +344,61 @@ class ShardedStreamRunner:
         except Exception:       # interpreter shutdown: the runtime may be gone already
             pass
 
+    # ---- small things every path of a call shares ---------------------------------------------------------------------------
+    def _kept(self, name: str, key, need, make):
+        """The scratch kept in attribute `name`, or a new one: kept while it was made for `key` (device, world size ...) and every
+        size of it is at least `need`'s; else make(*sizes) with each size the larger of `need`'s and the kept one's -- scratch lives
+        across calls and only ever grows (an allocation per call sat inside every timed region)."""
+        cur = getattr(self, name)
+        if cur is not None and cur[0] == key:
+            if all(h >= n for h, n in zip(cur[1], need)):
+                return cur[2]
+            need = tuple(max(h, n) for h, n in zip(cur[1], need))
+        made = make(*need)
+        setattr(self, name, (key, tuple(need), made))
+        return made
+
+    def _resolve_comm(self, comm):
+        """comm="auto": the C-side RCCL communicator of this shard's process group (None if it is not on RCCL); else the handle the
+        caller made (tests/loopback).  -> (comm, whether the rows travel by RCCL)."""
+        if comm != "auto":
+            return comm, comm is not None
+        nccl = self.G > 1 and not self.detached and dist.get_backend(self.group) == "nccl"
+        return (self._c_comm() if nccl else None), nccl
+
+    def _merge(self, out_pos, out_neg, merge_outputs: bool):
+        """The ranks' outputs are disjoint rows over zeros: one all-reduce merges them (a detached shard's driver does it itself)."""
+        if self.G > 1 and merge_outputs and not self.detached:
+            dist.all_reduce(out_pos, group=self.group)
+            if out_neg is not None:
+                dist.all_reduce(out_neg, group=self.group)
+        return out_pos, out_neg
+
+    def _halo_dst(self):
+        """Where whole rows that arrive land: layer 0 of the local table and copy 0 of layers 1..L, each [n_cap + H, .]."""
+        rp = self.rp
+        return rp._plist()[0].data, rp._eng["q"].view(2, rp.node_num, rp.num_layer * rp.dim)[0]
+
+    def _gather_rows(self, srcs, n: int, pads, gathered):
+        """The torch.distributed transport of both shards: the first n rows of every send buffer, padded to the ranks' common
+        size, all-gathered -> [(owner 0's buffers), (owner 1's), ...] as place_rows takes them."""
+        for s_, p_, g_ in zip(srcs, pads, gathered):
+            p_[:n].copy_(s_[:n])
+            dist.all_gather(g_, p_, group=self.group)
+        return list(zip(*gathered))
+
+    def _gather_buffers(self, rows: int, widths):
+        dev = self.rp._dev()
+        pads = [torch.zeros((rows, w), dtype=torch.float32, device=dev) for w in widths]
+        return pads, [[torch.empty_like(p_) for _ in range(self.G)] for p_ in pads]
+
     # ---- the stream -----------------------------------------------------------------------------------------------
     def relabel(self, src, dst, neg, batch_size: int):
         """Everything the per-batch loop needs, derived from the stream by every rank on its own (no request round):
         the touched-node lists, the local id of every list entry and of every edge endpoint, the rows to pack."""
         G, me, N, n_cap = self.G, self.me, self.N, self.n_cap
         E, B = int(src.numel()), int(batch_size)
-        nb = (E + B - 1) // B
+        nb = batch_count(E, B)
         dev = src.device
         nodes, counts, offsets = plan_touched(src, dst, neg, B, N, G)
         tot = counts.sum(axis=1)
@@ -293,22 +439,17 @@ class ShardedStreamRunner:
         lib = _lib.load()
         dev = rp._dev()
         E, B = int(src.numel()), int(batch_size)
-        nb = (E + B - 1) // B
+        nb = batch_count(E, B)
         L, d = rp.num_layer, rp.dim
         bundle = (L + 1) * d
-        NG = rp.pair_wise_feature_dim
         lam = float(rp.time_decay_weight)
-        out_pos = torch.zeros((E, NG), dtype=torch.float32, device=dev)
-        out_neg = torch.zeros((E, NG), dtype=torch.float32, device=dev) if neg is not None else None
+        out_pos, out_neg = output_buffers(E, rp.pair_wise_feature_dim, dev, neg is not None)
         if E == 0:
             return out_pos, out_neg
-        ends = [src, dst] + ([neg] if neg is not None else [])      # (the lists key on batch * N + node: a bad id would alias)
-        if int(torch.stack([x.min() for x in ends]).min()) < 0 or int(torch.stack([x.max() for x in ends]).max()) >= self.N:
-            raise IndexError(f"node id out of range for {self.N} nodes")
+        check_ids(self.N, src, dst, neg)
         R = self.relabel(src, dst, neg, B)
         counts, offsets, tot = R["counts"], R["offsets"], R["tot"]
-        last_idx = torch.clamp(torch.arange(1, nb + 1, device=dev) * B, max=E) - 1
-        t_last = t[last_idx].cpu().numpy() if t_host_last is None else np.asarray(t_host_last, dtype=np.float64)
+        t_last = batch_clocks(t, E, B, t_host_last)
         ws = rp._workspace(E, B)
         st = rp._state()
         stream = rp._stream()
@@ -373,13 +514,23 @@ class ShardedStreamRunner:
                 _lib.check(rc, "step_batch")
             now = t_last_l[b]
         rp._advanced(now)
-        if G > 1 and merge_outputs:
-            dist.all_reduce(out_pos, group=self.group)          # disjoint rows: the sum is a merge
-            if out_neg is not None:
-                dist.all_reduce(out_neg, group=self.group)
-        return out_pos, out_neg
+        return self._merge(out_pos, out_neg, merge_outputs)
 
     # ---- targeted exchange (v2) ------------------------------------------------------------------------------------
+    def _finished_plan(self, R, sstart=None):
+        """THE exchange plan of a stream as everything downstream reads it.  R holds the message sizes send_cnt / recv_cnt [nb, G],
+        the packing list pack_ids and the relabelled src / dst / neg (the torch plan: its lists too); added here: the rows sent and
+        received per batch stot / rtot, where a batch's part of pack_ids starts (sstart: given, else the batches' parts follow one
+        another) and the largest batch's send rows smax.  The one check that a batch's rows fit the halo."""
+        R["send_cnt"] = np.ascontiguousarray(R["send_cnt"], dtype=np.int64)
+        R["recv_cnt"] = np.ascontiguousarray(R["recv_cnt"], dtype=np.int64)
+        stot, rtot = R["send_cnt"].sum(axis=1), R["recv_cnt"].sum(axis=1)
+        if rtot.size and int(rtot.max()) > self.H:
+            raise ValueError(f"a batch reads {int(rtot.max())} rows of other ranks but the shard has {self.H} halo rows")
+        R.update(stot=stot, rtot=rtot, smax=max(int(stot.max()) if stot.size else 0, 1),
+                 sstart=np.ascontiguousarray(np.concatenate([[0], np.cumsum(stot)[:-1]]) if sstart is None else sstart, dtype=np.int64))
+        return R
+
     def relabel_targeted(self, src, dst, neg, batch_size: int):
         """plan_targeted + the local id of every edge endpoint: owned -> n // G; a remote node this rank receives in the
         edge's batch -> its halo row (n_cap + position in the batch's receive list); any other remote node -> the first halo
@@ -387,13 +538,9 @@ class ShardedStreamRunner:
         one of its pairs)."""
         G, me, N, n_cap = self.G, self.me, self.N, self.n_cap
         E, B = int(src.numel()), int(batch_size)
-        nb = (E + B - 1) // B
         dev = src.device
-        P = plan_targeted(src, dst, neg, B, N, G, me)
-        rtot = P["recv_cnt"].sum(axis=1)
-        if nb and int(rtot.max()) > self.H:
-            raise ValueError(f"a batch reads {int(rtot.max())} rows of other ranks but the shard has {self.H} halo rows")
-        rstart = np.concatenate([[0], np.cumsum(rtot)[:-1]]).astype(np.int64)
+        P = self._finished_plan(plan_targeted(src, dst, neg, B, N, G, me))
+        rstart = np.concatenate([[0], np.cumsum(P["rtot"])[:-1]]).astype(np.int64)
         slot = torch.arange(P["recv_nodes"].numel(), device=dev) - torch.from_numpy(rstart).to(dev)[P["recv_b"]]
         bidx = torch.arange(E, device=dev, dtype=torch.int64) // B
         keys = P["recv_keys"]
@@ -410,7 +557,7 @@ class ShardedStreamRunner:
             return torch.where(x % G == me, x // G, torch.where(hit, halo, torch.full_like(k, n_cap))).contiguous()
 
         P.update(src=local(src), dst=local(dst), neg=local(neg) if neg is not None else None,
-                 unpack_ids=(n_cap + slot).contiguous(), pack_ids=(P["send_nodes"] // G).contiguous(), rtot=rtot, rstart=rstart)
+                 unpack_ids=(n_cap + slot).contiguous(), pack_ids=(P["send_nodes"] // G).contiguous(), rstart=rstart)
         return P
 
     device_plan = True         # the targeted exchange's plan by tpnet_xplan_targeted (two launches, one read-back) where it applies
@@ -430,26 +577,17 @@ class ShardedStreamRunner:
     def _pinned(self, n_int64: int):
         """A pinned host buffer (+ the event of its last copy) for the one read-back of a cold exchange plan: `tensor.cpu()` was a
         pageable allocation + a blocking copy per call."""
-        pin = self.__dict__.get("_pin")
-        if pin is None or pin[0].numel() < n_int64:
-            pin = (torch.empty(max(n_int64, 1024), dtype=torch.int64).pin_memory(), torch.cuda.Event())
-            self.__dict__["_pin"] = pin
-        return pin
+        return self._kept("_pin", None, (max(n_int64, 1024),),
+                          lambda n: (torch.empty(n, dtype=torch.int64).pin_memory(), torch.cuda.Event()))
 
     def _small_scratch(self, nb, E, have_neg, dev, cap):
-        """Scratch of one exchange plan of the workgroup-per-batch kernel, kept across calls and only ever grown (torch.empty per call
-        was five allocations -- and a call longer than the ones before it paid them inside its timed region)."""
+        """Scratch of one exchange plan of the workgroup-per-batch kernel (torch.empty per call was five allocations -- and a call
+        longer than the ones before it paid them inside its timed region)."""
         G = self.G
-        sc = self.__dict__.get("_xplan_scratch")
-        if sc is None or sc["dev"] != dev or sc["nb"] < nb or sc["E"] < E or sc["G"] != G or (have_neg and sc["lneg"] is None):
-            nb_, E_ = max(nb, sc["nb"] if sc else 0), max(E, sc["E"] if sc else 0)
-            sc = dict(dev=dev, nb=nb_, E=E_, G=G, recv_keys=torch.empty((nb_, cap), dtype=torch.int32, device=dev),
-                      pack_ids=torch.empty((nb_, cap), dtype=torch.int64, device=dev),
-                      tail=torch.empty(nb_ * 2 * G + 1, dtype=torch.int64, device=dev),
-                      lsrc=torch.empty(E_, dtype=torch.int64, device=dev), ldst=torch.empty(E_, dtype=torch.int64, device=dev),
-                      lneg=torch.empty(E_, dtype=torch.int64, device=dev) if (have_neg or (sc and sc["lneg"] is not None)) else None)
-            self.__dict__["_xplan_scratch"] = sc
-        return sc
+        i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)
+        return self._kept("_xplan_scratch", (dev, G), (nb, E, int(have_neg)), lambda nb_, E_, neg_: dict(
+            recv_keys=torch.empty((nb_, cap), dtype=torch.int32, device=dev), pack_ids=i64(nb_, cap), tail=i64(nb_ * 2 * G + 1),
+            lsrc=i64(E_), ldst=i64(E_), lneg=i64(E_) if neg_ else None))
 
     def reserve_stream(self, max_edges: int, batch_size: int, have_neg: bool = True):
         """Size the runner's scratch (exchange plan, read-back buffer) and the module's workspace for run_stream calls of up to
@@ -457,7 +595,7 @@ class ShardedStreamRunner:
         rp = self.rp
         rp._ensure_engine()
         E, B = int(max_edges), int(batch_size)
-        nb = (E + B - 1) // B
+        nb = batch_count(E, B)
         dev = rp._dev()
         lib = _lib.load()
         cap = int(lib.tpnet_xplan_capacity())
@@ -477,13 +615,13 @@ class ShardedStreamRunner:
 
     def _check_pending_status(self):
         """The status words of a one-rank exchange plan whose read-back was left in flight (relabel_targeted_device, G = 1)."""
-        ps = self.__dict__.pop("_pending_status", None)
+        ps, self._pending_status = self._pending_status, None
         if ps is not None:
             pin, ev, off = ps
             ev.synchronize()
             if int(pin[off:off + 1].numpy().view(np.uint32)[0]):
-                self.__dict__["_xplan_cache"] = None
-                raise IndexError(f"node id out of range for {self.N} nodes")
+                self._xplan_cache = None
+                raise bad_id(self.N)
 
     def check_device_errors(self):
         """Raise IndexError if a call met a node id outside [0, node_num) since the last check (the shard's module included)."""
@@ -505,135 +643,100 @@ class ShardedStreamRunner:
             if x.dtype != torch.int64 or not x.is_contiguous() or x.device != src.device:
                 return None
         lib = _lib.load()
-        nb = (E + B - 1) // B
+        nb = batch_count(E, B)
         dev = src.device
         cap = int(lib.tpnet_xplan_capacity())
-        n_tail = nb * 2 * G + 1
+        n_cnt = nb * 2 * G
+        n_tail = n_cnt + 1                   # the message sizes [nb, 2, G], then one word of status
 
-        def read_back(tail):
-            """ONE read-back (message sizes + status) through a pinned buffer: an asynchronous copy + an event, no pageable staging"""
+        def plan(kernel, scratch_args, pack_ids, tail, lsrc, ldst, lneg, wait=True):
+            """One of the two kernels, then ONE read-back (message sizes + status) through a pinned buffer: an asynchronous copy + an
+            event, no pageable staging.  -> None (the kernel declined), or (a batch overflowed, recv_cnt, send_cnt); wait=False
+            leaves the read-back in flight for _check_pending_status."""
+            if kernel(src.data_ptr(), dst.data_ptr(), neg.data_ptr() if neg is not None else None, E, B, N, G, me, n_cap, *scratch_args,
+                      pack_ids.data_ptr(), tail.data_ptr(), tail[n_cnt:].data_ptr(), lsrc.data_ptr(), ldst.data_ptr(),
+                      lneg.data_ptr() if lneg is not None else None, self.rp._stream()):
+                return None
             pin, ev = self._pinned(n_tail)
             pin[:n_tail].copy_(tail, non_blocking=True)
             ev.record(torch.cuda.current_stream(dev))
+            if not wait:
+                self._pending_status = (pin, ev, n_cnt)
+                return False, np.zeros((nb, G), dtype=np.int64), np.zeros((nb, G), dtype=np.int64)
             ev.synchronize()
             host = pin[:n_tail].numpy()
-            st = host[nb * 2 * G:].view(np.uint32)
+            st = host[n_cnt:].view(np.uint32)
             if int(st[0]):
-                raise IndexError(f"node id out of range for {N} nodes")
-            c = host[: nb * 2 * G].reshape(nb, 2, G)
-            return int(st[1]), np.ascontiguousarray(c[:, 0, :]), np.ascontiguousarray(c[:, 1, :])   # (copies: the buffer is reused)
-
-        def result(lsrc, ldst, lneg, recv_cnt, send_cnt, pack_ids, sstart):
-            rtot = recv_cnt.sum(axis=1)
-            if nb and int(rtot.max()) > self.H:
-                raise ValueError(f"a batch reads {int(rtot.max())} rows of other ranks but the shard has {self.H} halo rows")
-            return dict(src=lsrc, dst=ldst, neg=lneg, send_cnt=send_cnt, recv_cnt=recv_cnt, rtot=rtot, pack_ids=pack_ids, sstart=sstart)
+                raise bad_id(N)
+            c = host[:n_cnt].reshape(nb, 2, G)
+            return bool(st[1]), c[:, 0, :].copy(), c[:, 1, :].copy()                 # (copies: the buffer is reused)
 
         # a workgroup per batch while a batch's lists can fit its LDS (at most 3 B items per list); else -- or when a batch
         # overflowed after all -- ONE device-wide sort of the call's keys (tpnet_xplan_targeted_large)
-        small = not self.xplan_force_large and 3 * B <= 4 * cap
-        if small:
+        if not self.xplan_force_large and 3 * B <= 4 * cap:
             sc = self._small_scratch(nb, E, neg is not None, dev, cap)
-            recv_keys, pack_ids, tail = sc["recv_keys"], sc["pack_ids"], sc["tail"][:n_tail]
             lsrc, ldst, lneg = sc["lsrc"][:E], sc["ldst"][:E], (sc["lneg"][:E] if neg is not None else None)
-            cnt, status = tail[: nb * 2 * G], tail[nb * 2 * G:]
-            rc = lib.tpnet_xplan_targeted(src.data_ptr(), dst.data_ptr(), neg.data_ptr() if neg is not None else None, E, B, N, G, me,
-                                          n_cap, recv_keys.data_ptr(), pack_ids.data_ptr(), cnt.data_ptr(), status.data_ptr(),
-                                          lsrc.data_ptr(), ldst.data_ptr(), lneg.data_ptr() if lneg is not None else None,
-                                          self.rp._stream())
-            if rc:
+            # (ONE rank: no message sizes to wait for -- the status words (ids out of range) are read back asynchronously and looked
+            # at by check_device_errors() / the next call; a bad id was relabelled to a halo row, never dereferenced wildly)
+            got = plan(lib.tpnet_xplan_targeted, (sc["recv_keys"].data_ptr(),), sc["pack_ids"], sc["tail"][:n_tail], lsrc, ldst, lneg,
+                       wait=G > 1)
+            if got is None:
                 return None
-            if G == 1:
-                # ONE rank: no message sizes to wait for -- the status words (ids out of range) are read back asynchronously and
-                # looked at by check_device_errors() / the next call; a bad id was relabelled to a halo row, never dereferenced wildly
-                pin, ev = self._pinned(n_tail)
-                pin[:n_tail].copy_(tail, non_blocking=True)
-                ev.record(torch.cuda.current_stream(dev))
-                self.__dict__["_pending_status"] = (pin, ev, nb * 2 * G)
-                z = np.zeros((nb, 1), dtype=np.int64)
-                return result(lsrc, ldst, lneg, z, z.copy(), pack_ids.view(-1), np.arange(nb, dtype=np.int64) * cap)
-            over, recv_cnt, send_cnt = read_back(tail)
-            if not over:
-                return result(lsrc, ldst, lneg, recv_cnt, send_cnt, pack_ids.view(-1), np.arange(nb, dtype=np.int64) * cap)
+            if not got[0]:
+                return self._finished_plan(dict(src=lsrc, dst=ldst, neg=lneg, recv_cnt=got[1], send_cnt=got[2],
+                                                pack_ids=sc["pack_ids"].view(-1)), sstart=np.arange(nb, dtype=np.int64) * cap)
         if 6 * E >= (1 << 32):
             return None
-        need = int(lib.tpnet_xplan_large_bytes(E, B, G))
-        key = ("l", nb, G, E, neg is not None, dev)
-        sc = self.__dict__.get("_xplan_scratch_l")
-        if sc is None or sc[0] != key:
-            sc = (key, torch.empty(need, dtype=torch.uint8, device=dev), torch.empty(3 * E, dtype=torch.int64, device=dev),
-                  torch.empty(n_tail, dtype=torch.int64, device=dev), torch.empty(E, dtype=torch.int64, device=dev),
-                  torch.empty(E, dtype=torch.int64, device=dev), torch.empty(E, dtype=torch.int64, device=dev) if neg is not None else None)
-            self.__dict__["_xplan_scratch_l"] = sc
-        _, scratch, pack_ids, tail, lsrc, ldst, lneg = sc
-        cnt, status = tail[: nb * 2 * G], tail[nb * 2 * G:]
-        rc = lib.tpnet_xplan_targeted_large(src.data_ptr(), dst.data_ptr(), neg.data_ptr() if neg is not None else None, E, B, N, G, me,
-                                            n_cap, scratch.data_ptr(), scratch.numel(), pack_ids.data_ptr(), cnt.data_ptr(),
-                                            status.data_ptr(), lsrc.data_ptr(), ldst.data_ptr(),
-                                            lneg.data_ptr() if lneg is not None else None, self.rp._stream())
-        if rc:
+        i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)
+        scratch, pack_ids, tail, lsrc, ldst, lneg = self._kept(
+            "_xplan_scratch_l", ("l", nb, G, E, neg is not None, dev), (),
+            lambda: (torch.empty(int(lib.tpnet_xplan_large_bytes(E, B, G)), dtype=torch.uint8, device=dev), i64(3 * E), i64(n_tail),
+                     i64(E), i64(E), i64(E) if neg is not None else None))
+        got = plan(lib.tpnet_xplan_targeted_large, (scratch.data_ptr(), scratch.numel()), pack_ids, tail, lsrc, ldst, lneg)
+        if got is None:
             return None
-        _, recv_cnt, send_cnt = read_back(tail)
-        stot = send_cnt.sum(axis=1)
-        return result(lsrc, ldst, lneg, recv_cnt, send_cnt, pack_ids, np.concatenate([[0], np.cumsum(stot)[:-1]]).astype(np.int64))
+        return self._finished_plan(dict(src=lsrc, dst=ldst, neg=lneg, recv_cnt=got[1], send_cnt=got[2], pack_ids=pack_ids))
 
     # a stream that is run again (same tensors, unchanged: _stream_sig) keeps its exchange plan, its relabelled ids and -- while
     # nothing else used the module's workspace and the clock it starts from is the same -- the plan of its kernels
     reuse_plans = True
 
     def _exchange_plan(self, src, dst, neg, t, B):
-        """The stream's exchange plan and relabelled ids (relabel_targeted), and the _Held of the tensors it was made from: the
+        """The stream's exchange plan and relabelled ids (_finished_plan), and the _Held of the tensors it was made from: the
         cached one if src / dst / neg / t are the very objects it was made from, at the same addresses, unchanged (the plan holds
         the relabelled negatives: a fresh `neg` in the block a freed one left is a new plan)."""
         E = int(src.numel())
         sig = self._stream_sig(src, dst, neg, t, E, B) if self.reuse_plans else None
         owners = _owners(src, dst, neg, t)
-        xc = self.__dict__.get("_xplan_cache")
+        xc = self._xplan_cache
         if sig is not None and xc is not None and xc[0] == sig and xc[2].same(owners):
             return xc[1], xc[2]
         R = self.relabel_targeted_device(src, dst, neg, B) if self.device_plan else None   # (checks the ids' range itself)
         if R is None:
-            ends = [src, dst] + ([neg] if neg is not None else [])  # (the lists key on batch * N + node: a bad id would alias)
-            if int(torch.stack([x.min() for x in ends]).min()) < 0 or int(torch.stack([x.max() for x in ends]).max()) >= self.N:
-                raise IndexError(f"node id out of range for {self.N} nodes")
+            check_ids(self.N, src, dst, neg)
             R = self.relabel_targeted(src, dst, neg, B)
         # (the device plan's lists live in the runner's scratch, which the NEXT cold plan overwrites -- and that plan replaces
         # this one in the one-entry cache at the same time; the module's own plan is dropped below for the same reason)
-        R["scnt"] = np.ascontiguousarray(R["send_cnt"], dtype=np.int64)
-        R["rcnt"] = np.ascontiguousarray(R["recv_cnt"], dtype=np.int64)
-        R["stot"] = R["scnt"].sum(axis=1)
-        R["sstart_"] = np.ascontiguousarray(R["sstart"] if "sstart" in R else
-                                            np.concatenate([[0], np.cumsum(R["stot"])[:-1]]), dtype=np.int64)
-        R["smax"] = max(int(R["stot"].max()), 1)
         held = _Held(owners)
         if sig is not None:
-            self.__dict__["_xplan_cache"] = (sig, R, held)
+            self._xplan_cache = (sig, R, held)
         # a plan the module's workspace still holds was built on OTHER relabelled arrays: nothing may be replayed across a cold
         # exchange plan
         self.rp._drop_plan()
         return R, held
 
-    def _send_buffers(self, d, L, smax, dev):
-        """The pack launch's two send buffers, kept across calls (torch.zeros of both per call sat inside every timed region)."""
-        b = self.__dict__.get("_send_bufs")
-        if b is None or b[0].shape[0] < smax or b[0].device != dev:
-            b = (torch.zeros((smax, d), dtype=torch.float32, device=dev), torch.zeros((smax, L * d), dtype=torch.float32, device=dev))
-            self.__dict__["_send_bufs"] = b
-        return b
-
     def prepare_targeted(self, src, dst, neg, t, batch_size: int, t_host_last=None, comm="auto", out_pos=None, out_neg=None,
                          zero_outputs: bool = True):
         """Everything a stream's per-batch calls need (exchange plan, relabelled ids, per-batch plan of the local kernels, send
-        buffers, outputs).  comm: "auto" = the C-side RCCL communicator of this shard's process group (None if it is not on
-        RCCL); or a communicator handle the caller made (tests/loopback).  out_pos / out_neg: the caller's [E, (2L+2)^2] buffers
+        buffers, outputs).  comm: see _resolve_comm.  out_pos / out_neg: the caller's [E, (2L+2)^2] buffers
         (default: fresh zeroed ones); zero_outputs=False leaves a caller's buffers as they are -- the rows of pairs whose src
         another rank owns then keep what they held (enough where the outputs stay sharded; a merge sums disjoint rows over zeros)."""
-        rp, G, me = self.rp, self.G, self.me
+        rp, G = self.rp, self.G
         rp._ensure_engine()
         lib = _lib.load()
         dev = rp._dev()
         E, B = int(src.numel()), int(batch_size)
-        nb = (E + B - 1) // B
+        nb = batch_count(E, B)
         L, d = rp.num_layer, rp.dim
         NG = rp.pair_wise_feature_dim
         lam = float(rp.time_decay_weight)
@@ -641,69 +744,37 @@ class ShardedStreamRunner:
             z = torch.zeros((0, NG), dtype=torch.float32, device=dev)
             return dict(E=0, B=B, nb=0, out_pos=z, out_neg=z.clone() if neg is not None else None, now=rp._now_host)
         self._check_pending_status()
-        if G == 1 and self.single_rank_pipeline and not rp.exact and src.is_cuda:
-            # ONE rank: every id is its own local row and nothing travels -- no exchange plan; the stream runs on the module's own
-            # schedules (the windowed pipeline from 16 batches on), which count ids out of range themselves (check_device_errors)
-            for name, o in (("out_pos", out_pos), ("out_neg", out_neg)):
-                if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or tuple(o.shape) != (E, NG)):
-                    raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({E}, {NG}) on {dev}")
-            if out_pos is None:
-                out_pos = torch.empty((E, NG), dtype=torch.float32, device=dev)
-            if neg is None:
-                out_neg = None
-            elif out_neg is None:
-                out_neg = torch.empty((E, NG), dtype=torch.float32, device=dev)
-            t_end = float(np.asarray(t_host_last, dtype=np.float64)[-1]) if t_host_last is not None else float(t[-1].item())
-            return dict(E=E, B=B, nb=nb, out_pos=out_pos, out_neg=out_neg, now=rp._now_host, ls=src, ld=dst, ln=neg, t=t,
-                        t_last=np.array([t_end], dtype=np.float64), windowed=True, comm=None, nccl=False)
-        R, held = self._exchange_plan(src, dst, neg, t, B)
-        if t_host_last is None:
-            last_idx = torch.clamp(torch.arange(1, nb + 1, device=dev) * B, max=E) - 1
-            t_last = t[last_idx].cpu().numpy()
-        else:
-            t_last = np.asarray(t_host_last, dtype=np.float64)
-        for name, o in (("out_pos", out_pos), ("out_neg", out_neg)):
-            if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or tuple(o.shape) != (E, NG)):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({E}, {NG}) on {dev}")
-        if out_pos is None:
-            out_pos = torch.zeros((E, NG), dtype=torch.float32, device=dev)
-        elif zero_outputs:
-            out_pos.zero_()
-        if neg is None:
-            out_neg = None
-        elif out_neg is None:
-            out_neg = torch.zeros((E, NG), dtype=torch.float32, device=dev)
-        elif zero_outputs:
-            out_neg.zero_()
-        send_p0, send_q = self._send_buffers(d, L, R["smax"], dev)
-        ctx = dict(E=E, B=B, nb=nb, out_pos=out_pos, out_neg=out_neg, now=rp._now_host)
+        single = G == 1 and self.single_rank_pipeline and not rp.exact
+        if not (single and src.is_cuda):           # (one rank, ids on the GPU: every id is its own local row -- nothing to plan)
+            R, held = self._exchange_plan(src, dst, neg, t, B)
+        if single:
+            # ONE rank: no halo, no exchange -- the stream runs whole on the module's own schedules (the windowed pipeline from 16
+            # batches on: RandomProjectionModule.run_stream in steps_targeted), which count ids out of range themselves
+            # (check_device_errors) and write every output row (no zeros needed)
+            ls, ld, ln = (src, dst, neg) if src.is_cuda else (R["src"], R["dst"], R["neg"])
+            out_pos, out_neg = output_buffers(E, NG, dev, neg is not None, out_pos, out_neg, alloc=torch.empty)
+            return dict(E=E, B=B, nb=nb, out_pos=out_pos, out_neg=out_neg, now=rp._now_host, ls=ls, ld=ld, ln=ln, t=t,
+                        t_last=np.array([batch_clocks(t, E, B, t_host_last, end_only=True)]), windowed=True, comm=None, nccl=False)
+        t_last = batch_clocks(t, E, B, t_host_last)
+        out_pos, out_neg = output_buffers(E, NG, dev, neg is not None, out_pos, out_neg, zero_outputs)
+        f32 = lambda n, w: torch.zeros((n, w), dtype=torch.float32, device=dev)
+        send_p0, send_q = self._kept("_send_bufs", dev, (R["smax"],), lambda n: (f32(n, d), f32(n, L * d)))   # the pack launch's send buffers
         flags = rp._readout_flags()
-        ls, ld, ln = R["src"], R["dst"], R["neg"]
-        if comm == "auto":
-            nccl = G > 1 and not self.detached and dist.get_backend(self.group) == "nccl"
-            comm = self._c_comm() if nccl else None
-        else:
-            nccl = comm is not None
-        ctx.update(R=R, t_last=np.ascontiguousarray(t_last, dtype=np.float64), flags=flags, lam=lam, ls=ls, ld=ld, ln=ln, t=t,
-                   scnt=R["scnt"], rcnt=R["rcnt"], stot=R["stot"], rtot=R["rtot"], sstart=R["sstart_"], send_p0=send_p0, send_q=send_q,
-                   comm=comm, nccl=nccl, windowed=False)
-        if G == 1 and self.single_rank_pipeline and not rp.exact:
-            # ONE rank: no halo, no exchange -- the stream takes the module's own schedules (the windowed pipeline from 16 batches on)
-            # on the relabelled ids: RandomProjectionModule.run_stream in steps_targeted
-            ctx["windowed"] = True
-            return ctx
+        ls, ld = R["src"], R["dst"]
+        comm, nccl = self._resolve_comm(comm)
         ws = rp._workspace(E, B, keep_plan=True)
         st = rp._state()
         stream = rp._stream()
         # (the kernels' plan is a function of the relabelled arrays -- the exchange plan `held` names -- t, the clock and the flags)
         psig = (held.gen, rp._now_host, lam, flags, ws.data_ptr(), ws.numel()) if self.reuse_plans else None
-        if psig is None or rp.__dict__.get("_rows_plan_sig") != psig:
+        if psig is None or rp._rows_plan_sig != psig:
             rp._drop_plan()
             _lib.check(lib.tpnet_plan_stream(C.byref(st), ls.data_ptr(), ld.data_ptr(), t.data_ptr(), E, B, rp._now_host,
                                              lam, flags, ws.data_ptr(), ws.numel(), stream), "plan_stream")
-            rp.__dict__["_rows_plan_sig"] = psig
-        ctx.update(ws=ws, st=st, stream=stream, lid0=rp._next_launch_ids(nb))
-        return ctx
+            rp._rows_plan_sig = psig
+        return dict(E=E, B=B, nb=nb, out_pos=out_pos, out_neg=out_neg, now=rp._now_host, R=R, t_last=t_last, flags=flags, lam=lam,
+                    ls=ls, ld=ld, ln=R["neg"], t=t, send_p0=send_p0, send_q=send_q, comm=comm, nccl=nccl, windowed=False,
+                    ws=ws, st=st, stream=stream, lid0=rp._next_launch_ids(nb))
 
     single_rank_pipeline = True     # G = 1: the stream runs on the module's own schedules (no halo rows, no exchange)
     schedule = None                 # ... this one (RandomProjectionModule.run_stream's `schedule`; None: the module's default, "auto")
@@ -724,10 +795,10 @@ class ShardedStreamRunner:
                           replay=None if self.reuse_plans else False)
             return
         lib = _lib.load()
-        ln, on = ctx["ln"], ctx["out_neg"]
-        args = (C.byref(ctx["st"]), ctx["comm"], ctx["R"]["pack_ids"].data_ptr(), ctx["sstart"].ctypes.data,
-                ctx["send_p0"].data_ptr(), ctx["send_q"].data_ptr(), ctx["scnt"].ctypes.data,
-                ctx["rcnt"].ctypes.data, self.G, self.me, ctx["now"], ctx["t_last"].ctypes.data,
+        R, ln, on = ctx["R"], ctx["ln"], ctx["out_neg"]
+        args = (C.byref(ctx["st"]), ctx["comm"], R["pack_ids"].data_ptr(), R["sstart"].ctypes.data,
+                ctx["send_p0"].data_ptr(), ctx["send_q"].data_ptr(), R["send_cnt"].ctypes.data,
+                R["recv_cnt"].ctypes.data, self.G, self.me, ctx["now"], ctx["t_last"].ctypes.data,
                 ctx["ls"].data_ptr(), ctx["ld"].data_ptr(), ln.data_ptr() if ln is not None else None,
                 ctx["t"].data_ptr(), ctx["E"], ctx["B"], int(b0), int(b1), ctx["lam"], ctx["lid0"],
                 ctx["flags"], self.n_cap, ctx["out_pos"].data_ptr(),
@@ -742,16 +813,34 @@ class ShardedStreamRunner:
         if rc:
             _lib.check(rc, "rows_stream_targeted")
 
+    # The phases of ONE batch of a prepared stream, for whoever moves the rows without the C communicator: run_stream_targeted's
+    # torch.distributed branch below, and the drivers that keep several detached shards in one process (tests/loopback, tools)
+    def pack_batch(self, ctx, b: int):
+        """Pack the owned rows batch b's readers need into ctx's send buffers, decayed to the clock the batch starts from."""
+        R = ctx["R"]
+        now = ctx["now"] if b == 0 else float(ctx["t_last"][b - 1])
+        _lib.check(_lib.load().tpnet_pack_split(C.byref(ctx["st"]), R["pack_ids"].data_ptr() + 8 * int(R["sstart"][b]), int(R["stot"][b]),
+                                                now, ctx["lam"], ctx["send_p0"].data_ptr(), ctx["send_q"].data_ptr(), self.n_cap,
+                                                int(R["rtot"][b]), ctx["stream"]), "pack_split")
+
+    def place_batch(self, bufs, send_cnt):
+        """The rows a batch receives -> its halo rows.  bufs[o] = owner o's (send_p0, send_q), send_cnt[o] = its send counts of the
+        batch (place_rows)."""
+        return place_rows(self._halo_dst(), self.n_cap, bufs, send_cnt, self.me)
+
+    def step_batch(self, ctx, b: int):
+        """The fused kernel of batch b on the local table, restricted to the targets / pairs this rank owns."""
+        ln, on = ctx["ln"], ctx["out_neg"]
+        _lib.check(_lib.load().tpnet_step_batch(C.byref(ctx["st"]), ctx["ls"].data_ptr(), ctx["ld"].data_ptr(),
+                                                ln.data_ptr() if ln is not None else None, ctx["t"].data_ptr(), ctx["E"], ctx["B"], b,
+                                                ctx["lam"], ctx["lid0"] + b, ctx["flags"], 0, self.n_cap, ctx["out_pos"].data_ptr(),
+                                                on.data_ptr() if on is not None else None, ctx["ws"].data_ptr(), ctx["ws"].numel(),
+                                                ctx["stream"]), "step_batch")
+
     def finish_targeted(self, ctx, merge_outputs: bool = True):
-        rp = self.rp
         if ctx["E"] and not ctx.get("windowed"):
-            rp._advanced(float(ctx["t_last"][-1]))
-        out_pos, out_neg = ctx["out_pos"], ctx["out_neg"]
-        if self.G > 1 and merge_outputs and not self.detached:
-            dist.all_reduce(out_pos, group=self.group)
-            if out_neg is not None:
-                dist.all_reduce(out_neg, group=self.group)
-        return out_pos, out_neg
+            self.rp._advanced(float(ctx["t_last"][-1]))
+        return self._merge(ctx["out_pos"], ctx["out_neg"], merge_outputs)
 
     def _agree_windowed(self, planned: bool, failed, release=None) -> bool:
         """All ranks of a call take the windowed shard or none does.  `planned`: this rank's tpnet_wshard_plan served the call;
@@ -781,10 +870,9 @@ class ShardedStreamRunner:
         communicator: the same pack launch, torch.distributed.all_to_all_single into the same rows; gloo in the tests: an
         all-gather of the send buffers from which every rank takes its parts.)  Same results as the all-gather variant; each
         rank receives only what it reads."""
-        rp, G, me = self.rp, self.G, self.me
+        rp, G = self.rp, self.G
         self.last_stream_windowed = False
-        nb_ = (int(src.numel()) + int(batch_size) - 1) // int(batch_size)
-        if self.windowed and G > 1 and nb_ >= self.windowed_min_batches and src.is_cuda:
+        if self.windowed and G > 1 and batch_count(int(src.numel()), int(batch_size)) >= self.windowed_min_batches and src.is_cuda:
             # every rank takes the same decision: tpnet_wshard_plan declines on shapes (all ranks alike) or on counts that all ranks
             # derive from the same stream -- except a batch whose OWNED contributions overflow one rank's sort: agreed on below
             self._check_pending_status()
@@ -808,88 +896,33 @@ class ShardedStreamRunner:
             return self.finish_targeted(ctx, merge_outputs)
         # another transport (torch.distributed all_to_all on RCCL without the C communicator; gloo in the tests): the same
         # pack launch, the rows moved into the same halo rows, the same step
-        lib = _lib.load()
-        dev = rp._dev()
-        E, B, nb = ctx["E"], ctx["B"], ctx["nb"]
-        L, d = rp.num_layer, rp.dim
-        lam, flags, stream, nccl = ctx["lam"], ctx["flags"], ctx["stream"], ctx["nccl"]
-        scnt, rcnt, stot, rtot, sstart = ctx["scnt"], ctx["rcnt"], ctx["stot"], ctx["rtot"], ctx["sstart"]
-        send_p0, send_q = ctx["send_p0"], ctx["send_q"]
-        stp = C.byref(ctx["st"])
-        pack_ptr = ctx["R"]["pack_ids"].data_ptr()
-        ls_p, ld_p, t_p = ctx["ls"].data_ptr(), ctx["ld"].data_ptr(), ctx["t"].data_ptr()
-        ln_p = ctx["ln"].data_ptr() if ctx["ln"] is not None else None
-        op_p = ctx["out_pos"].data_ptr(); on_p = ctx["out_neg"].data_ptr() if ctx["out_neg"] is not None else None
-        ws_p, ws_n = ctx["ws"].data_ptr(), ctx["ws"].numel()
-        lid0, n_cap = ctx["lid0"], self.n_cap
-        t_last_l = [float(x) for x in ctx["t_last"]]
-        now = ctx["now"]
-        p0_t = rp._plist()[0].data                                       # [n_cap + H, d]
-        q_t = rp._eng["q"].view(2, rp.node_num, L * d)                   # copy 0 receives
-        if not nccl:
+        R, nb, n_cap = ctx["R"], ctx["nb"], self.n_cap
+        sends = (ctx["send_p0"], ctx["send_q"])
+        if not ctx["nccl"]:
             all_scnt = [None] * G
-            dist.all_gather_object(all_scnt, scnt, group=self.group)
-            gmax = max(max(int(a.sum(axis=1).max()) for a in all_scnt), 1)
-            g_p0 = [torch.empty((gmax, d), dtype=torch.float32, device=dev) for _ in range(G)]
-            g_q = [torch.empty((gmax, L * d), dtype=torch.float32, device=dev) for _ in range(G)]
-            pad_p0 = torch.zeros((gmax, d), dtype=torch.float32, device=dev)
-            pad_q = torch.zeros((gmax, L * d), dtype=torch.float32, device=dev)
-        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(nb)] if timing is not None else None
-        cur = torch.cuda.current_stream(dev)
+            dist.all_gather_object(all_scnt, R["send_cnt"], group=self.group)
+            gbufs = self._gather_buffers(max(max(int(a.sum(axis=1).max()) for a in all_scnt), 1), [s_.shape[1] for s_ in sends])
+        timer = _StepTimer(timing, nb, rp._dev())
         for b in range(nb):
-            ns, nr = int(stot[b]), int(rtot[b])
-            if evs:
-                evs[b][0].record(cur)
-            _lib.check(lib.tpnet_pack_split(stp, pack_ptr + 8 * int(sstart[b]), ns, now, lam, send_p0.data_ptr(),
-                                            send_q.data_ptr(), n_cap, nr, stream), "pack_split")
-            if nccl:
-                dist.all_to_all_single(p0_t[n_cap:n_cap + nr], send_p0[:ns], output_split_sizes=rcnt[b].tolist(),
-                                       input_split_sizes=scnt[b].tolist(), group=self.group)
-                dist.all_to_all_single(q_t[0, n_cap:n_cap + nr], send_q[:ns], output_split_sizes=rcnt[b].tolist(),
-                                       input_split_sizes=scnt[b].tolist(), group=self.group)
+            timer.mark(b, 0)
+            self.pack_batch(ctx, b)
+            ns, nr = int(R["stot"][b]), int(R["rtot"][b])
+            if ctx["nccl"]:
+                for dst_, s_ in zip(self._halo_dst(), sends):
+                    dist.all_to_all_single(dst_[n_cap:n_cap + nr], s_[:ns], output_split_sizes=R["recv_cnt"][b].tolist(),
+                                           input_split_sizes=R["send_cnt"][b].tolist(), group=self.group)
             else:
-                pad_p0[:ns].copy_(send_p0[:ns]); pad_q[:ns].copy_(send_q[:ns])
-                dist.all_gather(g_p0, pad_p0, group=self.group)
-                dist.all_gather(g_q, pad_q, group=self.group)
-                o = 0
-                for s_ in range(G):                  # rows owner s_ packed for me: after what it packed for readers < me
-                    c = int(rcnt[b][s_])
-                    if c:
-                        a0 = int(all_scnt[s_][b][:me].sum())
-                        p0_t[n_cap + o:n_cap + o + c].copy_(g_p0[s_][a0:a0 + c])
-                        q_t[0, n_cap + o:n_cap + o + c].copy_(g_q[s_][a0:a0 + c])
-                        o += c
-            if evs:
-                evs[b][1].record(cur)
-            _lib.check(lib.tpnet_step_batch(stp, ls_p, ld_p, ln_p, t_p, E, B, b, lam, lid0 + b, flags, 0, n_cap, op_p, on_p,
-                                            ws_p, ws_n, stream), "step_batch")
-            if evs:
-                evs[b][2].record(cur)
-            now = t_last_l[b]
-        if evs:
-            evs[-1][2].synchronize()
-            timing.update(total_ms=evs[0][0].elapsed_time(evs[-1][2]), batches=nb,
-                          step_ms=sum(e[1].elapsed_time(e[2]) for e in evs) / nb,
-                          exchange_ms=sum(e[0].elapsed_time(e[1]) for e in evs) / nb)
+                self.place_batch(self._gather_rows(sends, ns, *gbufs), [a[b] for a in all_scnt])
+            timer.mark(b, 1)
+            self.step_batch(ctx, b)
+            timer.mark(b, 2)
+        timer.report("exchange_ms", "step_ms")
         return self.finish_targeted(ctx, merge_outputs)
 
     # ---- the shard on the windowed pipeline (csrc/wshard.hip) -------------------------------------------------------------------
     windowed = True                 # G > 1: one launch + one exchange per WINDOW of batches where tpnet_wshard_plan serves the call
     windowed_min_batches = 16       # (as the single-GPU schedule: below that the per-batch launches win)
     last_stream_windowed = False
-
-    def _wshard_buffers(self, d, L, n_p0, n_send, n_recv, dev):
-        """The windowed shard's exchange buffers, kept across calls and only ever grown."""
-        b = self.__dict__.get("_wshard_bufs")
-        need = (max(n_p0, 1), max(n_send, 1), max(n_recv, 1))
-        if b is None or b["dev"] != dev or any(x < y for x, y in zip(b["n"], need)):
-            n = tuple(max(x, y) for x, y in zip(b["n"], need)) if (b is not None and b["dev"] == dev) else need
-            b = dict(dev=dev, n=n, send_p0=torch.empty((n[0], d), dtype=torch.float32, device=dev),
-                     send_q=torch.empty((n[0], L * d), dtype=torch.float32, device=dev),
-                     sendbuf=torch.empty((n[1], d), dtype=torch.float32, device=dev),
-                     recvbuf=torch.empty((n[2], d), dtype=torch.float32, device=dev))
-            self.__dict__["_wshard_bufs"] = b
-        return b
 
     def plan_windowed(self, src, dst, neg, t, batch_size: int, want_pos: bool = True, want_neg: bool = True):
         """tpnet_wshard_plan for one call (the whole call is one chunk of the pipeline): a dict with the plan's handle, its counts
@@ -900,7 +933,7 @@ class ShardedStreamRunner:
         dev = rp._dev()
         E, B = int(src.numel()), int(batch_size)
         L, d = rp.num_layer, rp.dim
-        if E == 0 or rp.exact or (E + B - 1) // B < 4:
+        if E == 0 or rp.exact or batch_count(E, B) < 4:
             return None
         for x, dt in ((src, torch.int64), (dst, torch.int64), (t, torch.float64)) + (((neg, torch.int64),) if neg is not None else ()):
             if x.device != dev or x.dtype != dt or not x.is_contiguous() or x.numel() != E:
@@ -941,12 +974,42 @@ class ShardedStreamRunner:
         chunk_cnt = np.ctypeslib.as_array(pc, shape=(G,)).copy()
         send_cnt = np.ctypeslib.as_array(psc, shape=(nsteps, G)).copy()
         recv_cnt = np.ctypeslib.as_array(prc, shape=(nsteps, G)).copy()
-        bufs = self._wshard_buffers(d, L, int(chunk_cnt[me]), int(ms.value), int(mr.value), dev)
+        f32 = lambda n, w: torch.empty((n, w), dtype=torch.float32, device=dev)
+        bufs = self._kept("_wshard_bufs", dev, (max(int(chunk_cnt[me]), 1), max(int(ms.value), 1), max(int(mr.value), 1)),
+                          lambda n_p0, n_send, n_recv: dict(send_p0=f32(n_p0, d), send_q=f32(n_p0, L * d), sendbuf=f32(n_send, d),
+                                                            recvbuf=f32(n_recv, d)))
         _lib.check(lib.tpnet_wshard_set_buffers(h, bufs["send_p0"].data_ptr(), bufs["send_q"].data_ptr(), bufs["sendbuf"].data_ptr(),
                                                 bufs["recvbuf"].data_ptr()), "wshard_set_buffers")
-        hstart = np.concatenate([[0], np.cumsum([0 if o == me else int(chunk_cnt[o]) for o in range(G)])]).astype(np.int64)
         return dict(handle=h, nsteps=nsteps, halo=int(halo.value), chunk_cnt=chunk_cnt, send_cnt=send_cnt, recv_cnt=recv_cnt, bufs=bufs,
-                    hstart=hstart, E=E, B=B, ws=ws, want_pos=want_pos, want_neg=want_neg)
+                    E=E, B=B, ws=ws, want_pos=want_pos, want_neg=want_neg)
+
+    # The phases of a windowed plan W, for whoever moves the rows without the C communicator (_wshard_run_gloo below and the
+    # drivers of several detached shards in one process): begin, place the chunk's halo rows, then per step j launch / pack, place
+    # what the step receives, unpack; finish
+    def wshard_begin(self, W):
+        """Pack the rows of this rank that the chunk's other ranks read (every reader gets the same rows) into W's send_p0 / send_q."""
+        _lib.check(_lib.load().tpnet_wshard_begin(W["handle"], None, PH_PACK, self.rp._stream()), "wshard_begin")
+
+    def wshard_place_halo(self, W, bufs):
+        """The chunk's rows of the other ranks -> this rank's halo rows, owner by owner.  bufs[o] = owner o's (send_p0, send_q)."""
+        cnt = W["chunk_cnt"]
+        to_others = [[0 if r == o else int(cnt[o]) for r in range(self.G)] for o in range(self.G)]
+        return place_rows(self._halo_dst(), self.n_cap, bufs, to_others, self.me, shared=True)
+
+    def wshard_step(self, W, j: int, phases: int, out_pos, out_neg):
+        """The phases (PH_LAUNCH | PH_PACK | PH_UNPACK) of pipeline step j."""
+        _lib.check(_lib.load().tpnet_wshard_step(W["handle"], None, j, phases, out_pos.data_ptr(),
+                                                 out_neg.data_ptr() if out_neg is not None else None, self.rp._stream()), "wshard_step")
+
+    def wshard_place_step(self, W, bufs, send_cnt):
+        """What step j's launches of the other ranks packed for this one -> W's receive buffer.  bufs[o] = (owner o's sendbuf,),
+        send_cnt[o] = its send counts of the step (place_rows)."""
+        return place_rows((W["bufs"]["recvbuf"],), 0, bufs, send_cnt, self.me)
+
+    def wshard_finish(self, W, lid=None):
+        rp = self.rp
+        lid = rp._next_launch_ids(1) if lid is None else lid
+        _lib.check(_lib.load().tpnet_wshard_finish(W["handle"], lid, rp._stream()), "wshard_finish")
 
     def run_stream_windowed(self, src, dst, neg, t, batch_size: int, t_host_last=None, merge_outputs: bool = True, out_pos=None,
                             out_neg=None, comm="auto", plan=None, timing=None):
@@ -957,31 +1020,15 @@ class ShardedStreamRunner:
         if W is None:
             return None
         lib = _lib.load()
-        dev = rp._dev()
-        E, NG = W["E"], rp.pair_wise_feature_dim
         h = W["handle"]
         try:
-            zero = merge_outputs and G > 1
-            for name, o in (("out_pos", out_pos), ("out_neg", out_neg)):
-                if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or tuple(o.shape) != (E, NG)):
-                    raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({E}, {NG}) on {dev}")
-            if out_pos is None:
-                out_pos = torch.zeros((E, NG), dtype=torch.float32, device=dev)
-            elif zero:
-                out_pos.zero_()
-            if neg is None:
-                out_neg = None
-            elif out_neg is None:
-                out_neg = torch.zeros((E, NG), dtype=torch.float32, device=dev)
-            elif zero:
-                out_neg.zero_()
+            out_pos, out_neg = output_buffers(W["E"], rp.pair_wise_feature_dim, rp._dev(), neg is not None, out_pos, out_neg,
+                                              merge_outputs and G > 1)
             lid = rp._next_launch_ids(1)
-            stream = rp._stream()
-            op, on = out_pos.data_ptr(), (out_neg.data_ptr() if out_neg is not None else None)
-            if comm == "auto":
-                nccl = G > 1 and not self.detached and dist.get_backend(self.group) == "nccl"
-                comm = self._c_comm() if nccl else None
+            comm, _ = self._resolve_comm(comm)
             if comm is not None or G == 1:
+                stream = rp._stream()
+                op, on = out_pos.data_ptr(), (out_neg.data_ptr() if out_neg is not None else None)
                 if timing is not None:
                     tot, la, xc = C.c_float(0), C.c_float(0), C.c_float(0)
                     _lib.check(lib.tpnet_time_wshard_run(h, comm, op, on, lid, stream, C.byref(tot), C.byref(la), C.byref(xc)),
@@ -990,89 +1037,44 @@ class ShardedStreamRunner:
                 else:
                     _lib.check(lib.tpnet_wshard_run(h, comm, op, on, lid, stream), "wshard_run")
             else:
-                self._wshard_run_gloo(W, op, on, lid, stream, timing)
+                self._wshard_run_gloo(W, out_pos, out_neg, lid, timing)
             if timing is not None:
                 timing.update(windowed=True, launches=W["nsteps"], rows_sent_per_launch=float(W["send_cnt"].sum()) / W["nsteps"],
                               rows_received_per_launch=float(W["recv_cnt"].sum()) / W["nsteps"],
                               chunk_rows_sent=int(W["chunk_cnt"][me]) * (G - 1), chunk_rows_received=int(W["halo"]))
-            if t_host_last is not None:
-                t_end = float(np.asarray(t_host_last, dtype=np.float64)[-1])
-            else:
-                t_end = float(t[-1].item())
-            rp._advanced(t_end)
+            rp._advanced(batch_clocks(t, W["E"], W["B"], t_host_last, end_only=True))
         finally:
             lib.tpnet_wshard_destroy(h)
         self.last_stream_windowed = True
-        if G > 1 and merge_outputs and not self.detached:
-            dist.all_reduce(out_pos, group=self.group)
-            if out_neg is not None:
-                dist.all_reduce(out_neg, group=self.group)
-        return out_pos, out_neg
+        return self._merge(out_pos, out_neg, merge_outputs)
 
-    def _wshard_run_gloo(self, W, op, on, lid, stream, timing=None):
+    def _wshard_run_gloo(self, W, out_pos, out_neg, lid, timing=None):
         """The windowed shard's loop with the rows moved by torch.distributed (gloo in the tests; a process group without the C-side
         RCCL communicator): pack launches, an all-gather of the padded send buffers from which every rank takes its parts, unpack
         launches -- the same pack / unpack kernels and the same buffers as the RCCL loop."""
-        lib = _lib.load()
-        rp, G, me = self.rp, self.G, self.me
-        dev = rp._dev()
-        L, d = rp.num_layer, rp.dim
-        h, bufs = W["handle"], W["bufs"]
+        G, me, bufs = self.G, self.me, W["bufs"]
         all_plans = [None] * G
         dist.all_gather_object(all_plans, (W["chunk_cnt"], W["send_cnt"], W["recv_cnt"]), group=self.group)
-        PH_LAUNCH, PH_PACK, PH_UNPACK = 1, 2, 8
         # ---- the chunk's halo rows
-        _lib.check(lib.tpnet_wshard_begin(h, None, PH_PACK, stream), "wshard_begin")
-        cmax = max(int(max(p[0])) for p in all_plans) or 1
-        pad_p0 = torch.zeros((cmax, d), dtype=torch.float32, device=dev)
-        pad_q = torch.zeros((cmax, L * d), dtype=torch.float32, device=dev)
-        mine = int(W["chunk_cnt"][me])
-        pad_p0[:mine].copy_(bufs["send_p0"][:mine]); pad_q[:mine].copy_(bufs["send_q"][:mine])
-        g_p0 = [torch.empty_like(pad_p0) for _ in range(G)]
-        g_q = [torch.empty_like(pad_q) for _ in range(G)]
-        dist.all_gather(g_p0, pad_p0, group=self.group)
-        dist.all_gather(g_q, pad_q, group=self.group)
-        p0_t = rp._plist()[0].data
-        q_t = rp._eng["q"].view(2, rp.node_num, L * d)
-        for o in range(G):
-            c = int(W["chunk_cnt"][o])
-            if o != me and c:
-                a0 = self.n_cap + int(W["hstart"][o])
-                p0_t[a0:a0 + c].copy_(g_p0[o][:c])
-                q_t[0, a0:a0 + c].copy_(g_q[o][:c])
+        self.wshard_begin(W)
+        sends = (bufs["send_p0"], bufs["send_q"])
+        gbufs = self._gather_buffers(max(int(max(p[0])) for p in all_plans) or 1, [s_.shape[1] for s_ in sends])
+        self.wshard_place_halo(W, self._gather_rows(sends, int(W["chunk_cnt"][me]), *gbufs))
         # ---- the pipeline
-        smax = max(int(p[1].sum(axis=1).max()) for p in all_plans) or 1
-        pad = torch.zeros((smax, d), dtype=torch.float32, device=dev)
-        gath = [torch.empty_like(pad) for _ in range(G)]
-        cur = torch.cuda.current_stream(dev)
-        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(W["nsteps"])] if timing is not None else None
+        gbufs = self._gather_buffers(max(int(p[1].sum(axis=1).max()) for p in all_plans) or 1, [bufs["sendbuf"].shape[1]])
+        timer = _StepTimer(timing, W["nsteps"], self.rp._dev())
         for j in range(W["nsteps"]):
-            if evs:
-                evs[j][0].record(cur)
-            _lib.check(lib.tpnet_wshard_step(h, None, j, PH_LAUNCH, op, on, stream), "wshard_step")
-            if evs:
-                evs[j][1].record(cur)
-            _lib.check(lib.tpnet_wshard_step(h, None, j, PH_PACK, op, on, stream), "wshard_step")
+            timer.mark(j, 0)
+            self.wshard_step(W, j, PH_LAUNCH, out_pos, out_neg)
+            timer.mark(j, 1)
+            self.wshard_step(W, j, PH_PACK, out_pos, out_neg)
             if any(int(p[1][j].sum()) for p in all_plans):
-                ns = int(W["send_cnt"][j].sum())
-                pad[:ns].copy_(bufs["sendbuf"][:ns])
-                dist.all_gather(gath, pad, group=self.group)
-                ro = 0
-                for o in range(G):                      # what owner o packed for me sits behind what it packed for the peers before me
-                    c = int(W["recv_cnt"][j][o])
-                    if c:
-                        a0 = int(all_plans[o][1][j][:me].sum())
-                        bufs["recvbuf"][ro:ro + c].copy_(gath[o][a0:a0 + c])
-                    ro += c
-                _lib.check(lib.tpnet_wshard_step(h, None, j, PH_UNPACK, op, on, stream), "wshard_step")
-            if evs:
-                evs[j][2].record(cur)
-        _lib.check(lib.tpnet_wshard_finish(h, lid, stream), "wshard_finish")
-        if evs:
-            evs[-1][2].synchronize()
-            n = len(evs)
-            timing.update(total_ms=evs[0][0].elapsed_time(evs[-1][2]), step_ms=sum(e[0].elapsed_time(e[1]) for e in evs) / n,
-                          exchange_ms=sum(e[1].elapsed_time(e[2]) for e in evs) / n, batches=n)
+                self.wshard_place_step(W, self._gather_rows((bufs["sendbuf"],), int(W["send_cnt"][j].sum()), *gbufs),
+                                       [p[1][j] for p in all_plans])
+                self.wshard_step(W, j, PH_UNPACK, out_pos, out_neg)
+            timer.mark(j, 2)
+        self.wshard_finish(W, lid)
+        timer.report("step_ms", "exchange_ms")
 
     def gather_full_layers(self):
         """All ranks' owned rows interleaved back into global order: [L+1, N, d] on every rank (tests / checkpoints of small
