@@ -603,6 +603,29 @@ int tpnet_gram_finish(float* x, int64_t n, void* stream);
  * triangle and, unless TPNET_FLAG_NOT_SCALE, applies x<0 -> 0, log(x + 1). */
 int tpnet_gram_unpack(const float* packed, int64_t n, int32_t L, uint32_t flags, float* out, void* stream);
 
+/* ---- the encoder's input stage in one launch (additive to ABI 7; csrc/encoder_input.hip) ------------------
+ * TPNetEmbedding between the readout and the mixers (models/TPNet.py:297-330), n = n_nodes * K rows:
+ *   out[row] = W2 . relu(W1 . x[row] + b1) + b2
+ *   x[row]   = [ node_raw[neigh[row]] | cos(tw * log(f32(tq[row / K] - tn[row]) + 1) + tb) | edge_raw[eid[row]] | feat[row] | feat[n + row] ]
+ * fp32 class on the matrix cores (two bf16 pieces per operand, three products per term, fp32 accumulators); the concat is never
+ * written.  dims = HOST int32[6] {Dn, Dt, De, F, H, Dout}: W1 is [H][Dn + Dt + De + 2 F], W2 [Dout][H], both row-major f32.
+ * Served (tpnet_encoder_input_supported = 1): Dn, Dt, De, F, Dout multiples of 4 and >= 4, Din <= 1024, 1 <= H <= 512, Dout <= 256.
+ * tpnet_encoder_input_image_bytes: size of the split weights in the kernel's operand order (host arithmetic; 0 for unserved dims).
+ * tpnet_encoder_input_prepare: ONE launch that writes the image from the four Parameters; again whenever one of them changed.
+ * tpnet_encoder_input: one launch on `stream`, no synchronisation.  node_raw [n_node_rows][Dn], edge_raw [n_edge_rows][De], neigh /
+ *   eid int64 [n], tn f64 [n], tq f64 [n_nodes], tw / tb f32 [Dt], feat f32 [2 n][F], out f32 [n][Dout]; the f32 arrays 16-byte
+ *   aligned.  An id outside node_raw / edge_raw reads row 0 instead and sets err[0] (a device uint32 the caller zeroed once):
+ * tpnet_encoder_input_check copies the word to the host (synchronises the stream), clears it if set and returns TPNET_ERR_INDEX.
+ * Null pointers and sizes out of range: TPNET_ERR_BAD_ARG, nothing launched. */
+int tpnet_encoder_input_supported(int32_t Dn, int32_t Dt, int32_t De, int32_t F, int32_t H, int32_t Dout);
+size_t tpnet_encoder_input_image_bytes(int32_t Dn, int32_t Dt, int32_t De, int32_t F, int32_t H, int32_t Dout);
+int tpnet_encoder_input_prepare(const float* w1, const float* b1, const float* w2, const float* b2, const int32_t* dims, void* img,
+                                void* stream);
+int tpnet_encoder_input(const float* node_raw, int64_t n_node_rows, const float* edge_raw, int64_t n_edge_rows, const int64_t* neigh,
+                        const int64_t* eid, const double* tn, const double* tq, const float* tw, const float* tb, const float* feat,
+                        int64_t n_nodes, int32_t K, const int32_t* dims, const void* img, float* out, uint32_t* err, void* stream);
+int tpnet_encoder_input_check(uint32_t* err, void* stream);
+
 /* Copies st->err to the host (synchronises the stream): returns TPNET_ERR_INDEX if any bad id was seen since
  * the last call (and clears the words), TPNET_OK otherwise. */
 int tpnet_check_errors(const tpnet_state* st, void* stream);

@@ -125,6 +125,12 @@ SIGNATURES = {
     "tpnet_mlp_image_bytes": (C.c_size_t, []),
     "tpnet_mlp_prepare_image": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "tpnet_mlp_prepare": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "tpnet_encoder_input_supported": (C.c_int, [C.c_int32] * 6),
+    "tpnet_encoder_input_image_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "tpnet_encoder_input_prepare": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int32), _P, _P]),
+    "tpnet_encoder_input": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32,
+                                      C.POINTER(C.c_int32), _P, _P, _P, _P]),
+    "tpnet_encoder_input_check": (C.c_int, [_P, _P]),
     "tpnet_stage_create": (C.c_int, [C.c_int32, C.c_size_t, C.POINTER(_P)]),
     "tpnet_stage_create_ex": (C.c_int, [C.c_int32, C.c_size_t, C.c_int32, C.POINTER(_P)]),
     "tpnet_stage_in_device_memory": (C.c_int, [_P]),

@@ -8,8 +8,7 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `encoder_pair_indices`    -- the 4*B*K index pattern of the encoder's readout (models/TPNet.py:206-217,311-316).
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
-The dense encoder (MLP-Mixer) itself is out of scope (stock dense layers); `encoder` / `decoder`
-are plug-in callables here.
+The encoder itself is tpnet_amd/encoder.py (`TPNet`); `encoder` / `decoder` stay plug-in callables here.
 """
 from typing import Callable, Optional
 

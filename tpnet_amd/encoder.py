@@ -1,0 +1,240 @@
+"""TPNet's encoder as a drop-in (models/TPNet.py:160-416, models/modules.py:8-42): `TimeEncoder`, `FeedForwardNet`, `MLPMixer`,
+`TPNetEmbedding` and `TPNet`, restated the way callers.py restates `LinkPredictor_v1` -- the reference's constructor keywords,
+attributes, method names and state-dict keys (the shared `random_projections` and `time_encoder` registered under two prefixes
+each), so `TPNet(...)` at train_link_prediction.py:166 can be this class.
+
+What differs is where the work runs:
+* sampler -> readout: with a `GpuRecentNeighborSampler` the neighbour ids, edge ids and times never leave the device
+  (`sample_device` -> `RandomProjectionModule.get_pair_wise_feature_anchored`); a host sampler's three [2B, K] arrays are
+  copied to the device once.  Row widths the anchored readout does not serve (d < 36, d > 512, d % 4 != 0) take the general pair
+  readout and `rp.mlp` as the stock torch layers.
+* the input stage behind the readout (gathers, time encoding, concat, `projection_layer`; TPNet.py:297-330): under
+  `torch.no_grad()` / inference mode, with the module on the GPU, `fused_input` set and a served shape, ONE launch on the matrix
+  cores (tpnet_amd/fused_input.py, csrc/encoder_input.hip) that never writes the [2B, K, Din] concat.  When gradients are recorded
+  the torch layers serve, and autograd reaches `projection_layer`, the time encoder and `rp.mlp` as in the reference.
+* the MLP-Mixer layers and the mean over the K tokens are stock torch.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import fused_input as _fi
+
+
+class TimeEncoder(nn.Module):
+    """cos(Linear(1, time_dim)) with the reference's initial weights 1 / 10^linspace(0, 9, time_dim) and zero bias
+    (models/modules.py:8-42)."""
+
+    def __init__(self, time_dim: int, parameter_requires_grad: bool = True):
+        super().__init__()
+        self.time_dim = time_dim
+        self.w = nn.Linear(1, time_dim)
+        self.w.weight = nn.Parameter(torch.from_numpy(1 / 10 ** np.linspace(0, 9, time_dim, dtype=np.float32)).reshape(time_dim, -1))
+        self.w.bias = nn.Parameter(torch.zeros(time_dim))
+        if not parameter_requires_grad:
+            self.w.weight.requires_grad = False
+            self.w.bias.requires_grad = False
+
+    def forward(self, timestamps: torch.Tensor):
+        """timestamps [batch, seq_len] -> [batch, seq_len, time_dim]"""
+        return torch.cos(self.w(timestamps.unsqueeze(dim=2)))
+
+
+class FeedForwardNet(nn.Module):
+    """Linear -> GELU -> Dropout -> Linear -> Dropout (models/TPNet.py:341-368); keys ffn.0.*, ffn.3.*."""
+
+    def __init__(self, input_dim: int, dim_expansion_factor: float, dropout: float = 0.0):
+        super().__init__()
+        self.input_dim = input_dim
+        self.dim_expansion_factor = dim_expansion_factor
+        self.dropout = dropout
+        hidden = int(dim_expansion_factor * input_dim)
+        self.ffn = nn.Sequential(nn.Linear(in_features=input_dim, out_features=hidden), nn.GELU(), nn.Dropout(dropout),
+                                 nn.Linear(in_features=hidden, out_features=input_dim), nn.Dropout(dropout))
+
+    def forward(self, x: torch.Tensor):
+        return self.ffn(x)
+
+
+class MLPMixer(nn.Module):
+    """Token mixing then channel mixing, each LayerNorm -> FeedForwardNet -> residual (models/TPNet.py:371-416)."""
+
+    def __init__(self, num_tokens: int, num_channels: int, token_dim_expansion_factor: float = 0.5,
+                 channel_dim_expansion_factor: float = 4.0, dropout: float = 0.0):
+        super().__init__()
+        self.token_norm = nn.LayerNorm(num_tokens)
+        self.token_feedforward = FeedForwardNet(input_dim=num_tokens, dim_expansion_factor=token_dim_expansion_factor, dropout=dropout)
+        self.channel_norm = nn.LayerNorm(num_channels)
+        self.channel_feedforward = FeedForwardNet(input_dim=num_channels, dim_expansion_factor=channel_dim_expansion_factor,
+                                                  dropout=dropout)
+
+    def forward(self, input_tensor: torch.Tensor):
+        """[batch, num_tokens, num_channels] -> the same shape"""
+        hidden_tensor = self.token_norm(input_tensor.permute(0, 2, 1))
+        hidden_tensor = self.token_feedforward(hidden_tensor).permute(0, 2, 1)
+        output_tensor = hidden_tensor + input_tensor
+        hidden_tensor = self.channel_norm(output_tensor)
+        hidden_tensor = self.channel_feedforward(hidden_tensor)
+        return hidden_tensor + output_tensor
+
+
+def _on(x, dev, dtype):
+    """A host array or a tensor as a contiguous tensor of `dtype` on `dev` (one copy at most)."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype={torch.int64: np.int64, torch.float64: np.float64}[dtype]))
+    return x.to(device=dev, dtype=dtype).contiguous()
+
+
+class TPNetEmbedding(nn.Module):
+    """The embedding module (models/TPNet.py:236-338): projection_layer over [node | time | edge | r(w|u), r(w|v)] of every
+    sampled neighbour, `num_layers` MLP-Mixers over the K tokens, mean over the tokens.  Same constructor keywords and state-dict
+    keys (time_encoder.*, random_projections.*, projection_layer.{0,2}.*, mlp_mixers.*)."""
+
+    # the one-launch input stage when no gradient is recorded: measured against the stock-torch expression at B = 1000, K = 20
+    # (profiles/encoder_input.md)
+    fused_input = True
+
+    def __init__(self, node_raw_features: torch.Tensor, edge_raw_features: torch.Tensor, neighbor_sampler, time_encoder: nn.Module,
+                 node_feat_dim: int, edge_feat_dim: int, time_feat_dim: int, num_layers: int, num_neighbors: int, dropout: float,
+                 random_projections):
+        super().__init__()
+        self.node_raw_features = node_raw_features
+        self.edge_raw_features = edge_raw_features
+        self.neighbor_sampler = neighbor_sampler
+        self.time_encoder = time_encoder
+        self.node_feat_dim = node_feat_dim
+        self.edge_feat_dim = edge_feat_dim
+        self.time_feat_dim = time_feat_dim
+        self.num_layers = num_layers
+        self.num_neighbors = num_neighbors
+        self.dropout = dropout
+        self.random_projections = random_projections
+        self.random_feature_dim = 0 if random_projections is None else random_projections.pair_wise_feature_dim * 2
+        self.projection_layer = nn.Sequential(
+            nn.Linear(node_feat_dim + edge_feat_dim + time_feat_dim + self.random_feature_dim, self.node_feat_dim * 2), nn.ReLU(),
+            nn.Linear(self.node_feat_dim * 2, self.node_feat_dim))
+        self.mlp_mixers = nn.ModuleList([
+            MLPMixer(num_tokens=self.num_neighbors, num_channels=self.node_feat_dim, token_dim_expansion_factor=0.5,
+                     channel_dim_expansion_factor=4.0, dropout=self.dropout) for _ in range(self.num_layers)])
+
+    def compute_node_temporal_embeddings(self, node_ids: np.ndarray, src_node_ids: np.ndarray, dst_node_ids: np.ndarray,
+                                         node_interact_times: np.ndarray):
+        """Embeddings [len(node_ids), node_feat_dim] of `node_ids` at `node_interact_times`; src_node_ids / dst_node_ids are the
+        edge's two ends per row (the anchors of the relative encodings).  Sampler, readout, then embed_from_features
+        (TPNet.py:280-338)."""
+        dev = self.node_raw_features.device
+        K = self.num_neighbors
+        sampler = self.neighbor_sampler
+        tq = _on(node_interact_times, dev, torch.float64)
+        if dev.type == "cuda" and hasattr(sampler, "sample_device"):
+            neigh, eids, tn = sampler.sample_device(_on(node_ids, dev, torch.int64), tq, K, with_edges=True)
+        else:
+            neigh, eids, tn = sampler.get_historical_neighbors(node_ids=node_ids, node_interact_times=node_interact_times,
+                                                               num_neighbors=K)
+            neigh, eids, tn = _on(neigh, dev, torch.int64), _on(eids, dev, torch.int64), _on(tn, dev, torch.float64)
+        feats = None
+        rp = self.random_projections
+        if rp is not None:
+            # TPNet.py:313-316, [2 n K, F]: every neighbour against the row's two anchors
+            if dev.type == "cuda" and hasattr(rp, "get_pair_wise_feature_anchored") and rp.dim % 4 == 0 and 36 <= rp.dim <= 512:
+                feats = rp.get_pair_wise_feature_anchored(neigh, src_node_ids, dst_node_ids)
+            else:
+                # row widths the anchored readout does not serve (or another module): the general pair readout, then self.mlp as
+                # the stock torch layers -- true fp32 forward and backward, where the anchored path's dense layers are the fp32
+                # class on the matrix cores (2^-16 per product)
+                a1, a2 = _on(src_node_ids, dev, torch.int64), _on(dst_node_ids, dev, torch.int64)
+                u, v = neigh.reshape(-1).repeat(2), torch.cat([a1.repeat_interleave(K), a2.repeat_interleave(K)])
+                if dev.type == "cuda" and hasattr(rp, "pair_gram"):
+                    feats = rp.mlp(rp.pair_gram(u, v))
+                else:                                                    # (a host module takes the reference's numpy arrays)
+                    feats = rp.get_pair_wise_feature(src_node_ids=u.cpu().numpy(), dst_node_ids=v.cpu().numpy())
+        return self.embed_from_features(neigh, eids, tn, tq, feats)
+
+    def _fused_prep(self, dev, pair_features):
+        """The prepared weight image if the one-launch input stage serves this call, else None: no gradient recorded, module on
+        the GPU, `fused_input` set, relative encodings present and a shape tpnet_encoder_input_supported accepts."""
+        if torch.is_grad_enabled() or not self.fused_input or dev.type != "cuda" or pair_features is None:
+            return None
+        if self.random_feature_dim % 2 or pair_features.shape[1] * 2 != self.random_feature_dim:
+            return None
+        return _fi.prepared(self.projection_layer, self.node_feat_dim, self.time_feat_dim, self.edge_feat_dim, self.random_feature_dim // 2)
+
+    def embed_from_features(self, neighbor_node_ids, neighbor_edge_ids, neighbor_times, node_interact_times, pair_features):
+        """The tail behind the readout (TPNet.py:297-338).  neighbor_node_ids / neighbor_edge_ids int64 [n, K], neighbor_times
+        float64 [n, K], node_interact_times float64 [n] (host arrays or tensors), pair_features [2 n K, F] in the reference's row
+        order (all first anchors, then all second anchors) or None without relative encodings."""
+        dev = self.node_raw_features.device
+        neigh, eids = _on(neighbor_node_ids, dev, torch.int64), _on(neighbor_edge_ids, dev, torch.int64)
+        tn, tq = _on(neighbor_times, dev, torch.float64), _on(node_interact_times, dev, torch.float64)
+        n, K = neigh.shape
+        prep = self._fused_prep(dev, pair_features)
+        if prep is not None:
+            w = self.time_encoder.w
+            embeddings = _fi.encoder_input(prep, self.node_raw_features, self.edge_raw_features, neigh, eids, tn, tq, w.weight, w.bias,
+                                           pair_features)
+        else:
+            neighbor_node_features = self.node_raw_features[neigh]
+            # the delta in f64, cast to f32, then log(x + 1) (TPNet.py:299-301)
+            neighbor_delta_times = torch.log((tq[:, None] - tn).float() + 1.0)
+            neighbor_time_features = self.time_encoder(neighbor_delta_times)
+            neighbor_edge_features = self.edge_raw_features[eids]
+            parts = [neighbor_node_features, neighbor_time_features, neighbor_edge_features]
+            if pair_features is not None:
+                half = n * K
+                parts.append(torch.cat([pair_features[:half], pair_features[half:]], dim=1).reshape(n, K, -1))
+            embeddings = self.projection_layer(torch.cat(parts, dim=2))
+        # (TPNet.py:332 calls masked_fill out of place and drops the result: pad neighbours are NOT masked)
+        for mlp_mixer in self.mlp_mixers:
+            embeddings = mlp_mixer(embeddings)
+        return torch.mean(embeddings, dim=1)
+
+    def check_device_errors(self):
+        """Raise IndexError if a fused input-stage launch met a neighbour or edge id outside the raw feature tables since the last
+        check (such a row read row 0 instead, where the torch layers' gathers would have faulted).  Synchronises the stream: meant
+        for once per evaluation pass, not per batch."""
+        prep = _fi.cached(self.projection_layer)
+        if prep is not None:
+            _fi.check_errors(prep)
+
+
+class TPNet(nn.Module):
+    """models/TPNet.py:160-233: holds the raw features, the shared random projections and time encoder, and the embedding
+    module; state-dict keys random_projections.*, time_encoder.*, embedding_module.*."""
+
+    def __init__(self, node_raw_features: np.ndarray, edge_raw_features: np.ndarray, neighbor_sampler, time_feat_dim: int,
+                 dropout: float, random_projections, num_layers: int, num_neighbors: int, device: str):
+        super().__init__()
+        self.node_raw_features = torch.from_numpy(node_raw_features.astype(np.float32)).to(device)
+        self.edge_raw_features = torch.from_numpy(edge_raw_features.astype(np.float32)).to(device)
+        self.node_feat_dim = self.node_raw_features.shape[1]
+        self.edge_feat_dim = self.edge_raw_features.shape[1]
+        self.time_feat_dim = time_feat_dim
+        self.dropout = dropout
+        self.device = device
+        self.num_nodes = self.node_raw_features.shape[0]        # including the padded node
+        self.random_projections = random_projections
+        self.time_encoder = TimeEncoder(time_dim=time_feat_dim)
+        self.embedding_module = TPNetEmbedding(node_raw_features=self.node_raw_features, edge_raw_features=self.edge_raw_features,
+                                               neighbor_sampler=neighbor_sampler, time_encoder=self.time_encoder,
+                                               node_feat_dim=self.node_feat_dim, edge_feat_dim=self.edge_feat_dim,
+                                               time_feat_dim=self.time_feat_dim, num_layers=num_layers, num_neighbors=num_neighbors,
+                                               dropout=self.dropout, random_projections=self.random_projections)
+
+    def compute_src_dst_node_temporal_embeddings(self, src_node_ids: np.ndarray, dst_node_ids: np.ndarray,
+                                                 node_interact_times: np.ndarray):
+        """(src embeddings, dst embeddings), each [batch, node_feat_dim] (TPNet.py:206-222)."""
+        node_embeddings = self.embedding_module.compute_node_temporal_embeddings(
+            node_ids=np.concatenate([src_node_ids, dst_node_ids]), src_node_ids=np.tile(src_node_ids, 2),
+            dst_node_ids=np.tile(dst_node_ids, 2), node_interact_times=np.tile(node_interact_times, 2))
+        return node_embeddings[:len(src_node_ids)], node_embeddings[len(src_node_ids):]
+
+    def check_device_errors(self):
+        """embedding_module.check_device_errors(): IndexError if a fused input-stage launch met an id outside the raw feature tables."""
+        self.embedding_module.check_device_errors()
+
+    def set_neighbor_sampler(self, neighbor_sampler):
+        """TPNet.py:224-233: the random strategies restart their seeded state."""
+        self.embedding_module.neighbor_sampler = neighbor_sampler
+        if getattr(neighbor_sampler, "sample_neighbor_strategy", "recent") in ["uniform", "time_interval_aware"]:
+            assert neighbor_sampler.seed is not None
+            neighbor_sampler.reset_random_state()
