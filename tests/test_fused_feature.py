@@ -652,3 +652,69 @@ def test_one_launch_encoder_call_on_random_shapes():
         assert err <= 2e-5 * scale + 1e-6, (trial, d, K, n, err, scale)
     for rp in mods.values():
         rp.check_device_errors()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [33, 8192 + 33])
+def test_mlp64_f32_on_both_sides_of_its_switch(n):
+    """tpnet_mlp64_f32 through the shared dense-layer route: 33 rows take the tile kernel (one full and one partial tile), 8 225
+    rows the per-wave-tile kernel (from 8 192 rows on; a partial last tile).  Against the torch layers within the fp32-class bound
+    of this file (2e-5 of the output scale); on small integers -- every product and partial sum below 2^24, every value the sum
+    of two bf16 pieces -- bit for bit, so that a wrong lane or accumulator index cannot hide behind the tolerance."""
+    if not torch.cuda.is_available():
+        pytest.fail("needs a GPU")
+    from tpnet_amd import fused_feature as ff
+    gen = torch.Generator().manual_seed(n)
+    mlp = torch.nn.Sequential(torch.nn.Linear(64, 256), torch.nn.ReLU(), torch.nn.Linear(256, 64)).cuda()
+    x = (torch.rand(n, 64, generator=gen) * 12).cuda()           # log(1 + G) features: 0 .. ~12
+    with torch.no_grad():
+        got, want = ff.mlp_f32(mlp, x), mlp(x)
+        assert got is not None and torch.equal(got, ff.mlp_f32(mlp, x))
+        err, scale = float((got - want).abs().max()), max(1.0, float(want.abs().max()))
+        print(f"tpnet_mlp64_f32, {n} rows: err {err:.3e}, output scale {scale:.3f}")
+        assert err <= 2e-5 * scale
+        mlp[0].weight.copy_(torch.randint(-3, 4, (256, 64), generator=gen).float())
+        mlp[0].bias.copy_(torch.randint(-8, 9, (256,), generator=gen).float())
+        mlp[2].weight.copy_(torch.randint(-2, 3, (64, 256), generator=gen).float())
+        mlp[2].bias.copy_(torch.randint(-8, 9, (64,), generator=gen).float())
+        xi = torch.randint(0, 4, (n, 64), generator=gen).float().cuda()
+        got, want = ff.mlp_f32(mlp, xi), mlp(xi)
+        assert torch.equal(got, want), float((got - want).abs().max())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_rows", [5, 1100])
+def test_two_launch_anchored_route_equals_its_two_calls(n_rows):
+    """tpnet_anchored_features with TPNET_FLAG_NO_MFMA_READOUT (readout, then the dense layers through the shared route) at d = 64,
+    K = 4: 40 pairs take the tile kernel, 8 800 the per-wave-tile kernel.  Same kernels on the same inputs as
+    tpnet_pair_gram_anchored followed by tpnet_mlp64_f32: equal bytes, features and outputs."""
+    if not torch.cuda.is_available():
+        pytest.fail("needs a GPU")
+    from tpnet_amd import _lib, fused_feature as ff
+    K, N = 4, 300
+    rng = np.random.RandomState(n_rows)
+    rp = _module(N, 64, 3)
+    for src, dst, t in _stream(rng, N, 150, 3):
+        rp.update(src, dst, t)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    neigh, a1, a2 = dev(rng.randint(0, N, (n_rows, K))), dev(rng.randint(1, N, n_rows)), dev(rng.randint(1, N, n_rows))
+    prep = ff.prepared(rp.mlp, 64)
+    assert prep is not None
+    lib, half = _lib.load(), n_rows * K
+    flags = rp._readout_flags() | _lib.FLAG_NO_MFMA_READOUT
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    now, lam = rp._now_host, float(rp.time_decay_weight)
+    gram, out = torch.zeros(2 * half, 64, device="cuda"), torch.zeros(2 * half, 64, device="cuda")
+    _lib.check(lib.tpnet_anchored_features(rp._st_ref(), neigh.data_ptr(), a1.data_ptr(), a2.data_ptr(), n_rows, K, now, lam, flags,
+                                           prep.ref, gram.data_ptr(), out.data_ptr(), stream), "anchored_features")
+    gram2, out2 = torch.zeros_like(gram), torch.zeros_like(out)
+    _lib.check(lib.tpnet_pair_gram_anchored(rp._st_ref(), neigh.data_ptr(), a1.data_ptr(), a2.data_ptr(), n_rows, K, now, lam, flags,
+                                            gram2.data_ptr(), gram2[half:].data_ptr(), stream), "pair_gram_anchored")
+    _lib.check(lib.tpnet_mlp64_f32(gram2.data_ptr(), 2 * half, prep.ref, out2.data_ptr(), stream), "mlp64_f32")
+    torch.cuda.synchronize()
+    assert bool(gram.abs().sum() > 0) and bool(out.abs().sum() > 0)
+    assert torch.equal(gram, gram2) and torch.equal(out, out2)
+    with torch.no_grad():
+        want = rp.mlp(gram2)
+    assert float((out - want).abs().max()) <= 2e-5 * max(1.0, float(want.abs().max()))
+    rp.check_device_errors()

@@ -88,6 +88,103 @@ def dev(x, dt=torch.int64):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV, dt)
 
 
+def param_grads(mods, fn):
+    """fn() with gradients recorded: [out] + the gradients of every Parameter of `mods` after out.sum().backward()."""
+    for m in mods:
+        m.zero_grad(set_to_none=True)
+    out = fn()
+    out.sum().backward()
+    return [out] + [p.grad for m in mods for p in m.parameters() if p.grad is not None]
+
+
+def embedding_stage(rng, widths, hidden_out, n_nodes=300, K=20):
+    """A TPNetEmbedding of the given widths (hidden_out = (H, Dout): its projection_layer replaced, no mixers) and one call's
+    arrays with pad rows and repeated ids."""
+    import types
+    Dn, Dt, De, F = widths
+    Nn, Ne = 500, 3000
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
+    te = tpnet_amd.TimeEncoder(time_dim=Dt)
+    emb = tpnet_amd.TPNetEmbedding(node_raw_features=f32(rng.normal(0, 1, (Nn, Dn))), edge_raw_features=f32(rng.normal(0, 1, (Ne, De))),
+                                   neighbor_sampler=None, time_encoder=te, node_feat_dim=Dn, edge_feat_dim=De, time_feat_dim=Dt,
+                                   num_layers=2, num_neighbors=K, dropout=0.1,
+                                   random_projections=types.SimpleNamespace(pair_wise_feature_dim=F)).to(DEV)
+    if hidden_out is not None:
+        emb.projection_layer = nn.Sequential(nn.Linear(Dn + Dt + De + 2 * F, hidden_out[0]), nn.ReLU(),
+                                             nn.Linear(hidden_out[0], hidden_out[1])).to(DEV)
+        emb.mlp_mixers = nn.ModuleList()
+    emb.eval()
+    neigh, eids = rng.randint(1, Nn, (n_nodes, K)).astype(np.int64), rng.randint(1, Ne, (n_nodes, K)).astype(np.int64)
+    tq = rng.uniform(1e5, 2e6, n_nodes)
+    tn = tq[:, None] - rng.uniform(0, 1e5, (n_nodes, K))
+    pad = rng.rand(n_nodes, K) < 0.2
+    neigh[pad], eids[pad], tn[pad] = 0, 0, 0.0
+    neigh[:, K // 2] = neigh[:, 0]
+    return emb, (dev(neigh), dev(eids), dev(tn, torch.float64), dev(tq, torch.float64), f32(rng.normal(0, 1, (2 * n_nodes * K, F))))
+
+
+def dense_cases(rng):
+    """The dense-layer routes by their public names: fused_mlp.fused_mlp, LinkPredictor_v1.fused, fused_feature.mlp_f32 on both
+    sides of its kernel switch with mlp_backward both ways, TPNetEmbedding with fused_input on and off."""
+    from tpnet_amd import fused_feature as ff, fused_mlp as fm
+    from tpnet_amd.callers import LinkPredictor_v1
+    torch.manual_seed(11)
+    mlp = nn.Sequential(nn.Linear(64, 256), nn.ReLU(), nn.Linear(256, 64)).to(DEV)
+    rows = lambda n, w=64: torch.from_numpy(rng.uniform(0, 12, (n, w)).astype(np.float32)).to(DEV)   # log(1 + G) features: 0 .. ~12
+    x1k = rows(1000)
+    with torch.no_grad():
+        case("fused_mlp_fn", lambda: fm.fused_mlp(mlp, x1k))
+    case("fused_mlp_fn_grad", lambda: param_grads([mlp], lambda: fm.fused_mlp(mlp, x1k)))
+    for n in (33, 8225):
+        xn = rows(n)
+        with torch.no_grad():
+            case(f"mlp_f32_n{n}", lambda: ff.mlp_f32(mlp, xn))
+    x5k = rows(5000)
+    for mode in ("mfma", "torch"):
+        mlp.mlp_backward = mode
+        case(f"mlp_f32_n5000_grad_{mode}", lambda: param_grads([mlp], lambda: ff.mlp_f32(mlp, x5k)))
+    del mlp.mlp_backward
+    xg = rows(700).requires_grad_(True)
+    case("mlp_f32_input_grad", lambda: param_grads([mlp], lambda: ff.mlp_f32(mlp, xg)) + [xg.grad])
+    # ---- the decoder ------------------------------------------------------------------------------------------------------
+    rp = make(128, seed=6)
+    dec = LinkPredictor_v1(172, 172, 172, 1, rp, False).to(DEV)
+    dec.fused = True
+    a, b = ids(rng, 1000), ids(rng, 1000)
+    se = torch.from_numpy(rng.normal(0, 1, (1000, 172)).astype(np.float32)).to(DEV)
+    de = torch.from_numpy(rng.normal(0, 1, (1000, 172)).astype(np.float32)).to(DEV)
+    with torch.no_grad():
+        case("decoder_fused", lambda: dec(a, b, se, de))
+    seg, deg = se.clone().requires_grad_(True), de.clone().requires_grad_(True)
+    case("decoder_fused_grad", lambda: param_grads([dec.fc1, dec.fc2, rp.mlp], lambda: dec(a, b, seg, deg)) + [seg.grad, deg.grad])
+    # ---- the encoder module: fixture G11 end to end, then the input stage's two kernel variants --------------------------
+    g = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "g11_encoder.npz"))
+    for fused in (False, True):
+        rp11 = tpnet_amd.RandomProjectionModule(node_num=int(g["N"]), edge_num=int(g["E"]), dim_factor=10, num_layer=int(g["L"]),
+                                                time_decay_weight=float(g["lam"]), device=DEV, use_matrix=False,
+                                                beginning_time=np.float64(0.0), not_scale=False, enforce_dim=int(g["d"]))
+        sampler = GpuRecentNeighborSampler(g["src"], g["dst"], g["t"], g["eid"], device=DEV, num_nodes=int(g["N"]))
+        model = tpnet_amd.TPNet(node_raw_features=g["node_raw"], edge_raw_features=g["edge_raw"], neighbor_sampler=sampler,
+                                time_feat_dim=int(g["Dt"]), dropout=0.1, random_projections=rp11, num_layers=int(g["mixers"]),
+                                num_neighbors=int(g["K"]), device=DEV)
+        model.load_state_dict({str(k): torch.from_numpy(g[f"sd_{int(s)}"]) for k, s in zip(g["sd_keys"], g["sd_slot"])})
+        model = model.to(DEV).eval()
+        model.embedding_module.fused_input = fused
+        for bb in range(4):
+            sl = slice(50 * bb, 50 * bb + 50)
+            rp11.update(g["src"][sl], g["dst"][sl], g["t"][sl])
+        sl = slice(200, 200 + int(g["B"]))
+        with torch.no_grad():
+            case(f"g11_embeddings_fused_input_{int(fused)}",
+                 lambda: model.compute_src_dst_node_temporal_embeddings(g["src"][sl], g["dst"][sl], g["t"][sl]))
+    for tag, widths, hidden_out in (("narrow", (172, 100, 172, 64), None), ("wide", (256, 100, 172, 64), (320, 224))):
+        emb, arrays = embedding_stage(rng, widths, hidden_out)
+        for fused in (False, True):
+            emb.fused_input = fused
+            with torch.no_grad():
+                case(f"embedding_{tag}_fused_input_{int(fused)}", lambda: emb.embed_from_features(*arrays))
+
+
 def main():
     rng = np.random.RandomState(7)
     # ---- the decoder's calls from host arrays -----------------------------------------------------------------------------
@@ -227,6 +324,7 @@ def main():
         case(f"update_{tag}_now_time", lambda: rp.now_time.detach().clone())
         with torch.no_grad():
             case(f"update_{tag}_feature", lambda: rp.get_pair_wise_feature(a, b))
+    dense_cases(rng)
     # ---- MatrixMemory -----------------------------------------------------------------------------------------------------
     mm = MatrixMemory(num_node=60, num_hop=2, device=DEV).to(DEV)
     for k in range(3):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Developer tool: self.mlp in the fp32 class -- tpnet_mlp64_f32 (split-bf16 operands on the bf16 matrix cores by default; the
-fp32-MFMA variant with TPNET_DEV_MLP_F32_MODE=1 on the dev library) against the torch layers: time and error."""
+"""Developer tool: self.mlp in the fp32 class -- tpnet_mlp64_f32 (split-bf16 operands on the bf16 matrix cores) against the torch
+layers: time and error."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

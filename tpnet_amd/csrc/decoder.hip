@@ -15,11 +15,9 @@
 // wave a CU holds one 3-wave workgroup, whose staging and MFMA phases then run back to back: 518 us against 255 us at
 // n = 200 000.)
 #include "tpnet_common.h"
+#include "mfma_split.hpp"
 
 namespace tpnet {
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
 
 static constexpr int DEC_BLOCK = 256;
 
@@ -34,10 +32,7 @@ __device__ __forceinline__ bf16x8 load8_bf16(const float* __restrict__ row, int 
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = (c + i < width) ? row[c + i] : 0.0f;
     }
-    bf16x8 b;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) b[i] = (__bf16)v[i];
-    return b;
+    return cvt8(v);
 }
 
 template <int HT>
@@ -68,7 +63,7 @@ __global__ __launch_bounds__(DEC_BLOCK) void k_decoder_bf16(const float* __restr
 #pragma unroll
             for (int t = 0; t < HT; ++t) {
                 const bf16x8 a = *reinterpret_cast<const bf16x8*>(w1p + (int64_t)(t * 32 + r) * KP + kcol + 8 * h);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bx, acc[t], 0, 0, 0);
+                acc[t] = mfma(a, bx, acc[t]);
             }
         };
         if (src_emb) {
@@ -81,13 +76,13 @@ __global__ __launch_bounds__(DEC_BLOCK) void k_decoder_bf16(const float* __restr
             const float* xf = feat + prow * F;
             for (int s = 0; s < FS; ++s) step(load8_bf16(xf, 16 * s + 8 * h, F), 2 * DP + 16 * s);
         }
-        // register q of tile t = hidden unit 32 t + (q&3) + 8 (q>>2) + 4 h of pair r:  bias, ReLU, times w2, summed
+        // register q of tile t = hidden unit 32 t + acc_row(q, h) of pair r:  bias, ReLU, times w2, summed
         float part = 0.0f;
 #pragma unroll
         for (int t = 0; t < HT; ++t) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                const int hid = 32 * t + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int hid = 32 * t + acc_row(q, h);
                 float v = acc[t][q] + b1p[hid];
                 v = v > 0.0f ? v : 0.0f;
                 part = fmaf(v, w2p[hid], part);

@@ -7,22 +7,6 @@
 // their fusion INTO the anchored kernel.
 #include "tpnet_common.h"
 
-namespace tpnet {
-
-static int mlp_rows(const tpnet_mlp* mlp, const float* x, int64_t n, float* y, hipStream_t s) {
-    // long lists: every wave its own tiles, split weights in LDS (mlp_x3.hip)
-    if (n >= mlp_x3_from() && mlp_f32_mode() == 2 && mlp_x3_available() &&
-        launch_mlp_rows_x3(x, n, reinterpret_cast<const float*>(mlp->w1), mlp->b1, reinterpret_cast<const float*>(mlp->w2f),
-                           mlp->b2, y, s) == TPNET_OK)
-        return TPNET_OK;
-    tpnet_state st{};                      // (not dereferenced when the tile comes from `x`; geometry of d = 128 picks the 32-lane kernel)
-    st.N = 1; st.d = 128; st.L = 3;
-    return launch_pair_feature_bf16(st, nullptr, nullptr, n, 0.0, 0.0, 0, mlp->w1, mlp->b1, mlp->w2f, mlp->b2, nullptr, y, s,
-                                    mlp_f32_mode(), x);
-}
-
-}  // namespace tpnet
-
 using namespace tpnet;
 
 extern "C" {
@@ -52,7 +36,7 @@ int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const i
     const int64_t half = n_rows * (int64_t)K;                // pairs per anchor side
     int rc = tpnet_pair_gram_anchored(st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, gram, gram + half * F, stream);
     if (rc) return rc;
-    rc = mlp_rows(mlp, gram, 2 * half, out, s);
+    rc = launch_mlp_rows(mlp, gram, 2 * half, out, s);
     if (rc) return rc;
     return TPNET_OK;
 }
@@ -77,7 +61,7 @@ int tpnet_encoder_features(const tpnet_state* st, const void* sampler, int64_t E
         const int64_t half = 2 * B * (int64_t)K;
         rc = tpnet_pair_gram(st, neigh + half, neigh + 3 * half, 2 * half, now_time, lambda, flags, gram, stream);
         if (rc) return rc;
-        return mlp_rows(mlp, gram, 2 * half, out, (hipStream_t)stream);
+        return launch_mlp_rows(mlp, gram, 2 * half, out, (hipStream_t)stream);
     }
     return tpnet_anchored_features(st, neigh, a1, a2, 2 * B, K, now_time, lambda, flags, mlp, gram, out, stream);
 }

@@ -2,8 +2,8 @@
 // cos(tw * log(f32(tq - tn) + 1) + tb), the two halves of the relative encodings, and projection_layer = Linear(Din, H) -> ReLU ->
 // Linear(H, Dout) on the matrix cores.  The [n, Din] concat (91 MB per call at B = 1000, K = 20, Din = 572) is never written: every
 // lane builds the 8-float operand pieces of its row straight from the sources.
-// Arithmetic: the project's fp32 class as in mlp_x3.hip -- every operand x = hi + lo (bf16), every product lo*hi + hi*lo + hi*hi on
-// v_mfma_f32_32x32x16_bf16 with fp32 accumulators.  Layer 1 is computed as H^T = W1 . X^T, so a hidden slice's accumulator registers
+// Arithmetic: the project's fp32 class (mfma_split.hpp: two-piece operands, three products per term on v_mfma_f32_32x32x16_bf16,
+// fp32 accumulators).  Layer 1 is computed as H^T = W1 . X^T, so a hidden slice's accumulator registers
 // (row r of the tile, 16 hidden units per lane) are layer 2's B operand without a transpose.
 // Mapping: a workgroup of 4 waves takes 128 rows, one 32-row tile per wave.  The split weights (tpnet_encoder_input_prepare: 1.16 MB
 // at 572 -> 344 -> 172, in exactly the per-lane operand order) do not fit LDS; they are cut into equal chunks of 24 KB -- one k-step
@@ -13,11 +13,9 @@
 // more than 192 outputs take the second variant: passes of 8 slices over the row's operands.  313 workgroups at 40 000 rows.
 // Ids outside node_raw / edge_raw read row 0 and set err[0] (tpnet_encoder_input_check reports it); no hand-off between workgroups.
 #include "tpnet_common.h"
+#include "mfma_split.hpp"
 
 namespace tpnet {
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
 
 static constexpr int EI_T = 256;                 // threads per workgroup: 4 waves, one per SIMD (the accumulators want the registers)
 static constexpr int EI_ROWS = 128;              // rows per workgroup
@@ -57,21 +55,11 @@ static __host__ __device__ inline uint32_t ei_chunk_elems(const ei_dims& d) {
     return (uint32_t)(d.NP * (d.KS + d.HG)) * (uint32_t)d.CH;
 }
 
-static __device__ __forceinline__ void ei_split8(const float4 a, const float4 b, bf16x8& hi, bf16x8& lo) {
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 t = (__bf16)v[j];
-        hi[j] = t;
-        lo[j] = (__bf16)(v[j] - (float)t);
-    }
-}
-
 // ---- the weight image.  Chunks of CH elements in the order the kernel consumes them, per pass p (slices w0 = HG p .. w0 + HG - 1;
 // HG = 11, one pass and OS = 6 output tiles where H <= 352 and Dout <= 192, else HG = 8 and OS = 8: the kernel computes ALL of
 // them, so that every loop over slices and tiles has a compile-time count)
 //   k-step s = 0..KS-1:  element (wl * 2 + piece) * 64 + lane  = W1[32 (w0 + wl) + r][16 s + 8 h + j], piece 0 = hi, 1 = lo
-//   slice wl = 0..HG-1:  element ((s2 * OS + t) * 2 + piece) * 64 + lane = W2[32 t + r][32 (w0 + wl) + (q & 3) + 8 (q >> 2) + 4 h], q = 8 s2 + j
+//   slice wl = 0..HG-1:  element ((s2 * OS + t) * 2 + piece) * 64 + lane = W2[32 t + r][32 (w0 + wl) + acc_row(q, h)], q = 8 s2 + j
 // (lane = 32 h + r, j = 0..7 the element's eight bf16), zero beyond H / Din / Dout; then b1 padded to 32 NP HG and b2 to 32 OS floats.
 __global__ __launch_bounds__(256) void k_encoder_input_image(const float* __restrict__ w1, const float* __restrict__ b1,
                                                              const float* __restrict__ w2, const float* __restrict__ b2,
@@ -113,13 +101,13 @@ __global__ __launch_bounds__(256) void k_encoder_input_image(const float* __rest
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int q = 8 * s2 + j;
-                const int col = 32 * (w0 + wl) + (q & 3) + 8 * (q >> 2) + 4 * h;
+                const int col = 32 * (w0 + wl) + acc_row(q, h);
                 v[j] = (row < d.Dout && col < d.H) ? w2[(size_t)row * d.H + col] : 0.0f;
             }
         }
     }
     bf16x8 hi, lo;
-    ei_split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
+    split8(v, hi, lo);
     *reinterpret_cast<bf16x8*>(img + e) = piece ? lo : hi;
 }
 
@@ -208,11 +196,11 @@ __global__ __launch_bounds__(EI_T) void k_encoder_input(const float* __restrict_
         for (int s = 0; s < d.KS; ++s) {
             fetch(chunk + 1);
             bf16x8 bxh, bxl;
-            ei_split8(xa, xb, bxh, bxl);
+            split8(xa, xb, bxh, bxl);
             xa = x4(16 * (s + 1) + 8 * h);                                      // (beyond Din: zeros)
             xb = x4(16 * (s + 1) + 8 * h + 4);
             const bf16x8* W = reinterpret_cast<const bf16x8*>(buf[cur]) + lane;
-            // all operands of the k-step first (one LDS round trip, not one per product), then the products term by term: the
+            // all operands of the k-step first (one LDS round trip, not one per product), then the products term-major: the
             // three products of one accumulator lie HG instructions apart
             bf16x8 ah[HG], al[HG];
 #pragma unroll
@@ -222,37 +210,25 @@ __global__ __launch_bounds__(EI_T) void k_encoder_input(const float* __restrict_
             }
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * HG, 0);             // (the scheduler otherwise waits on every read in turn)
             __builtin_amdgcn_sched_group_barrier(0x008, 3 * HG, 0);
-#pragma unroll
-            for (int wl = 0; wl < HG; ++wl) acc[wl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[wl], bxh, acc[wl], 0, 0, 0);   // the small terms first
-#pragma unroll
-            for (int wl = 0; wl < HG; ++wl) acc[wl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[wl], bxl, acc[wl], 0, 0, 0);
-#pragma unroll
-            for (int wl = 0; wl < HG; ++wl) acc[wl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[wl], bxh, acc[wl], 0, 0, 0);
+            mm3(ah, al, bxh, bxl, acc);
             commit(cur ^ 1);
             cur ^= 1;
             ++chunk;
         }
-        // ---- layer 2, slice by slice: bias, ReLU and split of the slice's accumulators (register q = hidden unit
-        // 32 w + (q & 3) + 8 (q >> 2) + 4 h of row r) are the B operand; every output tile takes its share
+        // ---- layer 2, slice by slice: bias, ReLU and split of the slice's accumulators (relu_split16) are the B operand; every
+        // output tile takes its share
 #pragma unroll
         for (int wl = 0; wl < HG; ++wl) {
             {
                 fetch(chunk + 1);
-                bf16x8 bhh[2], bhl[2];
+                float bv[16];                                                   // b1 in accumulator order: acc_row(4 q4 + j, h) = 8 q4 + 4 h + j
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const float4 bb = *reinterpret_cast<const float4*>(bias + 32 * (w0 + wl) + 8 * q4 + 4 * h);
-                    const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int q = 4 * q4 + j;
-                        float x = acc[wl][q] + bv[j];
-                        x = x > 0.0f ? x : 0.0f;
-                        const __bf16 hi = (__bf16)x;
-                        bhh[q >> 3][q & 7] = hi;
-                        bhl[q >> 3][q & 7] = (__bf16)(x - (float)hi);
-                    }
+                    bv[4 * q4] = bb.x; bv[4 * q4 + 1] = bb.y; bv[4 * q4 + 2] = bb.z; bv[4 * q4 + 3] = bb.w;
                 }
+                bf16x8 bhh[2], bhl[2];
+                relu_split16(acc[wl], bv, bhh, bhl);
                 const bf16x8* W = reinterpret_cast<const bf16x8*>(buf[cur]) + lane;
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
@@ -262,12 +238,7 @@ __global__ __launch_bounds__(EI_T) void k_encoder_input(const float* __restrict_
                         ah[t] = W[((s2 * OSM + t) * 2) * 64];
                         al[t] = W[((s2 * OSM + t) * 2 + 1) * 64];
                     }
-#pragma unroll
-                    for (int t = 0; t < OSM; ++t) y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[t], bhh[s2], y[t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < OSM; ++t) y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bhl[s2], y[t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < OSM; ++t) y[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[t], bhh[s2], y[t], 0, 0, 0);
+                    mm3(ah, al, bhh[s2], bhl[s2], y);
                 }
                 commit(cur ^ 1);
                 cur ^= 1;

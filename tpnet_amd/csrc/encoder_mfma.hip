@@ -8,8 +8,8 @@
 //   B2 = 16 anchor rows: the two anchors x 4 layers of the node the tile starts in and of the next node (K >= 4: a tile spans
 //   at most two nodes); the anchors' own blocks come from B2 B2^T, formed once per anchor set.
 //   v_mfma_f32_16x16x32_bf16 on split operands: every f32 value x = h + m + l (three bf16 pieces, 24 significand bits) and every
-//   product as l*h + h*l + m*m + m*h + h*m + h*h with fp32 accumulation (small terms first): what is dropped is 2^-24 relative,
-//   the class of an fp32 fused multiply-add chain (SPLIT = 2: h + l and three products, 2^-16 -- kept for measurements).
+//   product as l*h + h*l + m*m + m*h + h*m + h*h with fp32 accumulation (mm6, mfma_split.hpp): what is dropped is 2^-24 relative,
+//   the class of an fp32 fused multiply-add chain.
 //
 // Operand layout (gfx950): lane (c = lane & 15, g = lane >> 4) holds row c, k-positions 8 g .. 8 g + 7 of a 32-deep step; any
 // fixed assignment of a row's floats to k-positions is a valid contraction as long as A and B use the same one, so a step takes
@@ -22,17 +22,15 @@
 // the reference's default rule gives 120 / 140 / 160 (models/TPNet.py:30-33) -- runs its last step with the pieces past the row's
 // end supplied as zeros (load_rows); nothing behind the accumulators depends on d.
 #include "device_common.hpp"
+#include "mfma_split.hpp"
 
 namespace tpnet {
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
 
 static constexpr int EMB = 256;           // threads per workgroup: 4 waves, every wave on its own tiles
 static constexpr int EM_RS = 68;          // floats per staged feature row (64 + 4: rows stay 16-byte aligned, b128 reads conflict-free)
 
 // ---- the fused kernel (k_encoder_fused): self.mlp = Linear(64, 256) -> ReLU -> Linear(256, 64) (models/TPNet.py:63-65, 129)
-// behind the Gram tiles in the same launch, fp32 class (two bf16 pieces per value, three products: the arithmetic of mlp_x3.hip on
+// behind the Gram tiles in the same launch, fp32 class (two bf16 pieces per value, three products: mm3 of mfma_split.hpp on
 // v_mfma_f32_16x16x32_bf16).  A workgroup of 8 waves, one per CU, is split by ROLE: waves 0..3 walk Gram tiles (latency- and
 // vector-ALU-bound: gathers, splits, logs), waves 4..7 run the dense layers (matrix-pipe- and LDS-bound), wave 4 + p on the rows
 // wave p produces -- the two share a SIMD, so one's matrix work runs under the other's loads and vector work (a first version in
@@ -47,8 +45,6 @@ static constexpr int EM_RS = 68;          // floats per staged feature row (64 +
 // pre-mlp features are stored only if the caller asks (a backward pass needs them): 20 MB of writes and 20 MB of reads less per
 // 80 000-pair call, and one launch instead of two.
 static constexpr int EMF_B = 512;                                           // threads per workgroup of the fused variant
-static constexpr int IMG_W1H = 0, IMG_W1L = 32768, IMG_W2H = 65536, IMG_W2L = 98304, IMG_B1 = 131072, IMG_B2 = IMG_B1 + 1024;
-static constexpr int IMG_BYTES = IMG_B2 + 256;                              // 132 352
 static constexpr int EMF_NP = 4;                                            // producer waves (= consumer waves) per workgroup
 static constexpr int EMF_TILE = 8 * EM_RS * 4;                              // bytes of a producer's own tile of 8 raw feature rows
 static constexpr int EMF_HAND = 2048;                                       // bytes of a hand-off buffer: 8 rows as layer 1's B operand,
@@ -69,43 +65,6 @@ __device__ unsigned long long g_em_stamps[4096 * 64];
 #else
 #define EM_STAMP(slot) do { } while (0)
 #endif
-
-template <int SPLIT>
-struct SplitOp {
-    bf16x8 p[SPLIT];                      // p[0] = the leading bf16 piece of 8 values, p[1], p[2] = the pieces below
-};
-
-template <int SPLIT>
-__device__ __forceinline__ void split8(const float* v, SplitOp<SPLIT>& o) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float x = v[j];
-#pragma unroll
-        for (int t = 0; t < SPLIT; ++t) {
-            const __bf16 b = (__bf16)x;
-            o.p[t][j] = b;
-            if (t + 1 < SPLIT) x = x - (float)b;
-        }
-    }
-}
-
-// c += A B^T over one 32-deep step of split operands, the small terms first
-template <int SPLIT>
-__device__ __forceinline__ f32x4 mm_step(const SplitOp<SPLIT>& a, const SplitOp<SPLIT>& b, f32x4 c) {
-    if constexpr (SPLIT == 3) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[2], b.p[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], b.p[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], b.p[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[0], c, 0, 0, 0);
-    } else {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], b.p[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[0], c, 0, 0, 0);
-    }
-    return c;
-}
 
 // 16 rows of KS 32-deep steps, one row pointer per load-layout lane (already offset by the lane's 16-byte piece):
 // raw[s][0..3] = floats 32 s + 4 p .., raw[s][4..7] = floats 32 s + 16 + 4 p ..
@@ -139,34 +98,7 @@ __device__ __forceinline__ void to_operands(const float (&raw)[KS][8], float rs,
     float v[KS][8];
     to_lanes<KS>(raw, rs, pull, v);
 #pragma unroll
-    for (int s = 0; s < KS; ++s) split8<SPLIT>(v[s], op[s]);
-}
-
-// cw += A A^T, ca += A B^T over one 32-deep step: the two accumulation chains take turns in the matrix pipe (a chain's next
-// product waits for its previous one), the small terms first
-template <int SPLIT>
-__device__ __forceinline__ void mm_step2(const SplitOp<SPLIT>& a, const SplitOp<SPLIT>& b, f32x4& cw, f32x4& ca) {
-    if constexpr (SPLIT == 3) {
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[2], a.p[0], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[2], b.p[0], ca, 0, 0, 0);
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], a.p[2], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[2], ca, 0, 0, 0);
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], a.p[1], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], b.p[1], ca, 0, 0, 0);
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], a.p[0], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], b.p[0], ca, 0, 0, 0);
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], a.p[1], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[1], ca, 0, 0, 0);
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], a.p[0], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[0], ca, 0, 0, 0);
-    } else {
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], a.p[0], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[1], b.p[0], ca, 0, 0, 0);
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], a.p[1], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[1], ca, 0, 0, 0);
-        cw = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], a.p[0], cw, 0, 0, 0);
-        ca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.p[0], b.p[0], ca, 0, 0, 0);
-    }
+    for (int s = 0; s < KS; ++s) split8(v[s], op[s]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -184,6 +116,7 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
                                            double now, double lambda, uint32_t flags, float* __restrict__ out1,
                                            float* __restrict__ out2, float* stg, int* sync) {
     constexpr int L = 3;
+    static_assert(SPLIT == 3, "walk_tiles: three-piece operands (mm6)");
     const int lane = threadIdx.x & 63;
     const int c = lane & 15, g = lane >> 4;        // operand layout: row c of the tile, k-group g
     const int lr = lane >> 2, lp = lane & 3;       // load layout: row lr, 16-byte piece lp of a 64-byte segment
@@ -267,7 +200,7 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
                 to_operands<KS, SPLIT>(ra, decay_pow(pre_g, l_layer), pull, anch);
                 daa = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-                for (int s = 0; s < KS; ++s) daa = mm_step<SPLIT>(anch[s], anch[s], daa);
+                for (int s = 0; s < KS; ++s) daa = mm6(anch[s], anch[s], daa);
             }
             // ---- this tile's rows -> operand lanes; the next tile's rows (and anchors) ride under the matrix work; then step by
             // step: split of step s + 1 under the products of step s
@@ -288,8 +221,8 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 SplitOp<SPLIT> aop;
-                split8<SPLIT>(av[s], aop);
-                mm_step2<SPLIT>(aop, anch[s], dww, dwa);
+                split8(av[s], aop);
+                mm6x2(aop, anch[s], dww, dwa);
             }
             {
                 const float p2 = gd * gd, p3 = p2 * gd;            // g, g*g, (g*g)*g: decay_pow's association
@@ -370,17 +303,12 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
                 if constexpr (HANDOFF) {
                     // the dense layers' B operand, already in two pieces (here every lane holds 4 features: the split is dense):
                     // feature f = 4 col4 + k of pair p sits in step s = f >> 5, k-group (f >> 3) & 3, element f & 7
-                    typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4;
-                    bf16x4 hi, lo;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const __bf16 hh = (__bf16)v[k];
-                        hi[k] = hh;
-                        lo[k] = (__bf16)(v[k] - (float)hh);
-                    }
+                    const float v4[4] = {v[0], v[1], v[2], v[3]};
+                    bf16x4 hl[2];
+                    split(v4, hl);
                     char* e = hb + (((col4 >> 3) * 4 + ((col4 >> 1) & 3)) * 8 + p) * 16 + (col4 & 1) * 8;
-                    *reinterpret_cast<bf16x4*>(e) = hi;
-                    *reinterpret_cast<bf16x4*>(e + 1024) = lo;
+                    *reinterpret_cast<bf16x4*>(e) = hl[0];
+                    *reinterpret_cast<bf16x4*>(e + 1024) = hl[1];
                 }
                 if (pin_g && (!HANDOFF || out1 != nullptr)) {
                     float* o = (it ? out2 : out1) + (int64_t)(base + 4 * t + g) * 64 + 4 * col4;
@@ -406,6 +334,7 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
 }
 
 // out1 / out2: the pre-mlp features of the two anchor sides, rows [slot][64]
+// (SPLIT = 3: the pieces per operand; part of the kernels' names in the profiles)
 template <int KS, bool FULL, int SPLIT>
 __global__ __launch_bounds__(EMB) void k_encoder_gram_mfma(tpnet_state S, const int64_t* __restrict__ neigh,
                                                            const int64_t* __restrict__ a1, const int64_t* __restrict__ a2,
@@ -474,49 +403,33 @@ __device__ __forceinline__ void dense_consumer(const char* smem, const float* st
         for (int t = 0; t < 4; ++t) yo[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
         // layer 1 of hidden slices 2 k2, 2 k2 + 1 (two accumulation chains taking turns, started from the bias: accumulator q of
         // lane (r, g) = hidden unit 16 w + 4 g + q of row r)
-        auto layer1 = [&](int k2, f32x4& a0, f32x4& a1) {
-            a0 = B1[(2 * k2) * 4];
-            a1 = B1[(2 * k2 + 1) * 4];
+        auto layer1 = [&](int k2, f32x4 (&a)[2]) {
+            a[0] = B1[(2 * k2) * 4];
+            a[1] = B1[(2 * k2 + 1) * 4];
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const bf16x8 h0 = W1H[((2 * k2) * 2 + s) * 64], l0 = W1L[((2 * k2) * 2 + s) * 64];
-                const bf16x8 h1 = W1H[((2 * k2 + 1) * 2 + s) * 64], l1 = W1L[((2 * k2 + 1) * 2 + s) * 64];
-                a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l0, bx[s].p[0], a0, 0, 0, 0);       // the small terms first
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(l1, bx[s].p[0], a1, 0, 0, 0);
-                a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h0, bx[s].p[1], a0, 0, 0, 0);
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h1, bx[s].p[1], a1, 0, 0, 0);
-                a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h0, bx[s].p[0], a0, 0, 0, 0);
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h1, bx[s].p[0], a1, 0, 0, 0);
+                const bf16x8 wh[2] = {W1H[((2 * k2) * 2 + s) * 64], W1H[((2 * k2 + 1) * 2 + s) * 64]};
+                const bf16x8 wl[2] = {W1L[((2 * k2) * 2 + s) * 64], W1L[((2 * k2 + 1) * 2 + s) * 64]};
+                mm3(wh, wl, bx[s].p[0], bx[s].p[1], a);
             }
         };
-        f32x4 a0, a1;
-        layer1(0, a0, a1);
+        f32x4 a[2];
+        layer1(0, a);
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2) {
             // the next slices' layer 1 enters the matrix pipe before this pair's ReLU + split: the vector work runs in its shadow
-            f32x4 n0 = a0, n1 = a1;
-            if (k2 + 1 < 8) layer1(k2 + 1, n0, n1);
+            f32x4 nx[2] = {a[0], a[1]};
+            if (k2 + 1 < 8) layer1(k2 + 1, nx);
             SplitOp<2> bh;                         // layer 2's B operand of this 32-deep step: hidden slices 2 k2 and 2 k2 + 1
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float x0 = relu1(a0[q]), x1 = relu1(a1[q]);
-                const __bf16 h0 = (__bf16)x0, h1 = (__bf16)x1;
-                bh.p[0][q] = h0;
-                bh.p[0][4 + q] = h1;
-                bh.p[1][q] = (__bf16)(x0 - (float)h0);
-                bh.p[1][4 + q] = (__bf16)(x1 - (float)h1);
-            }
+            const float x[8] = {relu1(a[0][0]), relu1(a[0][1]), relu1(a[0][2]), relu1(a[0][3]),
+                                relu1(a[1][0]), relu1(a[1][1]), relu1(a[1][2]), relu1(a[1][3])};
+            split8(x, bh);
             bf16x8 wh[4], wl[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) { wh[t] = W2H[(k2 * 4 + t) * 64]; wl[t] = W2L[(k2 * 4 + t) * 64]; }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) yo[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[t], bh.p[0], yo[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) yo[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[t], bh.p[1], yo[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) yo[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[t], bh.p[0], yo[t], 0, 0, 0);
-            a0 = n0;
-            a1 = n1;
+            mm3(wh, wl, bh.p[0], bh.p[1], yo);
+            a[0] = nx[0];
+            a[1] = nx[1];
         }
         // lane (r = c, g) holds outputs 16 t + 4 g + q of row r: pair p = r & 7 (side p >> 2, neighbour p & 3) of tile r >> 3
         const int p = c & 7;
@@ -601,24 +514,23 @@ int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const 
     if ((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15) return TPNET_ERR_BAD_ARG;
     const int T = (int)(n_rows * K);
     const int ntiles = (T + 3) / 4;
-    static const int split_dev = TPNET_DEV_INT(ENCODER_SPLIT, 3);
     // tiles per wave: ONE round of the waves the chip holds (2 per SIMD at 172 VGPRs: 8 per CU), at least two tiles each
     static const int waves_dev = TPNET_DEV_INT(ENCODER_WAVES, 256 * 8);
     int tpw = (ntiles + waves_dev - 1) / waves_dev;
     if (tpw < 2) tpw = 2;
     const int nwaves = (ntiles + tpw - 1) / tpw;
     const int grid = (nwaves + EMB / 64 - 1) / (EMB / 64);
-#define TPNET_EM_LAUNCH(KS_, FULL_, SP_)                                                                                        \
-    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, FULL_, SP_>), dim3(grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+#define TPNET_EM_LAUNCH(KS_, FULL_)                                                                                             \
+    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, FULL_, 3>), dim3(grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
                        tpw, now, lambda, flags, out1, out2)
-    if (st.d == 128) { if (split_dev == 2) TPNET_EM_LAUNCH(4, true, 2); else TPNET_EM_LAUNCH(4, true, 3); }
-    else if (st.d == 64) { if (split_dev == 2) TPNET_EM_LAUNCH(2, true, 2); else TPNET_EM_LAUNCH(2, true, 3); }
-    else                                           // (the two-piece split is a measuring aid of the whole widths only)
+    if (st.d == 128) TPNET_EM_LAUNCH(4, true);
+    else if (st.d == 64) TPNET_EM_LAUNCH(2, true);
+    else
         switch (encoder_steps(st.d)) {
-            case 2: TPNET_EM_LAUNCH(2, false, 3); break;
-            case 3: TPNET_EM_LAUNCH(3, false, 3); break;
-            case 4: TPNET_EM_LAUNCH(4, false, 3); break;
-            default: TPNET_EM_LAUNCH(5, false, 3); break;
+            case 2: TPNET_EM_LAUNCH(2, false); break;
+            case 3: TPNET_EM_LAUNCH(3, false); break;
+            case 4: TPNET_EM_LAUNCH(4, false); break;
+            default: TPNET_EM_LAUNCH(5, false); break;
         }
 #undef TPNET_EM_LAUNCH
     TPNET_HIP_TRY(hipGetLastError());
@@ -626,25 +538,17 @@ int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const 
 }
 
 // ---- the fused variant: readout + self.mlp in one launch -------------------------------------------------------------------
-// 0: not decided; 1: available; -1: this device / runtime does not give a workgroup 150 KB of LDS
-static int encoder_fused_state = 0;
+static LdsOptIn encoder_fused_lds;                    // a workgroup's 154 KB of LDS
 
 static bool encoder_fused_available() {
-    if (encoder_fused_state == 0) {
-        static const int off = TPNET_DEV_INT(NO_ENCODER_FUSED, 0);
-        bool ok = !off;
-        const void* const kernels[] = {reinterpret_cast<const void*>(k_encoder_fused<4, true, 3>),
-                                       reinterpret_cast<const void*>(k_encoder_fused<2, true, 3>),
-                                       reinterpret_cast<const void*>(k_encoder_fused<2, false, 3>),
-                                       reinterpret_cast<const void*>(k_encoder_fused<3, false, 3>),
-                                       reinterpret_cast<const void*>(k_encoder_fused<4, false, 3>),
-                                       reinterpret_cast<const void*>(k_encoder_fused<5, false, 3>)};
-        for (const void* k : kernels)
-            ok = ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, EMF_LDS) == hipSuccess;
-        (void)hipGetLastError();
-        encoder_fused_state = ok ? 1 : -1;
-    }
-    return encoder_fused_state == 1;
+    static const int off = TPNET_DEV_INT(NO_ENCODER_FUSED, 0);
+    return encoder_fused_lds.granted({reinterpret_cast<const void*>(k_encoder_fused<4, true, 3>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<2, true, 3>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<2, false, 3>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<3, false, 3>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<4, false, 3>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<5, false, 3>)},
+                                     EMF_LDS, off != 0);
 }
 
 bool encoder_fused_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp) {
@@ -679,7 +583,7 @@ int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int6
         }
 #undef TPNET_EMF_LAUNCH
     if (hipGetLastError() != hipSuccess) {             // (a runtime that refuses the launch: the callers fall back for good)
-        encoder_fused_state = -1;
+        encoder_fused_lds.refused();
         return TPNET_ERR_BAD_ARG;
     }
     return TPNET_OK;
@@ -699,7 +603,7 @@ __global__ __launch_bounds__(256) void k_mlp_image(const float* __restrict__ w1,
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = p[j];
         SplitOp<2> o;
-        split8<2>(v, o);
+        split8(v, o);
         reinterpret_cast<bf16x8*>(img + IMG_W1H)[i] = o.p[0];
         reinterpret_cast<bf16x8*>(img + IMG_W1L)[i] = o.p[1];
     } else if (i < 4096) {
@@ -709,7 +613,7 @@ __global__ __launch_bounds__(256) void k_mlp_image(const float* __restrict__ w1,
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = w2[(16 * t + (lane & 15)) * 256 + 16 * (2 * k2 + (j >> 2)) + 4 * (lane >> 4) + (j & 3)];
         SplitOp<2> o;
-        split8<2>(v, o);
+        split8(v, o);
         reinterpret_cast<bf16x8*>(img + IMG_W2H)[e] = o.p[0];
         reinterpret_cast<bf16x8*>(img + IMG_W2L)[e] = o.p[1];
     } else if (i < 4096 + 256) {

@@ -196,7 +196,7 @@ int launch_pair_feature(const tpnet_state& st, const int64_t* u, const int64_t* 
     // kernel's 8-pair workgroups spread a short list over more CUs
     static const int64_t mfma_from = (int64_t)TPNET_DEV_INT(FEATURE_MFMA_FROM, 2048);
     if (m.w1 && m.w2f && n >= mfma_from && pair_feature_mfma_supported(st) && !(reinterpret_cast<uintptr_t>(out) & 15))
-        return launch_pair_feature_bf16(st, u, v, n, now, lambda, flags, m.w1, m.b1, m.w2f, m.b2, out_gram, out, s, mlp_f32_mode());
+        return launch_pair_feature_bf16(st, u, v, n, now, lambda, flags, m.w1, m.b1, m.w2f, m.b2, out_gram, out, s, true);
     // pairs per workgroup: a short list is spread over as many CUs as it has tiles of 2 / 4 / 8 pairs -- a workgroup's dense
     // layers are 2 * 64 * 256 fmaf per pair on ONE wave per SIMD plus 128 KB of weights through its CU's L2 port, so the call's
     // latency falls with the tile until the launch fills the chip (C2, 1000 pairs: 13.9 us with 8 pairs per workgroup)

@@ -6,38 +6,19 @@
 // pre-permuted as in mlp.hip).  The eight partial Y tiles are added in a FIXED order through LDS (run-to-run identical
 // bits).  The features never leave the chip; the weights of a wave (its 32 rows of W1, its 32 columns of W2: 48 VGPRs)
 // are loaded once per workgroup.  bf16 operands, fp32 accumulation: 2e-2 class like tpnet_mlp64_bf16 -- opt-in.  L = 3.
-// MODE 2 (the default fp32-CLASS path): the bf16 matrix cores with SPLIT operands -- every f32 operand x = hi + lo with hi =
-// bf16(x), lo = bf16(x - hi) (16 bits of significand between them), every product as hi*hi + hi*lo + lo*hi in fp32 accumulators:
-// relative error ~2^-16 per product, the accuracy class of the fp32 paths (<= 2e-5 of the output scale against the torch
-// layers, exact on small integers), at 24 bf16 MFMAs per wave and tile instead of 64 fp32 ones of four times the cycles.  Same
-// inputs as MODE 1 (tpnet_mlp::w1, w2f: the split happens in registers).
-// MODE 1 (F32): the same kernel on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulation -- differs from
-// the torch layers in summation order only), which makes ONE launch the default get_pair_wise_feature for lists of any length:
-// k-step s of layer 1 takes features (s, s + 32) (lane half h reads 32 consecutive floats of its pair's LDS row and of its W1
-// row), k-step s of layer 2 takes the hidden units that register s of the two lane halves holds (W2 gathered to match).
+// MODE 2 (the default fp32-CLASS path): the bf16 matrix cores with SPLIT operands (mfma_split.hpp: x = hi + lo, three products per
+// term, fp32 accumulators: relative error ~2^-16 per product, the accuracy class of the fp32 paths), at 24 bf16 MFMAs per wave and
+// tile -- the fp32 matrix cores (v_mfma_f32_32x32x2_f32) take 64 products of four times the cycles for the same class: measured
+// and not kept; inputs tpnet_mlp::w1, w2f (f32: the split happens in registers), which makes ONE launch
+// the default get_pair_wise_feature for lists of any length.
 #include "readout.hpp"
+#include "mfma_split.hpp"
 
 namespace tpnet {
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
 
 static constexpr int MB = 512;            // threads per workgroup: 8 waves = the 8 hidden tiles
 static constexpr int MF = 64, MH = 256;
 static constexpr int TS = 68;             // floats per LDS row of the feature / partial tiles (64 + 4: bank spread)
-
-// 8 consecutive floats (16-byte aligned) -> hi = bf16(x), lo = bf16(x - hi)
-__device__ __forceinline__ void split8(const float* __restrict__ x, bf16x8& hi, bf16x8& lo) {
-    const float4 a = *reinterpret_cast<const float4*>(x);
-    const float4 b = *reinterpret_cast<const float4*>(x + 4);
-    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 t = (__bf16)v[j];
-        hi[j] = t;
-        lo[j] = (__bf16)(v[j] - (float)t);
-    }
-}
 
 template <int LPP, int VPL, int W, bool FULL, int MODE>
 __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const int64_t* __restrict__ u,
@@ -51,13 +32,14 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
     // compute on stale LDS rows and are never stored -- a pair is one column, nothing crosses columns)
     // feat_in != NULL: the dense layers alone on features that already exist ([n][64] f32): the tile is loaded, not formed
     // bf16: w1 = bf16 [256][64], w2p = bf16 [64][256] (hidden axis permuted per 32-tile, fused_mlp.permute_w2)
-    // f32:  w1 = f32 [256][64] (mlp[0].weight as is), w2f = f32 [8 waves][2 output tiles][64 lanes][16 k-steps]
+    // split: w1 = f32 [256][64] (mlp[0].weight as is), w2f = f32 [8 waves][2 output tiles][64 lanes][16 k-positions]
     const __bf16* __restrict__ w1 = reinterpret_cast<const __bf16*>(w1v);
     const __bf16* __restrict__ w2p = reinterpret_cast<const __bf16*>(w2v);
     const float* __restrict__ w1f = reinterpret_cast<const float*>(w1v);
     const float* __restrict__ w2f = reinterpret_cast<const float*>(w2v);
     constexpr int L = 3;
-    constexpr bool F32 = MODE == 1, X3 = MODE == 2;
+    static_assert(MODE == 0 || MODE == 2, "k_pair_feature_bf16: bf16 operands or split operands");
+    constexpr bool X3 = MODE == 2;
     constexpr int GPB = MB / LPP;             // pairs per readout pass
     constexpr int PT = 32 / GPB;              // passes per 32-pair tile
     static_assert(GPB * PT == 32 && LPP >= 16, "k_pair_feature_bf16: 16, 32 or 64 lanes per pair");
@@ -80,31 +62,15 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
     // ---- this wave's weights: rows [32 wave, 32 wave + 32) of W1 as A operand, the matching columns of (permuted) W2
     bf16x8 a1[4], a2[2][2];
     bf16x8 a1l[X3 ? 4 : 1], a2l[X3 ? 2 : 1][2];          // MODE 2: the low halves of the split weights
-    float f1[F32 ? 32 : 1], f2[2][F32 ? 16 : 1];
     if constexpr (X3) {
         // the bf16 kernel's operand layout, taken from the f32 sources: A of layer 1 = W1[32 wave + r][16 s + 8 h + j]; A of layer 2
-        // = W2[32 t + r][32 wave + 16 s2 + 8 (j>>2) + 4 h + (j&3)] = w2f[..][8 s2 + j] (the gathered f32 layout lists them in order)
+        // = W2[32 t + r][32 wave + acc_row(8 s2 + j, h)] = w2f[..][8 s2 + j] (the gathered f32 layout lists them in order)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) split8(w1f + (wave * 32 + r) * MF + 16 * s + 8 * h, a1[s], a1l[s]);
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) split8(w2f + (((wave * 2 + t2) * 64 + lane) * 16) + 8 * s2, a2[s2][t2], a2l[s2][t2]);
-    } else if constexpr (F32) {
-        // layer 1: A[m = hidden 32 wave + r][k] with k-step s <-> features (s, s + 32): lane half h holds W1[..][32 h + s]
-#pragma unroll
-        for (int q4 = 0; q4 < 8; ++q4) {
-            const float4 x = *reinterpret_cast<const float4*>(w1f + (wave * 32 + r) * MF + 32 * h + 4 * q4);
-            f1[4 * q4] = x.x; f1[4 * q4 + 1] = x.y; f1[4 * q4 + 2] = x.z; f1[4 * q4 + 3] = x.w;
-        }
-        // layer 2: A[m = output 32 t2 + r][k] with k-step s <-> hidden 32 wave + (s&3) + 8 (s>>2) + 4 h (gathered on the host)
+        for (int s = 0; s < 4; ++s) load_split8(w1f + (wave * 32 + r) * MF + 16 * s + 8 * h, a1[s], a1l[s]);
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const float4 x = *reinterpret_cast<const float4*>(w2f + (((wave * 2 + t2) * 64 + lane) * 16) + 4 * q4);
-                f2[t2][4 * q4] = x.x; f2[t2][4 * q4 + 1] = x.y; f2[t2][4 * q4 + 2] = x.z; f2[t2][4 * q4 + 3] = x.w;
-            }
+            for (int s2 = 0; s2 < 2; ++s2) load_split8(w2f + (((wave * 2 + t2) * 64 + lane) * 16) + 8 * s2, a2[s2][t2], a2l[s2][t2]);
     } else {
 #pragma unroll
         for (int s = 0; s < 4; ++s) a1[s] = *reinterpret_cast<const bf16x8*>(w1 + (wave * 32 + r) * MF + 16 * s + 8 * h);
@@ -117,7 +83,7 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
     }
     float bias1[16];
 #pragma unroll
-    for (int q = 0; q < 16; ++q) bias1[q] = b1[wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * h];
+    for (int q = 0; q < 16; ++q) bias1[q] = b1[wave * 32 + acc_row(q, h)];
 
     // features that already exist: a tile is 512 float4, one per thread; the NEXT tile's piece is fetched while this tile's
     // matrix products run (a tile is otherwise one global round trip + three barriers deep: 8.7 -> ~5 us per tile)
@@ -152,65 +118,24 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
             for (int i = tid; i < npair * MF; i += MB) out_gram[tile * tp * MF + i] = feat[(i / MF) * TS + (i % MF)];
         }
         // ---- layer 1, hidden tile `wave`: H^T = W1 . X^T; lane (r, h) holds X[pair r][16 s + 8 h + j] as B operand
-        f32x16 acc, y0, y1;
+        f32x16 acc, y[2];                         // y: the wave's share of the two output tiles
 #pragma unroll
-        for (int q = 0; q < 16; ++q) { acc[q] = 0.0f; y0[q] = 0.0f; y1[q] = 0.0f; }
-        if constexpr (F32) {
-            float xs[32];                         // X[pair r][32 h + s], s = 0..31
-#pragma unroll
-            for (int q4 = 0; q4 < 8; ++q4) {
-                const float4 x = *reinterpret_cast<const float4*>(feat + r * TS + 32 * h + 4 * q4);
-                xs[4 * q4] = x.x; xs[4 * q4 + 1] = x.y; xs[4 * q4 + 2] = x.z; xs[4 * q4 + 3] = x.w;
-            }
-#pragma unroll
-            for (int s = 0; s < 32; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f1[s], xs[s], acc, 0, 0, 0);
-            // register q = hidden row 32 wave + (q&3) + 8 (q>>2) + 4 h of pair r: bias, ReLU; it IS the B operand of k-step q
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                float x = acc[q] + bias1[q];
-                x = x > 0.0f ? x : 0.0f;
-                y0 = __builtin_amdgcn_mfma_f32_32x32x2f32(f2[0][q], x, y0, 0, 0, 0);
-                y1 = __builtin_amdgcn_mfma_f32_32x32x2f32(f2[1][q], x, y1, 0, 0, 0);
-            }
-        } else if constexpr (X3) {
+        for (int q = 0; q < 16; ++q) { acc[q] = 0.0f; y[0][q] = 0.0f; y[1][q] = 0.0f; }
+        if constexpr (X3) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 bf16x8 bxh, bxl;
-                split8(feat + r * TS + 16 * s + 8 * h, bxh, bxl);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l[s], bxh, acc, 0, 0, 0);     // the small terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[s], bxl, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[s], bxh, acc, 0, 0, 0);
+                load_split8(feat + r * TS + 16 * s + 8 * h, bxh, bxl);
+                acc = mm3(a1[s], a1l[s], bxh, bxl, acc);
             }
             bf16x8 bhh[2], bhl[2];
+            relu_split16(acc, bias1, bhh, bhl);
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                float x = acc[q] + bias1[q];
-                x = x > 0.0f ? x : 0.0f;
-                const __bf16 hi = (__bf16)x;
-                bhh[q >> 3][q & 7] = hi;
-                bhl[q >> 3][q & 7] = (__bf16)(x - (float)hi);
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                y0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2l[s2][0], bhh[s2], y0, 0, 0, 0);
-                y1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2l[s2][1], bhh[s2], y1, 0, 0, 0);
-                y0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[s2][0], bhl[s2], y0, 0, 0, 0);
-                y1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[s2][1], bhl[s2], y1, 0, 0, 0);
-                y0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[s2][0], bhh[s2], y0, 0, 0, 0);
-                y1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[s2][1], bhh[s2], y1, 0, 0, 0);
-            }
+            for (int s2 = 0; s2 < 2; ++s2) mm3(a2[s2], a2l[s2], bhh[s2], bhl[s2], y);       // the two output tiles taking turns
         } else {
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const float* xr = feat + r * TS + 16 * s + 8 * h;
-                const float4 lo = *reinterpret_cast<const float4*>(xr);
-                const float4 hi = *reinterpret_cast<const float4*>(xr + 4);
-                bf16x8 bx;
-                bx[0] = (__bf16)lo.x; bx[1] = (__bf16)lo.y; bx[2] = (__bf16)lo.z; bx[3] = (__bf16)lo.w;
-                bx[4] = (__bf16)hi.x; bx[5] = (__bf16)hi.y; bx[6] = (__bf16)hi.z; bx[7] = (__bf16)hi.w;
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[s], bx, acc, 0, 0, 0);
-            }
-            // register q = hidden row 32 wave + (q&3) + 8 (q>>2) + 4 h, column = pair r  ->  bias, ReLU, B operand of layer 2
+            for (int s = 0; s < 4; ++s) acc = mfma(a1[s], load_cvt8(feat + r * TS + 16 * s + 8 * h), acc);
+            // register q = hidden row 32 wave + acc_row(q, h), column = pair r  ->  bias, ReLU, B operand of layer 2
             bf16x8 bh[2];
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
@@ -220,19 +145,19 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                y0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[s2][0], bh[s2], y0, 0, 0, 0);
-                y1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[s2][1], bh[s2], y1, 0, 0, 0);
+                y[0] = mfma(a2[s2][0], bh[s2], y[0]);
+                y[1] = mfma(a2[s2][1], bh[s2], y[1]);
             }
         }
         // ---- the eight partial tiles, added in a fixed order: waves 0..3 park theirs, waves 4..7 add theirs on top, then
-        // every thread sums the four slabs for its outputs.  y0[4i..4i+3] = outputs 8i + 4h + (0..3) of pair r, y1: + 32
+        // every thread sums the four slabs for its outputs.  y[0][4i..4i+3] = outputs 8i + 4h + (0..3) of pair r, y[1]: + 32
         float* sl = slab[wave & 3] + r * TS;
         if (wave < 4) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int o = 8 * i + 4 * h;
-                *reinterpret_cast<float4*>(sl + o) = make_float4(y0[4 * i], y0[4 * i + 1], y0[4 * i + 2], y0[4 * i + 3]);
-                *reinterpret_cast<float4*>(sl + 32 + o) = make_float4(y1[4 * i], y1[4 * i + 1], y1[4 * i + 2], y1[4 * i + 3]);
+                *reinterpret_cast<float4*>(sl + o) = make_float4(y[0][4 * i], y[0][4 * i + 1], y[0][4 * i + 2], y[0][4 * i + 3]);
+                *reinterpret_cast<float4*>(sl + 32 + o) = make_float4(y[1][4 * i], y[1][4 * i + 1], y[1][4 * i + 2], y[1][4 * i + 3]);
             }
         }
         __syncthreads();
@@ -241,8 +166,8 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
             for (int i = 0; i < 4; ++i) {
                 const int o = 8 * i + 4 * h;
                 float4 a = *reinterpret_cast<float4*>(sl + o), b = *reinterpret_cast<float4*>(sl + 32 + o);
-                a.x += y0[4 * i]; a.y += y0[4 * i + 1]; a.z += y0[4 * i + 2]; a.w += y0[4 * i + 3];
-                b.x += y1[4 * i]; b.y += y1[4 * i + 1]; b.z += y1[4 * i + 2]; b.w += y1[4 * i + 3];
+                a.x += y[0][4 * i]; a.y += y[0][4 * i + 1]; a.z += y[0][4 * i + 2]; a.w += y[0][4 * i + 3];
+                b.x += y[1][4 * i]; b.y += y[1][4 * i + 1]; b.z += y[1][4 * i + 2]; b.w += y[1][4 * i + 3];
                 *reinterpret_cast<float4*>(sl + o) = a;
                 *reinterpret_cast<float4*>(sl + 32 + o) = b;
             }
@@ -268,12 +193,6 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
     }
 }
 
-// the fp32-class dense layers: 2 = split bf16 operands (default), 1 = fp32 MFMA (developer builds: TPNET_DEV_MLP_F32_MODE=1)
-int mlp_f32_mode() {
-    static const int m = TPNET_DEV_INT(MLP_F32_MODE, 2);
-    return m == 1 ? 1 : 2;
-}
-
 bool pair_feature_mfma_supported(const tpnet_state& st) {
     const Geom gm = pick_geom(st.d);
     return st.L == 3 && gm.w == 4 && gm.lpp >= 16;
@@ -281,7 +200,7 @@ bool pair_feature_mfma_supported(const tpnet_state& st) {
 
 int launch_pair_feature_bf16(const tpnet_state& st, const int64_t* u, const int64_t* v, int64_t n, double now, double lambda,
                              uint32_t flags, const void* w1, const float* b1, const void* w2p, const float* b2,
-                             float* out_gram, float* out, hipStream_t s, int mode, const float* feat_in) {
+                             float* out_gram, float* out, hipStream_t s, bool split, const float* feat_in) {
     if (n == 0) return TPNET_OK;
     if (st.L != 3 || (flags & TPNET_FLAG_PACKED)) return TPNET_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(b2)) & 15) return TPNET_ERR_BAD_ARG;
@@ -299,11 +218,8 @@ int launch_pair_feature_bf16(const tpnet_state& st, const int64_t* u, const int6
     const int grid = (int)(tiles < grid_cap ? tiles : grid_cap);
 #define TPNET_PF(LPP_, VPL_, FULL_)                                                                                          \
     do {                                                                                                                     \
-        if (mode == 2)                                                                                                       \
+        if (split)                                                                                                           \
             hipLaunchKernelGGL((k_pair_feature_bf16<LPP_, VPL_, 4, FULL_, 2>), dim3(grid), dim3(MB), 0, s, st, u, v, n, now,    \
-                               lambda, flags, w1, b1, w2p, b2, out_gram, out, feat_in, tp);                                         \
-        else if (mode == 1)                                                                                                  \
-            hipLaunchKernelGGL((k_pair_feature_bf16<LPP_, VPL_, 4, FULL_, 1>), dim3(grid), dim3(MB), 0, s, st, u, v, n, now,    \
                                lambda, flags, w1, b1, w2p, b2, out_gram, out, feat_in, tp);                                         \
         else                                                                                                                 \
             hipLaunchKernelGGL((k_pair_feature_bf16<LPP_, VPL_, 4, FULL_, 0>), dim3(grid), dim3(MB), 0, s, st, u, v, n, now,    \
@@ -331,9 +247,21 @@ __global__ void k_mlp_prepare(const float* __restrict__ w1, const float* __restr
         { const int h = i / F, f = i - h * F; w2t[i] = w2[f * H + h]; }
         if (w2f) {            // F = 64, H = 256: i = ((w * 2 + t) * 64 + lane) * 16 + s   (include/tpnet_hip.h, tpnet_mlp::w2f)
             const int s_ = i & 15, lane = (i >> 4) & 63, t = (i >> 10) & 1, w = i >> 11;
-            w2f[i] = w2[(32 * t + (lane & 31)) * H + 32 * w + (s_ & 3) + 8 * (s_ >> 2) + 4 * (lane >> 5)];
+            w2f[i] = w2[(32 * t + (lane & 31)) * H + 32 * w + acc_row(s_, lane >> 5)];
         }
     }
+}
+
+// the dense layers on existing rows: ONE route for tpnet_mlp64_f32 and the encoder's two-launch calls (encoder.hip)
+int launch_mlp_rows(const tpnet_mlp* mlp, const float* x, int64_t n, float* y, hipStream_t s) {
+    // long lists: every wave its own tiles, split weights in LDS (mlp_x3.hip)
+    if (n >= mlp_x3_from() && mlp_x3_available() &&
+        launch_mlp_rows_x3(x, n, reinterpret_cast<const float*>(mlp->w1), mlp->b1, reinterpret_cast<const float*>(mlp->w2f),
+                           mlp->b2, y, s) == TPNET_OK)
+        return TPNET_OK;
+    tpnet_state st{};                      // (not dereferenced when the tile comes from `x`; geometry of d = 128 picks the 32-lane kernel)
+    st.N = 1; st.d = 128; st.L = 3;
+    return launch_pair_feature_bf16(st, nullptr, nullptr, n, 0.0, 0.0, 0, mlp->w1, mlp->b1, mlp->w2f, mlp->b2, nullptr, y, s, true, x);
 }
 
 }  // namespace tpnet
@@ -356,7 +284,7 @@ extern "C" int tpnet_pair_feature_bf16(const tpnet_state* st, const int64_t* u, 
     if (check_state(st)) return TPNET_ERR_BAD_ARG;
     if (n < 0 || (n > 0 && (!u || !v || !out || !w1_bf16 || !b1 || !w2p_bf16 || !b2))) return TPNET_ERR_BAD_ARG;
     return launch_pair_feature_bf16(*st, u, v, n, now_time, lambda, flags, w1_bf16, b1, w2p_bf16, b2, out_gram, out,
-                                    (hipStream_t)stream, 0, nullptr);
+                                    (hipStream_t)stream, false, nullptr);
 }
 
 extern "C" int tpnet_mlp64_f32(const float* x, int64_t n, const tpnet_mlp* mlp, float* y, void* stream) {
@@ -364,13 +292,5 @@ extern "C" int tpnet_mlp64_f32(const float* x, int64_t n, const tpnet_mlp* mlp, 
     if (n == 0) return TPNET_OK;
     if (mlp->F != 64 || mlp->H != 256 || !mlp->w1 || !mlp->w2f || !mlp->b1 || !mlp->b2) return TPNET_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return TPNET_ERR_BAD_ARG;
-    // long lists: every wave its own tiles, split weights in LDS (mlp_x3.hip)
-    if (n >= mlp_x3_from() && mlp_f32_mode() == 2 && mlp_x3_available() &&
-        launch_mlp_rows_x3(x, n, reinterpret_cast<const float*>(mlp->w1), mlp->b1, reinterpret_cast<const float*>(mlp->w2f),
-                           mlp->b2, y, (hipStream_t)stream) == TPNET_OK)
-        return TPNET_OK;
-    tpnet_state st{};                      // (not dereferenced when the tile comes from `x`; geometry of d = 128 picks the 32-lane kernel)
-    st.N = 1; st.d = 128; st.L = 3;
-    return launch_pair_feature_bf16(st, nullptr, nullptr, n, 0.0, 0.0, 0, mlp->w1, mlp->b1, mlp->w2f, mlp->b2, nullptr, y,
-                                    (hipStream_t)stream, mlp_f32_mode(), x);
+    return launch_mlp_rows(mlp, x, n, y, (hipStream_t)stream);
 }

@@ -7,11 +7,9 @@
 // next MFMA's operand'); W2 is pre-permuted on the host to the k order that operand implies.
 // Only the (2L+2)^2 = 64 feature case (L = 3, the reference default) has an MFMA kernel; other L keep torch.
 #include "tpnet_common.h"
+#include "mfma_split.hpp"
 
 namespace tpnet {
-
-typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16;
 
 static constexpr int MLP_F = 64, MLP_H = 256;
 static constexpr int W1_STRIDE = MLP_F + 8;    // bf16 elements per LDS row: 144 B, ds_read_b128 conflict-free
@@ -48,12 +46,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void k_mlp64_bf16(const float* __restric
         // B operand of layer 1: X^T, k-step s, lane (r, h) holds X[pair r][16 s + 8 h + j]
         bf16x8 bx[4];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const float4 lo = *reinterpret_cast<const float4*>(xr + 16 * s + 8 * h);
-            const float4 hi = *reinterpret_cast<const float4*>(xr + 16 * s + 8 * h + 4);
-            bx[s][0] = (__bf16)lo.x; bx[s][1] = (__bf16)lo.y; bx[s][2] = (__bf16)lo.z; bx[s][3] = (__bf16)lo.w;
-            bx[s][4] = (__bf16)hi.x; bx[s][5] = (__bf16)hi.y; bx[s][6] = (__bf16)hi.z; bx[s][7] = (__bf16)hi.w;
-        }
+        for (int s = 0; s < 4; ++s) bx[s] = load_cvt8(xr + 16 * s + 8 * h);
         f32x16 y0, y1;
 #pragma unroll
         for (int q = 0; q < 16; ++q) { y0[q] = 0.0f; y1[q] = 0.0f; }
@@ -65,13 +58,13 @@ __global__ __launch_bounds__(MLP_BLOCK) void k_mlp64_bf16(const float* __restric
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const bf16x8 a = *reinterpret_cast<const bf16x8*>(&w1s[(ht * 32 + r) * W1_STRIDE + 16 * s + 8 * h]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bx[s], acc, 0, 0, 0);
+                acc = mfma(a, bx[s], acc);
             }
-            // register q of the tile = hidden row ht*32 + (q&3) + 8*(q>>2) + 4*h, column = pair r
+            // register q of the tile = hidden row ht*32 + acc_row(q, h), column = pair r
             bf16x8 bh[2];
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
-                float v = acc[q] + b1[ht * 32 + (q & 3) + 8 * (q >> 2) + 4 * h];
+                float v = acc[q] + b1[ht * 32 + acc_row(q, h)];
                 v = v > 0.0f ? v : 0.0f;
                 bh[q >> 3][q & 7] = (__bf16)v;
             }
@@ -80,15 +73,15 @@ __global__ __launch_bounds__(MLP_BLOCK) void k_mlp64_bf16(const float* __restric
                 const int off = ht * 32 + 16 * s2 + 8 * h;       // position inside the PERMUTED hidden axis
                 const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&w2s[r * W2_STRIDE + off]);
                 const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&w2s[(32 + r) * W2_STRIDE + off]);
-                y0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bh[s2], y0, 0, 0, 0);
-                y1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bh[s2], y1, 0, 0, 0);
+                y0 = mfma(a0, bh[s2], y0);
+                y1 = mfma(a1, bh[s2], y1);
             }
         }
         if (valid) {
             float* yr = Y + pair * MLP_F;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int o = 8 * i + 4 * h;                      // output rows (q&3) + 8*(q>>2) + 4*h, q = 4i..4i+3
+                const int o = 8 * i + 4 * h;                      // output rows acc_row(q, h), q = 4i..4i+3
                 const float4 bb0 = *reinterpret_cast<const float4*>(b2 + o);
                 const float4 bb1 = *reinterpret_cast<const float4*>(b2 + 32 + o);
                 *reinterpret_cast<float4*>(yr + o) =

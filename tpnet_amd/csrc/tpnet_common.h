@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <initializer_list>
 #include <new>
 #include "../../include/tpnet_hip.h"
 #include "tpnet_dev.h"
@@ -196,10 +197,30 @@ bool mlp_x3_available();
 int64_t mlp_x3_from();
 int launch_mlp_rows_x3(const float* x, int64_t n, const float* w1f, const float* b1, const float* w2f, const float* b2, float* y,
                        hipStream_t s);
+// split = false: bf16 operands (the opt-in class; w1 / w2p bf16); true: the fp32 class on split operands (w1 = f32 [256][64],
+// w2p = tpnet_mlp::w2f)
 int launch_pair_feature_bf16(const tpnet_state& st, const int64_t* u, const int64_t* v, int64_t n, double now, double lambda,
                              uint32_t flags, const void* w1, const float* b1, const void* w2p, const float* b2,
-                             float* out_gram, float* out, hipStream_t s, int mode, const float* feat_in = nullptr);
-int mlp_f32_mode();
+                             float* out_gram, float* out, hipStream_t s, bool split, const float* feat_in = nullptr);
+// the fp32-class dense layers on existing rows x [n][64] -> y: mlp_x3.hip's kernel from mlp_x3_from() rows on, else the tile kernel
+int launch_mlp_rows(const tpnet_mlp* mlp, const float* x, int64_t n, float* y, hipStream_t s);
+
+// "May these kernels have `bytes` of dynamic LDS?"  Asked once (hipFuncSetAttribute on every kernel of the list), remembered;
+// refused(): a launch was refused all the same -- never again, the callers take their other route for good.
+struct LdsOptIn {
+    int state = 0;                         // 0: not decided; 1: granted; -1: this device / runtime does not give a workgroup that much
+    bool granted(std::initializer_list<const void*> kernels, size_t bytes, bool off = false) {
+        if (state == 0) {
+            bool ok = !off;
+            for (const void* k : kernels)
+                ok = ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+            (void)hipGetLastError();
+            state = ok ? 1 : -1;
+        }
+        return state == 1;
+    }
+    void refused() { state = -1; }
+};
 
 // the plan of ONE batch by one workgroup (plan.hip, k_plan_one): same Plan contents as plan_build for batch 0 of a chunk
 static constexpr int64_t PLAN_ONE_MAX = 2048;

@@ -6,11 +6,12 @@ the fp32 path (expect ~1e-2 relative on a logit), so the default stays the torch
 kernel (no concatenated input, no hidden layer in memory); backward recomputes the hidden layer with torch in fp32 and
 returns exact fp32 gradients for fc1 / fc2 AND for the three inputs (the embeddings come from the trainable encoder, the
 feature from the trainable `rp.mlp`)."""
-import ctypes as C
+import weakref
+from typing import NamedTuple
 
 import torch
 
-from . import _lib
+from . import _dense, _lib
 
 
 def pack_weights(fc1: torch.nn.Linear, fc2: torch.nn.Linear, D: int, F: int):
@@ -40,16 +41,23 @@ def supported(fc1, fc2, D: int, F: int) -> bool:
             and (D > 0 or F > 0))
 
 
+class _Record(NamedTuple):
+    key: tuple
+    storage: tuple
+    packed: tuple
+
+
+_PREPARED = weakref.WeakKeyDictionary()     # the decoder module -> _Record
+
+
 def _prepared(owner, fc1, fc2, D, F):
     """Packed copies of the weights, rebuilt only when a parameter changed (optimizer step, load_state_dict, .to())."""
-    ps = (fc1.weight, fc1.bias, fc2.weight, fc2.bias)
-    key = tuple((p.data_ptr(), p._version, p.device) for p in ps) + (D, F)
-    cache = owner.__dict__.get("_tpnet_decoder_prepared")
-    if cache is None or cache[0] != key:
+    def build(_previous):
         with torch.no_grad():
-            cache = (key, pack_weights(fc1, fc2, D, F))
-        owner.__dict__["_tpnet_decoder_prepared"] = cache
-    return cache[1]
+            return _Record(key, (), pack_weights(fc1, fc2, D, F))
+
+    key = _dense.param_key(fc1.weight, fc1.bias, fc2.weight, fc2.bias) + (fc1.weight.device, D, F)
+    return _dense.cached(_PREPARED, owner, key, (), build).packed
 
 
 class _FusedDecoder(torch.autograd.Function):
@@ -65,11 +73,10 @@ class _FusedDecoder(torch.autograd.Function):
             feat = feat.contiguous()
         out = torch.empty((n, 1), dtype=torch.float32, device=ref.device)
         w1p, b1p, w2p, b2f, HT = prep
-        stream = C.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream)
         _lib.check(_lib.load().tpnet_decoder_bf16(
             None if not_encode else src.data_ptr(), None if not_encode else dst.data_ptr(), D,
             None if feat is None else feat.data_ptr(), F, n, w1p.data_ptr(), b1p.data_ptr(), w2p.data_ptr(), b2f, HT,
-            out.data_ptr(), stream), "decoder_bf16")
+            out.data_ptr(), _dense.stream_ptr(ref.device)), "decoder_bf16")
         ctx.not_encode = not_encode
         ctx.has_feat = feat is not None
         ctx.save_for_backward(src, dst, feat if feat is not None else src.new_empty(0), w1, b1, w2)
@@ -82,14 +89,7 @@ class _FusedDecoder(torch.autograd.Function):
         if ctx.not_encode:                                   # modules.py:106-108: the embeddings are replaced by zeros
             src = torch.zeros_like(src); dst = torch.zeros_like(dst)
         x = torch.cat([src, dst, feat], dim=1) if ctx.has_feat else torch.cat([src, dst], dim=1)
-        pre = torch.addmm(b1, x, w1.t())                     # fp32 recompute of the hidden layer
-        hid = torch.relu(pre)
-        gw2 = gout.t() @ hid
-        gb2 = gout.sum(0)
-        gh = (gout @ w2) * (pre > 0)
-        gw1 = gh.t() @ x
-        gb1 = gh.sum(0)
-        gx = gh @ w1
+        gw1, gb1, gw2, gb2, gx = _dense.layer_grads(x, gout, w1, b1, w2, input_grad=True)
         gsrc = None if ctx.not_encode else gx[:, :D]
         gdst = None if ctx.not_encode else gx[:, D:2 * D]
         gfeat = gx[:, 2 * D:] if ctx.has_feat else None

@@ -13,7 +13,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib
+from . import _dense, _lib
 
 _PREPARED = weakref.WeakKeyDictionary()     # mlp module -> Prepared (kept off the module: ctypes objects do not deepcopy)
 
@@ -33,11 +33,9 @@ MAX_PAIRS = int(os.environ.get("TPNET_DEV_FUSED_MAX_PAIRS", "8192"))
 
 
 def supported(mlp: torch.nn.Module, F: int) -> bool:
-    return (isinstance(mlp, torch.nn.Sequential) and len(mlp) == 3 and isinstance(mlp[0], torch.nn.Linear)
-            and isinstance(mlp[1], torch.nn.ReLU) and isinstance(mlp[2], torch.nn.Linear)
-            and mlp[0].in_features == F and mlp[0].out_features == 4 * F and mlp[2].in_features == 4 * F
-            and mlp[2].out_features == F and mlp[0].bias is not None and mlp[2].bias is not None
-            and mlp[0].weight.dtype == torch.float32 and mlp[0].weight.is_cuda)
+    ls = _dense.linear_relu_linear(mlp)
+    return (ls is not None and ls[0].in_features == F and ls[0].out_features == 4 * F and ls[1].out_features == F
+            and ls[0].weight.dtype == torch.float32 and ls[0].weight.is_cuda)
 
 
 _W2F_IDX = {}
@@ -90,24 +88,14 @@ def weight_grads_f32(x, gy, w1, b1, w2, prep, mode=None):
     if (mode == "mfma" and prep is not None and x.is_cuda and n >= MFMA_BWD_FROM and x.dtype == torch.float32 and prep.st.w1 and prep.st.w2t
             and prep.key[:6] == (w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version)):
         lib = _lib.load()
-        x = x.contiguous()
-        gy = gy.contiguous().float()
-        pf = int(lib.tpnet_mlp64_bwd_partial_floats())
-        nblk = min(256, (n + 31) // 32)
-        part = torch.empty((nblk, pf), dtype=torch.float32, device=x.device)
-        rc = lib.tpnet_mlp64_bwd_f32(x.data_ptr(), gy.data_ptr(), n, prep.ref, part.data_ptr(), nblk,
-                                     C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc > 0:
-            tot = part[:rc].sum(0)
-            H, F = w1.shape
-            return tot[:H * F].view(H, F), tot[2 * H * F:2 * H * F + H], tot[H * F:2 * H * F].view(F, H), gy.sum(0)
+        rc, grads = _dense.mlp64_bwd(lambda xp, gp, n_, part, nblk, stream: lib.tpnet_mlp64_bwd_f32(xp, gp, n_, prep.ref, part, nblk, stream),
+                                     x, gy, *w1.shape)
+        if grads is not None:
+            return grads
         if rc not in _declined_once:                    # (said once per code: the torch expressions below serve the call)
             _declined_once.add(rc)
             warnings.warn(f"tpnet_mlp64_bwd_f32 declined a call of {n} rows (rc {rc}): weight gradients by the fp32 torch expressions")
-    pre = torch.addmm(b1, x, w1.t())                 # fp32 recompute of the hidden layer
-    hid = torch.relu(pre)
-    gh = (gy @ w2) * (pre > 0)
-    return gh.t() @ x, gh.sum(0), gy.t() @ hid, gy.sum(0)
+    return _dense.layer_grads(x, gy, w1, b1, w2)
 
 
 class _MlpF32(torch.autograd.Function):
@@ -118,8 +106,7 @@ class _MlpF32(torch.autograd.Function):
         x = x.contiguous()
         y = torch.empty_like(x)
         if x.shape[0]:
-            rc = _lib.load().tpnet_mlp64_f32(x.data_ptr(), x.shape[0], mlp_ref, y.data_ptr(),
-                                             C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+            rc = _lib.load().tpnet_mlp64_f32(x.data_ptr(), x.shape[0], mlp_ref, y.data_ptr(), _dense.stream_ptr(x.device))
             if rc:
                 _lib.check(rc, "mlp64_f32")
         ctx.save_for_backward(x, w1, b1, w2)
@@ -131,10 +118,8 @@ class _MlpF32(torch.autograd.Function):
     def backward(ctx, gy):
         x, w1, b1, w2 = ctx.saved_tensors
         if ctx.needs_input_grad[0]:                            # (the readout's features carry no gradient; a caller's own x may)
-            pre = torch.addmm(b1, x, w1.t())
-            hid = torch.relu(pre)
-            gh = (gy @ w2) * (pre > 0)
-            return gh @ w1, gh.t() @ x, gh.sum(0), gy.t() @ hid, gy.sum(0), None, None, None
+            gw1, gb1, gw2, gb2, gx = _dense.layer_grads(x, gy, w1, b1, w2, input_grad=True)
+            return gx, gw1, gb1, gw2, gb2, None, None, None
         gw1, gb1, gw2, gb2 = weight_grads_f32(x, gy, w1, b1, w2, ctx.prep, ctx.mode)
         return None, gw1, gb1, gw2, gb2, None, None, None
 
@@ -184,17 +169,22 @@ def prepared(mlp, F):
             return None
     except (KeyError, AttributeError):
         return None
+    # (this runs on every per-batch call: the key and its check stay inline -- _dense.param_key / _dense.cached would add two
+    # Python frames to the hit path; the rebuild below goes through the shared cache function)
     key = (w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version, b2.data_ptr(), b2._version)
     cache = _PREPARED.get(mlp)
-    if cache is None or cache.key != key:
+    if cache is not None and cache.key == key:
+        return cache
+    storage = (w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr())
+
+    def build(previous):
         if not supported(mlp, F) or not (w1.is_contiguous() and w2.is_contiguous() and b1.is_contiguous() and b2.is_contiguous()):
             return None
         # the derived layouts (w1t, w2t and, for F = 64, the gathered w2f) live in buffers that stay with the module and are
         # rewritten by ONE launch (tpnet_mlp_prepare) when a parameter changed; b1, b2 and tpnet_mlp::w1 are the Parameters' own
         # storage.  (As torch expressions -- two transposes, a copy, an index gather -- this was ~100 us of every training step.)
-        storage = (w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr())
-        if cache is not None and cache.storage == storage:
-            keep, st = cache.derived, cache.st
+        if previous is not None:
+            keep, st = previous.derived, previous.st
         else:
             H = w1.shape[0]
             x64 = F == 64 and H == 256
@@ -207,14 +197,13 @@ def prepared(mlp, F):
                           w2f=keep[2].data_ptr() if keep[2] is not None else None,
                           wimg=keep[3].data_ptr() if keep[3] is not None else None)
         _lib.check(_lib.load().tpnet_mlp_prepare(w1.data_ptr(), w2.data_ptr(), F, w1.shape[0], keep[0].data_ptr(), keep[1].data_ptr(),
-                                                 keep[2].data_ptr() if keep[2] is not None else None,
-                                                 C.c_void_p(torch.cuda.current_stream(w1.device).cuda_stream)), "mlp_prepare")
+                                                 keep[2].data_ptr() if keep[2] is not None else None, _dense.stream_ptr(w1.device)), "mlp_prepare")
         if keep[3] is not None:
             _lib.check(_lib.load().tpnet_mlp_prepare_image(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), keep[3].data_ptr(),
-                                                           C.c_void_p(torch.cuda.current_stream(w1.device).cuda_stream)), "mlp_prepare_image")
-        cache = Prepared(key, st, C.byref(st), keep, (w1, b1, w2, b2), storage)
-        _PREPARED[mlp] = cache
-    return cache
+                                                           _dense.stream_ptr(w1.device)), "mlp_prepare_image")
+        return Prepared(key, st, C.byref(st), keep, (w1, b1, w2, b2), storage)
+
+    return _dense.cached(_PREPARED, mlp, key, storage, build)
 
 
 class _FusedFeature(torch.autograd.Function):

@@ -9,7 +9,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _lib
+from . import _dense, _lib
 
 _PREPARED = weakref.WeakKeyDictionary()     # projection_layer -> Prepared
 calls = {"forward": 0, "prepare": 0}        # launches made through this binding (tests assert the dispatch through it)
@@ -23,19 +23,9 @@ class Prepared(NamedTuple):
     storage: tuple      # device + the Parameters' data_ptr()s + dims: the same storage keeps the image buffer
 
 
-def _layers(proj):
-    if not (isinstance(proj, torch.nn.Sequential) and len(proj) == 3 and isinstance(proj[0], torch.nn.Linear)
-            and isinstance(proj[1], torch.nn.ReLU) and isinstance(proj[2], torch.nn.Linear)):
-        return None
-    l1, l2 = proj[0], proj[2]
-    if l1.bias is None or l2.bias is None or l2.in_features != l1.out_features:
-        return None
-    return l1, l2
-
-
 def dims_of(proj, Dn: int, Dt: int, De: int, F: int):
     """(Dn, Dt, De, F, H, Dout) if `proj` is Linear -> ReLU -> Linear with biases on Dn + Dt + De + 2 F inputs, else None."""
-    ls = _layers(proj)
+    ls = _dense.linear_relu_linear(proj)
     if ls is None or ls[0].in_features != Dn + Dt + De + 2 * F:
         return None
     return (int(Dn), int(Dt), int(De), int(F), int(ls[0].out_features), int(ls[1].out_features))
@@ -66,31 +56,30 @@ def cached(proj):
 def prepared(proj, Dn: int, Dt: int, De: int, F: int):
     """The Prepared record of `proj`, or None where the kernel does not serve it.  The image is rewritten in place, on the current
     stream, when a Parameter changed through a versioned op (optimizer step, load_state_dict, copy_())."""
-    ls = _layers(proj)
+    ls = _dense.linear_relu_linear(proj)
     if ls is None:
         return None
     w1, b1, w2, b2 = ls[0].weight, ls[0].bias, ls[1].weight, ls[1].bias
-    key = (Dn, Dt, De, F, w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version, b2.data_ptr(), b2._version)
-    cache = _PREPARED.get(proj)
-    if cache is not None and cache.key == key:
-        return cache
-    if not supported(proj, Dn, Dt, De, F) or not all(p.is_contiguous() and p.dtype == torch.float32 for p in (w1, b1, w2, b2)):
-        return None
-    lib = _lib.load()
-    d = dims_of(proj, Dn, Dt, De, F)
+    d = (int(Dn), int(Dt), int(De), int(F), int(ls[0].out_features), int(ls[1].out_features))
+
+    def build(previous):
+        if not supported(proj, Dn, Dt, De, F) or not all(p.is_contiguous() and p.dtype == torch.float32 for p in (w1, b1, w2, b2)):
+            return None
+        lib = _lib.load()
+        if previous is not None:
+            dims, img, err = previous.dims, previous.img, previous.err
+        else:
+            dims = (C.c_int32 * 6)(*d)
+            img = torch.empty(int(lib.tpnet_encoder_input_image_bytes(*d)), dtype=torch.uint8, device=w1.device)
+            err = torch.zeros(1, dtype=torch.int32, device=w1.device)
+        _lib.check(lib.tpnet_encoder_input_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), dims, img.data_ptr(),
+                                                   _dense.stream_ptr(w1.device)), "encoder_input_prepare")
+        calls["prepare"] += 1
+        return Prepared(key, dims, img, err, storage)
+
+    key = (Dn, Dt, De, F) + _dense.param_key(w1, b1, w2, b2)
     storage = (w1.device, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()) + d
-    if cache is not None and cache.storage == storage:
-        dims, img, err = cache.dims, cache.img, cache.err
-    else:
-        dims = (C.c_int32 * 6)(*d)
-        img = torch.empty(int(lib.tpnet_encoder_input_image_bytes(*d)), dtype=torch.uint8, device=w1.device)
-        err = torch.zeros(1, dtype=torch.int32, device=w1.device)
-    _lib.check(lib.tpnet_encoder_input_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), dims, img.data_ptr(),
-                                               C.c_void_p(torch.cuda.current_stream(w1.device).cuda_stream)), "encoder_input_prepare")
-    calls["prepare"] += 1
-    cache = Prepared(key, dims, img, err, storage)
-    _PREPARED[proj] = cache
-    return cache
+    return _dense.cached(_PREPARED, proj, key, storage, build)
 
 
 def encoder_input(prep: Prepared, node_raw, edge_raw, neigh, eids, tn, tq, tw, tb, feats):
@@ -114,13 +103,11 @@ def encoder_input(prep: Prepared, node_raw, edge_raw, neigh, eids, tn, tq, tw, t
     _lib.check(_lib.load().tpnet_encoder_input(
         node_raw.data_ptr(), node_raw.shape[0], edge_raw.data_ptr(), edge_raw.shape[0], neigh.data_ptr(), eids.data_ptr(), tn.data_ptr(),
         tq.data_ptr(), tw.data_ptr(), tb.data_ptr(), feats.data_ptr(), n, K, prep.dims, prep.img.data_ptr(), out.data_ptr(),
-        prep.err.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "encoder_input")
+        prep.err.data_ptr(), _dense.stream_ptr(dev)), "encoder_input")
     calls["forward"] += 1
     return out
 
 
 def check_errors(prep: Prepared):
     """Raise IndexError if a launch met a node / edge id outside the raw feature tables since the last check (synchronises)."""
-    _lib.check(_lib.load().tpnet_encoder_input_check(prep.err.data_ptr(),
-                                                     C.c_void_p(torch.cuda.current_stream(prep.err.device).cuda_stream)),
-               "encoder_input")
+    _lib.check(_lib.load().tpnet_encoder_input_check(prep.err.data_ptr(), _dense.stream_ptr(prep.err.device)), "encoder_input")

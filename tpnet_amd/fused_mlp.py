@@ -5,11 +5,12 @@ Opt-in (`RandomProjectionModule.fused_mlp = True`): bf16 operands with fp32 accu
 parity budget of the fp32 path (expect ~1e-2 relative), so the default stays the torch fp32 layers.  Forward runs
 the fused kernel; backward recomputes the hidden layer with torch in fp32 and returns exact fp32 gradients for the
 four parameter tensors (the input features carry no gradient: the projections are requires_grad=False)."""
-import ctypes as C
+import weakref
+from typing import NamedTuple
 
 import torch
 
-from . import _lib
+from . import _dense, _lib
 
 F, H = 64, 256
 
@@ -28,26 +29,32 @@ def permute_w2(w2: torch.Tensor) -> torch.Tensor:
 
 
 def supported(mlp: torch.nn.Module) -> bool:
-    return (isinstance(mlp, torch.nn.Sequential) and len(mlp) == 3 and isinstance(mlp[0], torch.nn.Linear)
-            and isinstance(mlp[1], torch.nn.ReLU) and isinstance(mlp[2], torch.nn.Linear)
-            and mlp[0].in_features == F and mlp[0].out_features == H and mlp[2].in_features == H
-            and mlp[2].out_features == F and mlp[0].bias is not None and mlp[2].bias is not None)
+    ls = _dense.linear_relu_linear(mlp)
+    return ls is not None and ls[0].in_features == F and ls[0].out_features == H and ls[1].out_features == F
+
+
+class _Record(NamedTuple):
+    key: tuple
+    storage: tuple
+    bufs: tuple
+
+
+_PREPARED = weakref.WeakKeyDictionary()     # mlp module -> _Record
 
 
 def _prepared(mlp):
     """bf16 / permuted copies of the weights, rebuilt only when a parameter changed (optimizer step, load_state_dict,
     .to()): keyed on (data_ptr, _version) of the four tensors."""
     ps = (mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias)
-    key = tuple((p.data_ptr(), p._version, p.device) for p in ps)
-    cache = getattr(mlp, "_tpnet_prepared", None)
-    if cache is None or cache[0] != key:
+
+    def build(_previous):
         with torch.no_grad():
-            prep = (ps[0].detach().to(torch.bfloat16).contiguous(), ps[1].detach().float().contiguous(),
-                    permute_w2(ps[2].detach()).to(torch.bfloat16).contiguous(), ps[3].detach().float().contiguous(),
-                    ps[2].detach().t().to(torch.bfloat16).contiguous())          # [4] = W2^T [256][64]: the backward's operand
-        cache = (key, prep)
-        mlp._tpnet_prepared = cache
-    return cache[1]
+            return _Record(key, (), (ps[0].detach().to(torch.bfloat16).contiguous(), ps[1].detach().float().contiguous(),
+                                     permute_w2(ps[2].detach()).to(torch.bfloat16).contiguous(), ps[3].detach().float().contiguous(),
+                                     ps[2].detach().t().to(torch.bfloat16).contiguous()))      # [4] = W2^T [256][64]: the backward's operand
+
+    key = _dense.param_key(*ps) + (ps[0].device,)
+    return _dense.cached(_PREPARED, mlp, key, (), build).bufs
 
 
 BACKWARD = "mfma"       # "mfma": tpnet_mlp64_bwd_bf16 (bf16 operands, fp32 accumulation); "torch": the fp32 expressions
@@ -59,23 +66,12 @@ def weight_grads(x, gy, w1, b1, w2, prep=None):
     workgroups' partial results, deterministic); `BACKWARD = "torch"` or CPU tensors take the fp32 expressions."""
     if BACKWARD == "mfma" and x.is_cuda and x.shape[0] > 0 and prep is not None:
         lib = _lib.load()
-        n = int(x.shape[0])
-        x = x.contiguous()
-        gy = gy.contiguous().float()
-        pf = int(lib.tpnet_mlp64_bwd_partial_floats())
-        nblk = min(256, (n + 31) // 32)
-        part = torch.empty((nblk, pf), dtype=torch.float32, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        rc = lib.tpnet_mlp64_bwd_bf16(x.data_ptr(), gy.data_ptr(), n, prep[0].data_ptr(), prep[1].data_ptr(),
-                                      prep[4].data_ptr(), part.data_ptr(), nblk, stream)
-        if rc < 0:
+        rc, grads = _dense.mlp64_bwd(lambda xp, gp, n, part, nblk, stream: lib.tpnet_mlp64_bwd_bf16(
+            xp, gp, n, prep[0].data_ptr(), prep[1].data_ptr(), prep[4].data_ptr(), part, nblk, stream), x, gy, H, F)
+        if grads is None:
             _lib.check(rc, "mlp64_bwd_bf16")
-        tot = part[:rc].sum(0)
-        return tot[:H * F].view(H, F), tot[2 * H * F:2 * H * F + H], tot[H * F:2 * H * F].view(F, H), gy.sum(0)
-    pre = torch.addmm(b1, x, w1.t())                 # fp32 recompute of the hidden layer
-    hid = torch.relu(pre)
-    gh = (gy @ w2) * (pre > 0)
-    return gh.t() @ x, gh.sum(0), gy.t() @ hid, gy.sum(0)
+        return grads
+    return _dense.layer_grads(x, gy, w1, b1, w2)
 
 
 class _FusedMLP(torch.autograd.Function):
@@ -87,9 +83,8 @@ class _FusedMLP(torch.autograd.Function):
         n = x.shape[0]
         y = torch.empty((n, F), dtype=torch.float32, device=x.device)
         w1b, b1c, w2p, b2c = prep[:4]
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         _lib.check(_lib.load().tpnet_mlp64_bf16(x.data_ptr(), n, w1b.data_ptr(), b1c.data_ptr(), w2p.data_ptr(),
-                                                b2c.data_ptr(), y.data_ptr(), stream), "mlp64_bf16")
+                                                b2c.data_ptr(), y.data_ptr(), _dense.stream_ptr(x.device)), "mlp64_bf16")
         ctx.save_for_backward(x, w1, b1, w2)
         ctx.prep = prep
         return y
