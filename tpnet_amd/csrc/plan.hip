@@ -2,7 +2,7 @@
 // keeping the reference's summation order inside a target (models/TPNet.py:93-96: all src-side scatter-adds in edge
 // order, then all dst-side ones).  Done for a whole chunk of the stream at once (one stable device radix sort over
 // (batch, target) keys), so the per-batch step kernels find ready-made item lists and the cost is amortised.
-#include "tpnet_common.h"
+#include "wplan_common.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -991,8 +991,8 @@ static size_t wplan_extra_bytes(int64_t Ec, int64_t batch, int64_t N, int d, int
     (void)K;
     const size_t nw = (size_t)((Ec + batch - 1) / batch);       // (room for windows of ONE batch: the window length is chosen per chunk)
     size_t tot = 0;
-    tot += align_up(nc * 4, 256) * 3;                           // s_ref, s_g, s_dec
-    tot += align_up(nc * 2, 256);                               // s_bc
+    tot += align_up(nc * 4, 256) * 3;                           // wscr: bsb, bri, rprevb of the planners that sort every batch
+    tot += align_up(nc * 2, 256);                               // (spare: the workspace's size is what it was with one array per field)
     tot += align_up(nw * sizeof(WinDesc), 256) + 256;           // wdesc, wb_count
     tot += align_up(3 * (size_t)Ec * 4, 256) * 2;               // e_ref, e_g
     tot += align_up(nc * (size_t)L * (size_t)d * 4, 256);       // version log
@@ -1046,10 +1046,8 @@ int wplan_carve(void* ws, size_t ws_bytes, int64_t Ec, int64_t batch, int64_t N,
     const size_t nc = 2 * (size_t)Ec;
     const int64_t Ew = (int64_t)K * batch;
     const size_t nw = (size_t)((Ec + batch - 1) / batch);
-    out->s_ref = (uint32_t*)take(nc * 4);
-    out->s_g = (float*)take(nc * 4);
-    out->s_dec = (float*)take(nc * 4);
-    out->s_bc = (uint16_t*)take(nc * 2);
+    out->wscr = (uint32_t*)take(3 * align_up(nc * 4, 256));     // (3 * nc words)
+    (void)take(nc * 2);
     out->wdesc = (WinDesc*)take(nw * sizeof(WinDesc));
     (void)take(256);
     out->e_ref = (uint32_t*)take(3 * (size_t)Ec * 4);
@@ -1070,7 +1068,13 @@ int wplan_carve(void* ws, size_t ws_bytes, int64_t Ec, int64_t batch, int64_t N,
     }
     out->heavy_thr = wplan_heavy_threshold(K, batch, d);
     out->chains = reinterpret_cast<Chain*>(out->base.light);
-    out->chains_sparse = reinterpret_cast<Chain*>(out->base.heavy);
+    // the records live where the per-batch schedule keeps its heavy items (32 bytes per contribution both, 256-byte aligned).  What
+    // the planners kept there moves: the sorted planner's sparse chain records to the hashed planner's tables (>= 64 bytes per
+    // contribution, and a chunk has ONE planner), the scratch of the planners that sort every batch to wscr -- the 14 bytes per
+    // contribution that s_ref, s_g, s_dec and s_bc took -- and vals_in (wplan_common.hpp: wtmp_of).  The workspace's size is unchanged.
+    static_assert(sizeof(WRec) == sizeof(Item), "WPlan::rec takes the place of Plan::heavy");
+    out->rec = reinterpret_cast<WRec*>(out->base.heavy);
+    out->chains_sparse = reinterpret_cast<Chain*>(out->wtab);
     // the second sort's keys live where the first sort's unsorted keys were (8 bytes per contribution, dead by then), its
     // payload where the first sort's payload was (dead once k_finish_w has read it)
     out->lk_in = reinterpret_cast<uint32_t*>(out->base.keys_in);
@@ -1237,10 +1241,6 @@ __device__ __forceinline__ void finish_w(uint32_t bx, uint32_t nbx, WPlan p, con
             int32_t partner;
             float wgt;
             contribution(p.base, src, dst, t, Ec, B, N, lambda, val, partner, wgt, err);
-            p.base.s_partner[j] = partner;
-            p.base.s_coef[j] = wgt;
-            p.s_bc[j] = (uint16_t)b;
-            p.base.s_target[j] = (int32_t)node;
 
             const bool has_prev = j > 0, has_next = j < nc - 1;
             const K kp = has_prev ? keys[j - 1] : key, kn = has_next ? keys[j + 1] : key;
@@ -1271,11 +1271,9 @@ __device__ __forceinline__ void finish_w(uint32_t bx, uint32_t nbx, WPlan p, con
             if (ri % WIN_BLOCK == 0) fl |= WREF_BLK_HEAD;
             if (ri % WIN_BLOCK == WIN_BLOCK - 1 || run_tail) fl |= WREF_BLK_TAIL;
             if (last_run) fl |= WREF_LAST_RUN;
-            p.s_ref[j] = ref | fl;
-            p.s_g[j] = g;
             float dec = 1.0f;
             if (run_head && same_node_prev) dec = decay_f32(lambda, Tb - desc[(int64_t)(kp & bmask)].t_last);
-            p.s_dec[j] = dec;
+            wrec_store(p.rec, (size_t)j, partner, wgt, ref | fl, g, dec, (int32_t)node, (uint32_t)b);   // the whole record, once
 
             if (chain_head) {
                 // the chain ends where the node or the window does: first key >= (node, first batch of the next window)
@@ -1301,7 +1299,7 @@ __device__ __forceinline__ void finish_w(uint32_t bx, uint32_t nbx, WPlan p, con
                 ch.target = (int32_t)node;
                 if (same_node_prev) {
                     ch.prev_ref = (uint32_t)(j - 1);
-                    ch.g_first = 1.0f;                       // (a log row's decay comes with the run: s_dec)
+                    ch.g_first = 1.0f;                       // (a log row's decay comes with the run: WRec::dec)
                 } else {
                     const NodeMeta m = meta[node];
                     const uint32_t c = m.ver & 1u;

@@ -307,15 +307,31 @@ struct Chain {            // all contributions of ONE node inside ONE window: so
 };
 static_assert(sizeof(Chain) == 32, "Chain must be 32 bytes");
 
+// Everything the pipeline reads of ONE sorted contribution, 32 bytes, 32-byte aligned.  A planner that places contributions
+// node-major from a batch-major order (dense, hashed) scatters them: neighbours in the sorted order come from different batches,
+// so every store of a field array of its own was a partial-line write of its own -- seven per contribution.  One record is one.
+// First half: what every contribution's walk needs (one 16-byte load); second half: what run heads / tails and the write-back need.
+// Written and read through wrec_store / wrec_load_walk / wrec_load (wplan_common.hpp) only.
+struct WRec {
+    int32_t partner;      // partner node of the contribution
+    float coef;           // time weight w_e = exp(-lambda (t_last - t_e))  (models/TPNet.py:78)
+    uint32_t ref;         // WREF_* flags | log slot of the partner's version (or WREF_TABLE | copy)
+    float g;              // decay of the partner's version to the run's clock: exp(-lambda (T_b - T_version))
+    float dec;            // at run heads: decay of the node's own previous run (in the chunk) to this run's clock
+    int32_t target;       // the node
+    uint32_t bc;          // batch (in the chunk) of the contribution
+    uint32_t spare;       // always written as 0
+};
+static_assert(sizeof(WRec) == 32, "WRec must be 32 bytes");
+
 struct WPlan {
-    Plan base;            // desc, sorted keys / payload, s_partner, s_coef, sort temp; light / heavy hold the Chain lists
-    uint32_t* s_ref;      // [2*Ec] per sorted contribution: flags | log slot of the partner's version
-    float* s_g;           // [2*Ec] decay of the partner's (log) version to the run's clock: exp(-lambda (T_b - T_version))
-    float* s_dec;         // [2*Ec] at run heads: decay of the node's own previous run (in the chunk) to this run's clock
-    uint16_t* s_bc;       // [2*Ec] batch (in the chunk) of the contribution
+    Plan base;            // desc, sorted keys / payload, sort temp; light / heavy hold the Chain lists (s_partner, s_coef, s_target: the
+                          // per-batch schedule's, not used here)
+    WRec* rec;            // [2*Ec] per sorted contribution (32-byte aligned; lives in base.heavy: wplan_carve)
+    uint32_t* wscr;       // [3][2*Ec] scratch of the planners that sort every batch (wplan_common.hpp: wtmp_of)
     WinDesc* wdesc;       // [nw]
     Chain* chains;        // [<= 2*Ec] every window's chains, window by window, longest first
-    Chain* chains_sparse; // [2*Ec] plan scratch: the chain record at its head's sorted position
+    Chain* chains_sparse; // [2*Ec] scratch of the sorted planner: the chain record at its head's sorted position (lives in wtab)
     uint32_t* lk_in;      // [2*Ec] x 4: keys / payload of the plan's second sort (chain heads by (window, length))
     uint32_t* lk_out;
     uint32_t* lv_in;

@@ -272,10 +272,6 @@ __device__ __forceinline__ void side_store(const WPlan& p, const WTmp& q, int64_
                                            const NodeMeta* __restrict__ meta, const uint32_t* cabs, int want_edges,
                                            const OwnSide me, const OwnSide other) {
     const uint32_t f = me.base + me.sb + me.ri;
-    p.base.s_partner[f] = me.partner;
-    p.base.s_coef[f] = me.coef;
-    p.base.s_target[f] = (int32_t)me.node;
-    p.s_bc[f] = (uint16_t)b;
     // the partner is the edge's other endpoint, a target in this batch too: the row it reads is that one's version
     VRef pr = other.ver;
     if ((uint32_t)me.partner != other.node)                   // (a bad edge: weight 0 whatever the row)
@@ -286,7 +282,7 @@ __device__ __forceinline__ void side_store(const WPlan& p, const WTmp& q, int64_
         if (me.fl & WT_CHAIN_HEAD) {
             float g_first = 1.0f;
             if (me.ver.ref & WREF_TABLE) g_first = decay3_f32(lambda, Tb - me.ver.t_src);
-            else dec = decay3_f32(lambda, Tb - me.ver.t_src);        // (a log row's decay comes with the run: s_dec)
+            else dec = decay3_f32(lambda, Tb - me.ver.t_src);        // (a log row's decay comes with the run: WRec::dec)
             // its place in the window's list of its length class: (class start) + (earlier workgroups) + (rank in its own)
             const int c = wchain_class(me.cnt, p.heavy_thr);
             const int64_t blk = b * q.bpb + (me.x - 2 * e0b) / 256;
@@ -298,9 +294,7 @@ __device__ __forceinline__ void side_store(const WPlan& p, const WTmp& q, int64_
         }
     }
     if ((me.fl & WT_WIN_LAST) && (w >= 63 || (me.wm >> (unsigned)(w + 1)) == 0ull)) out |= WREF_LAST_RUN;
-    p.s_ref[f] = out;
-    p.s_g[f] = decay3_f32(lambda, Tb - pr.t_src);
-    p.s_dec[f] = dec;
+    wrec_store(p.rec, f, me.partner, me.coef, out, decay3_f32(lambda, Tb - pr.t_src), dec, (int32_t)me.node, (uint32_t)b);   // the whole record, once
     if (want_edges) {
         p.e_ref[(int64_t)sd * Ec + e] = me.ver.ref;
         p.e_g[(int64_t)sd * Ec + e] = decay3_f32(lambda, Tnow - me.ver.t_src);

@@ -9,6 +9,35 @@
 
 namespace tpnet {
 
+// ---- WPlan::rec (tpnet_common.h: WRec): THE writer and THE reader of a contribution's record ----------------------------------
+// A planner forms the whole record in registers and stores it once at its sorted position: two 16-byte stores to the same 32
+// aligned bytes (every byte written, the spare word as 0; nothing is read back or patched afterwards).
+__device__ __forceinline__ void wrec_store(WRec* __restrict__ rec, size_t f, int32_t partner, float coef, uint32_t ref, float g,
+                                           float dec, int32_t target, uint32_t bc) {
+    uint4* r = reinterpret_cast<uint4*>(rec + f);
+    r[0] = make_uint4((uint32_t)partner, __float_as_uint(coef), ref, __float_as_uint(g));
+    r[1] = make_uint4(__float_as_uint(dec), (uint32_t)target, bc, 0u);
+}
+struct WRecWalk {         // first half: {partner, coef, ref, g}
+    int32_t partner;
+    float coef;
+    uint32_t ref;
+    float g;
+};
+struct WRecEnds {         // second half: {dec, target, bc}
+    float dec;
+    int32_t target;
+    uint32_t bc;
+};
+__device__ __forceinline__ WRecWalk wrec_load_walk(const WRec* __restrict__ rec, size_t f) {
+    const uint4 v = reinterpret_cast<const uint4*>(rec + f)[0];
+    return {(int32_t)v.x, __uint_as_float(v.y), v.z, __uint_as_float(v.w)};
+}
+__device__ __forceinline__ WRecEnds wrec_load_ends(const WRec* __restrict__ rec, size_t f) {
+    const uint4 v = reinterpret_cast<const uint4*>(rec + f)[1];
+    return {__uint_as_float(v.x), (int32_t)v.y, v.z};
+}
+
 static constexpr uint32_t WT_CHAIN_HEAD = 1u;       // bflags: first contribution of its node in the window
 static constexpr uint32_t WT_WIN_LAST = 2u;         // bflags: tail of its node's last run in the window
 static constexpr uint32_t WT_STRUCT_MASK = WREF_RUN_HEAD | WREF_RUN_TAIL | WREF_BLK_HEAD | WREF_BLK_TAIL;
@@ -84,16 +113,16 @@ static WTmp wtmp_of(const WPlan& p, size_t nc) {
     q.dbg = p.base.dbg;
     uint32_t* ki = reinterpret_cast<uint32_t*>(p.base.keys_in);     // 8 nc bytes
     uint32_t* ko = reinterpret_cast<uint32_t*>(p.base.keys_out);    // 8 nc bytes
-    uint32_t* hv = reinterpret_cast<uint32_t*>(p.base.heavy);       // 32 nc bytes (the chunk planner's chains_sparse)
     q.bkey = ki;
     q.bpart = reinterpret_cast<int32_t*>(ki + nc);
     q.bcoef = reinterpret_cast<float*>(ko);
     q.bval = p.base.vals_out;
     q.binv = p.inv;
-    q.bsb = hv;
-    q.bri = hv + nc;
-    q.rprevb = hv + 2 * nc;
-    q.bflags = hv + 3 * nc;
+    // (base.heavy holds the contributions' records, WPlan::rec; vals_in is the sorted planner's)
+    q.bsb = p.wscr;
+    q.bri = p.wscr + nc;
+    q.rprevb = p.wscr + 2 * nc;
+    q.bflags = p.base.vals_in;
     const uint32_t cap = wplan3_table_entries(nc);
     q.h2 = reinterpret_cast<CEnt*>(p.wtab);                          // (first: the fill of a plan ends behind what H2 uses)
     q.h1 = reinterpret_cast<HEnt*>(reinterpret_cast<char*>(p.wtab) + (wplan3_h2_bytes((int64_t)(nc / 2)) + 255) / 256 * 256);

@@ -85,10 +85,6 @@ __device__ __forceinline__ void dense_place(const WPlan& p, const WTmp& q, const
     const DVRef own = dense_version(desc, tl, mo, bo, o0, o1);
     const DVRef pr = dense_version(desc, tl, mp, bp, p0, p1);
     const uint32_t f = bo + mo.x + ri;
-    p.base.s_partner[f] = partner;
-    p.base.s_coef[f] = coef;
-    p.base.s_target[f] = (int32_t)node;
-    p.s_bc[f] = (uint16_t)b;
     uint32_t out = fl | pr.ref;
     float dec = 1.0f;
     if (fl & WREF_RUN_HEAD) {
@@ -98,7 +94,7 @@ __device__ __forceinline__ void dense_place(const WPlan& p, const WTmp& q, const
         if (chain_head) {
             float g_first = 1.0f;
             if (own.ref & WREF_TABLE) g_first = decay3_f32(a.lambda, Tb - own.t_src);
-            else dec = decay3_f32(a.lambda, Tb - own.t_src);    // (a log row's decay comes with the run: s_dec)
+            else dec = decay3_f32(a.lambda, Tb - own.t_src);    // (a log row's decay comes with the run: WRec::dec)
             const uint32_t cnt = wsl_own.x;                      // the node's contributions in the window (k_dense_win)
             const int c = wchain_class(cnt, p.heavy_thr);
             const uint32_t pair = (uint32_t)w * 8u + (uint32_t)c;
@@ -112,9 +108,8 @@ __device__ __forceinline__ void dense_place(const WPlan& p, const WTmp& q, const
         }
     }
     if ((fl & WREF_RUN_TAIL) && D.lastb[node] == (uint32_t)b) out |= WREF_LAST_RUN;
-    p.s_ref[f] = out;
-    p.s_g[f] = decay3_f32(a.lambda, Tb - pr.t_src);
-    p.s_dec[f] = dec;
+    // the whole record, once: f's neighbours in the node-major order come from other batches, written by other workgroups at other times
+    wrec_store(p.rec, f, partner, coef, out, decay3_f32(a.lambda, Tb - pr.t_src), dec, (int32_t)node, (uint32_t)b);
     if (a.nwhich >= 2) {
         const bool side = val >= (uint32_t)neb;
         const int64_t e = e0b + (side ? (int64_t)val - neb : (int64_t)val);

@@ -16,6 +16,7 @@
 // the stream is cut into windows:   new = old * g_u^i + S,   S = ((b_0 + b_1) + b_2) + ...,   b_k = the sum, in index order
 // (src side, then dst side), of the k-th block of WIN_BLOCK contributions c_j = (P[i-1][partner_j] * g_j^(i-1)) * w_j.
 #include "readout.hpp"
+#include "wplan_common.hpp"
 
 namespace tpnet {
 
@@ -56,7 +57,7 @@ __device__ __forceinline__ const float* partner_row(const tpnet_state& S, const 
 }
 
 // the row a chain starts from (layer `layer` of its node before the window) and, for a table row, its decay^layer to the
-// first run's clock (a log row's decay comes with the run: WPlan::s_dec)
+// first run's clock (a log row's decay comes with the run: WRec::dec)
 __device__ __forceinline__ const float* chain_start(const tpnet_state& S, const WPlan& P, const Chain& c, int layer,
                                                     float& g0) {
     const int d = S.d, L = S.L;
@@ -81,8 +82,7 @@ __device__ __forceinline__ void chain_light(const tpnet_state& S, const WPlan& P
     float g0;
     const float* qold = chain_start(S, P, c, layer, g0);
     const bool from_table = (c.prev_ref & WREF_TABLE) != 0;
-    const int32_t* __restrict__ s_partner = P.base.s_partner;
-    const float* __restrict__ s_coef = P.base.s_coef;
+    const WRec* __restrict__ rec = P.rec;
 
     for (int c0 = 0; c0 < (FULL ? 1 : nvec); c0 += LPP * VPL) {
         float acc[F], sblk[F], srun[F];
@@ -95,7 +95,7 @@ __device__ __forceinline__ void chain_light(const tpnet_state& S, const WPlan& P
         for (int x = 0; x < F; ++x) { sblk[x] = 0.0f; srun[x] = 0.0f; }
         bool firstblk = false;
         float cur_dec = 1.0f;
-        // a lane's contribution of a round of LPP: partner, weight, reference, decays -- the NEXT round's five loads are issued
+        // a lane's contribution of a round of LPP: partner, weight, reference, decays -- the NEXT round's record is requested
         // before this round's rows are walked (one more dependent round trip per 32 contributions otherwise)
         int32_t nx_pv = 0;
         float nx_w = 0.0f, nx_glog = 1.0f, nx_decr = 1.0f;
@@ -103,11 +103,13 @@ __device__ __forceinline__ void chain_light(const tpnet_state& S, const WPlan& P
         auto fetch_meta = [&](uint32_t r0) {
             const uint32_t jm = c.j0 + r0 + (uint32_t)gl;
             const bool mine = r0 + (uint32_t)gl < c.cnt;
-            nx_pv = mine ? s_partner[jm] : 0;
-            nx_w = mine ? s_coef[jm] : 0.0f;
-            nx_ref = mine ? P.s_ref[jm] : 0u;
-            nx_glog = mine ? P.s_g[jm] : 1.0f;
-            nx_decr = mine ? P.s_dec[jm] : 1.0f;
+            const WRecWalk rw = wrec_load_walk(rec, mine ? jm : c.j0);      // (position j0 of a valid chain, 0 otherwise: always a record)
+            const WRecEnds re = wrec_load_ends(rec, mine ? jm : c.j0);
+            nx_pv = mine ? rw.partner : 0;
+            nx_w = mine ? rw.coef : 0.0f;
+            nx_ref = mine ? rw.ref : 0u;
+            nx_glog = mine ? rw.g : 1.0f;
+            nx_decr = mine ? re.dec : 1.0f;
         };
         fetch_meta(0u);
         for (uint32_t r0 = 0; __any(r0 < c.cnt); r0 += LPP) {
@@ -283,9 +285,11 @@ __device__ __forceinline__ void chain_heavy(const tpnet_state& S, const WPlan& P
         for (int q = 0; q < 8; ++q) {
             const uint32_t p = p0 + (uint32_t)(q * WB + tid);
             const bool in = p < c.cnt;
-            ref[q] = in ? P.s_ref[c.j0 + p] : 0u;
-            dec[q] = in ? P.s_dec[c.j0 + p] : 1.0f;
-            bcq[q] = in ? (uint32_t)P.s_bc[c.j0 + p] : b0;
+            const WRecWalk rw = wrec_load_walk(P.rec, c.j0 + (in ? p : 0u));
+            const WRecEnds re = wrec_load_ends(P.rec, c.j0 + (in ? p : 0u));
+            ref[q] = in ? rw.ref : 0u;
+            dec[q] = in ? re.dec : 1.0f;
+            bcq[q] = in ? re.bc : b0;
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -361,10 +365,11 @@ __device__ __forceinline__ void chain_heavy(const tpnet_state& S, const WPlan& P
                 const bool ok = ti < Tend - T0 && k < t_n[ti < Tend - T0 ? ti : 0];
                 in[q] = ok;
                 const uint32_t jm = c.j0 + (ok ? t_pos[ti] + k : 0u);
-                pv[q] = ok ? P.base.s_partner[jm] : 0;
-                w[q] = ok ? P.base.s_coef[jm] : 0.0f;
-                ref[q] = ok ? P.s_ref[jm] : 0u;
-                glog[q] = ok ? P.s_g[jm] : 1.0f;
+                const WRecWalk rw = wrec_load_walk(P.rec, jm);
+                pv[q] = ok ? rw.partner : 0;
+                w[q] = ok ? rw.coef : 0.0f;
+                ref[q] = ok ? rw.ref : 0u;
+                glog[q] = ok ? rw.g : 1.0f;
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -581,11 +586,13 @@ __device__ __forceinline__ void chain_medium(const tpnet_state& S, const WPlan& 
         const uint32_t pos = s0 + (uint32_t)tid;
         const bool in = tid < SEGP && pos < c.cnt;
         const uint32_t jm = c.j0 + (in ? pos : 0u);
-        const int32_t pv = in ? P.base.s_partner[jm] : 0;
-        const float wgt = in ? P.base.s_coef[jm] : 0.0f;
-        const uint32_t ref = in ? P.s_ref[jm] : 0u;
-        const float glog = in ? P.s_g[jm] : 1.0f;
-        const float decr = in ? P.s_dec[jm] : 1.0f;
+        const WRecWalk rw = wrec_load_walk(P.rec, jm);
+        const WRecEnds re = wrec_load_ends(P.rec, jm);
+        const int32_t pv = in ? rw.partner : 0;
+        const float wgt = in ? rw.coef : 0.0f;
+        const uint32_t ref = in ? rw.ref : 0u;
+        const float glog = in ? rw.g : 1.0f;
+        const float decr = in ? re.dec : 1.0f;
         if (tid <= GPB) own[tid] = SEGP;
         // blocks are numbered in position order: heads counted by ballot over the segment's waves
         const bool head = in && (ref & WREF_BLK_HEAD) != 0;
@@ -941,8 +948,8 @@ __global__ __launch_bounds__(WB) void k_wwriteback(tpnet_state S, WPlan P, int64
         if (threadIdx.x == 0) n_list = 0;
         __syncthreads();
         const int64_t j = j0 + threadIdx.x;
-        if (threadIdx.x < WBS && j < nc && (P.s_ref[j] & WREF_LAST_RUN)) {
-            const int32_t u = P.base.s_target[j];
+        if (threadIdx.x < WBS && j < nc && (wrec_load_walk(P.rec, (size_t)j).ref & WREF_LAST_RUN)) {
+            const int32_t u = wrec_load_ends(P.rec, (size_t)j).target;
             const int c = (int)(meta[u].ver & 1u);
             const uint32_t k = atomicAdd(&n_list, 1u);
             l_pos[k] = (uint32_t)j;
@@ -976,7 +983,7 @@ __global__ __launch_bounds__(WB) void k_wwriteback(tpnet_state S, WPlan P, int64
         }
         if (threadIdx.x < n) {
             const uint32_t k = threadIdx.x;
-            publish_meta(meta + l_node[k], l_copy[k] ^ 1, P.base.desc[P.s_bc[l_pos[k]]].t_last, bid);
+            publish_meta(meta + l_node[k], l_copy[k] ^ 1, P.base.desc[wrec_load_ends(P.rec, l_pos[k]).bc].t_last, bid);
         }
     }
 }
