@@ -626,6 +626,28 @@ int tpnet_encoder_input(const float* node_raw, int64_t n_node_rows, const float*
                         int64_t n_nodes, int32_t K, const int32_t* dims, const void* img, float* out, uint32_t* err, void* stream);
 int tpnet_encoder_input_check(uint32_t* err, void* stream);
 
+/* ---- one MLP-Mixer layer in two launches, forward only (additive to ABI 7; csrc/mixer.hip) ------------------
+ * MLPMixer.forward (models/TPNet.py:371-416) with dropout as identity, x [n_nodes][K][C] f32:
+ *   tpnet_mixer_token:    out[node][:, c] = x[node][:, c] + W2 . gelu(W1 . LN_K(x[node][:, c]) + b1) + b2   for every channel c;
+ *                         gamma, beta [K], w1 [Kh][K], b1 [Kh], w2 [K][Kh], b2 [K].  Plain fp32 on the vector ALU.
+ *   tpnet_mixer_channel:  out[row] = x[row] + W2 . gelu(W1 . LN_C(x[row]) + b1) + b2   on n_rows = n_nodes * K rows of C floats;
+ *                         gamma, beta [C]; W1 [Ch][C], b1 [Ch], W2 [C][Ch], b2 [C] come as the image tpnet_mixer_channel_prepare wrote
+ *                         (ONE launch; again whenever one of the four changed).  fp32 class on the matrix cores (two bf16 pieces per
+ *                         operand, three products per term, fp32 accumulators); the normalised rows are never written.
+ * gelu is the exact one (erf); both LayerNorms use the biased variance and the call's eps.  Every launch goes to `stream`, nothing
+ * synchronises.  Served (tpnet_mixer_supported = 1, host arithmetic): 2 <= K <= 32, 1 <= Kh <= 32, C % 4 == 0, 4 <= C <= 256,
+ * 1 <= Ch <= 1024.  tpnet_mixer_channel_image_bytes: size of the image (a multiple of 16; 0 for unserved C, Ch).  x, out, the image and
+ * the channel call's gamma / beta 16-byte aligned; out must not be x.  Null pointers, misaligned arrays, out == x and unserved
+ * sizes: TPNET_ERR_BAD_ARG, nothing launched.  n_nodes / n_rows = 0: TPNET_OK, nothing launched. */
+int tpnet_mixer_supported(int32_t K, int32_t Kh, int32_t C, int32_t Ch);
+size_t tpnet_mixer_channel_image_bytes(int32_t C, int32_t Ch);
+int tpnet_mixer_channel_prepare(const float* w1, const float* b1, const float* w2, const float* b2, int32_t C, int32_t Ch, void* img,
+                                void* stream);
+int tpnet_mixer_token(const float* x, int64_t n_nodes, int32_t K, int32_t C, const float* gamma, const float* beta, float eps,
+                      const float* w1, const float* b1, int32_t Kh, const float* w2, const float* b2, float* out, void* stream);
+int tpnet_mixer_channel(const float* x, int64_t n_rows, int32_t C, int32_t Ch, const float* gamma, const float* beta, float eps,
+                        const void* img, float* out, void* stream);
+
 /* Copies st->err to the host (synchronises the stream): returns TPNET_ERR_INDEX if any bad id was seen since
  * the last call (and clears the words), TPNET_OK otherwise. */
 int tpnet_check_errors(const tpnet_state* st, void* stream);

@@ -1,7 +1,8 @@
-"""What the four fused_* modules share: the structural test of a Linear -> ReLU -> Linear block, the current stream as the C calls
-take it, the fp32 torch expressions of the two layers' gradients, the launch of the matrix-core weight-gradient kernels, and the
+"""What the fused_* modules share: the structural tests of a Linear -> ReLU -> Linear block and of an MLP-Mixer layer, the current
+stream as the C calls take it, the fp32 torch expressions of the two layers' gradients, the launch of the matrix-core weight-gradient kernels, and the
 cache of derived weight buffers."""
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -17,6 +18,44 @@ def linear_relu_linear(m):
     if l1.bias is None or l2.bias is None or l2.in_features != l1.out_features:
         return None
     return l1, l2
+
+
+class MixerLayers(NamedTuple):
+    token_norm: torch.nn.LayerNorm
+    token: tuple            # (first, second) Linear of token_feedforward.ffn
+    channel_norm: torch.nn.LayerNorm
+    channel: tuple          # ... of channel_feedforward.ffn
+    dropout: float          # the largest p of the four Dropouts
+
+
+def _gelu_ffn(ff):
+    """(first Linear, second Linear, largest dropout p) of `ff.ffn` if it is Sequential(Linear, GELU(approximate='none'), Dropout,
+    Linear, Dropout) with both biases, mapping n -> hidden -> n, else None."""
+    m = getattr(ff, "ffn", None)
+    nn = torch.nn
+    if not (isinstance(m, nn.Sequential) and len(m) == 5 and isinstance(m[0], nn.Linear) and isinstance(m[1], nn.GELU)
+            and getattr(m[1], "approximate", "none") == "none" and isinstance(m[2], nn.Dropout) and isinstance(m[3], nn.Linear)
+            and isinstance(m[4], nn.Dropout)):
+        return None
+    l1, l2 = m[0], m[3]
+    if l1.bias is None or l2.bias is None or l2.in_features != l1.out_features or l2.out_features != l1.in_features:
+        return None
+    return l1, l2, max(float(m[2].p), float(m[4].p))
+
+
+def mixer_layers(m):
+    """MixerLayers of `m` if it has the structure of the reference's MLPMixer (models/TPNet.py:371-416; by attributes, not by class:
+    the reference's own module passes): token_norm / channel_norm LayerNorms over one axis with affine parameters, token_feedforward /
+    channel_feedforward what _gelu_ffn accepts, the norms' widths the FFNs'.  Else None."""
+    tn, cn = getattr(m, "token_norm", None), getattr(m, "channel_norm", None)
+    for ln in (tn, cn):
+        if not (isinstance(ln, torch.nn.LayerNorm) and ln.elementwise_affine and ln.weight is not None and ln.bias is not None
+                and len(ln.normalized_shape) == 1):
+            return None
+    tf, cf = _gelu_ffn(getattr(m, "token_feedforward", None)), _gelu_ffn(getattr(m, "channel_feedforward", None))
+    if tf is None or cf is None or tn.normalized_shape[0] != tf[0].in_features or cn.normalized_shape[0] != cf[0].in_features:
+        return None
+    return MixerLayers(tn, tf[:2], cn, cf[:2], max(tf[2], cf[2]))
 
 
 def stream_ptr(device):

@@ -131,6 +131,11 @@ SIGNATURES = {
     "tpnet_encoder_input": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32,
                                       C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "tpnet_encoder_input_check": (C.c_int, [_P, _P]),
+    "tpnet_mixer_supported": (C.c_int, [C.c_int32] * 4),
+    "tpnet_mixer_channel_image_bytes": (C.c_size_t, [C.c_int32] * 2),
+    "tpnet_mixer_channel_prepare": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "tpnet_mixer_token": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "tpnet_mixer_channel": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P, _P]),
     "tpnet_stage_create": (C.c_int, [C.c_int32, C.c_size_t, C.POINTER(_P)]),
     "tpnet_stage_create_ex": (C.c_int, [C.c_int32, C.c_size_t, C.c_int32, C.POINTER(_P)]),
     "tpnet_stage_in_device_memory": (C.c_int, [_P]),

@@ -1,6 +1,6 @@
 // The fp32-class arithmetic of the matrix-core kernels, once (mlp.hip, mlp_x3.hip, mlp_bwd.hip, decoder.hip, feature_mfma.hip,
-// encoder_mfma.hip, encoder_input.hip).  Only the arithmetic atoms live here: every kernel keeps its own mapping, staging,
-// pipelining and scheduling barriers.
+// encoder_mfma.hip, and through dense2.hpp encoder_input.hip and mixer.hip).  Only the arithmetic atoms live here: every kernel
+// keeps its own mapping, staging, pipelining and scheduling barriers.
 //
 // SPLIT OPERANDS.  Every f32 operand is a sum of bf16 pieces, leading piece first: x = p[0] + p[1] (+ p[2]), p[0] = bf16(x),
 // p[1] = bf16(x - p[0]), p[2] = bf16(x - p[0] - p[1]).  Two pieces carry 16 bits of significand, three carry 24.
@@ -144,6 +144,19 @@ __device__ __forceinline__ void relu_split16(const f32x16& a, const float (&bias
         for (int j = 0; j < 8; ++j) {
             x[j] = a[8 * s2 + j] + bias[8 * s2 + j];
             x[j] = x[j] > 0.0f ? x[j] : 0.0f;
+        }
+        split8(x, bh[s2], bl[s2]);
+    }
+}
+// ... with the exact GELU x Phi(x) = 0.5 x (1 + erf(x / sqrt 2)) in place of the ReLU (torch.nn.GELU(approximate='none'))
+__device__ __forceinline__ void gelu_split16(const f32x16& a, const float (&bias)[16], bf16x8 (&bh)[2], bf16x8 (&bl)[2]) {
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            x[j] = a[8 * s2 + j] + bias[8 * s2 + j];
+            x[j] = 0.5f * x[j] * (1.0f + erff(x[j] * 0.70710678118654752440f));
         }
         split8(x, bh[s2], bl[s2]);
     }

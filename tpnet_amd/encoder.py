@@ -12,13 +12,18 @@ What differs is where the work runs:
   `torch.no_grad()` / inference mode, with the module on the GPU, `fused_input` set and a served shape, ONE launch on the matrix
   cores (tpnet_amd/fused_input.py, csrc/encoder_input.hip) that never writes the [2B, K, Din] concat.  When gradients are recorded
   the torch layers serve, and autograd reaches `projection_layer`, the time encoder and `rp.mlp` as in the reference.
-* the MLP-Mixer layers and the mean over the K tokens are stock torch.
+* the MLP-Mixer layers are stock torch unless `TPNetEmbedding.fused_mixer` is set (it defaults to False): then, under
+  `torch.no_grad()` / inference mode, on contiguous float32 embeddings on the GPU, with no dropout active (eval mode, or dropout 0)
+  and a served shape, every layer is TWO launches (tpnet_amd/fused_mixer.py, csrc/mixer.hip): token mixing in exact fp32, channel
+  mixing on the matrix cores in the project's fp32 class.  Any other call runs `mlp_mixer(embeddings)` as before.
+* the mean over the K tokens is stock torch.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import fused_input as _fi
+from . import fused_mixer as _fm
 
 
 class TimeEncoder(nn.Module):
@@ -93,6 +98,9 @@ class TPNetEmbedding(nn.Module):
     # the one-launch input stage when no gradient is recorded: measured against the stock-torch expression at B = 1000, K = 20
     # (profiles/encoder_input.md)
     fused_input = True
+    # the two-launch MLP-Mixer layers when no gradient is recorded and no dropout is active: opt-in (profiles/mixer.md; the
+    # channel FFN is the fp32 class, and the bound of the end-to-end fixture test with it on is a measurement of its own)
+    fused_mixer = False
 
     def __init__(self, node_raw_features: torch.Tensor, edge_raw_features: torch.Tensor, neighbor_sampler, time_encoder: nn.Module,
                  node_feat_dim: int, edge_feat_dim: int, time_feat_dim: int, num_layers: int, num_neighbors: int, dropout: float,
@@ -159,6 +167,18 @@ class TPNetEmbedding(nn.Module):
             return None
         return _fi.prepared(self.projection_layer, self.node_feat_dim, self.time_feat_dim, self.edge_feat_dim, self.random_feature_dim // 2)
 
+    def _fused_mixer_prep(self, mixer, x):
+        """The prepared channel image if the two-launch layer serves `mixer` on `x`, else None: `fused_mixer` set, no gradient
+        recorded, x contiguous float32 on the GPU, no dropout active (eval mode, or every dropout of the mixer 0 -- a no_grad call in
+        train mode keeps torch's dropout) and a shape tpnet_mixer_supported accepts."""
+        if not self.fused_mixer or torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+            return None
+        if self.training:
+            ls = _fm.layers_of(mixer)
+            if ls is None or ls.dropout != 0:
+                return None
+        return _fm.prepared(mixer)
+
     def embed_from_features(self, neighbor_node_ids, neighbor_edge_ids, neighbor_times, node_interact_times, pair_features):
         """The tail behind the readout (TPNet.py:297-338).  neighbor_node_ids / neighbor_edge_ids int64 [n, K], neighbor_times
         float64 [n, K], node_interact_times float64 [n] (host arrays or tensors), pair_features [2 n K, F] in the reference's row
@@ -185,7 +205,8 @@ class TPNetEmbedding(nn.Module):
             embeddings = self.projection_layer(torch.cat(parts, dim=2))
         # (TPNet.py:332 calls masked_fill out of place and drops the result: pad neighbours are NOT masked)
         for mlp_mixer in self.mlp_mixers:
-            embeddings = mlp_mixer(embeddings)
+            prep = self._fused_mixer_prep(mlp_mixer, embeddings)
+            embeddings = mlp_mixer(embeddings) if prep is None else _fm.mixer_forward(prep, mlp_mixer, embeddings)
         return torch.mean(embeddings, dim=1)
 
     def check_device_errors(self):
