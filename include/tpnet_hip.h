@@ -518,11 +518,23 @@ int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, in
  * tpnet_pair_gram_anchored's output [2][n_rows*K][64] (kept: what a backward pass needs), out = mlp(gram) in the fp32 class
  * (tpnet_mlp64_f32's kernel), both on `stream`: the encoder's call as ONE crossing.  Where tpnet_encoder_fused_supported
  * returns 1 (rows of 36..160 floats with d % 4 == 0, K >= 4, mlp->wimg given) readout and dense layers are ONE launch on the matrix cores
- * (csrc/encoder_mfma.hip) and gram may be NULL: the pre-mlp features are then never written. */
+ * (csrc/encoder_mfma.hip) and gram may be NULL: the pre-mlp features are then never written.  It also returns 1 for rows of
+ * 164..512 floats whose geometry class (32 lanes x 2 vectors up to d = 256, 64 x 2 from d = 260) is routed to the one-launch kernel
+ * of csrc/anchored_feature.hip -- a class is routed only where that kernel was measured faster than the two launches
+ * (profiles/encoder_wide.md: at present neither); TPNET_FLAG_NO_MFMA_READOUT selects the two launches at every width. */
 int tpnet_encoder_fused_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp);
 int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                             int32_t K, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram,
                             float* out, void* stream);
+/* The same call on rows of 164..512 floats (d % 4 == 0, L = 3, K >= 4, mlp->w1 / w2f given: tpnet_encoder_wide_supported returns
+ * 1) ALWAYS as one launch: the vector-ALU anchored walk with self.mlp on the matrix cores inside the kernel
+ * (csrc/anchored_feature.hip).  Pre-mlp features with the bits of tpnet_pair_gram_anchored(..., TPNET_FLAG_NO_MFMA_READOUT),
+ * outputs in the fp32 class; gram may be NULL.  TPNET_ERR_BAD_ARG on any other shape.  tpnet_anchored_features takes this kernel
+ * on its own only for the classes it is routed for; this entry reaches it whatever the route is (tests, rate tools). */
+int tpnet_encoder_wide_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp);
+int tpnet_anchored_features_wide(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
+                                 int32_t K, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram,
+                                 float* out, void* stream);
 /* tpnet_encoder_rows + tpnet_anchored_features: the encoder's whole readout for one (src, other) batch, ids resident on the
  * device, self.mlp included, ONE call. */
 int tpnet_encoder_features(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src,

@@ -5,6 +5,8 @@ pairs per call) and C3's (B = 10 000), every route the build under `--tree` has 
   anchored   get_pair_wise_feature_anchored(neigh, a1, a2) on device ids: one launch on the matrix cores where served
   dev_uv     get_pair_wise_feature(u, v) on device id tensors: general pair kernel, then self.mlp
   host_uv    get_pair_wise_feature(u, v) on host arrays, as the reference's encoder issues it (pattern recognised where served)
+  wide       tpnet_anchored_features_wide on device ids, no feature buffer: the one-launch kernel for rows of 164..512 floats
+             (csrc/anchored_feature.hip) whatever the default route of `anchored` is
 
     tools/encoder_width_rate.py --dim 120 128 140 160 [--shapes C2 C3] [--reps 11] [--inner 10] [--tree OTHER_CHECKOUT] [--json OUT]
 
@@ -12,6 +14,7 @@ One repeat = HIP events around `inner` calls, then a synchronise; per (shape, wi
 repeats, in us per call.  `--tree` imports tpnet_amd from another (built) checkout: the same command on the parent commit gives the
 A/B.  A route the build does not have at a width is listed with its error."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -68,9 +71,19 @@ for cfg in args.shapes:
                                               device="cuda:0", use_matrix=False, beginning_time=np.float64(0.0), not_scale=False,
                                               enforce_dim=d).to(dev)
         rp.run_stream(D(src), D(dst), None, D(t), B, want_neg=False, want_pos=False)
+        def wide(rp=rp):
+            from tpnet_amd import _lib
+            prep = rp._overlapped_mlp()
+            out = torch.empty((2 * n * K, 64), dtype=torch.float32, device=dev)
+            _lib.check(_lib.load().tpnet_anchored_features_wide(
+                rp._st_ref(), neigh_d.data_ptr(), a1_d.data_ptr(), a2_d.data_ptr(), n, K, rp._now_host, float(rp.time_decay_weight),
+                rp._readout_flags(), prep.ref, None, out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                "anchored_features_wide")
+            return out
+
         routes = {"anchored": lambda rp=rp: rp.get_pair_wise_feature_anchored(neigh_d, a1_d, a2_d),
                   "dev_uv": lambda rp=rp: rp.get_pair_wise_feature(u_d, v_d),
-                  "host_uv": lambda rp=rp: rp.get_pair_wise_feature(u, v)}
+                  "host_uv": lambda rp=rp: rp.get_pair_wise_feature(u, v), "wide": wide}
         ref = None
         for name in args.routes:
             try:

@@ -106,6 +106,9 @@ SIGNATURES = {
     "tpnet_encoder_rows": (C.c_int, [_SP, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, _P, C.c_size_t, _P]),
     "tpnet_anchored_features": (C.c_int, [_SP, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, C.POINTER(Mlp),
                                           _P, _P, _P]),
+    "tpnet_encoder_wide_supported": (C.c_int, [_SP, C.c_int64, C.c_int32, C.POINTER(Mlp)]),
+    "tpnet_anchored_features_wide": (C.c_int, [_SP, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32,
+                                               C.POINTER(Mlp), _P, _P, _P]),
     "tpnet_encoder_features": (C.c_int, [_SP, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                          C.c_uint32, C.POINTER(Mlp), _P, C.c_size_t, _P, _P, _P]),
     "tpnet_mlp64_bf16": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),

@@ -3,17 +3,41 @@
 // Measured and not kept (round 3): the dense layers of a chunk of rows on a helper stream BESIDE the readout of the next chunk.
 // Side by side the two kernels slow each other more than the overlap wins -- 800 000 pairs at d=256: readout 355 us + dense
 // layers 237 us = 592 us one after the other; 608 us in 2 chunks, 707 in 4, 752 in 8, 1 194 in 16 (tools/encoder_call_rate.py) --
-// both live on the memory system (gathers there, a 410 MB tile stream here).  What would remove the dense layers' traffic is
-// their fusion INTO the anchored kernel.
+// both live on the memory system (gathers there, a 410 MB tile stream here).  What removes the dense layers' traffic is their
+// fusion INTO the anchored kernel: encoder_mfma.hip for rows of 36..160 floats, anchored_feature.hip for rows of 164..512
+// (the latter is the route of a geometry class only where it was measured faster than the two launches).
 #include "tpnet_common.h"
 
 using namespace tpnet;
+
+// rows of 164..512 floats: is k_anchored_feature the ROUTE of this shape (tpnet_anchored_features_wide reaches it regardless)?
+// Per geometry class, by measurement (profiles/encoder_wide.md): 32 lanes x 2 vectors (d <= 256), 64 lanes x 2 vectors (d >= 260).
+static constexpr bool WIDE_ROUTE_32x2 = false, WIDE_ROUTE_64x2 = false;
+static bool encoder_wide_routed(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp) {
+    static const int off = TPNET_DEV_INT(NO_ENCODER_WIDE, 0);
+    if (off || !encoder_wide_supported(st, n_rows, K, mlp)) return false;
+    return encoder_wide_class(st) == 32 ? WIDE_ROUTE_32x2 : WIDE_ROUTE_64x2;
+}
 
 extern "C" {
 
 int tpnet_encoder_fused_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp) {
     if (!st || !st->p0 || !st->q || !st->meta || st->N < 1 || st->d < 1) return 0;
-    return encoder_fused_supported(*st, n_rows, K, mlp) ? 1 : 0;
+    return (encoder_fused_supported(*st, n_rows, K, mlp) || encoder_wide_routed(*st, n_rows, K, mlp)) ? 1 : 0;
+}
+
+int tpnet_encoder_wide_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp) {
+    if (!st || !st->p0 || !st->q || !st->meta || st->N < 1 || st->d < 1) return 0;
+    return encoder_wide_supported(*st, n_rows, K, mlp) ? 1 : 0;
+}
+
+int tpnet_anchored_features_wide(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
+                                 int32_t K, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram,
+                                 float* out, void* stream) {
+    if (check_state(st) || n_rows < 0 || K < 0 || !mlp) return TPNET_ERR_BAD_ARG;
+    if (n_rows == 0 || K == 0) return TPNET_OK;
+    if (!neigh || !a1 || !a2 || !out) return TPNET_ERR_BAD_ARG;
+    return launch_anchored_feature(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, mlp, gram, out, (hipStream_t)stream);
 }
 
 int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
@@ -29,6 +53,9 @@ int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const i
     if (!(flags & TPNET_FLAG_NO_MFMA_READOUT) && encoder_fused_supported(*st, n_rows, K, mlp) &&
         launch_encoder_fused(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, mlp, gram, out, (hipStream_t)stream) == TPNET_OK)
         return TPNET_OK;
+    // wide rows: the vector-ALU walk with the dense layers inside (anchored_feature.hip), where that is the class's route
+    if (!(flags & TPNET_FLAG_NO_MFMA_READOUT) && encoder_wide_routed(*st, n_rows, K, mlp))
+        return launch_anchored_feature(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, mlp, gram, out, (hipStream_t)stream);
     if (!gram) return TPNET_ERR_NEED_GRAM;             // (the fused launch was refused after the caller had been told it may pass NULL)
     if (!pair_gram_anchored_supported(*st)) return TPNET_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;

@@ -12,13 +12,9 @@
 // and not kept; inputs tpnet_mlp::w1, w2f (f32: the split happens in registers), which makes ONE launch
 // the default get_pair_wise_feature for lists of any length.
 #include "readout.hpp"
-#include "mfma_split.hpp"
+#include "dense_tile.hpp"                 // the dense block on a 32-row LDS tile (shared with anchored_feature.hip)
 
 namespace tpnet {
-
-static constexpr int MB = 512;            // threads per workgroup: 8 waves = the 8 hidden tiles
-static constexpr int MF = 64, MH = 256;
-static constexpr int TS = 68;             // floats per LDS row of the feature / partial tiles (64 + 4: bank spread)
 
 template <int LPP, int VPL, int W, bool FULL, int MODE>
 __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const int64_t* __restrict__ u,
@@ -31,12 +27,7 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
     // workgroup's readout is one memory round-trip chain deep instead of PT of them; columns of the matrix products beyond tp
     // compute on stale LDS rows and are never stored -- a pair is one column, nothing crosses columns)
     // feat_in != NULL: the dense layers alone on features that already exist ([n][64] f32): the tile is loaded, not formed
-    // bf16: w1 = bf16 [256][64], w2p = bf16 [64][256] (hidden axis permuted per 32-tile, fused_mlp.permute_w2)
-    // split: w1 = f32 [256][64] (mlp[0].weight as is), w2f = f32 [8 waves][2 output tiles][64 lanes][16 k-positions]
-    const __bf16* __restrict__ w1 = reinterpret_cast<const __bf16*>(w1v);
-    const __bf16* __restrict__ w2p = reinterpret_cast<const __bf16*>(w2v);
-    const float* __restrict__ w1f = reinterpret_cast<const float*>(w1v);
-    const float* __restrict__ w2f = reinterpret_cast<const float*>(w2v);
+    // w1v / w2v: the layouts of dense_tile_weights (bf16, or f32 for the split operands)
     constexpr int L = 3;
     static_assert(MODE == 0 || MODE == 2, "k_pair_feature_bf16: bf16 operands or split operands");
     constexpr bool X3 = MODE == 2;
@@ -49,7 +40,6 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
     const int tid = threadIdx.x;
     const int gl = tid % LPP, g = tid / LPP;
     const int lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
     const bool do_scale = !(flags & TPNET_FLAG_NOT_SCALE);
     const int64_t ntiles = (n + tp - 1) / tp;
     // the first tile's ids BEFORE the weights: vector loads return in order, and the ids (host-mapped memory in the per-batch
@@ -60,30 +50,8 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
         if (g < tp && p < n) { uu0 = u[p]; vv0 = v[p]; }
     }
     // ---- this wave's weights: rows [32 wave, 32 wave + 32) of W1 as A operand, the matching columns of (permuted) W2
-    bf16x8 a1[4], a2[2][2];
-    bf16x8 a1l[X3 ? 4 : 1], a2l[X3 ? 2 : 1][2];          // MODE 2: the low halves of the split weights
-    if constexpr (X3) {
-        // the bf16 kernel's operand layout, taken from the f32 sources: A of layer 1 = W1[32 wave + r][16 s + 8 h + j]; A of layer 2
-        // = W2[32 t + r][32 wave + acc_row(8 s2 + j, h)] = w2f[..][8 s2 + j] (the gathered f32 layout lists them in order)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) load_split8(w1f + (wave * 32 + r) * MF + 16 * s + 8 * h, a1[s], a1l[s]);
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) load_split8(w2f + (((wave * 2 + t2) * 64 + lane) * 16) + 8 * s2, a2[s2][t2], a2l[s2][t2]);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) a1[s] = *reinterpret_cast<const bf16x8*>(w1 + (wave * 32 + r) * MF + 16 * s + 8 * h);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const int off = wave * 32 + 16 * s2 + 8 * h;          // position inside the PERMUTED hidden axis
-            a2[s2][0] = *reinterpret_cast<const bf16x8*>(w2p + r * MH + off);
-            a2[s2][1] = *reinterpret_cast<const bf16x8*>(w2p + (32 + r) * MH + off);
-        }
-    }
-    float bias1[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) bias1[q] = b1[wave * 32 + acc_row(q, h)];
+    DenseTileW<X3> wt;
+    dense_tile_weights<X3>(wt, w1v, b1, w2v, wave, lane);
 
     // features that already exist: a tile is 512 float4, one per thread; the NEXT tile's piece is fetched while this tile's
     // matrix products run (a tile is otherwise one global round trip + three barriers deep: 8.7 -> ~5 us per tile)
@@ -117,75 +85,12 @@ __global__ __launch_bounds__(MB) void k_pair_feature_bf16(tpnet_state S, const i
         if (out_gram) {                           // the pre-mlp features, for a backward pass (training)
             for (int i = tid; i < npair * MF; i += MB) out_gram[tile * tp * MF + i] = feat[(i / MF) * TS + (i % MF)];
         }
-        // ---- layer 1, hidden tile `wave`: H^T = W1 . X^T; lane (r, h) holds X[pair r][16 s + 8 h + j] as B operand
-        f32x16 acc, y[2];                         // y: the wave's share of the two output tiles
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { acc[q] = 0.0f; y[0][q] = 0.0f; y[1][q] = 0.0f; }
-        if constexpr (X3) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                bf16x8 bxh, bxl;
-                load_split8(feat + r * TS + 16 * s + 8 * h, bxh, bxl);
-                acc = mm3(a1[s], a1l[s], bxh, bxl, acc);
-            }
-            bf16x8 bhh[2], bhl[2];
-            relu_split16(acc, bias1, bhh, bhl);
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) mm3(a2[s2], a2l[s2], bhh[s2], bhl[s2], y);       // the two output tiles taking turns
-        } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc = mfma(a1[s], load_cvt8(feat + r * TS + 16 * s + 8 * h), acc);
-            // register q = hidden row 32 wave + acc_row(q, h), column = pair r  ->  bias, ReLU, B operand of layer 2
-            bf16x8 bh[2];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                float x = acc[q] + bias1[q];
-                x = x > 0.0f ? x : 0.0f;
-                bh[q >> 3][q & 7] = (__bf16)x;
-            }
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                y[0] = mfma(a2[s2][0], bh[s2], y[0]);
-                y[1] = mfma(a2[s2][1], bh[s2], y[1]);
-            }
-        }
-        // ---- the eight partial tiles, added in a fixed order: waves 0..3 park theirs, waves 4..7 add theirs on top, then
-        // every thread sums the four slabs for its outputs.  y[0][4i..4i+3] = outputs 8i + 4h + (0..3) of pair r, y[1]: + 32
-        float* sl = slab[wave & 3] + r * TS;
-        if (wave < 4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int o = 8 * i + 4 * h;
-                *reinterpret_cast<float4*>(sl + o) = make_float4(y[0][4 * i], y[0][4 * i + 1], y[0][4 * i + 2], y[0][4 * i + 3]);
-                *reinterpret_cast<float4*>(sl + 32 + o) = make_float4(y[1][4 * i], y[1][4 * i + 1], y[1][4 * i + 2], y[1][4 * i + 3]);
-            }
-        }
-        __syncthreads();
-        if (wave >= 4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int o = 8 * i + 4 * h;
-                float4 a = *reinterpret_cast<float4*>(sl + o), b = *reinterpret_cast<float4*>(sl + 32 + o);
-                a.x += y[0][4 * i]; a.y += y[0][4 * i + 1]; a.z += y[0][4 * i + 2]; a.w += y[0][4 * i + 3];
-                b.x += y[1][4 * i]; b.y += y[1][4 * i + 1]; b.z += y[1][4 * i + 2]; b.w += y[1][4 * i + 3];
-                *reinterpret_cast<float4*>(sl + o) = a;
-                *reinterpret_cast<float4*>(sl + 32 + o) = b;
-            }
-        }
-        __syncthreads();
+        // ---- both layers on the tile (dense_tile.hpp), the eight partial tiles added in a fixed order
+        dense_tile_partials<X3>(wt, feat, slab, wave, lane);
         {
             const int pair = tid >> 4, o = (tid & 15) * 4;      // 512 threads x 4 outputs = 32 pairs x 64
             if (pair < npair) {
-                const float4 s0 = *reinterpret_cast<const float4*>(slab[0] + pair * TS + o);
-                const float4 s1 = *reinterpret_cast<const float4*>(slab[1] + pair * TS + o);
-                const float4 s2 = *reinterpret_cast<const float4*>(slab[2] + pair * TS + o);
-                const float4 s3 = *reinterpret_cast<const float4*>(slab[3] + pair * TS + o);
-                const float4 bb = *reinterpret_cast<const float4*>(b2 + o);
-                float4 y;
-                y.x = ((s0.x + s1.x) + (s2.x + s3.x)) + bb.x;
-                y.y = ((s0.y + s1.y) + (s2.y + s3.y)) + bb.y;
-                y.z = ((s0.z + s1.z) + (s2.z + s3.z)) + bb.z;
-                y.w = ((s0.w + s1.w) + (s2.w + s3.w)) + bb.w;
+                const float4 y = dense_tile_out4(slab, b2, pair, o);
                 *reinterpret_cast<float4*>(out + (tile * tp + pair) * MF + o) = y;
             }
         }

@@ -117,6 +117,15 @@ bool pair_gram_anchored_supported(const tpnet_state& st) {
     return gm.w == 4 && gm.lpp >= 16 && st.d <= gm.lpp * gm.vpl * 4;
 }
 
+// neighbours per unit of the anchored walks: >= ~8192 units in the launch, at least 4 neighbours each, KC = K on long lists
+int anchored_chunk(int64_t n_rows, int K) {
+    static const int kc_env = TPNET_DEV_INT(ANCHOR_KC, 0);
+    int64_t kc = ((int64_t)K * n_rows + 8191) / 8192;
+    kc = kc < 4 ? 4 : (kc > K ? K : kc);
+    if (kc_env > 0) kc = kc_env > K ? K : kc_env;
+    return (int)kc;
+}
+
 int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
                               int64_t n_rows, int K, double now, double lambda, uint32_t flags, float* out1, float* out2,
                               hipStream_t s) {
@@ -125,14 +134,11 @@ int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const
     // (measured and not kept, round 3: the 16-lane x 2-vector geometry for rows of 128 floats -- 80 000 pairs 40.4 us against 35.3)
     TPNET_DISPATCH(({
         if constexpr (W == 4 && LPP >= 16) {
-            static const int kc_env = TPNET_DEV_INT(ANCHOR_KC, 0);
-            int64_t kc = ((int64_t)K * n_rows + 8191) / 8192;            // >= ~8192 units in the launch
-            kc = kc < 4 ? 4 : (kc > K ? K : kc);
-            if (kc_env > 0) kc = kc_env > K ? K : kc_env;
+            const int kc = anchored_chunk(n_rows, K);
             const int64_t units = n_rows * ((K + kc - 1) / kc);
             const int grid = grid_for(units, RB / LPP, 256 * 16);
             hipLaunchKernelGGL((k_pair_gram_anchored<LPP, VPL, W, L, FULL>), dim3(grid), dim3(RB), 0, s, st, neigh, a1, a2,
-                               n_rows, K, (int)kc, now, lambda, flags, out1, out2);
+                               n_rows, K, kc, now, lambda, flags, out1, out2);
         } else {
             return TPNET_ERR_BAD_ARG;
         }

@@ -793,4 +793,202 @@ __device__ __forceinline__ void gram_anchored(const tpnet_state& S, const int64_
 }
 
 
+// gram_anchored's walk in pieces, for a kernel that steps all the lane groups of a workgroup through their units TOGETHER
+// (k_anchored_feature, anchored_feature.hip): begin() = the anchors of a unit (rows with their decay applied, their own blocks, the
+// per-lane output plan), fetch() + issue(0) = ids and meta records of up to LPP neighbours and the first one's rows, step(j) =
+// neighbour j's 42 inner products, reduced and finished (clamp, log).  The same operations in the same order as gram_anchored: the
+// features of the two are the same bits (tests/test_encoder_wide.py compares them with torch.equal).  gram_anchored keeps its own
+// text: written through these pieces its kernels compile to other register counts (k_pair_gram_anchored at 16 lanes x 1 vector,
+// L = 3: 166 -> 171 VGPRs, three waves per SIMD -> two), and that kernel is not to move.
+template <int LPP, int VPL, int W, int L, bool FULL>
+struct AnchorWalk {
+    using C = GramCfg<LPP, L>;
+    using AC = AnchorCfg<LPP, L>;
+    static constexpr int NR = C::NR, NN = C::NN, F = VPL * W, PER = C::PER;
+    float fa[2][NR][F];                      // the anchors' rows, decay applied
+    int o_s1[PER], o_s2[PER];                // per-lane output plan (invariant over the unit): the slot of each output element ...
+    bool o_aa[PER], o_in[PER];               // ... or the anchors' own block, finished once per unit
+    float o_y1[PER], o_y2[PER];
+    bool aok;
+    int64_t my_w;                            // lane gl: neighbour kc + gl of the current fetch
+    bool my_ok;
+    MetaView my_m;
+    float fn[NR][F];                         // rows of the NEXT neighbour (raw)
+
+    // one chunk per row (d <= LPP * VPL * W); !FULL: lanes whose vector lies past the row's end hold zeros
+    __device__ __forceinline__ void begin(const tpnet_state& S, int64_t a1, int64_t a2, bool valid, double now, double lambda,
+                                          bool do_scale, int gl) {
+        const int d = S.d;
+        const int nvec = d / W;
+        const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
+        aok = valid && (uint64_t)a1 < (uint64_t)S.N && (uint64_t)a2 < (uint64_t)S.N;
+        if (valid && !aok && gl == 0) atomicAdd(S.err, 1u);
+        if (!aok) { a1 = 0; a2 = 0; }
+        // ---- the anchors: rows (decay applied) and their own blocks, once per row
+        {
+            const int64_t ids[2] = {a1, a2};
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const MetaView m = read_meta(meta, ids[s], READER_BID, now, lambda);
+                const float* qb = S.q + ((int64_t)m.copy * S.N + ids[s]) * ((int64_t)L * d);
+#pragma unroll
+                for (int j = 0; j < VPL; ++j)
+                    ldv_maybe<W, FULL>(S.p0 + ids[s] * (int64_t)d, j * LPP + gl, j * LPP + gl < nvec,
+                                       &fa[s][0][j * W]);
+                float g = 1.0f;
+#pragma unroll
+                for (int i = 1; i <= L; ++i) {
+                    g *= m.g;
+#pragma unroll
+                    for (int j = 0; j < VPL; ++j)
+                        ldv_maybe<W, FULL>(qb + (int64_t)(i - 1) * d, j * LPP + gl, j * LPP + gl < nvec,
+                                           &fa[s][i][j * W]);
+#pragma unroll
+                    for (int k = 0; k < F; ++k) fa[s][i][k] *= g;
+                }
+            }
+        }
+        float aa[2][AC::TRI];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int a = 0; a < NR; ++a) {
+#pragma unroll
+                for (int b = a; b < NR; ++b) aa[s][AC::tri(a, b)] = group_allreduce<LPP>(dot_chunk<F, false>(fa[s][a], fa[s][b]));
+            }
+        }
+        // per-lane output plan (loop-invariant): where each of this lane's PER output elements comes from; the anchors' own
+        // block is finished (clamp, log) once per row
+#pragma unroll
+        for (int kk = 0; kk < PER; ++kk) {
+            int idx = gl * PER + kk;
+            o_in[kk] = idx < C::NG;
+            idx = o_in[kk] ? idx : 0;
+            const int a = idx / NN, b = idx - a * NN;
+            o_aa[kk] = false;
+            o_y1[kk] = 0.0f;
+            o_y2[kk] = 0.0f;
+            if (a < NR && b < NR) {
+                const int i = a < b ? a : b, j = a < b ? b : a;
+                o_s1[kk] = o_s2[kk] = AC::O_WW + AC::tri(i, j);
+            } else if (a < NR) {                       // (w row a, anchor row b-NR)
+                o_s1[kk] = AC::O_WA1 + a * NR + (b - NR);
+                o_s2[kk] = AC::O_WA2 + a * NR + (b - NR);
+            } else if (b < NR) {                       // mirrored
+                o_s1[kk] = AC::O_WA1 + b * NR + (a - NR);
+                o_s2[kk] = AC::O_WA2 + b * NR + (a - NR);
+            } else {
+                const int x = a - NR, y = b - NR;
+                const int ta = AC::tri(x < y ? x : y, x < y ? y : x);
+                o_aa[kk] = true;
+                o_s1[kk] = o_s2[kk] = 0;
+                float y1 = 0.0f, y2 = 0.0f;
+#pragma unroll
+                for (int q = 0; q < AC::TRI; ++q) {     // (register arrays: a select chain, no dynamic indexing)
+                    y1 = (ta == q) ? aa[0][q] : y1;
+                    y2 = (ta == q) ? aa[1][q] : y2;
+                }
+                if (do_scale) {
+                    y1 = (y1 < 0.0f) ? 0.0f : y1;
+                    y2 = (y2 < 0.0f) ? 0.0f : y2;
+                    y1 = logf(y1 + 1.0f);
+                    y2 = logf(y2 + 1.0f);
+                }
+                o_y1[kk] = y1;
+                o_y2[kk] = y2;
+            }
+        }
+    }
+
+    // ids and meta records of the neighbours w[0 .. nk) (nk <= LPP), fetched lane-parallel: two round trips for all of them
+    __device__ __forceinline__ void fetch(const tpnet_state& S, const int64_t* __restrict__ w, int nk, bool valid, double now,
+                                          double lambda, int gl) {
+        const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
+        my_w = (valid && gl < nk) ? w[gl] : 0;
+        my_ok = aok && (uint64_t)my_w < (uint64_t)S.N;
+        if (valid && aok && gl < nk && !my_ok) atomicAdd(S.err, 1u);
+        if (!my_ok) my_w = 0;
+        my_m = read_meta(meta, my_w, READER_BID, now, lambda);
+    }
+
+    // the rows of neighbour j of the fetch -> fn (in flight while the neighbour before it is worked on)
+    __device__ __forceinline__ void issue(const tpnet_state& S, int j, int gl) {
+        const int d = S.d;
+        const int nvec = d / W;
+        const int64_t w = __shfl(my_w, j, LPP);
+        const int cp = __shfl(my_m.copy, j, LPP);
+        const float* qb = S.q + ((int64_t)cp * S.N + w) * ((int64_t)L * d);
+#pragma unroll
+        for (int jj = 0; jj < VPL; ++jj)
+            ldv_maybe<W, FULL>(S.p0 + w * (int64_t)d, jj * LPP + gl, jj * LPP + gl < nvec,
+                               &fn[0][jj * W]);
+#pragma unroll
+        for (int i = 1; i <= L; ++i) {
+#pragma unroll
+            for (int jj = 0; jj < VPL; ++jj)
+                ldv_maybe<W, FULL>(qb + (int64_t)(i - 1) * d, jj * LPP + gl, jj * LPP + gl < nvec,
+                                   &fn[i][jj * W]);
+        }
+    }
+
+    // neighbour j of the fetch (its rows in fn; `more`: issue neighbour j + 1 behind it): emit(idx, x1, x2) for each of this lane's
+    // elements idx = gl * PER + kk (< NG) of the two finished feature rows G(w, a1), G(w, a2)
+    template <class Emit>
+    __device__ __forceinline__ void step(const tpnet_state& S, int j, bool more, bool do_scale, int gl, Emit&& emit) {
+        const bool wok = __shfl((int)my_ok, j, LPP) != 0;
+        const float mg = __shfl(my_m.g, j, LPP);
+        float fw[NR][F];
+#pragma unroll
+        for (int x = 0; x < F; ++x) fw[0][x] = fn[0][x];
+        {
+            float g = 1.0f;
+#pragma unroll
+            for (int i = 1; i <= L; ++i) {
+                g *= mg;
+#pragma unroll
+                for (int x = 0; x < F; ++x) fw[i][x] = fn[i][x] * g;
+            }
+        }
+        if (more) issue(S, j + 1, gl);
+        float acc[AC::MPS];
+#pragma unroll
+        for (int i = 0; i < AC::MPS; ++i) acc[i] = 0.0f;
+#pragma unroll
+        for (int a = 0; a < NR; ++a) {
+#pragma unroll
+            for (int b = a; b < NR; ++b) acc[AC::O_WW + AC::tri(a, b)] = dot_chunk<F, false>(fw[a], fw[b]);
+#pragma unroll
+            for (int b = 0; b < NR; ++b) {
+                acc[AC::O_WA1 + a * NR + b] = dot_chunk<F, false>(fw[a], fa[0][b]);
+                acc[AC::O_WA2 + a * NR + b] = dot_chunk<F, false>(fw[a], fa[1][b]);
+            }
+        }
+        Halve<AC::MPS, LPP / 2>::run(acc, gl);        // lane gl now holds the complete sums of slots [gl*PERS, ...)
+        // output elements of the two Gram matrices [w rows | anchor rows]^2 from their slots (or the anchors' block)
+#pragma unroll
+        for (int kk = 0; kk < PER; ++kk) {
+            const int idx = o_in[kk] ? gl * PER + kk : 0;
+            const bool in = o_in[kk];
+            float x1 = 0.0f, x2 = 0.0f;
+#pragma unroll
+            for (int j2 = 0; j2 < AC::PERS; ++j2) {
+                const float t1 = __shfl(acc[j2], o_s1[kk] / AC::PERS, LPP);
+                const float t2 = __shfl(acc[j2], o_s2[kk] / AC::PERS, LPP);
+                x1 = (o_s1[kk] % AC::PERS == j2) ? t1 : x1;
+                x2 = (o_s2[kk] % AC::PERS == j2) ? t2 : x2;
+            }
+            if (do_scale) {
+                x1 = (x1 < 0.0f) ? 0.0f : x1;          // NaN < 0 is false: NaN passes through (:127)
+                x2 = (x2 < 0.0f) ? 0.0f : x2;
+                x1 = logf(x1 + 1.0f);                  // log(x + 1), not log1p (:128)
+                x2 = logf(x2 + 1.0f);
+            }
+            if (o_aa[kk]) { x1 = o_y1[kk]; x2 = o_y2[kk]; }
+            if (!wok) { x1 = __builtin_nanf(""); x2 = x1; }
+            if (in) emit(idx, x1, x2);
+        }
+    }
+};
+
+
 }  // namespace tpnet

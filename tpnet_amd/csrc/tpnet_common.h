@@ -170,6 +170,14 @@ int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const 
 bool encoder_fused_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp);
 int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows, int K,
                          double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram, float* out, hipStream_t s);
+// anchored_feature.hip: the vector-ALU anchored walk + self.mlp in ONE launch for rows of 164..512 floats (d % 4 == 0), L = 3,
+// K >= 4, units cut by anchored_chunk (readout.hip) as the walk's own kernel cuts them; encoder_wide_class: 32 / 64 = the lanes
+// per unit of the geometry that serves st.d, 0 = not a wide row
+int anchored_chunk(int64_t n_rows, int K);
+bool encoder_wide_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp);
+int encoder_wide_class(const tpnet_state& st);
+int launch_anchored_feature(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows, int K,
+                            double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram, float* out, hipStream_t s);
 // One launch: readout of batch b (if out_pos/out_neg) on the pre-batch state + update of batch b.
 int launch_step(const tpnet_state& st, const StreamArgs& a, const Plan& p, int64_t b, int64_t batch, int32_t ne,
                 double lambda, uint32_t launch_id, uint32_t flags, hipStream_t s);

@@ -6,7 +6,9 @@ each), so `TPNet(...)` at train_link_prediction.py:166 can be this class.
 What differs is where the work runs:
 * sampler -> readout: with a `GpuRecentNeighborSampler` the neighbour ids, edge ids and times never leave the device
   (`sample_device` -> `RandomProjectionModule.get_pair_wise_feature_anchored`); a host sampler's three [2B, K] arrays are
-  copied to the device once.  Row widths the anchored readout does not serve (d < 36, d > 512, d % 4 != 0) take the general pair
+  copied to the device once.  The call is one launch on rows of 36..160 floats, and on rows of 164..512 floats where
+  `tpnet_encoder_fused_supported` says so (csrc/anchored_feature.hip; else the anchored walk and `rp.mlp`'s dense layers as two
+  launches).  Row widths the anchored readout does not serve (d < 36, d > 512, d % 4 != 0) take the general pair
   readout and `rp.mlp` as the stock torch layers.
 * the input stage behind the readout (gathers, time encoding, concat, `projection_layer`; TPNet.py:297-330): under
   `torch.no_grad()` / inference mode, with the module on the GPU, `fused_input` set and a served shape, ONE launch on the matrix

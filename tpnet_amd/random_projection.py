@@ -776,7 +776,7 @@ class RandomProjectionModule(nn.Module):
             # 5. the encoder's call as the reference issues it (models/TPNet.py:311-316: src = tile(neigh, 2), dst = concat(repeat(a1,
             #    K), repeat(a2, K)) on the host): recognised in one pass over the two arrays in C; n / 2 neighbour ids + 2 n / (2 K)
             #    anchors go up instead of 2 n ids, the anchored readout and the dense layers run as one call (dim % 4 == 0,
-            #    36 <= dim <= 512; one launch on the matrix cores up to dim = 160)
+            #    36 <= dim <= 512; one launch on the matrix cores up to dim = 160, and beyond where tpnet_encoder_fused_supported)
             feats = self._encoder_pattern_features(src, dst_node_ids, n)
             if feats is not None:
                 return feats
@@ -812,8 +812,8 @@ class RandomProjectionModule(nn.Module):
         """A readout + self.mlp call, `launch(gram)` -> the [n, (2L+2)^2] features, `gram` = where the kernel leaves the pre-mlp
         features (None: nowhere).  With gradients recorded, the autograd node allocates that buffer and keeps it for the backward
         pass.  Without: no buffer -- for the encoder's calls (`rows_k` = their (rows, K)) only where readout and dense layers are
-        ONE launch (tpnet_encoder_fused_supported: rows of 36..160 floats, dim % 4 == 0, K >= 4), else a scratch tensor between
-        the two launches; and if the runtime refuses the one launch after all (TPNET_ERR_NEED_GRAM), once more with a scratch."""
+        ONE launch (tpnet_encoder_fused_supported: rows of 36..160 floats, dim % 4 == 0, K >= 4; rows of 164..512 floats where
+        their geometry class is routed to csrc/anchored_feature.hip), else a scratch tensor between the two launches; and if the runtime refuses the one launch after all (TPNET_ERR_NEED_GRAM), once more with a scratch."""
         NG = self.pair_wise_feature_dim
         if _ff.needs_grad(prep.params):
             return _ff.apply_with_grad(self.mlp, launch, n, NG)
@@ -939,7 +939,10 @@ class RandomProjectionModule(nn.Module):
 
     def get_pair_wise_feature_anchored(self, neighbor_ids, first_anchor_ids, second_anchor_ids):
         """Extension: the encoder's call (models/TPNet.py:313-316) from its natural arguments; [2*n*K, (2L+2)^2] in the
-        reference's row order, self.mlp applied.  Needs what pair_gram_anchored needs (dim % 4 == 0, 36 <= dim <= 512)."""
+        reference's row order, self.mlp applied.  Needs what pair_gram_anchored needs (dim % 4 == 0, 36 <= dim <= 512).  Device
+        ids, L = 3, K >= 4: one launch on rows of 36..160 floats (csrc/encoder_mfma.hip); on rows of 164..512 floats one launch
+        (csrc/anchored_feature.hip) where that kernel is the route of the width's geometry class, else the anchored walk and the
+        dense layers as two launches (tpnet_encoder_fused_supported tells which)."""
         prep = self._overlapped_mlp() if self._plist()[0].device.type == "cuda" else None
         if prep is not None and isinstance(neighbor_ids, torch.Tensor) and neighbor_ids.is_cuda:
             self._ensure_engine()
