@@ -976,11 +976,15 @@ def test_version_protocol_under_multi_pass_grids(d, B, N):
 @pytest.mark.parametrize("d,L,N,B,nb", [(128, 3, 400, 64, 50), (64, 2, 3000, 200, 90), (128, 3, 9000, 1000, 20),
                                         (256, 3, 500, 500, 13), (16, 4, 300, 100, 70), (512, 1, 200, 2048, 5),
                                         (120, 3, 260, 40, 200), (128, 3, 50, 1000, 12),
-                                        (16, 3, 60000, 100, 40)])      # (many nodes, few edges: the chain table is hashed)
+                                        (16, 3, 60000, 100, 40),       # (many nodes, few edges: the chain table is hashed)
+                                        # N > 12 288 and 12 N <= 4 B L d: the dense planner's SORTING phase A on every tile but
+                                        # the largest (k_dense_sort<256,2>, <512,2>, <1024,2>; B = 2048 above is <1024,4>)
+                                        (128, 3, 13000, 250, 8), (128, 3, 13000, 500, 6), (128, 3, 13000, 1000, 4)])
 def test_three_launch_planner_equals_chunk_planner(d, L, N, B, nb):
     """All three planners of the windowed schedule (the one-launch dense planner where the table is small against the stream --
-    every case but the last --, the hashed planner, the sorted chunk planner) describe the same runs (blocks of 8 contributions
-    in index order, the same versions read): features and state are equal bit for bit, whatever the window length each picks."""
+    every case but the one with 60 000 nodes --, the hashed planner, the sorted chunk planner) describe the same runs (blocks of 8
+    contributions in index order, the same versions read): features and state are equal bit for bit, whatever the window length
+    each picks."""
     _need_gpu()
     rng = np.random.RandomState(d + B + nb)
     E = nb * B - B // 3

@@ -140,6 +140,37 @@ __device__ __forceinline__ MetaView read_meta(const NodeMeta* __restrict__ meta,
     return meta_view(p[0], p[1], bid, now, lambda);
 }
 
+// inclusive scan of one value per lane over the wavefront (shuffles only)
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+    const int lane = threadIdx.x & 63;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    return inc;
+}
+// exclusive scan of one value per thread over the workgroup (wave shuffles + one LDS word per wave); total = the sum.
+// FENCE_WSUM = false where nothing can still be reading wsum from an earlier scan: one barrier instead of two.
+template <int BS, bool FENCE_WSUM = true>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum /* [BS / 64] */, uint32_t& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t inc = wave_incl_scan(v);
+    if constexpr (FENCE_WSUM) __syncthreads();
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < BS / 64; ++i) {
+        const uint32_t s = wsum[i];
+        if (i < wave) base += s;
+        tot += s;
+    }
+    total = tot;
+    return base + inc - v;
+}
+
 // Recursive halving: MP partial sums per lane over a group of 2*M lanes -> lane gl ends with the MP/(2M) complete sums
 // of indices [gl*MP/(2M), ...).  63 exchanges for 64 values over 64 lanes instead of 6*64 for a butterfly all-reduce.
 // Exchanges never touch LDS: v_permlane32_swap / v_permlane16_swap (gfx950) trade the two halves in one instruction

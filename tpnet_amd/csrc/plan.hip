@@ -340,14 +340,10 @@ __global__ __launch_bounds__(BS) void k_plan_one(Plan p, const int64_t* __restri
                                                  const double* __restrict__ t_c, int64_t Ec, int32_t Bfull, int64_t N,
                                                  int node_bits, double now_time, const double* __restrict__ t_prev,
                                                  double lambda, int L, uint32_t heavy_threshold, uint32_t* err, int eager) {
-    // workgroup b plans batch b of the chunk: edges [b * Bfull, ...), sorted positions [2 * b * Bfull, ...) (as plan_build lays
-    // a chunk out); a single-batch call is the chunk of one batch
     const int64_t bb = blockIdx.x;
-    const int64_t e0 = bb * Bfull;
-    const int32_t B = (int32_t)((Ec - e0 < Bfull) ? (Ec - e0) : Bfull);
-    const int64_t* __restrict__ src = src_c + e0;
-    const int64_t* __restrict__ dst = dst_c + e0;
-    const double* __restrict__ t = t_c + e0;
+    const BatchSpan sp = batch_span(bb, src_c, dst_c, t_c, Ec, Bfull);
+    const int64_t e0 = sp.e0;
+    const int32_t B = sp.B;
     p.s_partner += 2 * e0;
     p.s_coef += 2 * e0;
     p.s_target += 2 * e0;
@@ -359,7 +355,7 @@ __global__ __launch_bounds__(BS) void k_plan_one(Plan p, const int64_t* __restri
         typename Sort::storage_type sort;
         struct { uint32_t key[NC]; uint32_t val[NC]; } s;
     } u;
-    __shared__ uint32_t e_src[NC / 2], e_dst[NC / 2];   // endpoint (0 if out of range) | bit 31: the EDGE has a bad endpoint
+    __shared__ uint32_t e_src[NC / 2], e_dst[NC / 2];   // (batch_wg.hpp: edges_stage)
     __shared__ float e_w[NC / 2];
     __shared__ uint32_t n_light, n_heavy;
     static_assert(sizeof(U) + 3 * (NC / 2) * 4 + 8 <= 64 * 1024, "k_plan_one: LDS budget");
@@ -368,50 +364,13 @@ __global__ __launch_bounds__(BS) void k_plan_one(Plan p, const int64_t* __restri
     [[maybe_unused]] unsigned long long* dbg = p.dbg;     // (phase stamps of diagnostic builds)
     PSTAMP(0);
     if (tid == 0) { n_light = 0; n_heavy = 0; }
-    // every thread's edges in ONE burst of independent loads (src / dst / t may sit in host memory: a load is microseconds)
-    constexpr int EPT = IPT / 2;
-    int64_t rs[EPT], rd[EPT];
-    double rt[EPT];
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) {
-        const int e = q * BS + tid;
-        const int ec = e < B ? e : B - 1;
-        rs[q] = src[ec];
-        rd[q] = dst[ec];
-        rt[q] = t[ec];
-    }
-    const double t_last = t[B - 1];                      // next_time = node_interact_times[-1]   (TPNet.py:76)
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) {
-        const int e = q * BS + tid;
-        if (e < B) {
-            const int64_t s = rs[q], dd = rd[q];
-            const bool oks = (uint64_t)s < (uint64_t)N, okd = (uint64_t)dd < (uint64_t)N;
-            const uint32_t bad = (oks && okd) ? 0u : 0x80000000u;
-            if (bad) atomicAdd(err, 1u);                 // once per bad edge
-            e_src[e] = (oks ? (uint32_t)s : 0u) | bad;
-            e_dst[e] = (okd ? (uint32_t)dd : 0u) | bad;
-            // time weight with the reference's casts (models/TPNet.py:77-78), as contribution()
-            const float x = (float)t_last - (float)rt[q];
-            e_w[e] = bad ? 0.0f : expf((float)(-lambda) * x);
-        }
-    }
+    const auto burst = edges_load<BS, IPT / 2>(sp);
+    const double t_last = burst.t_last;
+    edges_stage<BS>(burst, B, N, lambda, err, e_src, e_dst, e_w);
     __syncthreads();
     PSTAMP(1);
     uint32_t keys[IPT], vals[IPT];
-    const uint32_t pad_key = 1u << node_bits;            // above every node id: padding sorts last
-#pragma unroll
-    for (int q = 0; q < IPT; ++q) {
-        const int j = tid * IPT + q;
-        vals[q] = (uint32_t)j;
-        if (j < nc) {
-            const bool side = j >= B;                    // first the src-side scatter-adds, then the dst-side ones (TPNet.py:93-96)
-            const int e = side ? j - B : j;
-            keys[q] = (side ? e_dst[e] : e_src[e]) & 0x7FFFFFFFu;
-        } else {
-            keys[q] = pad_key;
-        }
-    }
+    sort_keys(keys, vals, nc, B, node_bits, e_src, e_dst);
     Sort().sort(keys, vals, u.sort, 0u, (unsigned)(node_bits + 1));
     __syncthreads();
     PSTAMP(2);
@@ -422,15 +381,6 @@ __global__ __launch_bounds__(BS) void k_plan_one(Plan p, const int64_t* __restri
     }
     __syncthreads();
     PSTAMP(3);
-    auto contrib = [&](uint32_t val, int32_t& partner, float& w) {
-        const bool side = val >= (uint32_t)B;
-        const int e = side ? (int)val - B : (int)val;
-        const uint32_t es = e_src[e], ed = e_dst[e];
-        const bool ok = !(es & 0x80000000u);
-        partner = ok ? (int32_t)((side ? es : ed) & 0x7FFFFFFFu) : 0;
-        w = ok ? e_w[e] : 0.0f;
-    };
-    const int lane = tid & 63;
     for (int jb = 0; jb < nc; jb += BS) {                // (uniform trip count: the list appends below are wave-wide)
         const int j = jb + tid;
         Item it;
@@ -439,7 +389,7 @@ __global__ __launch_bounds__(BS) void k_plan_one(Plan p, const int64_t* __restri
             const uint32_t key = u.s.key[j];
             int32_t partner;
             float w;
-            contrib(u.s.val[j], partner, w);
+            contrib_partner_weight((int)u.s.val[j], B, e_src, e_dst, e_w, partner, w);
             p.s_partner[j] = partner;
             p.s_coef[j] = w;
             p.s_target[j] = (int32_t)key;
@@ -466,46 +416,16 @@ __global__ __launch_bounds__(BS) void k_plan_one(Plan p, const int64_t* __restri
                 it.p1 = 0;
                 it.w1 = 0.0f;
                 it.pad = 0;
-                if (it.cnt >= 2) contrib(u.s.val[j + 1], it.p1, it.w1);
+                if (it.cnt >= 2) contrib_partner_weight((int)u.s.val[j + 1], B, e_src, e_dst, e_w, it.p1, it.w1);
             }
         }
-        // list appends, one LDS atomic per wave and list (a typical batch has ~1500 leaders: as many same-address atomics)
-        const bool hv = lead && it.cnt > heavy_threshold, lt = lead && !hv;
-        const unsigned long long ml = __ballot(lt), mh = __ballot(hv);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (ml) {
-            const int first = __ffsll((long long)ml) - 1;
-            uint32_t base = 0;
-            if (lane == first) base = atomicAdd(&n_light, (uint32_t)__popcll(ml));
-            base = __shfl(base, first);
-            if (lt) p.light[base + (uint32_t)__popcll(ml & below)] = it;
-        }
-        if (mh) {
-            const int first = __ffsll((long long)mh) - 1;
-            uint32_t base = 0;
-            if (lane == first) base = atomicAdd(&n_heavy, (uint32_t)__popcll(mh));
-            base = __shfl(base, first);
-            if (hv) p.heavy[base + (uint32_t)__popcll(mh & below)] = it;
-        }
+        const bool hv = lead && it.cnt > heavy_threshold;
+        append_items(lead && !hv, hv, it, &n_light, &n_heavy, p.light, p.heavy);
     }
     __syncthreads();
     PSTAMP(4);
-    if (tid == 0) {
-        BatchDesc D;
-        D.e0 = e0;
-        D.ne = B;
-        D.pad = 0;
-        D.t_last = t_last;
-        D.now = (bb == 0) ? (t_prev ? *t_prev : now_time) : t_c[e0 - 1];   // clock left by the previous batch (TPNet.py:99)
-        D.n_light = n_light;
-        D.n_heavy = n_heavy;
-        // the dense decay's factors only where a dense decay will read them (k_decay_desc, eager mode): exp + pow in f64 are
-        // ~2 us of this one thread's time behind the kernel's last barrier
-        const double g = eager ? exp(-lambda * (t_last - D.now)) : 1.0;
-        for (int i = 0; i < TPNET_MAX_LAYERS; ++i)
-            D.decay[i] = (eager && i < L) ? (float)pow(g, (double)(i + 1)) : 1.0f;
-        p.desc[bb] = D;
-    }
+    if (tid == 0)
+        batch_desc_store(p.desc, bb, sp, batch_clock(bb, e0, t_c, t_prev, now_time), t_last, n_light, n_heavy, eager != 0, lambda, L);
     PSTAMP(5);
 }
 
@@ -535,11 +455,9 @@ __global__ __launch_bounds__(BS) void k_plan_one_h(Plan p, const int64_t* __rest
     constexpr uint32_t SMALL = 16;                       // groups up to this size are ranked by their own members
     static_assert(NC <= 2048 && BMW <= 64, "k_plan_one_h: j fits 11 bits, a hub's bitmap one word per lane");
     const int64_t bb = blockIdx.x;
-    const int64_t e0 = bb * Bfull;
-    const int32_t B = (int32_t)((Ec - e0 < Bfull) ? (Ec - e0) : Bfull);
-    const int64_t* __restrict__ src = src_c + e0;
-    const int64_t* __restrict__ dst = dst_c + e0;
-    const double* __restrict__ t = t_c + e0;
+    const BatchSpan sp = batch_span(bb, src_c, dst_c, t_c, Ec, Bfull);
+    const int64_t e0 = sp.e0;
+    const int32_t B = sp.B;
     p.s_partner += 2 * e0;
     p.s_coef += 2 * e0;
     p.s_target += 2 * e0;
@@ -551,59 +469,25 @@ __global__ __launch_bounds__(BS) void k_plan_one_h(Plan p, const int64_t* __rest
     __shared__ uint16_t sorted[NC];                      // position -> j (bit 15: the first of its group)
     __shared__ uint16_t cnt_at[NC];                      // at a group's first position: its size
     __shared__ uint32_t bm[NW][BMW];                     // a wave's bitmap over j for the hub it ranks
-    __shared__ uint32_t e_src[NC / 2], e_dst[NC / 2];    // endpoint (0 if out of range) | bit 31: the EDGE has a bad endpoint
+    __shared__ uint32_t e_src[NC / 2], e_dst[NC / 2];    // (batch_wg.hpp: edges_stage)
     __shared__ float e_w[NC / 2];
     __shared__ uint32_t n_light, n_heavy, n_big, wsum[NW];
     __shared__ uint16_t big[NC / SMALL];                 // slots of the groups larger than SMALL
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int nc = 2 * B;
     [[maybe_unused]] unsigned long long* dbg = p.dbg;
     PSTAMP(0);
-    constexpr int EPT = IPT / 2;
-    int64_t rs[EPT], rd[EPT];
-    double rt[EPT];
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) {                      // (the loads are in flight while the table is cleared)
-        const int e = q * BS + tid;
-        const int ec = e < B ? e : B - 1;
-        rs[q] = src[ec];
-        rd[q] = dst[ec];
-        rt[q] = t[ec];
-    }
-    const double t_last = t[B - 1];                      // next_time = node_interact_times[-1]   (TPNet.py:76)
+    const auto burst = edges_load<BS, IPT / 2>(sp);      // (the loads are in flight while the table is cleared)
+    const double t_last = burst.t_last;
     if (tid == 0) { n_light = 0; n_heavy = 0; n_big = 0; }
 #pragma unroll
     for (int k = 0; k < SPT; ++k) {
         hkey[k * BS + tid] = EMPTY;
         hcb[k * BS + tid] = 0;
     }
-#pragma unroll
-    for (int q = 0; q < EPT; ++q) {
-        const int e = q * BS + tid;
-        if (e < B) {
-            const int64_t s = rs[q], dd = rd[q];
-            const bool oks = (uint64_t)s < (uint64_t)N, okd = (uint64_t)dd < (uint64_t)N;
-            const uint32_t bad = (oks && okd) ? 0u : 0x80000000u;
-            if (bad) atomicAdd(err, 1u);                 // once per bad edge
-            e_src[e] = (oks ? (uint32_t)s : 0u) | bad;
-            e_dst[e] = (okd ? (uint32_t)dd : 0u) | bad;
-            const float x = (float)t_last - (float)rt[q];   // the reference's casts (models/TPNet.py:77-78), as contribution()
-            e_w[e] = bad ? 0.0f : expf((float)(-lambda) * x);
-        }
-    }
+    edges_stage<BS>(burst, B, N, lambda, err, e_src, e_dst, e_w);
     __syncthreads();
     PSTAMP(1);
-    auto target_of = [&](int j) -> uint32_t {            // first the src-side scatter-adds, then the dst-side ones (TPNet.py:93-96)
-        return ((j >= B) ? e_dst[j - B] : e_src[j]) & 0x7FFFFFFFu;
-    };
-    auto contrib = [&](int j, int32_t& partner, float& w) {
-        const bool side = j >= B;
-        const int e = side ? j - B : j;
-        const uint32_t es = e_src[e], ed = e_dst[e];
-        const bool ok = !(es & 0x80000000u);
-        partner = ok ? (int32_t)((side ? es : ed) & 0x7FFFFFFFu) : 0;
-        w = ok ? e_w[e] : 0.0f;
-    };
     // group by target: slot and arrival number of every contribution
     uint32_t slot[IPT], arr[IPT];
 #pragma unroll
@@ -612,7 +496,7 @@ __global__ __launch_bounds__(BS) void k_plan_one_h(Plan p, const int64_t* __rest
         slot[q] = 0;
         arr[q] = 0;
         if (j < nc) {
-            const uint32_t key = target_of(j);
+            const uint32_t key = contrib_target(j, B, e_src, e_dst);
             uint32_t h = (key * 2654435761u) >> (32 - LOG_SLOTS);
             for (;;) {                                   // (the table is never more than half full: the walk ends)
                 const uint32_t prev = atomicCAS(&hkey[h], EMPTY, key);
@@ -632,18 +516,8 @@ __global__ __launch_bounds__(BS) void k_plan_one_h(Plan p, const int64_t* __rest
         c[k] = hcb[tid * SPT + k];
         tsum += c[k];
     }
-    uint32_t inc = tsum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t base = inc - tsum;
-#pragma unroll
-    for (int i = 0; i < NW; ++i)
-        if (i < wave) base += wsum[i];
+    uint32_t total;
+    uint32_t base = block_excl_scan<BS, false>(tsum, wsum, total);
 #pragma unroll
     for (int k = 0; k < SPT; ++k) {
         hcb[tid * SPT + k] = (base << 16) | c[k];
@@ -658,66 +532,11 @@ __global__ __launch_bounds__(BS) void k_plan_one_h(Plan p, const int64_t* __rest
     }
     __syncthreads();
     PSTAMP(3);
-    // ranks and the sorted arrays
-    auto emit = [&](int j, uint32_t pos, bool first, uint32_t cnt) {    // (the arrays themselves are written by position below: coalesced)
-        sorted[pos] = (uint16_t)(j | (first ? 0x8000 : 0));
-        if (first) cnt_at[pos] = (uint16_t)cnt;
-    };
-#pragma unroll
-    for (int q = 0; q < IPT; ++q) {
-        const int j = q * BS + tid;
-        if (j < nc) {
-            const uint32_t cb = hcb[slot[q]];
-            const uint32_t gb = cb >> 16, cnt = cb & 0xFFFFu;
-            if (cnt <= SMALL) {
-                uint32_t rank = 0;
-                if (cnt > 1) {
-                    for (uint32_t m = 0; m < cnt; m += 4) {          // (four independent LDS reads per round; the span of the
-#pragma unroll                                                       //  last group ends inside mem[], a read past a span is masked)
-                        for (uint32_t k = 0; k < 4; ++k) {
-                            const uint32_t mm = m + k;
-                            const uint32_t o = mem[(gb + mm) < (uint32_t)NC ? gb + mm : 0u];
-                            rank += (mm < cnt && o < (uint32_t)j) ? 1u : 0u;
-                        }
-                    }
-                }
-                emit(j, gb + rank, rank == 0, cnt);
-            }
-        }
-    }
-    const uint32_t nbig = n_big;
-    for (uint32_t k = wave; k < nbig; k += NW) {         // a hub: one wave, a bitmap over j, prefix pop-counts
-        const uint32_t cb = hcb[big[k]];
-        const uint32_t gb = cb >> 16, cnt = cb & 0xFFFFu;
-        if (lane < BMW) bm[wave][lane] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t m = lane; m < cnt; m += 64) {
-            const uint32_t j = mem[gb + m];
-            atomicOr(&bm[wave][j >> 5], 1u << (j & 31u));
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t word = lane < BMW ? bm[wave][lane] : 0u;
-        uint32_t pre = (uint32_t)__popc(word);
-        const uint32_t own = pre;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = (uint32_t)__shfl_up((int)pre, o, 64);
-            if (lane >= o) pre += v;
-        }
-        pre -= own;
-        for (uint32_t m0 = 0; m0 < cnt; m0 += 64) {      // (uniform trip count: the shuffles are wave-wide)
-            const uint32_t m = m0 + lane;
-            const bool on = m < cnt;
-            const uint32_t j = on ? mem[gb + m] : 0u;
-            const uint32_t pw = (uint32_t)__shfl((int)pre, (int)(j >> 5), 64);
-            const uint32_t ww = (uint32_t)__shfl((int)word, (int)(j >> 5), 64);
-            const uint32_t rank = pw + (uint32_t)__popc(ww & ((1u << (j & 31u)) - 1u));
-            if (on) emit((int)j, gb + rank, rank == 0, cnt);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    // ranks and the sorted arrays (the arrays themselves are written by position below: coalesced)
+    rank_groups<BS, IPT, SMALL>(hcb, slot, nc, mem, big, n_big, bm, [&](uint32_t j, uint32_t gb, uint32_t rank, uint32_t cnt) {
+        sorted[gb + rank] = (uint16_t)(j | (rank == 0 ? 0x8000u : 0u));
+        if (rank == 0) cnt_at[gb] = (uint16_t)cnt;
+    });
     __syncthreads();
     PSTAMP(4);
     // the items: one per group, at the group's first position
@@ -730,8 +549,8 @@ __global__ __launch_bounds__(BS) void k_plan_one_h(Plan p, const int64_t* __rest
             const uint32_t v = sorted[pos];
             lead = (v & 0x8000u) != 0;
             const int j = (int)(v & 0x7FFFu);
-            const int32_t tg = (int32_t)target_of(j);
-            contrib(j, it.p0, it.w0);
+            const int32_t tg = (int32_t)contrib_target(j, B, e_src, e_dst);
+            contrib_partner_weight(j, B, e_src, e_dst, e_w, it.p0, it.w0);
             p.s_partner[pos] = it.p0;
             p.s_coef[pos] = it.w0;
             p.s_target[pos] = tg;
@@ -742,43 +561,22 @@ __global__ __launch_bounds__(BS) void k_plan_one_h(Plan p, const int64_t* __rest
                 it.p1 = 0;
                 it.w1 = 0.0f;
                 it.pad = 0;
-                if (it.cnt >= 2) contrib((int)(sorted[pos + 1] & 0x7FFFu), it.p1, it.w1);
+                if (it.cnt >= 2) contrib_partner_weight((int)(sorted[pos + 1] & 0x7FFFu), B, e_src, e_dst, e_w, it.p1, it.w1);
             }
         }
-        const bool hv = lead && it.cnt > heavy_threshold, lt = lead && !hv;
-        const unsigned long long ml = __ballot(lt), mh = __ballot(hv);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (ml) {
-            const int first = __ffsll((long long)ml) - 1;
-            uint32_t lb = 0;
-            if (lane == first) lb = atomicAdd(&n_light, (uint32_t)__popcll(ml));
-            lb = __shfl(lb, first);
-            if (lt) p.light[lb + (uint32_t)__popcll(ml & below)] = it;
-        }
-        if (mh) {
-            const int first = __ffsll((long long)mh) - 1;
-            uint32_t hb = 0;
-            if (lane == first) hb = atomicAdd(&n_heavy, (uint32_t)__popcll(mh));
-            hb = __shfl(hb, first);
-            if (hv) p.heavy[hb + (uint32_t)__popcll(mh & below)] = it;
-        }
+        const bool hv = lead && it.cnt > heavy_threshold;
+        append_items(lead && !hv, hv, it, &n_light, &n_heavy, p.light, p.heavy);
     }
     __syncthreads();
     PSTAMP(5);
-    if (tid == 0) {
-        BatchDesc D;
-        D.e0 = e0;
-        D.ne = B;
-        D.pad = 0;
-        D.t_last = t_last;
-        D.now = (bb == 0) ? (t_prev ? *t_prev : now_time) : t_c[e0 - 1];   // clock left by the previous batch (TPNet.py:99)
-        D.n_light = n_light;
-        D.n_heavy = n_heavy;
-        const double g = eager ? exp(-lambda * (t_last - D.now)) : 1.0;    // (as k_plan_one)
-        for (int i = 0; i < TPNET_MAX_LAYERS; ++i)
-            D.decay[i] = (eager && i < L) ? (float)pow(g, (double)(i + 1)) : 1.0f;
-        p.desc[bb] = D;
-    }
+    if (tid == 0)
+        batch_desc_store(p.desc, bb, sp, batch_clock(bb, e0, t_c, t_prev, now_time), t_last, n_light, n_heavy, eager != 0, lambda, L);
+}
+
+// (the grouping planner holds at most 2 048 contributions: the ladder's last tile has no instantiation and is never asked for)
+template <int BS, int IPT, typename... A>
+static void launch_plan_one_h(int64_t nbl, hipStream_t s, A... a) {
+    if constexpr (BS * IPT <= 2048) hipLaunchKernelGGL((k_plan_one_h<BS, IPT>), dim3((unsigned)nbl), dim3(BS), 0, s, a...);
 }
 
 int64_t plan_one_max_batch() {
@@ -807,24 +605,21 @@ int plan_blocks(const tpnet_state& st, const Plan& p, const int64_t* src, const 
     const int64_t nc = 2 * B;
     static const int sort_env = TPNET_DEV_INT(PLAN_ONE_SORT, 0);   // developer override: the sorting planner for every size
 #define TPNET_PLAN_ONE_H(BS_, IPT_)                                                                                         \
-    hipLaunchKernelGGL((k_plan_one_h<BS_, IPT_>), dim3((unsigned)nbl), dim3(BS_), 0, s, p, src, dst, t, Ec, (int32_t)B, st.N, \
-                       now_time, t_prev_dev, lambda, (int)st.L, thr, st.err, (flags & TPNET_FLAG_EAGER_DECAY) ? 1 : 0)
+    launch_plan_one_h<BS_, IPT_>(nbl, s, p, src, dst, t, Ec, (int32_t)B, st.N, now_time, t_prev_dev, lambda, (int)st.L, thr, \
+                                 st.err, (flags & TPNET_FLAG_EAGER_DECAY) ? 1 : 0)
     if (nc <= 2048 && !sort_env) {
-        if (nc <= 512) TPNET_PLAN_ONE_H(256, 2);
-        else if (nc <= 1024) TPNET_PLAN_ONE_H(512, 2);
-        else TPNET_PLAN_ONE_H(1024, 2);
+        TPNET_FOR_BATCH_TILE(nc, TPNET_PLAN_ONE_H);
         TPNET_HIP_TRY(hipGetLastError());
         return TPNET_OK;
     }
 #undef TPNET_PLAN_ONE_H
-    if (nc <= 512) {
-        if (bs_env == 512) TPNET_PLAN_ONE(256, 2); else TPNET_PLAN_ONE(256, 2);
-    } else if (nc <= 1024) {
-        if (bs_env == 256) TPNET_PLAN_ONE(256, 4); else TPNET_PLAN_ONE(512, 2);
-    } else if (nc <= 2048) {
-        if (bs_env == 256) TPNET_PLAN_ONE(256, 8); else if (bs_env == 512) TPNET_PLAN_ONE(512, 4); else TPNET_PLAN_ONE(1024, 2);
+    // (PLAN_ONE_BS = 256 / 512: the same contributions over fewer threads, where that is another tile than the default)
+    if (bs_env == 256 && nc > 512) {
+        if (nc <= 1024) TPNET_PLAN_ONE(256, 4); else if (nc <= 2048) TPNET_PLAN_ONE(256, 8); else TPNET_PLAN_ONE(256, 16);
+    } else if (bs_env == 512 && nc > 1024) {
+        if (nc <= 2048) TPNET_PLAN_ONE(512, 4); else TPNET_PLAN_ONE(512, 8);
     } else {
-        if (bs_env == 256) TPNET_PLAN_ONE(256, 16); else if (bs_env == 512) TPNET_PLAN_ONE(512, 8); else TPNET_PLAN_ONE(1024, 4);
+        TPNET_FOR_BATCH_TILE(nc, TPNET_PLAN_ONE);
     }
 #undef TPNET_PLAN_ONE
     TPNET_HIP_TRY(hipGetLastError());

@@ -145,12 +145,7 @@ __global__ __launch_bounds__(9 * 64) void k_wscan(WPlan p, WTmp q, int64_t nb) {
     for (int64_t k0 = b0 * q.bpb; k0 < b1 * q.bpb; k0 += 64) {
         const int64_t k = k0 + lane;
         const uint32_t v = (k < b1 * q.bpb) ? cnt[k * 9 + c] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t u = (uint32_t)__shfl_up((int)inc, o, 64);
-            if (lane >= o) inc += u;
-        }
+        const uint32_t inc = wave_incl_scan(v);
         if (k < b1 * q.bpb) base[k * 9 + c] = run + inc - v;
         run += (uint32_t)__shfl((int)inc, 63, 64);
     }
@@ -329,13 +324,7 @@ __global__ __launch_bounds__(256) void k_wrefs(WPlan p, WTmp q, const int64_t* _
             t8[k] = wv < nw ? q.wtot[wv * 9 + k] : 0u;
             n += t8[k];
         }
-        uint32_t inc = n;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = (uint32_t)__shfl_up((int)inc, o, 64);
-            if (wv >= o) inc += v;
-        }
-        uint32_t at = inc - n;
+        uint32_t at = wave_incl_scan(n) - n;                 // (wave 0: wv is the lane)
         if (blockIdx.x == 0 && wv < nw) {
             WinDesc D;
             D.start = at;
@@ -472,10 +461,7 @@ int wplan3_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipS
     hipLaunchKernelGGL((k_wsort<BS_, IPT_>), dim3((unsigned)nb), dim3(BS_), 0, s, q, p.base.desc, src, dst, t, Ec,           \
                        (int32_t)batch, st.N, node_bits, now_time, t_prev_dev, lambda, (int)st.L, st.err, (int)p.K)
         const int64_t n2 = 2 * batch;
-        if (n2 <= 512) TPNET_WSORT(256, 2);
-        else if (n2 <= 1024) TPNET_WSORT(512, 2);
-        else if (n2 <= 2048) TPNET_WSORT(1024, 2);
-        else TPNET_WSORT(1024, 4);
+        TPNET_FOR_BATCH_TILE(n2, TPNET_WSORT);
 #undef TPNET_WSORT
         TPNET_HIP_TRY(hipGetLastError());
     }

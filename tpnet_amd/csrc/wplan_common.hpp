@@ -4,6 +4,7 @@
 #pragma once
 #include "tpnet_common.h"
 #include "device_common.hpp"
+#include "batch_wg.hpp"
 
 #include <rocprim/block/block_radix_sort.hpp>
 
@@ -252,11 +253,9 @@ __device__ __forceinline__ void wsort_batch(WSortShared<BS, IPT>& sh, const WTmp
                                             const double* __restrict__ t_c, int64_t Ec, int32_t Bfull, int64_t N, int node_bits,
                                             double now_time, const double* __restrict__ t_prev, double lambda, int L, uint32_t* err,
                                             int KW, int64_t bb, uint16_t* __restrict__ lenrow) {
-    const int64_t e0 = bb * Bfull;
-    const int32_t B = (int32_t)((Ec - e0 < Bfull) ? (Ec - e0) : Bfull);
-    const int64_t* __restrict__ src = src_c + e0;
-    const int64_t* __restrict__ dst = dst_c + e0;
-    const double* __restrict__ t = t_c + e0;
+    const BatchSpan sp = batch_span(bb, src_c, dst_c, t_c, Ec, Bfull);
+    const int64_t e0 = sp.e0;
+    const int32_t B = sp.B;
     const int64_t g0 = 2 * e0;
     using Sort = typename WSortShared<BS, IPT>::Sort;
     constexpr int NC = BS * IPT;
@@ -277,49 +276,13 @@ __device__ __forceinline__ void wsort_batch(WSortShared<BS, IPT>& sh, const WTmp
         // (16-bit stores, coalesced; the barriers between here and the scatter of the runs' lengths order the two)
         for (int64_t n = tid; n < N; n += BS) lenrow[n] = 0;
     }
-    constexpr int EPT = IPT / 2;
-    int64_t rs[EPT], rd[EPT];
-    double rt[EPT];
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        const int e = k * BS + tid;
-        const int ec = e < B ? e : B - 1;
-        rs[k] = src[ec];
-        rd[k] = dst[ec];
-        rt[k] = t[ec];
-    }
-    const double t_last = t[B - 1];                      // next_time = node_interact_times[-1]   (TPNet.py:76)
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        const int e = k * BS + tid;
-        if (e < B) {
-            const int64_t s = rs[k], dd = rd[k];
-            const bool oks = (uint64_t)s < (uint64_t)N, okd = (uint64_t)dd < (uint64_t)N;
-            const uint32_t bad = (oks && okd) ? 0u : 0x80000000u;
-            if (bad) atomicAdd(err, 1u);                 // once per bad edge
-            e_src[e] = (oks ? (uint32_t)s : 0u) | bad;
-            e_dst[e] = (okd ? (uint32_t)dd : 0u) | bad;
-            // time weight with the reference's casts: absolute times rounded to f32 BEFORE the subtraction (models/TPNet.py:77-78)
-            const float x = (float)t_last - (float)rt[k];
-            e_w[e] = bad ? 0.0f : expf((float)(-lambda) * x);
-        }
-    }
+    const auto burst = edges_load<BS, IPT / 2>(sp);
+    const double t_last = burst.t_last;
+    edges_stage<BS>(burst, B, N, lambda, err, e_src, e_dst, e_w);
     __syncthreads();
     WSTAMP(1);
     uint32_t keys[IPT], vals[IPT];
-    const uint32_t pad_key = 1u << node_bits;            // above every node id: padding sorts last
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        const int j = tid * IPT + k;
-        vals[k] = (uint32_t)j;
-        if (j < nc) {
-            const bool side = j >= B;                    // first the src-side scatter-adds, then the dst-side ones (TPNet.py:93-96)
-            const int e = side ? j - B : j;
-            keys[k] = (side ? e_dst[e] : e_src[e]) & 0x7FFFFFFFu;
-        } else {
-            keys[k] = pad_key;
-        }
-    }
+    sort_keys(keys, vals, nc, B, node_bits, e_src, e_dst);
     Sort().sort(keys, vals, u.sort, 0u, (unsigned)(node_bits + 1));
     __syncthreads();
     WSTAMP(2);
@@ -337,73 +300,29 @@ __device__ __forceinline__ void wsort_batch(WSortShared<BS, IPT>& sh, const WTmp
         hcount += hd[k] ? 1u : 0u;
         if (j < nc) {
             const uint32_t val = vals[k];
-            const bool side = val >= (uint32_t)B;
-            const int e = side ? (int)val - B : (int)val;
-            const uint32_t es = e_src[e], ed = e_dst[e];
-            const bool ok = !(es & 0x80000000u);
+            int32_t partner;
+            float w;
+            contrib_partner_weight((int)val, B, e_src, e_dst, e_w, partner, w);
             q.bkey[g0 + j] = keys[k];
-            q.bpart[g0 + j] = ok ? (int32_t)((side ? es : ed) & 0x7FFFFFFFu) : 0;
-            q.bcoef[g0 + j] = ok ? e_w[e] : 0.0f;
+            q.bpart[g0 + j] = partner;
+            q.bcoef[g0 + j] = w;
             q.bval[g0 + j] = val;
             q.binv[g0 + val] = (uint32_t)(g0 + j);
         }
     }
-    uint32_t inc = hcount;
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
+    uint32_t total;
+    const uint32_t rank = block_excl_scan<BS, false>(hcount, wsum, total);
     WSTAMP(3);
     if constexpr (!DENSE)
-        for (uint32_t i = tid; i < SEG / 2; i += BS) e_all[i] = 0u;  // (every thread has read its edges' entries: the barrier above)
-    uint32_t base = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < BS / 64; ++i) {
-        const uint32_t v = wsum[i];
-        if (i < wave) base += v;
-        total += v;
-    }
-    uint32_t rank = base + inc - hcount;
-    uint32_t myrun[IPT];                                 // the run every item of this thread belongs to
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        if (hd[k]) {
-            u.s.ustart[rank] = (uint32_t)(tid * IPT + k);
-            ++rank;
-        }
-        myrun[k] = rank - 1u;                            // (item 0 is a head: never underflows for j < nc)
-    }
+        for (uint32_t i = tid; i < SEG / 2; i += BS) e_all[i] = 0u;  // (every thread has read its edges' entries: the scan's barrier)
+    uint32_t myrun[IPT];
+    run_starts(hd, rank, u.s.ustart, myrun);
     __syncthreads();
     WSTAMP(4);
-    // every contribution's rank inside its run and the structure bits that follow from it (k_wchains adds the chain's bits)
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        const int j = tid * IPT + k;
-        if (j < nc) {
-            const uint32_t st = u.s.ustart[myrun[k]];
-            const uint32_t en = (myrun[k] + 1 < total) ? u.s.ustart[myrun[k] + 1] : (uint32_t)nc;
-            const uint32_t ri = (uint32_t)j - st;
-            const bool tail = (uint32_t)j + 1u == en;
-            uint32_t fl = 0;
-            if (ri == 0) fl |= WREF_RUN_HEAD;
-            if (tail) fl |= WREF_RUN_TAIL;
-            if (ri % WIN_BLOCK == 0) fl |= WREF_BLK_HEAD;
-            if (ri % WIN_BLOCK == WIN_BLOCK - 1 || tail) fl |= WREF_BLK_TAIL;
-            q.bri[g0 + j] = ri;
-            q.bflags[g0 + j] = fl;
-        }
-    }
+    run_ranks_store(myrun, u.s.ustart, total, nc, q.bri + g0, q.bflags + g0);
     if constexpr (DENSE) {
         // ---- the runs: this batch's row of the run-length matrix (zeroed by this workgroup before its first barrier)
-        for (uint32_t r = tid; r < total; r += BS) {
-            const uint32_t st = u.s.ustart[r];
-            const uint32_t en = (r + 1 < total) ? u.s.ustart[r + 1] : (uint32_t)nc;
-            lenrow[u.s.key[st]] = (uint16_t)(en - st);
-        }
+        run_lengths_store<BS>(u.s.key, u.s.ustart, total, nc, lenrow);
     } else {
     // ---- the runs: the batch's segment of H1 in LDS (slot = run + 1; the runs' nodes are distinct: a claim needs no key
     // compare), the node's entry of the chain table marked with this batch
@@ -443,20 +362,8 @@ __device__ __forceinline__ void wsort_batch(WSortShared<BS, IPT>& sh, const WTmp
     }
     }
     WSTAMP(5);
-    if (tid == 0) {
-        BatchDesc D;
-        D.e0 = e0;
-        D.ne = B;
-        D.pad = 0;
-        D.t_last = t_last;
-        D.now = (bb == 0) ? (t_prev ? *t_prev : now_time) : t_c[e0 - 1];   // clock left by the previous batch (TPNet.py:99)
-        D.n_light = 0;
-        D.n_heavy = 0;
-        // (the dense decay's factors are read by the eager mode only, which never takes the windowed schedule: no exp / pow here --
-        // ~2 us of this one thread's time at the tail of the workgroup)
-        for (int i = 0; i < TPNET_MAX_LAYERS; ++i) D.decay[i] = 1.0f;
-        desc[bb] = D;
-    }
+    // (eager = false: the dense decay's factors are read by the eager mode only, which never takes the windowed schedule)
+    if (tid == 0) batch_desc_store(desc, bb, sp, batch_clock(bb, e0, t_c, t_prev, now_time), t_last, 0u, 0u, false, lambda, L);
     WSTAMP(6);
 }
 

@@ -179,58 +179,28 @@ __global__ __launch_bounds__(BS) void k_dense_group(WPlan p, WTmp q, DView D, DA
     constexpr uint32_t SMALL = 16;
     static_assert(NC <= 2048 && BMW <= 64, "k_dense_group: j fits 11 bits, a hub's bitmap one word per lane");
     const int64_t bb = blockIdx.x;
-    const int64_t e0 = bb * a.Bfull;
-    const int32_t B = (int32_t)((a.Ec - e0 < a.Bfull) ? (a.Ec - e0) : a.Bfull);
-    const int64_t* __restrict__ src = a.src + e0;
-    const int64_t* __restrict__ dst = a.dst + e0;
-    const double* __restrict__ t = a.t + e0;
+    const BatchSpan sp = batch_span(bb, a.src, a.dst, a.t, a.Ec, a.Bfull);
+    const int64_t e0 = sp.e0;
+    const int32_t B = sp.B;
     const int64_t g0 = 2 * e0;
     uint16_t* __restrict__ lenrow = D.len + bb * D.Ns;
     __shared__ __attribute__((aligned(16))) uint32_t tab[NT];   // contributions of node n; after the scan: span base << 16 | count
     __shared__ uint16_t mem[NC];                         // members of the groups, span by span, in arrival order
     __shared__ uint32_t sorted[NC];                      // position -> j | rank << 11 | (count - 1) << 22
     __shared__ uint32_t bm[NW][BMW];                     // a wave's bitmap over j for the hub it ranks
-    __shared__ uint32_t e_src[NC / 2], e_dst[NC / 2];    // endpoint (0 if out of range) | bit 31: the EDGE has a bad endpoint
+    __shared__ uint32_t e_src[NC / 2], e_dst[NC / 2];    // (batch_wg.hpp: edges_stage)
     __shared__ float e_w[NC / 2];
     __shared__ uint32_t n_big, wsum[NW];
     __shared__ uint32_t big[NC / SMALL];                 // the nodes of the groups larger than SMALL
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int nc = 2 * B;
-    constexpr int EPT = IPT / 2;
-    int64_t rs[EPT], rd[EPT];
-    double rt[EPT];
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {                      // (the loads are in flight while the table is cleared)
-        const int e = k * BS + tid;
-        const int ec = e < B ? e : B - 1;
-        rs[k] = src[ec];
-        rd[k] = dst[ec];
-        rt[k] = t[ec];
-    }
-    const double t_last = t[B - 1];                      // next_time = node_interact_times[-1]   (TPNet.py:76)
-    // clock left by the previous batch (TPNet.py:99)
-    const double t_now = (bb == 0) ? (a.t_prev ? *a.t_prev : a.now_time) : a.t[e0 - 1];
+    const auto burst = edges_load<BS, IPT / 2>(sp);      // (the loads are in flight while the table is cleared)
+    const double t_now = batch_clock(bb, e0, a.t, a.t_prev, a.now_time);
     if (tid == 0) n_big = 0;
 #pragma unroll
     for (int k = 0; k < SPT / 4; ++k) reinterpret_cast<uint4*>(tab)[k * BS + tid] = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        const int e = k * BS + tid;
-        if (e < B) {
-            const int64_t s = rs[k], dd = rd[k];
-            const bool oks = (uint64_t)s < (uint64_t)a.N, okd = (uint64_t)dd < (uint64_t)a.N;
-            const uint32_t bad = (oks && okd) ? 0u : 0x80000000u;
-            if (bad) atomicAdd(a.err, 1u);               // once per bad edge
-            e_src[e] = (oks ? (uint32_t)s : 0u) | bad;
-            e_dst[e] = (okd ? (uint32_t)dd : 0u) | bad;
-            const float x = (float)t_last - (float)rt[k];   // the reference's casts (models/TPNet.py:77-78), as wsort_batch
-            e_w[e] = bad ? 0.0f : expf((float)(-a.lambda) * x);
-        }
-    }
+    edges_stage<BS>(burst, B, a.N, a.lambda, a.err, e_src, e_dst, e_w);
     __syncthreads();
-    auto target_of = [&](int j) -> uint32_t {            // first the src-side scatter-adds, then the dst-side ones (TPNet.py:93-96)
-        return ((j >= B) ? e_dst[j - B] : e_src[j]) & 0x7FFFFFFFu;
-    };
     uint32_t key[IPT], arr[IPT];
 #pragma unroll
     for (int k = 0; k < IPT; ++k) {
@@ -238,7 +208,7 @@ __global__ __launch_bounds__(BS) void k_dense_group(WPlan p, WTmp q, DView D, DA
         key[k] = 0;
         arr[k] = 0;
         if (j < nc) {
-            key[k] = target_of(j);
+            key[k] = contrib_target(j, B, e_src, e_dst);
             arr[k] = atomicAdd(&tab[key[k]], 1u);
         }
     }
@@ -251,23 +221,13 @@ __global__ __launch_bounds__(BS) void k_dense_group(WPlan p, WTmp q, DView D, DA
         c[4 * k] = v.x; c[4 * k + 1] = v.y; c[4 * k + 2] = v.z; c[4 * k + 3] = v.w;
         tsum += v.x + v.y + v.z + v.w;
     }
-    uint32_t inc = tsum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) wsum[wave] = inc;
 #pragma unroll
     for (int k = 0; k < SPT; ++k) {
         const int64_t n = (int64_t)tid * SPT + k;
         if (n < a.N) lenrow[n] = (uint16_t)c[k];
     }
-    __syncthreads();
-    uint32_t base = inc - tsum;
-#pragma unroll
-    for (int i = 0; i < NW; ++i)
-        if (i < wave) base += wsum[i];
+    uint32_t total;
+    uint32_t base = block_excl_scan<BS, false>(tsum, wsum, total);
     if (tsum) {
 #pragma unroll
         for (int k = 0; k < SPT; ++k) {
@@ -283,64 +243,9 @@ __global__ __launch_bounds__(BS) void k_dense_group(WPlan p, WTmp q, DView D, DA
         if (j < nc) mem[(tab[key[k]] >> 16) + arr[k]] = (uint16_t)j;
     }
     __syncthreads();
-    auto emit = [&](uint32_t j, uint32_t gb, uint32_t rank, uint32_t cnt) {
+    rank_groups<BS, IPT, SMALL>(tab, key, nc, mem, big, n_big, bm, [&](uint32_t j, uint32_t gb, uint32_t rank, uint32_t cnt) {
         sorted[gb + rank] = j | (rank << 11) | ((cnt - 1u) << 22);
-    };
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        const int j = k * BS + tid;
-        if (j < nc) {
-            const uint32_t cb = tab[key[k]];
-            const uint32_t gb = cb >> 16, cnt = cb & 0xFFFFu;
-            if (cnt <= SMALL) {
-                uint32_t rank = 0;
-                if (cnt > 1) {
-                    for (uint32_t m = 0; m < cnt; m += 4) {          // (four independent LDS reads per round; a read past the
-#pragma unroll                                                       //  span is masked)
-                        for (uint32_t i = 0; i < 4; ++i) {
-                            const uint32_t mm = m + i;
-                            const uint32_t o = mem[(gb + mm) < (uint32_t)NC ? gb + mm : 0u];
-                            rank += (mm < cnt && o < (uint32_t)j) ? 1u : 0u;
-                        }
-                    }
-                }
-                emit((uint32_t)j, gb, rank, cnt);
-            }
-        }
-    }
-    const uint32_t nbig = n_big;
-    for (uint32_t k = wave; k < nbig; k += NW) {         // a hub: one wave, a bitmap over j, prefix pop-counts
-        const uint32_t cb = tab[big[k]];
-        const uint32_t gb = cb >> 16, cnt = cb & 0xFFFFu;
-        if (lane < BMW) bm[wave][lane] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t m = lane; m < cnt; m += 64) {
-            const uint32_t j = mem[gb + m];
-            atomicOr(&bm[wave][j >> 5], 1u << (j & 31u));
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t word = lane < BMW ? bm[wave][lane] : 0u;
-        uint32_t pre = (uint32_t)__popc(word);
-        const uint32_t own = pre;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = (uint32_t)__shfl_up((int)pre, o, 64);
-            if (lane >= o) pre += v;
-        }
-        pre -= own;
-        for (uint32_t m0 = 0; m0 < cnt; m0 += 64) {      // (uniform trip count: the shuffles are wave-wide)
-            const uint32_t m = m0 + lane;
-            const bool on = m < cnt;
-            const uint32_t j = on ? mem[gb + m] : 0u;
-            const uint32_t pw = (uint32_t)__shfl((int)pre, (int)(j >> 5), 64);
-            const uint32_t ww = (uint32_t)__shfl((int)word, (int)(j >> 5), 64);
-            const uint32_t rank = pw + (uint32_t)__popc(ww & ((1u << (j & 31u)) - 1u));
-            if (on) emit(j, gb, rank, cnt);
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    });
     __syncthreads();
     // the batch's arrays, span by span (coalesced)
 #pragma unroll
@@ -349,37 +254,20 @@ __global__ __launch_bounds__(BS) void k_dense_group(WPlan p, WTmp q, DView D, DA
         if (pos < nc) {
             const uint32_t v = sorted[pos];
             const uint32_t j = v & 0x7FFu, ri = (v >> 11) & 0x7FFu, cnt = (v >> 22) + 1u;
-            const bool side = j >= (uint32_t)B;
-            const int e = side ? (int)j - B : (int)j;
-            const uint32_t es = e_src[e], ed = e_dst[e];
-            const bool ok = !(es & 0x80000000u);
-            const bool tail = ri + 1u == cnt;
-            uint32_t fl = 0;
-            if (ri == 0) fl |= WREF_RUN_HEAD;
-            if (tail) fl |= WREF_RUN_TAIL;
-            if (ri % WIN_BLOCK == 0) fl |= WREF_BLK_HEAD;
-            if (ri % WIN_BLOCK == WIN_BLOCK - 1 || tail) fl |= WREF_BLK_TAIL;
-            q.bkey[g0 + pos] = (side ? ed : es) & 0x7FFFFFFFu;
-            q.bpart[g0 + pos] = ok ? (int32_t)((side ? es : ed) & 0x7FFFFFFFu) : 0;
-            q.bcoef[g0 + pos] = ok ? e_w[e] : 0.0f;
+            int32_t partner;
+            float w;
+            contrib_partner_weight((int)j, B, e_src, e_dst, e_w, partner, w);
+            q.bkey[g0 + pos] = contrib_target((int)j, B, e_src, e_dst);
+            q.bpart[g0 + pos] = partner;
+            q.bcoef[g0 + pos] = w;
             q.bval[g0 + pos] = j;
             q.binv[g0 + j] = (uint32_t)(g0 + pos);
             q.bri[g0 + pos] = ri;
-            q.bflags[g0 + pos] = fl;
+            q.bflags[g0 + pos] = wref_run_flags(ri, ri + 1u == cnt);
         }
     }
-    if (tid == 0) {
-        BatchDesc Dn;
-        Dn.e0 = e0;
-        Dn.ne = B;
-        Dn.pad = 0;
-        Dn.t_last = t_last;
-        Dn.now = t_now;
-        Dn.n_light = 0;
-        Dn.n_heavy = 0;
-        for (int i = 0; i < TPNET_MAX_LAYERS; ++i) Dn.decay[i] = 1.0f;            // (as wsort_batch: read by the eager mode only)
-        p.base.desc[bb] = Dn;
-    }
+    // (eager = false: the decay's factors are read by the eager mode only)
+    if (tid == 0) batch_desc_store(p.base.desc, bb, sp, t_now, burst.t_last, 0u, 0u, false, a.lambda, a.L);
 }
 
 // ---- A (row shard): the batch holds the edges of ALL ranks (local ids: rows < own are this rank's, the rows behind them halo rows
@@ -407,11 +295,12 @@ __global__ __launch_bounds__(BS) void k_dense_sort_shard(WPlan p, WTmp q, DView 
     static_assert(sizeof(U) + sizeof(uint32_t) * HBITS <= 62 * 1024, "k_dense_sort_shard: LDS budget");
     const int64_t bb = blockIdx.x;
     const int tid = threadIdx.x;
-    const int64_t e0 = bb * a.Bfull;
-    const int32_t B = (int32_t)((a.Ec - e0 < a.Bfull) ? (a.Ec - e0) : a.Bfull);
-    const int64_t* __restrict__ src = a.src + e0;
-    const int64_t* __restrict__ dst = a.dst + e0;
-    const double* __restrict__ t = a.t + e0;
+    const BatchSpan sp = batch_span(bb, a.src, a.dst, a.t, a.Ec, a.Bfull);
+    const int64_t e0 = sp.e0;
+    const int32_t B = sp.B;
+    const int64_t* __restrict__ src = sp.src;
+    const int64_t* __restrict__ dst = sp.dst;
+    const double* __restrict__ t = sp.t;
     const int64_t g0 = 2 * e0;
     uint16_t* __restrict__ lenrow = D.len + bb * D.Ns;
     for (int i = tid; i < HBITS; i += BS) hbits[i] = 0u;
@@ -494,51 +383,16 @@ __global__ __launch_bounds__(BS) void k_dense_sort_shard(WPlan p, WTmp q, DView 
         }
     }
     uint32_t htotal;
-    uint32_t rank = block_excl_scan<BS>(hcount, wsum, htotal);
+    const uint32_t rank = block_excl_scan<BS>(hcount, wsum, htotal);
     uint32_t myrun[IPT];
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        if (hd[k]) {
-            u.s.ustart[rank] = (uint32_t)(tid * IPT + k);
-            ++rank;
-        }
-        myrun[k] = rank - 1u;
-    }
+    run_starts(hd, rank, u.s.ustart, myrun);
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        const int j = tid * IPT + k;
-        if (j < nc) {
-            const uint32_t st = u.s.ustart[myrun[k]];
-            const uint32_t en = (myrun[k] + 1 < htotal) ? u.s.ustart[myrun[k] + 1] : (uint32_t)nc;
-            const uint32_t ri = (uint32_t)j - st;
-            const bool tail = (uint32_t)j + 1u == en;
-            uint32_t fl = 0;
-            if (ri == 0) fl |= WREF_RUN_HEAD;
-            if (tail) fl |= WREF_RUN_TAIL;
-            if (ri % WIN_BLOCK == 0) fl |= WREF_BLK_HEAD;
-            if (ri % WIN_BLOCK == WIN_BLOCK - 1 || tail) fl |= WREF_BLK_TAIL;
-            q.bri[g0 + j] = ri;
-            q.bflags[g0 + j] = fl;
-        }
-    }
-    for (uint32_t r = tid; r < htotal; r += BS) {
-        const uint32_t st = u.s.ustart[r];
-        const uint32_t en = (r + 1 < htotal) ? u.s.ustart[r + 1] : (uint32_t)nc;
-        lenrow[u.s.key[st]] = (uint16_t)(en - st);
-    }
-    if (tid == 0) {
-        BatchDesc Dd;
-        Dd.e0 = e0;
-        Dd.ne = B;
-        Dd.pad = 0;
-        Dd.t_last = t_last;
-        Dd.now = (bb == 0) ? (a.t_prev ? *a.t_prev : a.now_time) : a.t[e0 - 1];
-        Dd.n_light = (uint32_t)nc;
-        Dd.n_heavy = 0;
-        for (int i = 0; i < TPNET_MAX_LAYERS; ++i) Dd.decay[i] = 1.0f;
-        p.base.desc[bb] = Dd;
-    }
+    run_ranks_store(myrun, u.s.ustart, htotal, nc, q.bri + g0, q.bflags + g0);
+    run_lengths_store<BS>(u.s.key, u.s.ustart, htotal, nc, lenrow);
+    // (n_light = the kept contributions; eager = false: the decay's factors are read by the eager mode only)
+    if (tid == 0)
+        batch_desc_store(p.base.desc, bb, sp, batch_clock(bb, e0, a.t, a.t_prev, a.now_time), t_last, (uint32_t)nc, 0u, false,
+                         a.lambda, a.L);
 }
 
 // ---- B1: a workgroup per (chunk of DCH nodes, window), a thread per node: the node's contributions in the window and the
@@ -816,10 +670,7 @@ int wplan_dense_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& pa
     if (shard) hipLaunchKernelGGL((k_dense_sort_shard<1024, 4>), dim3((unsigned)nb), dim3(1024), 0, s, p, q, D, a);
     else if (!no_group && n2 <= 2048 && st.N <= DENSE_GROUP_MAX_N)
         hipLaunchKernelGGL((k_dense_group<1024, 2, DENSE_GROUP_MAX_N>), dim3((unsigned)nb), dim3(1024), 0, s, p, q, D, a);
-    else if (n2 <= 512) TPNET_WDENSE(256, 2);
-    else if (n2 <= 1024) TPNET_WDENSE(512, 2);
-    else if (n2 <= 2048) TPNET_WDENSE(1024, 2);
-    else TPNET_WDENSE(1024, 4);
+    else TPNET_FOR_BATCH_TILE(n2, TPNET_WDENSE);
 #undef TPNET_WDENSE
     const unsigned bgrid = (unsigned)((int64_t)a.nchunks * a.nw);
     hipLaunchKernelGGL(k_dense_win, dim3(bgrid), dim3(DCH), 0, s, p, D, a);

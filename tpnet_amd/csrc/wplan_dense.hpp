@@ -53,30 +53,6 @@ static inline DView dview_of(const WPlan& p, int64_t Ec, int64_t batch, int64_t 
     return v;
 }
 
-// exclusive scan of one value per thread over the workgroup (wave shuffles + one LDS word per wave); total = the sum
-template <int BS>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum /* [BS / 64] */, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = (uint32_t)__shfl_up((int)inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();                                        // (wsum may still be read from an earlier scan)
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < BS / 64; ++i) {
-        const uint32_t s = wsum[i];
-        if (i < wave) base += s;
-        tot += s;
-    }
-    total = tot;
-    return base + inc - v;
-}
-
 struct DVRef { uint32_t ref; double t_src; };
 
 // the version of node v before batch b, given m[b][v] (and, speculatively loaded, base[v] and the node's meta record)
