@@ -167,23 +167,26 @@ def test_decoder_logits_match_reference(golden_dir):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed,N,E,K", [(0, 40, 300, 5), (1, 500, 5000, 20), (2, 7, 60, 3), (3, 30, 0, 4)])
-def test_gpu_recent_sampler_matches_host_restatement(seed, N, E, K):
+@pytest.mark.parametrize("seed,N,E,K,shift", [(0, 40, 300, 5, 0.0), (1, 500, 5000, 20, 0.0), (2, 7, 60, 3, 0.0), (3, 30, 0, 4, 0.0),
+                                              (1, 500, 5000, 20, 1.7e9), (0, 40, 300, 5, -1.0e6)],
+                         ids=["0-40-300-5", "1-500-5000-20", "2-7-60-3", "3-30-0-4", "1-500-5000-20-epoch", "0-40-300-5-negative"])
+def test_gpu_recent_sampler_matches_host_restatement(seed, N, E, K, shift):
     """f-3: the device sampler against RecentNeighborSampler (itself pinned to the reference's NeighborSampler through
-    fixture G8): ties in time, nodes without history, queries before the first edge, ids outside the graph."""
+    fixture G8): ties in time, nodes without history, queries before the first edge, ids outside the graph.  `shift` moves the
+    stamps and the query times alike: to Unix-epoch scale, and below zero (the sign branch of the sampler's time key)."""
     if not torch.cuda.is_available():
         pytest.fail("needs a GPU")
     from tpnet_amd.sampler import GpuRecentNeighborSampler
     rng = np.random.RandomState(seed)
     src = rng.randint(1, N, E).astype(np.int64)
     dst = rng.randint(1, N, E).astype(np.int64)
-    t = np.sort(np.round(rng.uniform(0, 50.0, E), 0 if seed != 1 else 3))       # many equal timestamps
+    t = np.sort(np.round(rng.uniform(0, 50.0, E), 0 if seed != 1 else 3)) + shift   # many equal timestamps
     if E:
         dst[::11] = src[::11]                                                    # self loops
     gpu = GpuRecentNeighborSampler(src, dst, t, num_nodes=N + 3)
     host = RecentNeighborSampler(src, dst, t) if E else None
     q_nodes = rng.randint(0, N + 3, 400).astype(np.int64)
-    q_times = np.concatenate([rng.uniform(-1.0, 60.0, 300), rng.choice(t, 100) if E else rng.uniform(0, 1, 100)])
+    q_times = np.concatenate([rng.uniform(-1.0, 60.0, 300) + shift, rng.choice(t, 100) if E else rng.uniform(0, 1, 100)])
     got = gpu.get_historical_neighbors(q_nodes, q_times, K)
     if host is None:
         assert all(np.all(g == 0) for g in got)

@@ -282,10 +282,11 @@ def test_kernel_matches_recorded_projection_output(golden_dir):
         emb.check_device_errors()
 
 
-def _real_stage(n_nodes, K, seed, dev="cuda:0", widths=REAL, hidden_out=None):
+def _real_stage(n_nodes, K, seed, dev="cuda:0", widths=REAL, hidden_out=None, t_offset=0.0):
     """A TPNetEmbedding at 172 / 100 / 172 / 64 (or `widths`) and one call's arrays: pad rows (id 0, edge 0, time 0), repeated ids,
     query times equal to neighbour times.  hidden_out = (H, Dout): a projection_layer of those widths instead of the module's
-    2 Dn / Dn, and no mixers behind it (their width is Dn)."""
+    2 Dn / Dn, and no mixers behind it (their width is Dn).  t_offset != 0: the query times moved up by it, the deltas log-uniform
+    in [0.5, 1e5] with exact 1 (and, as always, 0) among them; pad rows keep time 0."""
     import tpnet_amd
     rng = np.random.RandomState(seed)
     torch.manual_seed(seed)
@@ -310,10 +311,19 @@ def _real_stage(n_nodes, K, seed, dev="cuda:0", widths=REAL, hidden_out=None):
     eids = rng.randint(1, Ne, (n_nodes, K)).astype(np.int64)
     tq = rng.uniform(1e5, 2e6, n_nodes)
     tn = tq[:, None] - rng.uniform(0, 1e5, (n_nodes, K))
+    if t_offset:
+        tq = tq + t_offset
+        delta = np.exp(rng.uniform(np.log(0.5), np.log(1e5), (n_nodes, K)))
+        delta[rng.rand(n_nodes, K) < 0.1] = 1.0
+        delta[0, K - 1] = 1.0
+        tn = tq[:, None] - delta
     pad = rng.rand(n_nodes, K) < 0.2
     neigh[pad], eids[pad], tn[pad] = 0, 0, 0.0
     same = rng.rand(n_nodes, K) < 0.1
     tn[same] = np.broadcast_to(tq[:, None], tn.shape)[same]                 # delta 0: log(1) = 0
+    if t_offset:
+        tn[0, 0], tn[0, K - 1] = tq[0], tq[0] - 1.0                         # (whatever the draws: one delta 0, one delta 1, ...
+        neigh[0, 1], eids[0, 1], tn[0, 1] = 0, 0, 0.0                       #  ... one pad row)
     neigh[:, K // 2] = neigh[:, 0]                                          # repeated ids
     if n_nodes > 1:
         neigh[1], eids[1] = neigh[0], eids[0]
