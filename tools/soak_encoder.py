@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool: random shapes of the encoder's call from HOST index arrays (the reference's tile / repeat layout, and arrays that
 just miss it) through get_pair_wise_feature -- the one-crossing path (tpnet_host_anchored_features), the staged path behind it, the
-general path -- against the general kernel on device ids + torch's layers.  usage: python tools/soak_encoder.py [cases] [seed]"""
+general path -- against the general kernel on device ids + torch's layers.  usage: python tools/soak_encoder.py [cases] [seed]
+The suite holds these shapes to the oracle and asserts the route of every call: tests/test_host_routes.py."""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

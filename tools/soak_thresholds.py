@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer tool: the per-batch calls from HOST arrays at sizes either side of the staging ring's thresholds (pairs per slot, batch
-planned from the slot, batch staged and copied) against the same calls on device tensors: features and state bit for bit."""
+planned from the slot, batch staged and copied) against the same calls on device tensors: features and state bit for bit.
+The suite holds these thresholds to the oracle and asserts the route of every call: tests/test_host_routes.py."""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
