@@ -494,6 +494,29 @@ int tpnet_sampler_build(void* sampler, size_t sampler_bytes, const int64_t* src,
 int tpnet_sample_recent(const void* sampler, int64_t E, int64_t num_nodes, const int64_t* node_ids, const double* times,
                         int64_t n, int32_t K, int64_t* out_ids, int64_t* out_eids, double* out_times, void* stream);
 
+/* ---- the reference's two random strategies on the same CSR ('uniform', 'time_interval_aware': utils/utils.py:123-224) ----------
+ * Per query: the n interactions of the node strictly before the query time (the cut of tpnet_sample_recent), K positions drawn
+ * WITH replacement, the K triples written in ascending CSR position (a time sort; ties in the CSR's append order).  n == 0 or a
+ * node id outside [0, num_nodes): a row of zeros.
+ *   uniform:              every position with probability 1/n.
+ *   time_interval_aware:  P(j) ~ w_j = exp((double)(float)p_j), p_j = E_j / cumsum(E)_j over the node's WHOLE list,
+ *                         E_j = exp(time_scaling_factor * (t_j - t_last)) in float64; w_j = 0 where p_j is NaN; a prefix whose
+ *                         weights are all 0 is drawn uniformly.  This is the reference's softmax(float32(p[:n])) with NaN -> -1e10.
+ * Random numbers: Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (row & 0xffffffff, row >> 32, slot >> 2,
+ * call_index), word used = out[slot & 3]; row = the query's index within the call.  A draw depends on (seed, call_index, row,
+ * slot) alone -- reproducible per seed, NOT numpy's RandomState.choice stream.  From the word r: uniform position =
+ * (uint64(r) * n) >> 32; weighted: x = (r + 0.5) * 2^-32 * W[cut-1], position = first j of the prefix with W[j] >= x, W = the
+ * per-node inclusive prefix sum of w (float64). */
+size_t tpnet_sampler_weights_bytes(int64_t E);          /* W table + its build scratch */
+/* weights: caller-owned device buffer of tpnet_sampler_weights_bytes(E); `sampler` was built by tpnet_sampler_build on the same
+ * stream (or the build has finished).  Once per sampler and time_scaling_factor. */
+int tpnet_sampler_build_weights(const void* sampler, int64_t E, int64_t num_nodes, double time_scaling_factor, void* weights,
+                                size_t weights_bytes, void* stream);
+/* weights NULL = uniform.  1 <= K <= 256.  out_eids / out_times may be NULL as in tpnet_sample_recent. */
+int tpnet_sample_random(const void* sampler, const void* weights, int64_t E, int64_t num_nodes, const int64_t* node_ids,
+                        const double* times, int64_t n, int32_t K, uint64_t seed, uint32_t call_index, int64_t* out_ids,
+                        int64_t* out_eids, double* out_times, void* stream);
+
 /* The encoder's readout with the ids resident on the device end to end (models/TPNet.py:280-324, SURVEY §8 f-3 -> f-2): for one
  * (src, other) batch of B edges -- other = dst or the negatives -- the 2B nodes [src; other] at times tile(t, 2) draw their K most
  * recent neighbours from the device sampler, and every neighbour is paired with the edge's two endpoints: out[0][(i*K + k)] =

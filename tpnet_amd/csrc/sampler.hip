@@ -1,7 +1,8 @@
 // Device-side 'recent' neighbour sampler: the step in front of the hot path.  The reference builds
 // per-node time-sorted adjacency lists on the host and, per query, runs np.searchsorted + a last-K slice in a Python
 // loop over the batch (utils/utils.py:140-152, 160-224, 293-312).  Here: one CSR of the undirected interaction graph
-// (stable sort by (node, time), ties in the reference's append order) and one thread per (query, slot).
+// (stable sort by (node, time), ties in the reference's append order) and one thread per (query, slot).  The two random strategies
+// ('uniform', 'time_interval_aware') draw from the same CSR with a counter-based generator: k_sampler_weights / k_sample_random.
 #include "tpnet_common.h"
 
 #include <cstring>
@@ -100,6 +101,145 @@ __global__ void k_sample_recent(const int64_t* __restrict__ row_start, const int
         if (out_eids) out_eids[x] = ee;
         if (out_t) out_t[x] = tt;
     }
+}
+
+// ---- the reference's random strategies, 'uniform' and 'time_interval_aware' (utils/utils.py:123-224) ----
+
+// inclusive scan of one double per thread over a 256-thread workgroup; sh = 4 doubles of LDS; total = the workgroup's sum
+__device__ __forceinline__ double wg_scan256(double v, double* sh, double& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int off = 1; off < 64; off <<= 1) {
+        const double u = __shfl_up(v, off, 64);
+        if (lane >= off) v += u;
+    }
+    if (lane == 63) sh[wave] = v;
+    __syncthreads();
+    double base = 0.0;
+    for (int w = 0; w < wave; ++w) base += sh[w];
+    total = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();
+    return base + v;
+}
+
+// The weights table of 'time_interval_aware', once per sampler: one workgroup per node walks the node's time-sorted list in
+// chunks of 256 with two running carries.  E_j = exp(s (t_j - t_last)) and p_j = E_j / cumsum(E)_j in float64 over the WHOLE
+// list (compute_sampled_probabilities, utils/utils.py:123-139); the reference then takes softmax(float32(p[:n])) with NaN -> -1e10
+// (:194), i.e. P(j) ~ w_j = exp((double)(float)p_j) and 0 for a NaN p_j; W = the node's inclusive prefix sum of w.
+__global__ __launch_bounds__(256) void k_sampler_weights(const int64_t* __restrict__ row_start, const double* __restrict__ nbr_t,
+                                                         int64_t num_nodes, double s, double* __restrict__ W) {
+    __shared__ double sh[4];
+    for (int64_t node = blockIdx.x; node < num_nodes; node += gridDim.x) {
+        const int64_t lo = row_start[node], hi = row_start[node + 1];
+        if (hi <= lo) continue;                                   // (block-uniform)
+        const double t_last = nbr_t[hi - 1];
+        double carry_e = 0.0, carry_w = 0.0;
+        for (int64_t base = lo; base < hi; base += 256) {
+            const int64_t j = base + threadIdx.x;
+            const double e = j < hi ? exp(s * (nbr_t[j] - t_last)) : 0.0;
+            double tot_e, tot_w;
+            const double ce = carry_e + wg_scan256(e, sh, tot_e);
+            const double p = e / ce;
+            const double w = (j < hi && p == p) ? exp((double)(float)p) : 0.0;
+            const double cw = carry_w + wg_scan256(w, sh, tot_w);
+            if (j < hi) W[j] = cw;
+            carry_e += tot_e;
+            carry_w += tot_w;
+        }
+    }
+}
+
+// Philox4x32-10 (Salmon et al., SC'11): counter-based, so a draw depends on (key, counter) alone, never on the launch geometry
+__device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                                int word) {
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
+}
+
+// One workgroup holds 256 / K whole rows (one row when K > 128); thread = (row, slot).  The row's first lane does the cut search
+// and shares (row start, prefix length, total weight) through LDS; every thread draws its position, and after a barrier finds its
+// rank among the row's K positions (smaller positions, plus equal ones in lower slots) and writes its triple to output slot `rank`:
+// the row comes out in ascending CSR position, which is a time sort.  W == nullptr: uniform.
+__global__ __launch_bounds__(256) void k_sample_random(const int64_t* __restrict__ row_start, const int32_t* __restrict__ nbr,
+                                                       const int64_t* __restrict__ nbr_eid, const double* __restrict__ nbr_t,
+                                                       const double* __restrict__ W, int64_t num_nodes,
+                                                       const int64_t* __restrict__ node_ids, const double* __restrict__ times,
+                                                       int64_t n, int K, int rows_per_wg, uint32_t k0, uint32_t k1,
+                                                       uint32_t call_index, int64_t* __restrict__ out_ids,
+                                                       int64_t* __restrict__ out_eids, double* __restrict__ out_t) {
+    __shared__ int64_t s_lo[256];
+    __shared__ uint32_t s_len[256];
+    __shared__ double s_wtot[256];
+    __shared__ uint32_t s_pos[256];
+    const int tid = threadIdx.x;
+    const int r = tid / K, slot = tid - r * K;
+    const int64_t row = (int64_t)blockIdx.x * rows_per_wg + r;
+    const bool live = r < rows_per_wg && row < n;
+    if (live && slot == 0) {
+        const int64_t nid = node_ids[row];
+        int64_t lo0 = 0, cut = 0;
+        if ((uint64_t)nid < (uint64_t)num_nodes) {
+            lo0 = row_start[nid];
+            const double q = times[row];
+            int64_t lo = lo0, hi = row_start[nid + 1];
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (nbr_t[mid] < q) lo = mid + 1; else hi = mid;
+            }
+            cut = lo;
+        }
+        s_lo[r] = lo0;
+        s_len[r] = (uint32_t)(cut - lo0);                       // (2E < 2^31: tpnet_sampler_build)
+        s_wtot[r] = (W && cut > lo0) ? W[cut - 1] : 0.0;
+    }
+    __syncthreads();
+    const int64_t lo0 = live ? s_lo[r] : 0;
+    const uint32_t len = live ? s_len[r] : 0u;
+    uint32_t pos = 0;
+    if (len) {
+        const uint32_t rnd = philox_word((uint32_t)row, (uint32_t)((uint64_t)row >> 32), (uint32_t)slot >> 2, call_index, k0, k1,
+                                         slot & 3);
+        const double wtot = s_wtot[r];
+        if (wtot > 0.0) {
+            const double x = ((double)rnd + 0.5) * 0x1p-32 * wtot;
+            uint32_t a = 0, b = len - 1;                          // first j with W[j] >= x, clamped to the prefix's last entry
+            while (a < b) {
+                const uint32_t mid = (a + b) >> 1;
+                if (W[lo0 + mid] < x) a = mid + 1; else b = mid;
+            }
+            pos = a;
+        } else {
+            pos = (uint32_t)(((uint64_t)rnd * (uint64_t)len) >> 32);
+        }
+    }
+    s_pos[tid] = pos;
+    __syncthreads();
+    if (!live) return;
+    const int64_t o = row * K;
+    if (!len) {
+        out_ids[o + slot] = 0;
+        if (out_eids) out_eids[o + slot] = 0;
+        if (out_t) out_t[o + slot] = 0.0;
+        return;
+    }
+    int rank = 0;
+    const uint32_t* rp = s_pos + r * K;
+    for (int k = 0; k < K; ++k) {
+        const uint32_t pk = rp[k];
+        rank += (pk < pos || (pk == pos && k < slot)) ? 1 : 0;
+    }
+    const int64_t j = lo0 + pos;
+    out_ids[o + rank] = nbr[j];
+    if (out_eids) out_eids[o + rank] = nbr_eid[j];
+    if (out_t) out_t[o + rank] = nbr_t[j];
 }
 
 // the encoder's rows for one (src, other) batch (models/TPNet.py:280-316): nodes = [src; other], times = tile(t, 2), and the
@@ -256,6 +396,42 @@ int tpnet_sample_recent(const void* sampler, int64_t E, int64_t num_nodes, const
     if (grid > 8192) grid = 8192;
     hipLaunchKernelGGL(k_sample_recent, dim3(grid), dim3(256), 0, (hipStream_t)stream, v.row_start, v.nbr, v.nbr_eid,
                        v.nbr_t, num_nodes, node_ids, times, n, (int)K, out_ids, out_eids, out_times);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+size_t tpnet_sampler_weights_bytes(int64_t E) {
+    return al(2 * (size_t)(E < 1 ? 1 : E) * 8) + 256;           // W[2E] doubles; the scan keeps its carries in registers
+}
+
+int tpnet_sampler_build_weights(const void* sampler, int64_t E, int64_t num_nodes, double time_scaling_factor, void* weights,
+                                size_t weights_bytes, void* stream) {
+    if (!sampler || !weights || E < 0 || E >= (1ll << 30) || num_nodes < 1 || num_nodes >= (1ll << 31)) return TPNET_ERR_BAD_ARG;
+    if (weights_bytes < tpnet_sampler_weights_bytes(E)) return TPNET_ERR_WORKSPACE;
+    if (E == 0) return TPNET_OK;
+    SamplerView v = carve(const_cast<void*>(sampler), E, num_nodes);
+    double* W = (double*)(((size_t)weights + 255) / 256 * 256);
+    const int grid = (int)(num_nodes < 8192 ? num_nodes : 8192);
+    hipLaunchKernelGGL(k_sampler_weights, dim3(grid), dim3(256), 0, (hipStream_t)stream, v.row_start, v.nbr_t, num_nodes,
+                       time_scaling_factor, W);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+int tpnet_sample_random(const void* sampler, const void* weights, int64_t E, int64_t num_nodes, const int64_t* node_ids,
+                        const double* times, int64_t n, int32_t K, uint64_t seed, uint32_t call_index, int64_t* out_ids,
+                        int64_t* out_eids, double* out_times, void* stream) {
+    if (!sampler || n < 0 || K < 1 || K > 256 || E < 0 || num_nodes < 1 || (n > 0 && (!node_ids || !times || !out_ids)))
+        return TPNET_ERR_BAD_ARG;
+    if (n == 0) return TPNET_OK;
+    const int rows_per_wg = 256 / K;                             // whole rows per workgroup (K > 128: one)
+    const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
+    if (grid > 0x7fffffffll) return TPNET_ERR_BAD_ARG;
+    SamplerView v = carve(const_cast<void*>(sampler), E, num_nodes);
+    const double* W = (weights && E > 0) ? (const double*)(((size_t)weights + 255) / 256 * 256) : nullptr;
+    hipLaunchKernelGGL(k_sample_random, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, v.row_start, v.nbr, v.nbr_eid,
+                       v.nbr_t, W, num_nodes, node_ids, times, n, (int)K, rows_per_wg, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       call_index, out_ids, out_eids, out_times);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }

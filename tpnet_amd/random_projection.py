@@ -961,9 +961,22 @@ class RandomProjectionModule(nn.Module):
         """Extension: the encoder's whole readout for one (src, other) batch with the ids resident on the device
         (models/TPNet.py:280-324): `sampler` = a GpuRecentNeighborSampler, src_ids / other_ids int64 [B] and times float64 [B] on
         the device, or all three as host numpy arrays (the reference's batch slices: staged, no copy enqueued).  Returns (features [4*B*K, (2L+2)^2] in the reference's row order with self.mlp applied, neighbour ids
-        [2B, K] on the device).  One FFI call = row set-up + neighbour sampling + anchored readout; self.mlp behind it."""
+        [2B, K] on the device).  One FFI call = row set-up + neighbour sampling + anchored readout; self.mlp behind it.
+        A sampler of another strategy ('uniform', 'time_interval_aware') draws its own neighbours: the 2B rows go through its
+        `sample_device` (one call of its random sequence), then `get_pair_wise_feature_anchored`."""
         self._ensure_engine()
         dev = self._dev()
+        if getattr(sampler, "sample_neighbor_strategy", "recent") != "recent":
+            if isinstance(src_ids, np.ndarray):
+                src_d, other_d, t_d = self._to_device(self._ids(src_ids, "src_ids"), self._ids(other_ids, "other_ids"),
+                                                      np.ascontiguousarray(np.asarray(times), dtype=np.float64))
+            else:
+                src_d, other_d, t_d = src_ids, other_ids, times
+            for name, x, dt in (("src_ids", src_d, torch.int64), ("other_ids", other_d, torch.int64), ("times", t_d, torch.float64)):
+                if not isinstance(x, torch.Tensor) or x.device != dev or x.dtype != dt or x.dim() != 1 or x.numel() != t_d.numel():
+                    raise ValueError(f"encoder_pair_features: {name} must be a one-dimensional {dt} tensor on {dev}, all three of one length")
+            neigh, _, _ = sampler.sample_device(torch.cat([src_d, other_d]), t_d.repeat(2), int(num_neighbors), with_edges=False)
+            return self.get_pair_wise_feature_anchored(neigh, src_d.repeat(2), other_d.repeat(2)), neigh
         host = isinstance(src_ids, np.ndarray)
         if host:
             # the batch's arrays as the reference's loop holds them (numpy slices of the edge list): staged through the pinned ring
