@@ -5,7 +5,8 @@ exception's type and text instead.  Two trees compute the same thing by the same
 file by file (`cmp`): the paths differ in summation order, so equal bytes pin the route.  With rocprofv3 --kernel-trace --stats
 around it, the kernel names and call counts close the gap.
 
-    python tools/feature_paths.py OUT_DIR
+    python tools/feature_paths.py OUT_DIR              # everything (the readout section first: 374 of the files)
+    python tools/feature_paths.py OUT_DIR readout      # only the readout kernels' matrix (readout_cases)
 """
 import os
 import sys
@@ -20,6 +21,7 @@ from tpnet_amd.matrix_memory import MatrixMemory
 from tpnet_amd.sampler import GpuRecentNeighborSampler
 
 OUT = sys.argv[1] if len(sys.argv) > 1 else "feature_paths_out"
+ONLY = sys.argv[2:]
 os.makedirs(OUT, exist_ok=True)
 DEV = "cuda:0"
 N = 5000
@@ -185,7 +187,46 @@ def dense_cases(rng):
                 case(f"embedding_{tag}_fused_input_{int(fused)}", lambda: emb.embed_from_features(*arrays))
 
 
+def readout_cases():
+    """The readout kernels by geometry and store path (csrc/readout.hpp): the three standalone readouts at eight row widths x L = 1..4,
+    and run_stream's readouts on both schedules and in exact mode."""
+    rng = np.random.RandomState(21)
+    n_nodes, n, K = 64, 37, 5
+    with torch.no_grad():
+        for d in (12, 16, 32, 64, 100, 256, 260, 30):
+            for L in (1, 2, 3, 4):
+                rp = make(d, L=L, n_nodes=n_nodes, seed=d + L, batches=L + 1)
+                u, v, v2 = (dev(ids(rng, n, n_nodes)) for _ in range(3))
+                neigh = dev(ids(rng, n * K, n_nodes).reshape(n, K))
+                tag = f"readout_d{d}_L{L}"
+                case(f"{tag}_default", lambda: rp.pair_gram(u, v))
+                case(f"{tag}_raw", lambda: rp.pair_gram(u, v, raw=True))
+                case(f"{tag}_packed", lambda: rp.pair_gram(u, v, packed=True))
+                rp.not_scale = True
+                case(f"{tag}_not_scale", lambda: rp.pair_gram(u, v))
+                rp.not_scale = False
+                case(f"{tag}_shared", lambda: rp.pair_gram_shared(u, v, v2))
+                case(f"{tag}_anchored", lambda: rp.pair_gram_anchored(neigh, u, v, matrix_cores=False))   # (d outside 36..512: the error text)
+        streams = [(d, 64, 20, 500) for d in (16, 64, 128, 256)] + [(64, 2600, 3, 6000)]      # (B = 2600: the edge-fused step)
+        for d, B, nb, nn_ in streams:
+            E = B * nb
+            src, dst, neg = (dev(ids(rng, E, nn_)) for _ in range(3))
+            t = dev(np.sort(rng.uniform(1.0, 2.0e5, E)), torch.float64)
+            for mode in ("batch", "windowed", "exact"):
+                for packed in (False, True):
+                    rp = make(d, n_nodes=nn_, seed=d, batches=0, exact=(mode == "exact"))
+                    sched = None if mode == "exact" else mode
+                    case(f"stream_d{d}_B{B}_{mode}_packed{int(packed)}",
+                         lambda: list(rp.run_stream(src, dst, neg, t, B, packed=packed, schedule=sched)) + list(rp.backup_random_projections()[1]))
+
+
 def main():
+    if ONLY:
+        for name in ONLY:
+            {"readout": readout_cases}[name]()
+        print(f"{len(SAVED)} files in {OUT}")
+        return
+    readout_cases()
     rng = np.random.RandomState(7)
     # ---- the decoder's calls from host arrays -----------------------------------------------------------------------------
     rp128 = make(128)

@@ -1,7 +1,7 @@
 // gfx950 kernels that walk or gather the table itself: init / import / export / dense decay (models/TPNet.py:83-85,
 // :131-157), row and element gathers (:101-110; models/MemoryModel.py:396-405), the row exchange of the row-sharded
 // layout, and the readout's element-wise tail on summed partial Gram entries (:126-128).
-#include "device_common.hpp"
+#include "readout.hpp"
 
 namespace tpnet {
 
@@ -422,14 +422,11 @@ int launch_gather_rows(const tpnet_state& st, const int64_t* ids, int64_t n, dou
     return TPNET_OK;
 }
 
-// element-wise tail of the readout on a buffer of raw Gram entries (same two operations, in the same order, as the
-// fused store of gram_pair)
+// element-wise tail of the readout on a buffer of raw Gram entries (finish_feature, as in the fused store of gram_pair)
 __global__ void k_gram_finish(float* __restrict__ x, int64_t n) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float v = x[i];
-        v = (v < 0.0f) ? 0.0f : v;
-        x[i] = logf(v + 1.0f);
+        x[i] = finish_feature(x[i], true);
     }
 }
 
@@ -443,12 +440,8 @@ __global__ void k_gram_unpack(const float* __restrict__ packed, int64_t n, int N
         const int idx = (int)(i - p * NG);
         int a = idx / NN, b = idx - a * NN;
         if (a > b) { const int z = a; a = b; b = z; }
-        float v = packed[p * NT + a * NN - (a * (a - 1)) / 2 + (b - a)];
-        if (do_scale) {
-            v = (v < 0.0f) ? 0.0f : v;
-            v = logf(v + 1.0f);
-        }
-        out[i] = v;
+        const float v = packed[p * NT + tri_slot(NN, a, b)];
+        out[i] = finish_feature(v, do_scale != 0);
     }
 }
 

@@ -869,17 +869,10 @@ __global__ __launch_bounds__(WB, wpipe_min_waves(LPP, VPL, L, FULL)) void k_wpip
                 const float gs_e = P.e_g[(int64_t)which[s] * Ec + e];
                 const uint32_t ref = idok ? ref_e : WREF_TABLE;
                 const float gs = idok ? gs_e : 1.0f;
-                const float* qb = (ref & WREF_TABLE) ? S.q + ((int64_t)(ref & 1u) * S.N + ids[s]) * ((int64_t)L * d)
+                // (bundle_rows for a windowed reference; why it is no function of its own: profiles/readout_phases.md)
+                const float* qb = (ref & WREF_TABLE) ? bundle_base(S, (int)(ref & 1u), ids[s], L)
                                                      : P.log + (int64_t)(ref & WREF_SLOT_MASK) * ((int64_t)L * d);
-                rowp[s * NR] = S.p0 + ids[s] * (int64_t)d;
-                rs[s * NR] = 1.0f;
-                float gg = 1.0f;
-#pragma unroll
-                for (int i = 1; i <= L; ++i) {
-                    gg *= gs;
-                    rowp[s * NR + i] = qb + (int64_t)(i - 1) * d;
-                    rs[s * NR + i] = gg;
-                }
+                decay_rows<L>(S.p0 + ids[s] * (int64_t)d, qb, d, gs, rowp + s * NR, rs + s * NR);
             }
             if (packed)
                 gram_rows<RLPP, RVPL, W, L, FULL, true, LR>(rowp, rs, d, valid, idok, do_scale, out, rgl, stage);
