@@ -43,7 +43,8 @@ extern "C" {
                                     tpnet_run_stream_tagged replays streams of up to 64 chunks;
                                7: + tpnet_stream_schedule (which schedule tpnet_run_stream would take); tpnet_xplan_targeted serves G = 1;
                                     tpnet_xplan_targeted_large (batches beyond one workgroup's lists); tpnet_wshard_* (a row shard on the windowed pipeline);
-                                    the side-by-side plans of a multi-chunk stream are bounded (TPNET_ARENA_MAX_RATIO) */
+                                    the side-by-side plans of a multi-chunk stream are bounded (TPNET_ARENA_MAX_RATIO);
+                                    added since without a new number: tpnet_neg_* (the negative edge sampler's three strategies) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -516,6 +517,54 @@ int tpnet_sampler_build_weights(const void* sampler, int64_t E, int64_t num_node
 int tpnet_sample_random(const void* sampler, const void* weights, int64_t E, int64_t num_nodes, const int64_t* node_ids,
                         const double* times, int64_t n, int32_t K, uint64_t seed, uint32_t call_index, int64_t* out_ids,
                         int64_t* out_eids, double* out_times, void* stream);
+
+/* ---- the reference's negative edge sampler on the device (additive to ABI 7; csrc/negsampler.hip) ----------
+ * NegativeEdgeSampler (utils/utils.py:315-505), strategies 'random', 'historical', 'inductive'.  With the sampler's own E edges
+ * (src, dst, t), a batch window [t0, t1] and the batch's own B pairs:
+ *   candidates C: the unique edges e with first_time(e) <= t0 and no occurrence in [t0, t1] (both ends inclusive); 'inductive': and
+ *                 first_time(e) > last_observed_time.  M = |C|, cand[0..M) = C in ascending (src << 32 | dst) order.
+ *   size <= M:    out[i] = cand[perm(M, tag 0, i)]: `size` distinct candidates, uniform.
+ *   size >  M:    F = size - M, Us / Ud = the sorted unique src / dst ids, D = |Us| |Ud|, index x = the pair (Us[x / |Ud|], Ud[x % |Ud|]).
+ *                 Trial slot j < min(D, F + B) holds x = perm(D, tag 1, j); it is valid when its pair is none of the batch's B pairs.
+ *                 At least F valid trials (always so when P = |Us x Ud - batch pairs| >= F): the first F valid ones in slot order fill
+ *                 out[0..F) -- distinct.  Otherwise the whole domain was enumerated and P < F: out[i] = valid[(word(2, i, 0) * P) >> 32],
+ *                 valid = the P valid pairs in slot order (with replacement).  P = 0: out[0..F) = -1 and the sampler's error word is
+ *                 set (tpnet_neg_check).  out[F + j] = cand[j], j < M: ALL candidates follow the fill.
+ *   'random':     out_src[i] = Us[(word(3, i, 0) * |Us|) >> 32], out_dst[i] = Ud[(word(4, i, 0) * |Ud|) >> 32].
+ * word(tag, a, b) = word 0 of Philox4x32-10 with counter (a, b, tag, call_index) and key (seed & 0xffffffff, seed >> 32).
+ * perm(n, tag, i), a keyed permutation of [0, n) evaluated per slot in O(1) memory: n <= 1: 0.  Else bits = bitlength(n - 1), a = bits / 2
+ * (rounded down), b = bits - a, x = i; repeat { (L, R) = (x >> b, x & (2^b - 1)); three times, r = 0, 2, 4: L ^= word(tag, R, r) & (2^a - 1),
+ * then R ^= word(tag, L, r + 1) & (2^b - 1); x = L << b | R } until x < n.  (Six rounds of an alternating Feistel network: each xor is
+ * undone by itself, so the network is a bijection of [0, 2^bits), and walking its cycle back into [0, n) keeps it one; 2^bits < 2 n, so
+ * fewer than two passes on average.)
+ * The draws follow the reference's probabilities and depend on (seed, call_index, slot) alone; they are NOT numpy's RandomState.choice
+ * stream, and the order inside C (Python-set order in the reference) is the key order here.
+ *
+ * tpnet_neg_build, once per sampler: sorts the edges by (src, dst, time) and writes, into the caller-owned device buffer `neg` of
+ *   tpnet_neg_bytes(E): the table of the U unique edges (key, first time, start of the ascending occurrence-time list, observed bit =
+ *   first_time <= last_observed_time when has_observed) and Us / Ud.  src / dst / t: device arrays of E (t may be NULL: all times 0);
+ *   1 <= E < 2^30; every id in [0, 2^31), else TPNET_ERR_INDEX.  counts: HOST int64[3] = {U, |Us|, |Ud|}; the call synchronises `stream`.
+ * tpnet_neg_uniques copies Us / Ud (n_src / n_dst entries, as counts gave them) to device arrays of the caller.
+ * tpnet_neg_sample: 3 launches (flag + tile sums, scan of the sums, compaction) + 1 (pick) on `stream` -- 'random': 1 -- and no
+ *   synchronisation; a batch of more than 1024 pairs adds a key sort (smaller ones are looked up in an LDS table).  batch_src / batch_dst:
+ *   device arrays of B (not read by 'random', and read only by the fill); scratch: tpnet_neg_scratch_bytes(E, size, B) device bytes (not
+ *   needed by 'random'); out_src / out_dst: device int64[size].  size, B < 2^31.  size == 0: TPNET_OK, nothing launched.
+ * tpnet_neg_check copies the error word to the host (synchronises), clears it if set and returns TPNET_ERR_BAD_ARG: a fill found every pair
+ *   of Us x Ud in its batch (possible only when |Us| |Ud| <= B).
+ * Null pointers and sizes out of range: TPNET_ERR_BAD_ARG (size helpers: 0), nothing launched. */
+#define TPNET_NEG_RANDOM 0
+#define TPNET_NEG_HISTORICAL 1
+#define TPNET_NEG_INDUCTIVE 2
+size_t tpnet_neg_bytes(int64_t E);
+int tpnet_neg_build(void* neg, size_t neg_bytes, const int64_t* src, const int64_t* dst, const double* t, int64_t E,
+                    double last_observed_time, int32_t has_observed, int64_t* counts, void* stream);
+int tpnet_neg_uniques(const void* neg, int64_t E, int64_t n_src, int64_t n_dst, int64_t* unique_src, int64_t* unique_dst,
+                      void* stream);
+size_t tpnet_neg_scratch_bytes(int64_t E, int64_t size, int64_t B);
+int tpnet_neg_sample(void* neg, int64_t E, int32_t strategy, int64_t size, const int64_t* batch_src, const int64_t* batch_dst,
+                     int64_t B, double t0, double t1, uint64_t seed, uint32_t call_index, void* scratch, size_t scratch_bytes,
+                     int64_t* out_src, int64_t* out_dst, void* stream);
+int tpnet_neg_check(void* neg, void* stream);
 
 /* The encoder's readout with the ids resident on the device end to end (models/TPNet.py:280-324, SURVEY §8 f-3 -> f-2): for one
  * (src, other) batch of B edges -- other = dst or the negatives -- the 2B nodes [src; other] at times tile(t, 2) draw their K most

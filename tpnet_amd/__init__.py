@@ -6,7 +6,8 @@ drop-in `RandomProjectionModule` mirroring /root/reference/models/TPNet.py:9-157
 from .random_projection import RandomProjectionModule  # noqa: F401
 from ._lib import TPNetHipError, load as load_library  # noqa: F401
 from .sampler import GpuRecentNeighborSampler, GpuNeighborSampler  # noqa: F401
+from .negative_sampler import GpuNegativeEdgeSampler  # noqa: F401
 from .encoder import TimeEncoder, FeedForwardNet, MLPMixer, TPNetEmbedding, TPNet  # noqa: F401
 
 __all__ = ["RandomProjectionModule", "TPNetHipError", "load_library", "TimeEncoder", "FeedForwardNet", "MLPMixer", "TPNetEmbedding",
-           "TPNet", "GpuRecentNeighborSampler", "GpuNeighborSampler"]
+           "TPNet", "GpuRecentNeighborSampler", "GpuNeighborSampler", "GpuNegativeEdgeSampler"]

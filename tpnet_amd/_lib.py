@@ -104,6 +104,13 @@ SIGNATURES = {
     "tpnet_sampler_build_weights": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_double, _P, C.c_size_t, _P]),
     "tpnet_sample_random": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32, _P, _P,
                                       _P, _P]),
+    "tpnet_neg_bytes": (C.c_size_t, [C.c_int64]),
+    "tpnet_neg_build": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_int64, C.c_double, C.c_int32, C.POINTER(C.c_int64), _P]),
+    "tpnet_neg_uniques": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    "tpnet_neg_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "tpnet_neg_sample": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_uint64,
+                                   C.c_uint32, _P, C.c_size_t, _P, _P, _P]),
+    "tpnet_neg_check": (C.c_int, [_P, _P]),
     "tpnet_encoder_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "tpnet_encoder_gram": (C.c_int, [_SP, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_uint32, _P, C.c_size_t, _P, _P]),

@@ -6,6 +6,7 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `RecentNeighborSampler`   -- the 'recent' strategy of NeighborSampler (utils/utils.py:82-224), host side.
 * `RandomNegativeSampler`   -- NegativeEdgeSampler.random_sample (utils/utils.py:388-400): draw order matters.
 * `encoder_pair_indices`    -- the 4*B*K index pattern of the encoder's readout (models/TPNet.py:206-217,311-316).
+* `run_evaluation`          -- the evaluation loop's order with any of the three negative strategies (evaluate_models_utils.py:56-72).
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
 The encoder itself is tpnet_amd/encoder.py (`TPNet`); `encoder` / `decoder` stay plug-in callables here.
@@ -126,45 +127,73 @@ def encoder_pair_indices(neighbor_node_ids: np.ndarray, src_node_ids: np.ndarray
 
 
 def link_prediction_batch(rp, neighbor_sampler, src: np.ndarray, dst: np.ndarray, neg_dst: np.ndarray, t: np.ndarray,
-                          num_neighbors: int, encoder: Optional[Callable] = None, decoder: Optional[Callable] = None):
+                          num_neighbors: int, encoder: Optional[Callable] = None, decoder: Optional[Callable] = None,
+                          neg_src: Optional[np.ndarray] = None):
     """One batch in the reference's order (train_link_prediction.py:325-373, evaluate_models_utils.py:132-184):
     encoder readout for (src,dst), encoder readout for (src,neg), decoder readout (src,dst), decoder readout
     (src,neg), THEN update(src,dst,t).  `encoder(pair_features[2B,K,2*F], node_ids, times) -> [2B, D]` and
     `decoder(src_ids, dst_ids, src_emb, dst_emb) -> logits` are optional plug-ins; without them the four pairwise
-    feature tensors are returned."""
+    feature tensors are returned.  `neg_src` (evaluation under the 'historical' / 'inductive' negatives, whose source is
+    not the batch's own: evaluate_models_utils.py:72-91): the negative readouts pair (neg_src, neg_dst); None: (src, neg_dst)."""
     B = len(src)
+    pairs = ((src, dst), (src if neg_src is None else neg_src, neg_dst))
     feats = []
     embs = []
     on_device = hasattr(neighbor_sampler, "sample_device") and hasattr(rp, "get_pair_wise_feature_shared")
     if on_device:      # ids stay on the GPU from the sampler to the readout (same pairs, same order as the host path)
         dev = neighbor_sampler.device
-        src_t = torch.from_numpy(np.ascontiguousarray(src, dtype=np.int64)).to(dev)
+        to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+        src_t = to_dev(src)
         t2_t = torch.from_numpy(np.tile(np.asarray(t, dtype=np.float64), 2)).to(dev)
-    for other in (dst, neg_dst):
-        node_ids = np.concatenate([src, other])
+    for first, other in pairs:
+        node_ids = np.concatenate([first, other])
         if on_device:
-            other_t = torch.from_numpy(np.ascontiguousarray(other, dtype=np.int64)).to(dev)
-            neigh, _, _ = neighbor_sampler.sample_device(torch.cat([src_t, other_t]), t2_t, num_neighbors, with_edges=False)
-            f = rp.get_pair_wise_feature_shared(neigh.reshape(-1), src_t.repeat(2).repeat_interleave(num_neighbors),
+            first_t = src_t if first is src else to_dev(first)
+            other_t = to_dev(other)
+            neigh, _, _ = neighbor_sampler.sample_device(torch.cat([first_t, other_t]), t2_t, num_neighbors, with_edges=False)
+            f = rp.get_pair_wise_feature_shared(neigh.reshape(-1), first_t.repeat(2).repeat_interleave(num_neighbors),
                                                 other_t.repeat(2).repeat_interleave(num_neighbors))
         else:
             neigh, _, _ = neighbor_sampler.get_historical_neighbors(node_ids=node_ids,
                                                                     node_interact_times=np.tile(t, 2),
                                                                     num_neighbors=num_neighbors)
-            u, v = encoder_pair_indices(neigh, src, other)
+            u, v = encoder_pair_indices(neigh, first, other)
             f = rp.get_pair_wise_feature(src_node_ids=u, dst_node_ids=v)             # [4BK, F]
         half = 2 * B * num_neighbors
         f = torch.cat([f[:half], f[half:]], dim=1).reshape(2 * B, num_neighbors, -1)  # TPNet.py:318-321
         feats.append(f)
         embs.append(encoder(f, node_ids, np.tile(t, 2)) if encoder is not None else None)
     outs = []
-    for other, e in zip((dst, neg_dst), embs):
+    for (first, other), e in zip(pairs, embs):
         if decoder is not None and e is not None:
-            outs.append(decoder(src_node_ids=src, dst_node_ids=other, src_node_embeddings=e[:B], dst_node_embeddings=e[B:]))
+            outs.append(decoder(src_node_ids=first, dst_node_ids=other, src_node_embeddings=e[:B], dst_node_embeddings=e[B:]))
         else:
-            outs.append(rp.get_pair_wise_feature(src_node_ids=src, dst_node_ids=other))
+            outs.append(rp.get_pair_wise_feature(src_node_ids=first, dst_node_ids=other))
     rp.update(src_node_ids=src, dst_node_ids=dst, node_interact_times=t)             # after both readouts (:372)
     return feats, outs
+
+
+def run_evaluation(rp, neighbor_sampler, negative_sampler, src: np.ndarray, dst: np.ndarray, t: np.ndarray, batch_size: int,
+                   num_neighbors: int, encoder=None, decoder=None, on_batch: Optional[Callable] = None):
+    """The reference's evaluation call sequence (evaluate_models_utils.py:56-72, 182-184): chronological batches, NO reset of the
+    projections; a 'historical' / 'inductive' negative sampler is given the batch's arrays and its first and last stamp and returns
+    the negative source as well, a 'random' one is asked for `size` destinations and the negative source is the batch's own.
+    `on_batch(index, neg_src, neg_dst, result)`."""
+    results = []
+    for b0 in range(0, len(src), batch_size):
+        s = slice(b0, min(b0 + batch_size, len(src)))
+        if negative_sampler.negative_sample_strategy != "random":
+            neg_src, neg_dst = negative_sampler.sample(size=s.stop - s.start, batch_src_node_ids=src[s], batch_dst_node_ids=dst[s],
+                                                       current_batch_start_time=t[s][0], current_batch_end_time=t[s][-1])
+        else:
+            _, neg_dst = negative_sampler.sample(size=s.stop - s.start)
+            neg_src = None                                         # the batch's own source (:72)
+        res = link_prediction_batch(rp, neighbor_sampler, src[s], dst[s], neg_dst, t[s], num_neighbors, encoder, decoder,
+                                    neg_src=neg_src)
+        if on_batch is not None:
+            on_batch(b0 // batch_size, src[s] if neg_src is None else neg_src, neg_dst, res)
+        results.append(res)
+    return results
 
 
 def run_epoch(rp, neighbor_sampler, negative_sampler, src: np.ndarray, dst: np.ndarray, t: np.ndarray,

@@ -4,6 +4,7 @@
 // (stable sort by (node, time), ties in the reference's append order) and one thread per (query, slot).  The two random strategies
 // ('uniform', 'time_interval_aware') draw from the same CSR with a counter-based generator: k_sampler_weights / k_sample_random.
 #include "tpnet_common.h"
+#include "draw_common.hpp"
 
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -11,12 +12,6 @@
 namespace tpnet {
 
 static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
-
-// order-preserving map of an IEEE double onto uint64
-__device__ __forceinline__ uint64_t time_key(double t) {
-    const uint64_t b = (uint64_t)__double_as_longlong(t);
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
 
 // entry 2e = (node src[e] -> neighbour dst[e]), entry 2e+1 = (node dst[e] -> neighbour src[e]): the reference's
 // append order (utils/utils.py:307-309)
@@ -105,22 +100,6 @@ __global__ void k_sample_recent(const int64_t* __restrict__ row_start, const int
 
 // ---- the reference's random strategies, 'uniform' and 'time_interval_aware' (utils/utils.py:123-224) ----
 
-// inclusive scan of one double per thread over a 256-thread workgroup; sh = 4 doubles of LDS; total = the workgroup's sum
-__device__ __forceinline__ double wg_scan256(double v, double* sh, double& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int off = 1; off < 64; off <<= 1) {
-        const double u = __shfl_up(v, off, 64);
-        if (lane >= off) v += u;
-    }
-    if (lane == 63) sh[wave] = v;
-    __syncthreads();
-    double base = 0.0;
-    for (int w = 0; w < wave; ++w) base += sh[w];
-    total = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return base + v;
-}
-
 // The weights table of 'time_interval_aware', once per sampler: one workgroup per node walks the node's time-sorted list in
 // chunks of 256 with two running carries.  E_j = exp(s (t_j - t_last)) and p_j = E_j / cumsum(E)_j in float64 over the WHOLE
 // list (compute_sampled_probabilities, utils/utils.py:123-139); the reference then takes softmax(float32(p[:n])) with NaN -> -1e10
@@ -146,22 +125,6 @@ __global__ __launch_bounds__(256) void k_sampler_weights(const int64_t* __restri
             carry_w += tot_w;
         }
     }
-}
-
-// Philox4x32-10 (Salmon et al., SC'11): counter-based, so a draw depends on (key, counter) alone, never on the launch geometry
-__device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                                int word) {
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
 }
 
 // One workgroup holds 256 / K whole rows (one row when K > 128); thread = (row, slot).  The row's first lane does the cut search
