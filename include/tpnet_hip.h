@@ -44,7 +44,8 @@ extern "C" {
                                7: + tpnet_stream_schedule (which schedule tpnet_run_stream would take); tpnet_xplan_targeted serves G = 1;
                                     tpnet_xplan_targeted_large (batches beyond one workgroup's lists); tpnet_wshard_* (a row shard on the windowed pipeline);
                                     the side-by-side plans of a multi-chunk stream are bounded (TPNET_ARENA_MAX_RATIO);
-                                    added since without a new number: tpnet_neg_* (the negative edge sampler's three strategies) */
+                                    added since without a new number: tpnet_neg_* (the negative edge sampler's three strategies);
+                                    tpnet_lp_metrics* (a batch's BCE loss, average precision and ROC-AUC as one device record) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -565,6 +566,39 @@ int tpnet_neg_sample(void* neg, int64_t E, int32_t strategy, int64_t size, const
                      int64_t B, double t0, double t1, uint64_t seed, uint32_t call_index, void* scratch, size_t scratch_bytes,
                      int64_t* out_src, int64_t* out_dst, void* stream);
 int tpnet_neg_check(void* neg, void* stream);
+
+/* ---- a batch's link-prediction metrics on the device (additive to ABI 7; csrc/metrics.hip) ------------------
+ * What the reference's evaluation loop brings to the host per batch (evaluate_models_utils.py:187-193, utils/metrics.py:8-22):
+ * BCEWithLogitsLoss(...).item() and sklearn's average_precision_score / roc_auc_score on predicts.sigmoid().cpu().
+ * p[0..P) = the fp32 scores of the positives, q[0..N) = those of the negatives.  Per positive i, three integers:
+ *   a_i = #{ j : p_j >= p_i } (i itself included),  b_i = #{ k : q_k >= p_i },  c_i = #{ k : q_k == p_i }
+ * and then, in float64:
+ *   AP  = (1 / P) sum_i a_i / (a_i + b_i)
+ *   U2  = sum_i (2 (N - b_i) + c_i)          (int64, exact)
+ *   AUC = U2 / (2 P N)
+ * -- sklearn's definitions with ties: tied scores share one threshold (at the threshold p_i, a_i of the a_i + b_i scores at or above it
+ * are positives; the recall step of a threshold, spread over the positives tied at it, is 1 / P each), and AUC counts a tied
+ * (positive, negative) pair as half.  Comparisons are IEEE: -0.0 ties with +0.0.
+ *   loss = (1 / (P + N)) sum over the P + N logits x with label y (1: positive, 0: negative) of max(x, 0) - x y + log1p(exp(-|x|)),
+ *          every term evaluated in float64 from the fp32 logit, the terms summed in float64.
+ * The a / b / c counts are combined across workgroups with integer atomics, the float64 sums run in a fixed order -- AP: entry k,
+ * k + 1024, ... per thread, then a halving tree over 1024 threads; loss: per chunk of the counting kernel (256 consecutive logits, positives
+ * before negatives) a halving tree over 256 threads, then the chunks' sums the same way over 1024 threads --: the same input gives the
+ * same bits every time.
+ * Degenerate batches are reported, not refused:  P == 0 or N == 0: AP = AUC = NaN, flag bit 0 (value 1), U2 = 0;  any NaN among the
+ * scores: AP = AUC = NaN, flag bit 1 (value 2) -- a NaN compares false both ways, U2 is what the counts then give;  P + N == 0: the
+ * loss is 0 / 0.
+ * record: ONE 64-byte device record, 8-byte aligned:
+ *   { double loss, double ap, double auc, int64 u2, int64 n_pos, int64 n_neg, int64 flags, int64 reserved (0) }
+ * pos_logit / neg_logit may be NULL: no loss is computed, record.loss = NaN (the pointer of an EMPTY side is not looked at).
+ * scratch: tpnet_lp_metrics_scratch_bytes(n_pos, n_neg) device bytes, 8-byte aligned (the 3 P counters, a NaN word, one partial loss
+ * per chunk; not needed when P + N is 0).
+ * Launches, all on `stream`: the counters' fill, the counting kernel on a (256 positives) x (256 scores) grid -- its first row
+ * of workgroups also sums the loss terms and looks for NaN --, one finish workgroup; no host copy, no synchronisation.  The counting is O(P (P + N)) and meant for a batch: P + N > 2^18, a negative size or a missing
+ * pointer: TPNET_ERR_BAD_ARG (the size helper: 0), nothing launched; a short scratch: TPNET_ERR_WORKSPACE. */
+size_t tpnet_lp_metrics_scratch_bytes(int64_t n_pos, int64_t n_neg);
+int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
+                     const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, void* stream);
 
 /* The encoder's readout with the ids resident on the device end to end (models/TPNet.py:280-324, SURVEY §8 f-3 -> f-2): for one
  * (src, other) batch of B edges -- other = dst or the negatives -- the 2B nodes [src; other] at times tile(t, 2) draw their K most

@@ -7,6 +7,7 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `RandomNegativeSampler`   -- NegativeEdgeSampler.random_sample (utils/utils.py:388-400): draw order matters.
 * `encoder_pair_indices`    -- the 4*B*K index pattern of the encoder's readout (models/TPNet.py:206-217,311-316).
 * `run_evaluation`          -- the evaluation loop's order with any of the three negative strategies (evaluate_models_utils.py:56-72).
+* `evaluate_link_prediction` -- the same loop scored on the device: per-batch loss, AP and ROC-AUC (evaluate_models_utils.py:186-198).
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
 The encoder itself is tpnet_amd/encoder.py (`TPNet`); `encoder` / `decoder` stay plug-in callables here.
@@ -194,6 +195,27 @@ def run_evaluation(rp, neighbor_sampler, negative_sampler, src: np.ndarray, dst:
             on_batch(b0 // batch_size, src[s] if neg_src is None else neg_src, neg_dst, res)
         results.append(res)
     return results
+
+
+def evaluate_link_prediction(rp, neighbor_sampler, negative_sampler, src: np.ndarray, dst: np.ndarray, t: np.ndarray, batch_size: int,
+                             num_neighbors: int, encoder: Callable, decoder: Callable, meter=None):
+    """`evaluate_model_link_prediction` (evaluate_models_utils.py:52-198) on `run_evaluation`: every batch's positive and negative
+    logits from `decoder` go to a `LinkPredictionMeter` (tpnet_amd/metrics.py) -- loss, average precision and ROC-AUC are computed on
+    the device and no batch synchronises for them; the log is read once at the end.  -> `meter.results()`: the reference's
+    `(evaluate_losses, evaluate_metrics)`, with the records' flags as `.flags`.  meter: None = a new one of one record per batch; a
+    given one is appended to, and everything it holds is returned."""
+    from .metrics import LinkPredictionMeter
+    if meter is None:
+        meter = LinkPredictionMeter(max(1, -(-len(src) // batch_size)), rp.random_projections[0].device)
+
+    def on_batch(index, neg_src, neg_dst, result):
+        pos_logits, neg_logits = result[1]
+        meter.add(pos_logits, neg_logits)
+
+    with torch.no_grad():                                          # (:52)
+        run_evaluation(rp, neighbor_sampler, negative_sampler, src, dst, t, batch_size, num_neighbors, encoder, decoder,
+                       on_batch=on_batch)
+    return meter.results()
 
 
 def run_epoch(rp, neighbor_sampler, negative_sampler, src: np.ndarray, dst: np.ndarray, t: np.ndarray,

@@ -1,0 +1,189 @@
+// Link-prediction metrics of one batch on the device: BCE loss, average precision and ROC-AUC (the reference's per-batch
+// `loss.item()`, `predicts.sigmoid().cpu()` and the two sklearn calls: evaluate_models_utils.py:187-193, utils/metrics.py:8-22).
+// No sort: every positive counts the scores at or above its own -- a_i among the positives, b_i among the negatives -- and the
+// negatives equal to it, c_i; AP = mean a_i / (a_i + b_i), AUC = sum(2 (N - b_i) + c_i) / (2 P N).  The rule is spelled out in
+// include/tpnet_hip.h.  Everything that crosses threads out of order is an integer, and the float64 sums are reduced in a fixed
+// order, so a call's record does not depend on scheduling.
+#include "tpnet_common.h"
+
+#include <math.h>
+
+namespace tpnet {
+
+static constexpr int LPM_TILE = 256;                 // positives per workgroup of the counting kernel, one per thread
+static constexpr int LPM_CHUNK = 256;                // scores of the (positives, negatives) axis a workgroup stages in LDS
+static constexpr int LPM_FIN = 1024;                 // threads of the finish kernel's one workgroup
+static constexpr int64_t LPM_MAX_SCORES = 1 << 18;   // P + N of a call
+
+// Sum over the workgroup in a fixed order: a halving tree over the threads' values (sh: NT entries).  Every thread gets the sum.
+template <int NT, class T>
+__device__ T lpm_tree_sum(T v, T* sh) {
+    __syncthreads();                                           // (the previous sum's readers are done with sh)
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+__device__ inline double lpm_bce_term(float logit, double y) {
+    const double x = (double)logit;
+    return fmax(x, 0.0) - x * y + log1p(exp(-fabs(x)));
+}
+
+// the scratch buffer: cnt [3][P] uint32 = a | b | c, then (256-byte aligned) the NaN word, then (256 further on) part double[chunks]
+struct LpmScratch {
+    uint32_t* cnt;
+    uint32_t* nan;
+    double* part;
+    size_t zero_bytes;   // cnt and the NaN word are zeroed by one fill before the counting kernel; part is written whole
+};
+static size_t lpm_zero_bytes(int64_t P) { return ((size_t)P * 12 + 255) / 256 * 256 + 256; }
+static LpmScratch lpm_carve(void* scratch, uint32_t P) {
+    const size_t z = lpm_zero_bytes(P);
+    return {(uint32_t*)scratch, (uint32_t*)((char*)scratch + z - 256), (double*)((char*)scratch + z), z};
+}
+
+// Workgroup (x, y): positives [256 x, 256 x + 256) against scores [256 y, 256 y + 256) of the concatenated axis (the P
+// positives, then the N negatives).  The chunk's positives and its negatives are staged as two runs, each padded with NaN -- which
+// compares false both ways -- to whole float4s: the loops read no labels and no bounds, and every lane reads the same 16 bytes (a
+// broadcast).  The workgroups x = 0 see every score once while staging: they raise the NaN word and sum their chunk's loss terms
+// (thread k: entries k, k + 256, ... of the staged order, then a tree) into part[y].
+__global__ __launch_bounds__(LPM_TILE) void k_lpm_count(const float* __restrict__ pos, uint32_t P, const float* __restrict__ neg,
+                                                        uint32_t N, const float* __restrict__ pos_logit,
+                                                        const float* __restrict__ neg_logit, int has_loss,
+                                                        uint32_t* __restrict__ cnt, uint32_t* __restrict__ nan_word,
+                                                        double* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float sh[LPM_CHUNK + 8];
+    __shared__ double shd[LPM_TILE];
+    const uint32_t i = blockIdx.x * LPM_TILE + threadIdx.x;
+    const uint32_t c0 = blockIdx.y * LPM_CHUNK;
+    const uint32_t c1 = min(c0 + (uint32_t)LPM_CHUNK, P + N);
+    const uint32_t np = c0 < P ? min(c1, P) - c0 : 0u;        // positives / negatives of the chunk
+    const uint32_t nn = (c1 - c0) - np;
+    const uint32_t np4 = (np + 3u) & ~3u, nn4 = (nn + 3u) & ~3u;   // np4 + nn4 <= LPM_CHUNK + 6
+    const uint32_t n0 = c0 + np - P;                          // first negative of the chunk (nn > 0: c0 + np >= P)
+    const bool first = blockIdx.x == 0;
+    double loss = 0.0;
+    bool bad = false;
+    for (uint32_t k = threadIdx.x; k < np4 + nn4; k += LPM_TILE) {
+        float v = NAN;
+        if (k < np) {
+            v = pos[c0 + k];
+            bad |= isnan(v);
+            if (first && has_loss) loss += lpm_bce_term(pos_logit[c0 + k], 1.0);
+        } else if (k >= np4 && k - np4 < nn) {
+            v = neg[n0 + (k - np4)];
+            bad |= isnan(v);
+            if (first && has_loss) loss += lpm_bce_term(neg_logit[n0 + (k - np4)], 0.0);
+        }
+        sh[k] = v;
+    }
+    if (first) {                                              // (uniform over the workgroup: the tree's barriers are met by all)
+        if (bad) atomicOr(nan_word, 1u);
+        if (has_loss) {
+            loss = lpm_tree_sum<LPM_TILE>(loss, shd);
+            if (threadIdx.x == 0) part[blockIdx.y] = loss;
+        }
+    }
+    __syncthreads();
+    if (i >= P) return;
+    const float p = pos[i];
+    const float4* s4 = reinterpret_cast<const float4*>(sh);
+    uint32_t a = 0, b = 0, c = 0;
+#pragma unroll 4
+    for (uint32_t k = 0; k < np4 / 4u; ++k) {
+        const float4 v = s4[k];
+        a += (uint32_t)(v.x >= p) + (uint32_t)(v.y >= p) + (uint32_t)(v.z >= p) + (uint32_t)(v.w >= p);
+    }
+#pragma unroll 4
+    for (uint32_t k = np4 / 4u; k < (np4 + nn4) / 4u; ++k) {
+        const float4 v = s4[k];
+        b += (uint32_t)(v.x >= p) + (uint32_t)(v.y >= p) + (uint32_t)(v.z >= p) + (uint32_t)(v.w >= p);
+        c += (uint32_t)(v.x == p) + (uint32_t)(v.y == p) + (uint32_t)(v.z == p) + (uint32_t)(v.w == p);
+    }
+    if (a) atomicAdd(&cnt[i], a);
+    if (b) atomicAdd(&cnt[P + i], b);
+    if (c) atomicAdd(&cnt[2u * P + i], c);
+}
+
+// ONE workgroup: thread k takes entries k, k + 1024, ... of every list in ascending order, the 1024 partial sums meet in the tree.
+// n_part: the counting kernel's chunks (0: no loss).
+__global__ __launch_bounds__(LPM_FIN) void k_lpm_finish(uint32_t P, uint32_t N, const uint32_t* __restrict__ cnt,
+                                                        const uint32_t* __restrict__ nan_word, const double* __restrict__ part,
+                                                        uint32_t n_part, int has_loss, void* __restrict__ record) {
+    __shared__ double shd[LPM_FIN];
+    __shared__ long long shi[LPM_FIN];
+    double ap = 0.0, loss = 0.0;
+    long long u2 = 0;
+    for (uint32_t i = threadIdx.x; i < P; i += LPM_FIN) {
+        const uint32_t a = cnt[i], b = cnt[P + i], c = cnt[2u * P + i];
+        ap += (double)a / (double)(a + b);                     // (a NaN positive: 0 / 0, and the flag below)
+        u2 += 2ll * (long long)(N - b) + (long long)c;
+    }
+    if (has_loss)
+        for (uint32_t j = threadIdx.x; j < n_part; j += LPM_FIN) loss += part[j];
+    ap = lpm_tree_sum<LPM_FIN>(ap, shd);
+    loss = lpm_tree_sum<LPM_FIN>(loss, shd);
+    u2 = lpm_tree_sum<LPM_FIN>(u2, shi);
+    if (threadIdx.x == 0) {
+        const long long flags = ((P == 0 || N == 0) ? 1ll : 0ll) | ((P + N > 0 && *nan_word) ? 2ll : 0ll);
+        const double nan = __builtin_nan("");
+        double* rd = reinterpret_cast<double*>(record);
+        long long* ri = reinterpret_cast<long long*>(record);
+        rd[0] = has_loss ? loss / (double)((long long)P + (long long)N) : nan;
+        rd[1] = flags ? nan : ap / (double)P;
+        rd[2] = flags ? nan : (double)u2 / (double)(2ll * (long long)P * (long long)N);
+        ri[3] = u2;
+        ri[4] = (long long)P;
+        ri[5] = (long long)N;
+        ri[6] = flags;
+        ri[7] = 0;
+    }
+}
+
+static bool lpm_sizes_ok(int64_t n_pos, int64_t n_neg) {
+    return n_pos >= 0 && n_neg >= 0 && n_pos <= LPM_MAX_SCORES && n_neg <= LPM_MAX_SCORES && n_pos + n_neg <= LPM_MAX_SCORES;
+}
+
+}  // namespace tpnet
+
+using namespace tpnet;
+
+extern "C" {
+
+size_t tpnet_lp_metrics_scratch_bytes(int64_t n_pos, int64_t n_neg) {
+    if (!lpm_sizes_ok(n_pos, n_neg)) return 0;
+    const size_t chunks = (size_t)(n_pos + n_neg + LPM_CHUNK - 1) / LPM_CHUNK;
+    return lpm_zero_bytes(n_pos) + (chunks * 8 + 255) / 256 * 256;
+}
+
+int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
+                     const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, void* stream) {
+    if (!lpm_sizes_ok(n_pos, n_neg) || !record || ((size_t)record & 7) || (n_pos > 0 && !pos_score) || (n_neg > 0 && !neg_score))
+        return TPNET_ERR_BAD_ARG;
+    const bool any = n_pos + n_neg > 0;
+    if (any && (!scratch || ((size_t)scratch & 7))) return TPNET_ERR_BAD_ARG;
+    if (any && scratch_bytes < tpnet_lp_metrics_scratch_bytes(n_pos, n_neg)) return TPNET_ERR_WORKSPACE;
+    // the loss needs the logits of every side that is not empty
+    const bool has_loss = (pos_logit || neg_logit) && (n_pos == 0 || pos_logit) && (n_neg == 0 || neg_logit);
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t P = (uint32_t)n_pos, N = (uint32_t)n_neg;
+    const LpmScratch w = any ? lpm_carve(scratch, P) : LpmScratch{nullptr, nullptr, nullptr, 0};
+    uint32_t chunks = 0;
+    if (any) {
+        const uint32_t gx = P ? (P + LPM_TILE - 1) / LPM_TILE : 1u;          // (no positives: one row of workgroups for the loss)
+        chunks = (P + N + LPM_CHUNK - 1) / LPM_CHUNK;
+        TPNET_HIP_TRY(hipMemsetAsync(scratch, 0, w.zero_bytes, s));
+        hipLaunchKernelGGL(k_lpm_count, dim3(gx, chunks), dim3(LPM_TILE), 0, s, pos_score, P, neg_score, N, pos_logit, neg_logit,
+                           (int)has_loss, w.cnt, w.nan, w.part);
+    }
+    hipLaunchKernelGGL(k_lpm_finish, dim3(1), dim3(LPM_FIN), 0, s, P, N, (const uint32_t*)w.cnt, (const uint32_t*)w.nan,
+                       (const double*)w.part, chunks, (int)has_loss, record);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,179 @@
+"""Link-prediction metrics of a batch: BCE loss, average precision and ROC-AUC (C ABI: tpnet_lp_metrics, csrc/metrics.hip).
+
+The reference scores every evaluation batch on the host (evaluate_models_utils.py:186-193, utils/metrics.py:8-22): `loss.item()`,
+`predicts.sigmoid().cpu()` and sklearn's `average_precision_score` / `roc_auc_score` -- two synchronisations and two CPU sorts per
+batch.  Here a batch's three numbers are one 64-byte record that a kernel appends to a device-resident log; nothing synchronises
+until the log is read, once, when the split is over (`LinkPredictionMeter`).
+
+The rule (include/tpnet_hip.h spells it out): with the scores p[0..P) of the positives and q[0..N) of the negatives, per positive i
+  a_i = #{j : p_j >= p_i},  b_i = #{k : q_k >= p_i},  c_i = #{k : q_k == p_i}
+  AP = (1 / P) sum_i a_i / (a_i + b_i),   U2 = sum_i (2 (N - b_i) + c_i),   AUC = U2 / (2 P N)
+which is sklearn's definition with ties; the loss is the mean of max(x, 0) - x y + log1p(exp(-|x|)) over the P + N logits, in float64."""
+import ctypes as C
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_SCORES = 1 << 18          # P + N of one device call
+FLAG_ONE_CLASS = 1            # P == 0 or N == 0: AP = AUC = NaN
+FLAG_NAN_SCORE = 2            # a NaN among the scores: AP = AUC = NaN
+_RECORD_WORDS = 8             # {f64 loss, f64 ap, f64 auc, i64 u2, i64 n_pos, i64 n_neg, i64 flags, i64 reserved}
+
+
+def _has_loss(P, N, pos_logit, neg_logit):
+    """The loss needs the logits of every side that is not empty (tpnet_lp_metrics: the pointer of an empty side is not looked at)."""
+    return (pos_logit is not None or neg_logit is not None) and (P == 0 or pos_logit is not None) and (N == 0 or neg_logit is not None)
+
+
+def link_prediction_metrics_host(pos, neg, pos_logit=None, neg_logit=None):
+    """The rule in numpy: -> {'loss', 'ap', 'auc', 'u2', 'n_pos', 'n_neg', 'flags'}, the fields of the device record.  pos / neg: the
+    scores (taken as fp32); pos_logit / neg_logit (optional, fp32): without them the loss is NaN.  The counts come from binary
+    searches in the sorted scores, which is the same three integers per positive; a NaN score compares false and is counted nowhere.
+    This is the CPU path of `get_link_prediction_metrics` and what the device record is held to."""
+    p = np.asarray(pos, dtype=np.float32).reshape(-1)
+    q = np.asarray(neg, dtype=np.float32).reshape(-1)
+    P, N = len(p), len(q)
+    nan_p, nan_q = np.isnan(p), np.isnan(q)
+    ps, qs = np.sort(p[~nan_p]), np.sort(q[~nan_q])
+    lo = np.searchsorted(qs, p, side="left")
+    a = np.where(nan_p, 0, len(ps) - np.searchsorted(ps, p, side="left")).astype(np.int64)
+    b = np.where(nan_p, 0, len(qs) - lo).astype(np.int64)
+    c = np.where(nan_p, 0, np.searchsorted(qs, p, side="right") - lo).astype(np.int64)
+    u2 = int(np.sum(2 * (N - b) + c))
+    flags = (FLAG_ONE_CLASS if P == 0 or N == 0 else 0) | (FLAG_NAN_SCORE if nan_p.any() or nan_q.any() else 0)
+    if flags:
+        ap = auc = float("nan")
+    else:
+        ap = float(np.sum(a.astype(np.float64) / (a + b).astype(np.float64)) / P)
+        auc = u2 / (2 * P * N)
+    loss = float("nan")
+    if _has_loss(P, N, pos_logit, neg_logit) and P + N > 0:
+        xs = [np.asarray(v, dtype=np.float32).reshape(-1).astype(np.float64) for v in (pos_logit, neg_logit) if v is not None]
+        x = np.concatenate(xs)
+        assert len(x) == P + N, "one logit per score"
+        y = np.concatenate([np.ones(P), np.zeros(N)])
+        loss = float(np.sum(np.maximum(x, 0.0) - x * y + np.log1p(np.exp(-np.abs(x)))) / (P + N))
+    return {"loss": loss, "ap": ap, "auc": auc, "u2": u2, "n_pos": P, "n_neg": N, "flags": flags}
+
+
+def _flat_f32(x, device, what):
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != device:
+        raise TypeError(f"{what}: an fp32 tensor on {device} is expected")
+    return x.detach().reshape(-1).contiguous()
+
+
+def _enqueue(pos, neg, pos_logit, neg_logit, scratch, record_ptr, device):
+    """tpnet_lp_metrics on the current stream of `device`: flat fp32 device tensors -> the record at record_ptr."""
+    ptr = lambda v: v.data_ptr() if v is not None and v.numel() else None
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _lib.check(_lib.load().tpnet_lp_metrics(ptr(pos), pos.numel(), ptr(neg), neg.numel(), ptr(pos_logit), ptr(neg_logit),
+                                            ptr(scratch), scratch.numel() if scratch is not None else 0, record_ptr, stream),
+               "lp_metrics")
+
+
+def _scratch_for(P, N, old, device):
+    need = _lib.load().tpnet_lp_metrics_scratch_bytes(P, N)
+    if need == 0:
+        raise _lib.TPNetHipError(f"tpnet_hip lp_metrics: {P} + {N} scores are more than one call counts ({MAX_SCORES})")
+    if old is None or old.numel() < need:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    return old
+
+
+def get_link_prediction_metrics(predicts, labels):
+    """The reference's `get_link_prediction_metrics` (utils/metrics.py:8-22): predicts = the scores, labels = 1 for a positive, anything
+    else for a negative -> {'average_precision': float, 'roc_auc': float}.  CUDA tensors are split by `labels` with torch and counted by
+    the kernel; this call SYNCHRONISES, because it returns Python floats (`LinkPredictionMeter` is the path that does not).  CPU
+    tensors and arrays take `link_prediction_metrics_host`.  A batch of one class, or one with a NaN score, gives NaN for both where
+    sklearn raises."""
+    if isinstance(predicts, torch.Tensor) and predicts.is_cuda:
+        device = predicts.device
+        s = predicts.detach().reshape(-1).to(torch.float32)
+        m = torch.as_tensor(labels, device=device).reshape(-1) == 1
+        pos, neg = s[m].contiguous(), s[~m].contiguous()
+        record = torch.zeros(_RECORD_WORDS, dtype=torch.int64, device=device)
+        scratch = _scratch_for(pos.numel(), neg.numel(), None, device)
+        _enqueue(pos, neg, None, None, scratch, record.data_ptr(), device)
+        r = record.cpu().numpy().view(np.float64)
+        return {"average_precision": float(r[1]), "roc_auc": float(r[2])}
+    to_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    s, m = to_np(predicts).reshape(-1), to_np(labels).reshape(-1) == 1
+    r = link_prediction_metrics_host(s[m], s[~m])
+    return {"average_precision": r["ap"], "roc_auc": r["auc"]}
+
+
+class LinkPredictionResults(tuple):
+    """`(losses, metrics)`, the return value of the reference's `evaluate_model_link_prediction` (evaluate_models_utils.py:198): a list
+    of floats and a list of {'average_precision', 'roc_auc'} dicts, one entry per batch.  `.flags` holds the records' flag words
+    (FLAG_ONE_CLASS, FLAG_NAN_SCORE) in the same order."""
+
+    def __new__(cls, losses, metrics, flags):
+        self = super().__new__(cls, (losses, metrics))
+        self.flags = flags
+        return self
+
+
+class LinkPredictionMeter:
+    """A device-resident log of up to `capacity` batches' loss, average precision and ROC-AUC.
+
+    `add` enqueues torch's sigmoid and the three launches of tpnet_lp_metrics on the current stream and returns; it copies nothing to
+    the host and never synchronises.  `results` reads the log with ONE copy.  The scratch buffer is the meter's own: calls belong on
+    one stream."""
+
+    def __init__(self, capacity: int, device="cuda:0"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.TPNetHipError("LinkPredictionMeter needs a cuda device (link_prediction_metrics_host is the CPU path)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        _lib.load()
+        self.capacity = int(capacity)
+        assert self.capacity > 0
+        self._log = torch.zeros((self.capacity, _RECORD_WORDS), dtype=torch.int64, device=self.device)
+        self._n = 0
+        self._scratch = None
+        self._warned = False
+
+    def __len__(self):
+        return self._n
+
+    def add(self, pos_logits: torch.Tensor, neg_logits: torch.Tensor) -> int:
+        """The decoder's logits of a batch's positive and negative pairs (fp32 tensors on the meter's device, any shape: flattened) ->
+        the index of the record written.  The scores that are ranked are torch's own `sigmoid` of the logits, as in the reference
+        (`predicts.sigmoid()`): where the fp32 sigmoid saturates it creates ties that the logits do not have."""
+        if self._n >= self.capacity:
+            raise IndexError(f"LinkPredictionMeter: the log of {self.capacity} records is full (results(), then reset())")
+        pl = _flat_f32(pos_logits, self.device, "pos_logits")
+        nl = _flat_f32(neg_logits, self.device, "neg_logits")
+        self._scratch = _scratch_for(pl.numel(), nl.numel(), self._scratch, self.device)
+        ps, ns = torch.sigmoid(pl), torch.sigmoid(nl)
+        k = self._n
+        _enqueue(ps, ns, pl, nl, self._scratch, self._log.data_ptr() + k * _RECORD_WORDS * 8, self.device)
+        self._n = k + 1
+        return k
+
+    def records(self) -> np.ndarray:
+        """The log's records so far as an int64 array [n][8] on the host (one copy; synchronises); words 0..2 are float64 bits."""
+        return self._log[:self._n].cpu().numpy()
+
+    def results(self) -> LinkPredictionResults:
+        """One device-to-host copy (synchronises) -> `(losses, metrics)` with `.flags`.  Warns, once per meter, if any record is
+        flagged: its AP and AUC are NaN."""
+        rec = self.records()
+        f = rec.view(np.float64)
+        losses = [float(v) for v in f[:, 0]]
+        metrics = [{"average_precision": float(r[1]), "roc_auc": float(r[2])} for r in f]
+        flags = [int(v) for v in rec[:, 6]]
+        if any(flags) and not self._warned:
+            self._warned = True
+            bad = [k for k, v in enumerate(flags) if v]
+            warnings.warn(f"LinkPredictionMeter: {len(bad)} of {len(flags)} batches have no AP / AUC (first: batch {bad[0]}, flags "
+                          f"{flags[bad[0]]}: 1 = only one class, 2 = a NaN score)", RuntimeWarning, stacklevel=2)
+        return LinkPredictionResults(losses, metrics, flags)
+
+    def reset(self):
+        """Empties the log: the next `add` writes record 0.  (Records are overwritten, the buffer is kept.)"""
+        self._n = 0
