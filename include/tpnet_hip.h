@@ -45,7 +45,8 @@ extern "C" {
                                     tpnet_xplan_targeted_large (batches beyond one workgroup's lists); tpnet_wshard_* (a row shard on the windowed pipeline);
                                     the side-by-side plans of a multi-chunk stream are bounded (TPNET_ARENA_MAX_RATIO);
                                     added since without a new number: tpnet_neg_* (the negative edge sampler's three strategies);
-                                    tpnet_lp_metrics* (a batch's BCE loss, average precision and ROC-AUC as one device record) */
+                                    tpnet_lp_metrics* (a batch's BCE loss, average precision and ROC-AUC as one device record);
+                                    tpnet_edgebank_* (the EdgeBank baseline's three memory modes on a prefix of one static stream) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -599,6 +600,59 @@ int tpnet_neg_check(void* neg, void* stream);
 size_t tpnet_lp_metrics_scratch_bytes(int64_t n_pos, int64_t n_neg);
 int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
                      const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, void* stream);
+
+/* ---- the EdgeBank baseline on the device (additive to ABI 7; csrc/edgebank.hip) ------------------------------
+ * models/EdgeBank.py as evaluate_models_utils.py:269-318 drives it: for every test batch the reference builds a memory over
+ * train + val + test[:batch_start] and answers "is (u, v) in it" for the batch's positive and negative pairs.
+ * One table holds the whole chronological stream, E edges (src[p], dst[p], t[p]), p = 0..E-1, t non-decreasing in p.  A call names a
+ * history length h, 1 <= h <= E; the memory is what the reference builds from the first h edges -- the POSITION prefix, not a time cut: an
+ * edge at a position >= h is no history even when its stamp equals t[h - 1].
+ * For a query pair (u, v): p_0 < p_1 < ... the positions of its occurrences, c = #{ p_i < h }.  c == 0: the prediction is 0.  Else
+ *   TPNET_EB_UNLIMITED:         1.
+ *   TPNET_EB_TIME_WINDOW:       1 iff t[p_(c-1)] >= window_start  (the latest occurrence inside the prefix decides, because t is
+ *                               non-decreasing; window_end = t[h - 1] never binds).
+ *   TPNET_EB_REPEAT_THRESHOLD:  1 iff (double)c >= (double)h / (double)n_present(h), n_present(h) = the distinct edges among the first h
+ *                               (np.mean of the reference's frequency dict).
+ * window_start:
+ *   TPNET_EB_FIXED_PROPORTION:  np.quantile(t[:h], 1 - proportion), method 'linear', in O(1) on the sorted prefix: q = 1 - proportion,
+ *                               v = (h - 1) q, i = floor(v), g = v - i, a = t[i], b = t[min(i + 1, h - 1)];
+ *                               g >= 0.5 ? b - (b - a) (1 - g) : a + (b - a) g  -- NumPy's _lerp, every operation rounded on its own
+ *                               (no fused multiply-add), so the result equals NumPy's bit for bit.
+ *   TPNET_EB_REPEAT_INTERVAL:   t[h - 1] - S / n_present(h), S = the sum over the distinct edges with c > 1 of their mean
+ *                               inter-occurrence interval, which telescopes to (t[p_(c-1)] - t[p_0]) / (c - 1); the singletons count in
+ *                               the denominator, as in the reference.  S is a float64 sum in a fixed order: thread k of workgroup w
+ *                               of G = min(256, ceil(E / 256)) takes the unique edges (ascending src << 32 | dst order) 256 w + k,
+ *                               + 256 G, ...; a halving tree over each wave's lanes, the four waves in order; then the G partials in
+ *                               index order.  The same call gives the same bits; against the reference's dict-order sum the last
+ *                               bits may differ.
+ * Query ids outside [0, 2^31), negative ones included, and pairs that are not in the table predict 0.
+ *
+ * tpnet_edgebank_build, once per stream: checks ids and stamps on the device, sorts (src << 32 | dst, position) with one stable radix
+ *   sort and writes, into the caller-owned device buffer `eb` of tpnet_edgebank_bytes(E): the U unique keys, the start of each one's
+ *   ascending position list (U + 1 entries), the positions, a copy of t, and present[0..E], present[h] = n_present(h).  src / dst / t:
+ *   device arrays of E; 1 <= E < 2^30.  An id outside [0, 2^31): TPNET_ERR_INDEX; a stamp below its predecessor's, or a NaN:
+ *   TPNET_ERR_BAD_ARG (streams are refused, not sorted).  counts: HOST int64[1] = {U}; the call synchronises `stream` once.
+ * tpnet_edgebank_predict: h by value, nothing read back, no synchronisation, at most two launches on `stream`: the partial sums of S
+ *   (TIME_WINDOW with REPEAT_INTERVAL only), then one thread per query of BOTH lists -- list 0 (Q0 pairs -> out0) and list 1 (Q1 pairs
+ *   -> out1, may be empty) -- so a batch's positives and negatives share one reduction.  out0 / out1: device fp32, 0.0 or 1.0.
+ *   window_mode and proportion are checked always and used by TIME_WINDOW only.  scratch: tpnet_edgebank_scratch_bytes(E) device bytes,
+ *   needed by REPEAT_INTERVAL only.  out_window: device double[2] or NULL: {window_start, window_end = t[h - 1]} (TIME_WINDOW),
+ *   {threshold, n_present(h)} (REPEAT_THRESHOLD), {-inf, t[h - 1]} (UNLIMITED).
+ * TPNET_ERR_BAD_ARG, nothing launched: a null table, a null array or output of a list that is not empty, h < 1 or h > E, proportion
+ *   outside [0, 1], an unknown mode, Q < 0 (or >= 2^31), E outside [1, 2^30) (size helpers: 0), REPEAT_INTERVAL without scratch.  A short
+ *   scratch: TPNET_ERR_WORKSPACE.  Q0 + Q1 == 0: TPNET_OK, nothing launched. */
+#define TPNET_EB_UNLIMITED 0
+#define TPNET_EB_TIME_WINDOW 1
+#define TPNET_EB_REPEAT_THRESHOLD 2
+#define TPNET_EB_FIXED_PROPORTION 0
+#define TPNET_EB_REPEAT_INTERVAL 1
+size_t tpnet_edgebank_bytes(int64_t E);
+int tpnet_edgebank_build(void* eb, size_t bytes, const int64_t* src, const int64_t* dst, const double* t, int64_t E, int64_t* counts,
+                         void* stream);
+size_t tpnet_edgebank_scratch_bytes(int64_t E);
+int tpnet_edgebank_predict(const void* eb, int64_t E, int32_t memory_mode, int32_t window_mode, double proportion, int64_t h,
+                           const int64_t* src0, const int64_t* dst0, int64_t Q0, float* out0, const int64_t* src1, const int64_t* dst1,
+                           int64_t Q1, float* out1, void* scratch, size_t scratch_bytes, double* out_window, void* stream);
 
 /* The encoder's readout with the ids resident on the device end to end (models/TPNet.py:280-324, SURVEY §8 f-3 -> f-2): for one
  * (src, other) batch of B edges -- other = dst or the negatives -- the 2B nodes [src; other] at times tile(t, 2) draw their K most

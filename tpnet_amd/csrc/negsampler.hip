@@ -6,6 +6,7 @@
 // so the |Us| x |Ud| domain of the fill is never materialised.  The draw rule is spelled out in include/tpnet_hip.h.
 #include "tpnet_common.h"
 #include "draw_common.hpp"
+#include "scan_common.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -20,56 +21,6 @@ static constexpr uint64_t NEG_EMPTY = ~0ull;         // no pair of ids < 2^31 ha
 
 // header words of the sampler buffer
 enum { NEG_U = 0, NEG_NUS = 1, NEG_NUD = 2, NEG_ERR = 3, NEG_BAD = 4 };
-
-// ---- scan + compaction: flags of one element per thread, tiles of 256, a second level over the tile sums --------------------------
-// n = *n_dev when given (a count that lives on the device), else n_host.  k_scan_count: blk[tile] = flags set in the tile;
-// k_scan_blocks (ONE workgroup, chunks of 256 tile sums with a running carry): blk -> exclusive, *total = the sum;
-// k_scan_emit: position of a set flag = blk[tile] + its exclusive rank inside the tile.
-template <class Flag>
-__global__ __launch_bounds__(256) void k_scan_count(Flag f, const uint32_t* n_dev, uint32_t n_host, uint32_t* __restrict__ blk) {
-    __shared__ uint32_t sh[4];
-    const uint32_t n = n_dev ? *n_dev : n_host;
-    const uint32_t nb = (n + 255u) / 256u;
-    for (uint32_t tile = blockIdx.x; tile < nb; tile += gridDim.x) {
-        const uint32_t j = tile * 256u + threadIdx.x;
-        const uint32_t v = j < n ? f(j) : 0u;
-        uint32_t tot;
-        wg_scan256(v, sh, tot);
-        if (threadIdx.x == 0) blk[tile] = tot;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_scan_blocks(uint32_t* __restrict__ blk, const uint32_t* n_dev, uint32_t n_host,
-                                                     uint32_t* __restrict__ total) {
-    __shared__ uint32_t sh[4];
-    const uint32_t n = n_dev ? *n_dev : n_host;
-    const uint32_t nb = (n + 255u) / 256u;
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += 256u) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < nb ? blk[i] : 0u;
-        uint32_t tot;
-        const uint32_t incl = wg_scan256(v, sh, tot);
-        if (i < nb) blk[i] = carry + incl - v;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-template <class Flag, class Emit>
-__global__ __launch_bounds__(256) void k_scan_emit(Flag f, Emit e, const uint32_t* n_dev, uint32_t n_host,
-                                                   const uint32_t* __restrict__ blk) {
-    __shared__ uint32_t sh[4];
-    const uint32_t n = n_dev ? *n_dev : n_host;
-    const uint32_t nb = (n + 255u) / 256u;
-    for (uint32_t tile = blockIdx.x; tile < nb; tile += gridDim.x) {
-        const uint32_t j = tile * 256u + threadIdx.x;
-        const uint32_t v = j < n ? f(j) : 0u;
-        uint32_t tot;
-        const uint32_t incl = wg_scan256(v, sh, tot);
-        if (v) e(j, blk[tile] + incl - v);
-    }
-}
 
 // ---- build ---------------------------------------------------------------------------------------------------------------------
 __global__ void k_neg_keys(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, const double* __restrict__ t, int64_t E,

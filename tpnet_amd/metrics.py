@@ -155,6 +155,25 @@ class LinkPredictionMeter:
         self._n = k + 1
         return k
 
+    def add_probabilities(self, pos_prob: torch.Tensor, neg_prob: torch.Tensor) -> int:
+        """Probabilities of a batch's positive and negative pairs (fp32 tensors on the meter's device, any shape: flattened), as a
+        model that has no logits gives them -- EdgeBank's 0 / 1 -> the index of the record written.  They are ranked as they are (no
+        sigmoid).  The loss word is the reference's `nn.BCELoss` (evaluate_models_utils.py:257, 314): the mean over the P + N
+        probabilities p with label y of -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)), formed in float64 from the fp32
+        probabilities by torch on the same stream and copied into the record on the device; nothing synchronises."""
+        if self._n >= self.capacity:
+            raise IndexError(f"LinkPredictionMeter: the log of {self.capacity} records is full (results(), then reset())")
+        pp = _flat_f32(pos_prob, self.device, "pos_prob")
+        nq = _flat_f32(neg_prob, self.device, "neg_prob")
+        self._scratch = _scratch_for(pp.numel(), nq.numel(), self._scratch, self.device)
+        k = self._n
+        _enqueue(pp, nq, None, None, self._scratch, self._log.data_ptr() + k * _RECORD_WORDS * 8, self.device)   # loss word: NaN
+        terms = torch.cat([torch.log(pp.double()), torch.log(1.0 - nq.double())]).clamp_min(-100.0)
+        loss = -terms.sum() / terms.numel()
+        self._log[k, 0:1].copy_(loss.reshape(1).view(torch.int64))       # after the record's kernel, on its stream
+        self._n = k + 1
+        return k
+
     def records(self) -> np.ndarray:
         """The log's records so far as an int64 array [n][8] on the host (one copy; synchronises); words 0..2 are float64 bits."""
         return self._log[:self._n].cpu().numpy()
