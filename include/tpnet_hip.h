@@ -46,7 +46,8 @@ extern "C" {
                                     the side-by-side plans of a multi-chunk stream are bounded (TPNET_ARENA_MAX_RATIO);
                                     added since without a new number: tpnet_neg_* (the negative edge sampler's three strategies);
                                     tpnet_lp_metrics* (a batch's BCE loss, average precision and ROC-AUC as one device record);
-                                    tpnet_edgebank_* (the EdgeBank baseline's three memory modes on a prefix of one static stream) */
+                                    tpnet_edgebank_* (the EdgeBank baseline's three memory modes on a prefix of one static stream);
+                                    tpnet_mlp_rows_* (self.mlp on the matrix cores for num_layer 1 and 2) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -196,6 +197,19 @@ int tpnet_pair_feature(const tpnet_state* st, const int64_t* u, const int64_t* v
 /* self.mlp alone on the fp32 matrix cores (L = 3: 64 -> 256 -> 64; mlp->w1 / w2f required): y[n][64] = mlp(x[n][64]), for
  * features that a separate readout produced (the anchored / shared-first-node kernels of the encoder's call). */
 int tpnet_mlp64_f32(const float* x, int64_t n, const tpnet_mlp* mlp, float* y, void* stream);
+
+/* Which (F, H) tpnet_mlp_rows_f32 serves: 1 for (16, 64) and (36, 144) -- num_layer 1 and 2 -- else 0.  (64, 256) is
+ * tpnet_mlp64_f32's; (100, 400), num_layer 4, is not served: its split weights (320 KB) do not fit a CU's LDS.  Pure host arithmetic. */
+int tpnet_mlp_rows_supported(int32_t F, int32_t H);
+/* self.mlp alone for num_layer 1 and 2 in the fp32 class on the matrix cores: y[n][F] = mlp(x[n][F]) in ONE launch on the caller's
+ * stream, no synchronisation (csrc/mlp_rows.hip: two-piece bf16 operands, three products per term, fp32 accumulators; <= 2e-5 of
+ * the output scale against the torch layers, exact on small integers).  Weights from mlp->w1t, b1, w2t, b2 (mlp->w1 / w2f / wimg
+ * are not read and stay NULL for these widths).  x and y: device, 16-byte aligned, x read only inside its n * F floats, y written
+ * only inside its n * F floats.  n == 0: TPNET_OK.  TPNET_ERR_BAD_ARG, before any HIP call: a null pointer, an (F, H) that
+ * tpnet_mlp_rows_supported refuses, a misaligned x or y; also when the runtime refuses the kernel's LDS (71 KB at F = 36) or
+ * the launch -- the caller then runs the layers its other way.  A row of x that holds a NaN gives unspecified values in THAT row
+ * of y (a NaN hidden unit passes the ReLU as 0); every other row is unaffected. */
+int tpnet_mlp_rows_f32(const float* x, int64_t n, const tpnet_mlp* mlp, float* y, void* stream);
 
 /* The derived layouts of a tpnet_mlp from the Parameters of self.mlp = Linear(F, H) -> ReLU -> Linear(H, F) (models/TPNet.py:63-65)
  * in ONE launch: w1 = mlp[0].weight [H][F], w2 = mlp[2].weight [F][H] (device, contiguous) -> w1t [F][H], w2t [H][F] and, for

@@ -99,16 +99,20 @@ def weight_grads_f32(x, gy, w1, b1, w2, prep, mode=None):
 
 
 class _MlpF32(torch.autograd.Function):
-    """self.mlp alone on the fp32 matrix cores (tpnet_mlp64_f32); backward = weight_grads_f32."""
+    """self.mlp alone on the fp32 matrix cores (tpnet_mlp64_f32 at 64 columns, tpnet_mlp_rows_f32 at 16 and 36); backward =
+    weight_grads_f32 (which has a matrix-core kernel for 64 columns only: the torch expressions serve 16 and 36)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, mlp_ref, prep=None, mode=None):
         x = x.contiguous()
         y = torch.empty_like(x)
         if x.shape[0]:
-            rc = _lib.load().tpnet_mlp64_f32(x.data_ptr(), x.shape[0], mlp_ref, y.data_ptr(), _dense.stream_ptr(x.device))
-            if rc:
-                _lib.check(rc, "mlp64_f32")
+            if x.shape[1] == 64:
+                rc = _lib.load().tpnet_mlp64_f32(x.data_ptr(), x.shape[0], mlp_ref, y.data_ptr(), _dense.stream_ptr(x.device))
+                if rc:
+                    _lib.check(rc, "mlp64_f32")
+            elif _lib.load().tpnet_mlp_rows_f32(x.data_ptr(), x.shape[0], mlp_ref, y.data_ptr(), _dense.stream_ptr(x.device)):
+                raise _RowsDeclined()                          # (nothing was launched: mlp_f32 hands the call back to torch)
         ctx.save_for_backward(x, w1, b1, w2)
         ctx.prep = prep
         ctx.mode = mode
@@ -124,16 +128,42 @@ class _MlpF32(torch.autograd.Function):
         return None, gw1, gb1, gw2, gb2, None, None, None
 
 
+# rows from which tpnet_mlp_rows_f32 (csrc/mlp_rows.hip: num_layer 1 and 2) takes self.mlp from the torch layers, per width; None =
+# reachable through the C call, never routed.  The rule (tools/mlp_rows_rate.py): the smallest measured n from which the kernel's
+# median is below torch's by more than the larger of the two spreads.  Measured (profiles/mlp_rows.md): at 1 000 rows, the smallest
+# size of the protocol, one launch takes 10.7 / 11.7 us against 47.6 / 49.6 us of the torch layers' launches; 800 000 rows
+# 24.7 / 85.1 against 279 / 684 us.  Shorter lists were not measured and stay with torch.
+MLP_ROWS_FROM = {16: 1000, 36: 1000}
+
+
+class _RowsDeclined(Exception):
+    """tpnet_mlp_rows_f32 returned an error before launching anything (a runtime that refuses the kernel's LDS or the launch)."""
+
+
 def mlp_f32(mlp, x):
-    """mlp(x) through tpnet_mlp64_f32 if `mlp` is the reference's 64-256-64 on this GPU (else None)."""
-    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2 or x.shape[1] != 64:
+    """mlp(x) on the fp32 matrix cores where a kernel serves it on this GPU (else None): tpnet_mlp64_f32 if `mlp` is the reference's
+    64-256-64, tpnet_mlp_rows_f32 if it is the 16-64-16 or 36-144-36 of num_layer 1 / 2 and x has MLP_ROWS_FROM[width] rows or more."""
+    if x.dtype != torch.float32 or not x.is_cuda or x.dim() != 2:
         return None
-    prep = prepared(mlp, 64)
-    if prep is None or not prep.st.w1:
+    F = x.shape[1]
+    if F == 64:
+        prep = prepared(mlp, 64)
+        if prep is None or not prep.st.w1:
+            return None
+    else:
+        rows_from = MLP_ROWS_FROM.get(F)
+        if rows_from is None or x.shape[0] < rows_from:
+            return None
+        prep = prepared(mlp, F)
+        if prep is None or prep.st.F != F or not _lib.load().tpnet_mlp_rows_supported(prep.st.F, prep.st.H):
+            return None
+    try:
+        # (a caller's own x that requires grad gets its gradient at 16 / 36 columns as it does from the torch layers)
+        if needs_grad(prep.params) or (F != 64 and x.requires_grad and torch.is_grad_enabled()):
+            return _MlpF32.apply(x, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, prep.ref, prep, getattr(mlp, "mlp_backward", None))
+        return _MlpF32.forward(_NoCtx(), x, None, None, None, None, prep.ref)
+    except _RowsDeclined:
         return None
-    if needs_grad(prep.params):
-        return _MlpF32.apply(x, mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, prep.ref, prep, getattr(mlp, "mlp_backward", None))
-    return _MlpF32.forward(_NoCtx(), x, None, None, None, None, prep.ref)
 
 
 class _NoCtx:

@@ -1054,7 +1054,7 @@ class RandomProjectionModule(nn.Module):
     def _apply_mlp(self, feats: torch.Tensor) -> torch.Tensor:
         if self.fused_mlp and _fm.supported(self.mlp):
             return _fm.fused_mlp(self.mlp, feats)
-        y = _ff.mlp_f32(self.mlp, feats) if self.num_layer == 3 else None      # the fp32 matrix-core kernel where it applies
+        y = _ff.mlp_f32(self.mlp, feats)                   # the fp32 matrix-core kernels where one serves this width and length
         return y if y is not None else self.mlp(feats)
 
     def reset_random_projections(self):
