@@ -47,7 +47,8 @@ extern "C" {
                                     added since without a new number: tpnet_neg_* (the negative edge sampler's three strategies);
                                     tpnet_lp_metrics* (a batch's BCE loss, average precision and ROC-AUC as one device record);
                                     tpnet_edgebank_* (the EdgeBank baseline's three memory modes on a prefix of one static stream);
-                                    tpnet_mlp_rows_* (self.mlp on the matrix cores for num_layer 1 and 2) */
+                                    tpnet_mlp_rows_* (self.mlp on the matrix cores for num_layer 1 and 2);
+                                    tpnet_mlp_rows_bwd_* (its weight gradients on the matrix cores, same widths) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -759,6 +760,21 @@ int tpnet_mlp64_bwd_bf16(const float* x, const float* gy, int64_t n, const void*
  * mlp[2].weight transposed [256][64], mlp->b1).  Same partial layout and return value as tpnet_mlp64_bwd_bf16. */
 int tpnet_mlp64_bwd_f32(const float* x, const float* gy, int64_t n, const tpnet_mlp* mlp, float* partial, int32_t n_partial,
                         void* stream);
+/* The fp32-class backward for num_layer 1 and 2 (csrc/mlp_rows_bwd.hip): the weight gradients of self.mlp = Linear(F, 4F) -> ReLU ->
+ * Linear(4F, F) for the (F, H) that tpnet_mlp_rows_supported accepts, (16, 64) and (36, 144), in ONE launch on the caller's stream,
+ * no synchronisation.  x: the pre-mlp features [n][F] f32, gy: the gradient of the output [n][F] f32, both device, 16-byte aligned,
+ * read only inside their n * F floats; weights from mlp->w1t, b1, w2t (what tpnet_mlp_rows_f32 reads).  fp32 class: two-piece bf16
+ * operands with fp32 accumulation, the pre-activations that decide the ReLU in exact f32.  Every workgroup writes ONE
+ * partial result of tpnet_mlp_rows_bwd_partial_floats(F, H) floats (0 for a width that is not served; 2 112 at F = 16, 10 512 at
+ * F = 36), laid out gW1 [H][F] | gW2 [F][H] | gb1 [H], unpadded (gb2 = the column sums of gy is the caller's).  Returns the number of
+ * partials written, min(n_partial, ceil(n / 32)); the caller sums them (fixed order: deterministic) and nothing beyond them is
+ * written.  n == 0: nothing is written, returns 0.  TPNET_ERR_BAD_ARG, before any HIP call: a null pointer, a width that
+ * tpnet_mlp_rows_supported refuses, a misaligned x or gy, n_partial < 1; a negative code also when the runtime refuses the kernel's
+ * LDS (80 KB at F = 36) or the launch -- the caller then computes the gradients its other way.  A NaN in a row of x or gy reaches
+ * the gradients, as it does in the torch expressions; memory outside the two lists never does. */
+int64_t tpnet_mlp_rows_bwd_partial_floats(int32_t F, int32_t H);
+int tpnet_mlp_rows_bwd_f32(const float* x, const float* gy, int64_t n, const tpnet_mlp* mlp, float* partial, int32_t n_partial,
+                           void* stream);
 
 /* get_pair_wise_feature with self.mlp on the bf16 matrix cores INSIDE the readout kernel (L = 3, d % 4 == 0 and d >= 64):
  * 8 waves form the features of 32 pairs into an LDS tile, which is the B operand of layer 1; wave w owns hidden units

@@ -73,14 +73,16 @@ def layer_grads(x, gy, w1, b1, w2, input_grad=False):
     return grads + (gh @ w1,) if input_grad else grads
 
 
-def mlp64_bwd(call, x, gy, H=256, F=64):
-    """One launch of a tpnet_mlp64_bwd_* kernel + the fixed-order sum of its workgroups' partial results (deterministic).
+def mlp64_bwd(call, x, gy, H=256, F=64, pf=None):
+    """One launch of a weight-gradient kernel (tpnet_mlp64_bwd_*; tpnet_mlp_rows_bwd_f32 with its (H, F) and partial size `pf`) +
+    the fixed-order sum of its workgroups' partial results (deterministic).  A partial is gW1 [H][F] | gW2 [F][H] | gb1 [H].
     call(x_ptr, gy_ptr, n, partial_ptr, n_partial, stream) -> the C call's return value rc: the number of partials written, or
     <= 0 where it declined.  Returns (rc, (gw1, gb1, gw2, gb2) or None)."""
     n = int(x.shape[0])
     x = x.contiguous()
     gy = gy.contiguous().float()
-    pf = int(_lib.load().tpnet_mlp64_bwd_partial_floats())
+    if pf is None:
+        pf = int(_lib.load().tpnet_mlp64_bwd_partial_floats())
     nblk = min(256, (n + 31) // 32)
     part = torch.empty((nblk, pf), dtype=torch.float32, device=x.device)
     rc = call(x.data_ptr(), gy.data_ptr(), n, part.data_ptr(), nblk, stream_ptr(x.device))

@@ -73,34 +73,69 @@ MFMA_BWD_FROM = 512
 # A module overrides the process-wide value with an attribute of the same name on its self.mlp (rp.mlp.mlp_backward = "torch").
 mlp_backward = "mfma"
 _declined_once = set()
+# rows from which tpnet_mlp_rows_bwd_f32 (csrc/mlp_rows_bwd.hip: num_layer 1 and 2) takes the weight gradients from the torch
+# expressions, per width; None = reachable through the C call, never routed.  MLP_ROWS_FROM's rule (below), measured by the backward
+# leg of tools/mlp_rows_rate.py (profiles/mlp_rows.md): one launch + the sum of the partials against _dense.layer_grads on the same
+# tensors in one process.  At 1 000 rows, the smallest size of the protocol, 28.7 / 28.6 us against 115 / 142 us; 80 000 rows
+# 53.5 / 80.8 against 311 / 516 us; 800 000 rows 236 / 456 against 2 380 / 4 029 us.  Shorter lists were not measured and stay
+# with torch.
+MLP_ROWS_BWD_FROM = {16: 1000, 36: 1000}
+calls = {"rows_bwd": 0}                     # launches of tpnet_mlp_rows_bwd_f32 made from here (tests assert the dispatch through it)
+
+
+def _bwd_kernel(x, prep, n):
+    """(name, call, partial floats) of the matrix-core weight-gradient kernel that serves x [n, F] under `prep`, or None."""
+    lib, st = _lib.load(), prep.st
+    if st.w1 and st.w2t:                                 # 64 columns
+        if n < MFMA_BWD_FROM:
+            return None
+        return ("tpnet_mlp64_bwd_f32", lambda xp, gp, n_, part, nblk, stream: lib.tpnet_mlp64_bwd_f32(xp, gp, n_, prep.ref, part, nblk, stream),
+                None)
+    F = int(x.shape[1])
+    rows_from = MLP_ROWS_BWD_FROM.get(F)
+    if rows_from is None or n < rows_from or st.F != F:
+        return None
+    pf = int(lib.tpnet_mlp_rows_bwd_partial_floats(st.F, st.H))
+    if not pf:
+        return None
+
+    def call(xp, gp, n_, part, nblk, stream):
+        rc = lib.tpnet_mlp_rows_bwd_f32(xp, gp, n_, prep.ref, part, nblk, stream)
+        calls["rows_bwd"] += rc > 0
+        return rc
+
+    return "tpnet_mlp_rows_bwd_f32", call, pf
 
 
 def weight_grads_f32(x, gy, w1, b1, w2, prep, mode=None):
-    """Gradients of (mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias) given the pre-mlp features x [n, 64] and the gradient
-    gy [n, 64] of self.mlp's output, fp32 class.  Long lists (the encoder's calls: 80 000 rows each at C2) take ONE launch on the
-    matrix cores (tpnet_mlp64_bwd_f32: hidden layer recomputed, both weight-gradient products contracted over the rows with
+    """Gradients of (mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias) given the pre-mlp features x [n, F] and the gradient
+    gy [n, F] of self.mlp's output, fp32 class.  Long lists (the encoder's calls: 80 000 rows each at C2) take ONE launch on the
+    matrix cores (tpnet_mlp64_bwd_f32 at 64 columns from MFMA_BWD_FROM rows, tpnet_mlp_rows_bwd_f32 at 16 and 36 columns from
+    MLP_ROWS_BWD_FROM[F] rows: hidden layer recomputed, both weight-gradient products contracted over the rows with
     two-piece bf16 operands and fp32 accumulation, one partial result per workgroup, summed in a fixed order) instead of five
-    fp32 GEMMs and three elementwise passes over n x 256 floats; `prep` = the prepared() entry the forward used -- if a Parameter
+    fp32 GEMMs and three elementwise passes over n x 4F floats; `prep` = the prepared() entry the forward used -- if a Parameter
     changed since (never in a normal training step), or for short lists and CPU tensors, the torch expressions serve.
     mode: "mfma" | "torch" (None: the module-level `mlp_backward`)."""
     mode = mode or mlp_backward
     n = int(x.shape[0])
-    if (mode == "mfma" and prep is not None and x.is_cuda and n >= MFMA_BWD_FROM and x.dtype == torch.float32 and prep.st.w1 and prep.st.w2t
+    if (mode == "mfma" and prep is not None and x.is_cuda and x.dtype == torch.float32
             and prep.key[:6] == (w1.data_ptr(), w1._version, b1.data_ptr(), b1._version, w2.data_ptr(), w2._version)):
-        lib = _lib.load()
-        rc, grads = _dense.mlp64_bwd(lambda xp, gp, n_, part, nblk, stream: lib.tpnet_mlp64_bwd_f32(xp, gp, n_, prep.ref, part, nblk, stream),
-                                     x, gy, *w1.shape)
-        if grads is not None:
-            return grads
-        if rc not in _declined_once:                    # (said once per code: the torch expressions below serve the call)
-            _declined_once.add(rc)
-            warnings.warn(f"tpnet_mlp64_bwd_f32 declined a call of {n} rows (rc {rc}): weight gradients by the fp32 torch expressions")
+        kernel = _bwd_kernel(x, prep, n)
+        if kernel is not None:
+            name, call, pf = kernel
+            rc, grads = _dense.mlp64_bwd(call, x, gy, *w1.shape, pf)
+            if grads is not None:
+                return grads
+            if (name, rc) not in _declined_once:            # (said once per code: the torch expressions below serve the call)
+                _declined_once.add((name, rc))
+                warnings.warn(f"{name} declined a call of {n} rows (rc {rc}): weight gradients by the fp32 torch expressions")
     return _dense.layer_grads(x, gy, w1, b1, w2)
 
 
 class _MlpF32(torch.autograd.Function):
     """self.mlp alone on the fp32 matrix cores (tpnet_mlp64_f32 at 64 columns, tpnet_mlp_rows_f32 at 16 and 36); backward =
-    weight_grads_f32 (which has a matrix-core kernel for 64 columns only: the torch expressions serve 16 and 36)."""
+    weight_grads_f32 (matrix-core kernels for all three widths: tpnet_mlp64_bwd_f32, tpnet_mlp_rows_bwd_f32), except when x itself
+    needs a gradient: the torch expressions give all five."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, mlp_ref, prep=None, mode=None):
