@@ -850,6 +850,41 @@ int tpnet_mixer_token(const float* x, int64_t n_nodes, int32_t K, int32_t C, con
 int tpnet_mixer_channel(const float* x, int64_t n_rows, int32_t C, int32_t Ch, const float* gamma, const float* beta, float eps,
                         const void* img, float* out, void* stream);
 
+/* ---- the token-mixing half in a training step: forward with dropout, backward (additive to ABI 7; csrc/mixer_token_train.hip,
+ * DESIGN.md section 3.6) ---------------------------------------------------------------------------------------------------------
+ * Per (node, channel) column v[0 .. K) of x [n_nodes][K][C] f32, with s = 1 / (1 - p) in float and the keep masks m1 [Kh], m2 [K] of
+ * the two Dropout(p) of FeedForwardNet (behind the GELU, behind the second Linear); arguments as tpnet_mixer_token's:
+ *   tpnet_mixer_token_train:  ln = LN_K(v); a[j] = sum_k w1[j][k] ln[k] + b1[j]; h[j] = gelu(a[j]) m1[j] s;
+ *                             out[k] = (sum_j w2[k][j] h[j] + b2[k]) m2[k] s + v[k].  ONE launch.  p = 0: nothing is drawn and out has
+ *                             the bits of tpnet_mixer_token's.
+ *   tpnet_mixer_token_bwd:    from gy = dL/dout (as x: [n_nodes][K][C], 16-byte aligned), ONE launch that recomputes the column's
+ *                             forward from x and the key (the caller saves x alone) and writes gx = dL/dx (gx may be NULL: not
+ *                             computed; else as x, and neither x nor gy) and min(n_partial, batches) partial sums of the six parameter
+ *                             gradients, batches = ceil(n_nodes C / 256) (/ 128 where 4 K + 2 Kh > 159).  A partial is
+ *                             tpnet_mixer_token_bwd_partial_floats(K, Kh) = 3 K + 2 K Kh + Kh floats (0 for an unserved K / Kh), laid out
+ *                             ggamma [K] | gbeta [K] | gw1 [Kh][K] | gb1 [Kh] | gw2 [K][Kh] | gb2 [K], unpadded, partial i at
+ *                             partial + i * that many floats; `partial` holds n_partial >= 1 of them, those beyond the returned count
+ *                             are not written.  Returns that count (>= 0; 0 for n_nodes = 0) or a negative error.  The caller adds
+ *                             the partials in a fixed order; the kernel uses no atomics, so two calls give equal bits.
+ *   tpnet_mixer_token_masks:  m1 as bytes [n_nodes][C][Kh] and m2 as bytes [n_nodes][K][C] (1 = kept; p = 0: all 1), for evaluating the
+ *                             same dropout elsewhere.
+ * THE DRAWS.  Column index i = node * C + channel.  Draw d of column i, 0 <= d < Kh + K, is word d % 4 of the Philox4x32-10 block with
+ * counter (i & 0xffffffff, i >> 32, d / 4, 0x4D58544B) and key (key & 0xffffffff, key >> 32).  m1[j] = draw j, m2[k] = draw Kh + k;
+ * a unit is kept when its word >= floor(p 2^32) (p the float argument, the product in double).  A draw depends on (key, column, slot)
+ * alone, never on the launch geometry.  These are Dropout(p)'s probabilities, NOT torch's dropout stream.
+ * 0 <= p < 1 (else, as for a null pointer, a misaligned array, out == x, an unserved size or n_partial < 1: TPNET_ERR_BAD_ARG,
+ * nothing launched; all of these are checked before any GPU call).  The backward's LDS (up to 159 KB) needs the runtime's grant:
+ * TPNET_ERR_BAD_ARG if refused.  n_nodes = 0: TPNET_OK / 0, nothing launched.  Exact fp32 on the vector ALU throughout. */
+int tpnet_mixer_token_train(const float* x, int64_t n_nodes, int32_t K, int32_t C, const float* gamma, const float* beta, float eps,
+                            const float* w1, const float* b1, int32_t Kh, const float* w2, const float* b2, float p, uint64_t key,
+                            float* out, void* stream);
+int64_t tpnet_mixer_token_bwd_partial_floats(int32_t K, int32_t Kh);
+int tpnet_mixer_token_bwd(const float* x, const float* gy, int64_t n_nodes, int32_t K, int32_t C, const float* gamma, const float* beta,
+                          float eps, const float* w1, const float* b1, int32_t Kh, const float* w2, const float* b2, float p,
+                          uint64_t key, float* gx, float* partial, int32_t n_partial, void* stream);
+int tpnet_mixer_token_masks(int64_t n_nodes, int32_t K, int32_t Kh, int32_t C, float p, uint64_t key, uint8_t* m1, uint8_t* m2,
+                            void* stream);
+
 /* Copies st->err to the host (synchronises the stream): returns TPNET_ERR_INDEX if any bad id was seen since
  * the last call (and clears the words), TPNET_OK otherwise. */
 int tpnet_check_errors(const tpnet_state* st, void* stream);

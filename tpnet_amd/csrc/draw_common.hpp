@@ -1,5 +1,5 @@
 // What the two device samplers share (sampler.hip: neighbours, negsampler.hip: negative edges): the order-preserving time key, the
-// 256-thread workgroup scan and the counter-based generator.  One copy of each.
+// 256-thread workgroup scan and the counter-based generator (also the dropout draws of mixer_token_train.hip).  One copy of each.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,6 +43,21 @@ __device__ __forceinline__ uint32_t philox_word(uint32_t c0, uint32_t c1, uint32
         k1 += 0xBB67AE85u;
     }
     return word == 0 ? c0 : word == 1 ? c1 : word == 2 ? c2 : c3;
+}
+
+// all four words of the block: .x .. .w = philox_word(..., 0 .. 3)
+__device__ __forceinline__ uint4 philox_block(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
 }
 
 }  // namespace tpnet

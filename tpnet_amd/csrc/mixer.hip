@@ -12,12 +12,9 @@
 // (mean = m0 + dl, x - mean = (x - m0) - dl, var = sum (x - m0)^2 / n - dl^2): a row of mean >> spread loses nothing, a constant row
 // normalises to beta exactly as torch's does.
 #include "dense2.hpp"
+#include "mixer_token.hpp"                       // MX_KMAX, gelu_erf: shared with mixer_token_train.hip
 
 namespace tpnet {
-
-static constexpr int MX_KMAX = 32;               // tokens and token-hidden units the token kernel serves
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // KC, KHC: compile-time K and Kh (20 and 10: the reference's num_neighbors), or 0: the caller's, up to MX_KMAX -- the loops over
 // the tokens are then unrolled to MX_KMAX and guarded by a wave-uniform test, so that the per-thread arrays stay registers, and the

@@ -18,6 +18,12 @@ What differs is where the work runs:
   `torch.no_grad()` / inference mode, on contiguous float32 embeddings on the GPU, with no dropout active (eval mode, or dropout 0)
   and a served shape, every layer is TWO launches (tpnet_amd/fused_mixer.py, csrc/mixer.hip): token mixing in exact fp32, channel
   mixing on the matrix cores in the project's fp32 class.  Any other call runs `mlp_mixer(embeddings)` as before.
+* with `TPNetEmbedding.fused_token_training` set (it defaults to False), when a gradient IS recorded, on contiguous float32
+  embeddings on the GPU, with a served shape and both dropouts of the token FFN at the same p < 1, the token-mixing half of every
+  layer is ONE launch forward and ONE backward in exact fp32 (fused_mixer.token_train, csrc/mixer_token_train.hip); the backward
+  recomputes the forward, so the layer's input is the only activation kept.  In train mode its dropout masks follow nn.Dropout's
+  probabilities but come from a counter-based generator on the device, keyed from torch's default CPU generator
+  (torch.manual_seed reproduces a run): they are NOT torch's dropout stream.  The channel-mixing half stays stock torch there.
 * the mean over the K tokens is stock torch.
 """
 import numpy as np
@@ -103,6 +109,9 @@ class TPNetEmbedding(nn.Module):
     # the two-launch MLP-Mixer layers when no gradient is recorded and no dropout is active: opt-in (profiles/mixer.md; the
     # channel FFN is the fp32 class, and the bound of the end-to-end fixture test with it on is a measurement of its own)
     fused_mixer = False
+    # the token-mixing half of every mixer as one launch forward and one backward when a gradient IS recorded: opt-in
+    # (profiles/mixer_token_training.md); its dropout masks are the device generator's, not torch's stream
+    fused_token_training = False
 
     def __init__(self, node_raw_features: torch.Tensor, edge_raw_features: torch.Tensor, neighbor_sampler, time_encoder: nn.Module,
                  node_feat_dim: int, edge_feat_dim: int, time_feat_dim: int, num_layers: int, num_neighbors: int, dropout: float,
@@ -181,6 +190,21 @@ class TPNetEmbedding(nn.Module):
                 return None
         return _fm.prepared(mixer)
 
+    def _fused_token_rate(self, mixer, x):
+        """The dropout rate at which the token-mixing half of `mixer` runs as token_train on `x`, else None: `fused_token_training`
+        set, a gradient recorded, x contiguous float32 on the GPU, a shape tpnet_mixer_supported accepts and both dropouts of the
+        token FFN at the same p < 1.  In eval mode the rate is 0."""
+        if not self.fused_token_training or not torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 \
+                or not x.is_contiguous():
+            return None
+        if _fm.layers_of(mixer) is None:
+            return None
+        ffn = mixer.token_feedforward.ffn
+        p = float(ffn[2].p)
+        if p != float(ffn[4].p) or not 0.0 <= p < 1.0 or not _fm.supported(mixer):
+            return None
+        return p if self.training else 0.0
+
     def embed_from_features(self, neighbor_node_ids, neighbor_edge_ids, neighbor_times, node_interact_times, pair_features):
         """The tail behind the readout (TPNet.py:297-338).  neighbor_node_ids / neighbor_edge_ids int64 [n, K], neighbor_times
         float64 [n, K], node_interact_times float64 [n] (host arrays or tensors), pair_features [2 n K, F] in the reference's row
@@ -207,6 +231,11 @@ class TPNetEmbedding(nn.Module):
             embeddings = self.projection_layer(torch.cat(parts, dim=2))
         # (TPNet.py:332 calls masked_fill out of place and drops the result: pad neighbours are NOT masked)
         for mlp_mixer in self.mlp_mixers:
+            rate = self._fused_token_rate(mlp_mixer, embeddings)
+            if rate is not None:
+                tokens = _fm.token_train(mlp_mixer, embeddings, rate)
+                embeddings = mlp_mixer.channel_feedforward(mlp_mixer.channel_norm(tokens)) + tokens
+                continue
             prep = self._fused_mixer_prep(mlp_mixer, embeddings)
             embeddings = mlp_mixer(embeddings) if prep is None else _fm.mixer_forward(prep, mlp_mixer, embeddings)
         return torch.mean(embeddings, dim=1)

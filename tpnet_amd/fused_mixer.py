@@ -3,7 +3,13 @@
 fp32 class, dropout as identity.  Forward only and opt-in: the caller (tpnet_amd/encoder.py, TPNetEmbedding.fused_mixer) takes it
 when no gradient is recorded and no dropout is active.  The split weights of the channel FFN are kept per mixer like
 fused_input.prepared() keeps projection_layer's: rewritten by one launch when a Parameter's (data_ptr, _version) changed.  The
-LayerNorms' and the token FFN's Parameters are read in place at every call and need no image."""
+LayerNorms' and the token FFN's Parameters are read in place at every call and need no image.
+
+The token-mixing half also runs in a TRAINING step (csrc/mixer_token_train.hip; opt-in, TPNetEmbedding.fused_token_training):
+`token_train` is x + token_feedforward(token_norm(x^T))^T with both dropouts as ONE launch forward and ONE launch backward under
+autograd.  The backward recomputes the forward from x, so x is the only activation saved.  The dropout masks come from a
+counter-based generator on the device, keyed per call (include/tpnet_hip.h): they follow nn.Dropout's probabilities but are NOT
+torch's dropout stream."""
 import weakref
 from typing import NamedTuple
 
@@ -12,7 +18,10 @@ import torch
 from . import _dense, _lib
 
 _PREPARED = weakref.WeakKeyDictionary()                 # mixer -> Prepared
-calls = {"token": 0, "channel": 0, "prepare": 0}        # launches made through this binding (tests assert the dispatch through it)
+# launches made through this binding (tests assert the dispatch through it)
+calls = {"token": 0, "channel": 0, "prepare": 0, "token_train": 0, "token_bwd": 0}
+MAX_PARTIALS = 256                                      # workgroups of a backward launch = partial sums it writes, at most
+_PARTIALS = {}                                          # (device, floats per partial) -> the reused [MAX_PARTIALS, floats] buffer
 
 layers_of = _dense.mixer_layers                         # the structural test: MixerLayers, or None for another module
 
@@ -122,3 +131,97 @@ def mixer_channel(prep: Prepared, mixer, x):
 def mixer_forward(prep: Prepared, mixer, x):
     """MLPMixer.forward of x [n, K, C] with dropout as identity, as a new tensor: two launches."""
     return mixer_channel(prep, mixer, mixer_token(mixer, x))
+
+
+def _check_token_input(ls, x, what):
+    K, _, C, _ = _dims(ls)
+    if x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape[1:]) != (K, C) or not x.is_contiguous() \
+            or x.device != ls.token_norm.weight.device:
+        raise ValueError(f"{what}: x must be a contiguous float32 [n, K, C] on the mixer's device")
+
+
+def _new_key():
+    """64 bits from torch's default CPU generator: no device synchronisation, reproducible under torch.manual_seed."""
+    hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+    return hi << 32 | lo
+
+
+class _TokenTrain(torch.autograd.Function):
+    """Forward: tpnet_mixer_token_train.  Saved: x and the six Parameters.  Backward: tpnet_mixer_token_bwd + the fixed-order sum of
+    its partials."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, w1, b1, w2, b2, eps, p, key):
+        n, K, C = x.shape
+        Kh = w1.shape[0]
+        out = torch.empty_like(x)
+        _lib.check(_lib.load().tpnet_mixer_token_train(x.data_ptr(), n, K, C, gamma.data_ptr(), beta.data_ptr(), eps, w1.data_ptr(),
+                                                       b1.data_ptr(), Kh, w2.data_ptr(), b2.data_ptr(), p, key, out.data_ptr(),
+                                                       _dense.stream_ptr(x.device)), "mixer_token_train")
+        calls["token_train"] += 1
+        ctx.save_for_backward(x, gamma, beta, w1, b1, w2, b2)
+        ctx.consts = (eps, p, key)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, gamma, beta, w1, b1, w2, b2 = ctx.saved_tensors
+        eps, p, key = ctx.consts
+        n, K, C = x.shape
+        Kh = w1.shape[0]
+        gy = gy.contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        tot = None
+        if n > 0:
+            lib = _lib.load()
+            pf = int(lib.tpnet_mixer_token_bwd_partial_floats(K, Kh))
+            part = _PARTIALS.get((x.device, pf))
+            if part is None:
+                part = _PARTIALS[(x.device, pf)] = torch.empty((MAX_PARTIALS, pf), dtype=torch.float32, device=x.device)
+            rc = lib.tpnet_mixer_token_bwd(x.data_ptr(), gy.data_ptr(), n, K, C, gamma.data_ptr(), beta.data_ptr(), eps, w1.data_ptr(),
+                                           b1.data_ptr(), Kh, w2.data_ptr(), b2.data_ptr(), p, key,
+                                           None if gx is None else gx.data_ptr(), part.data_ptr(), MAX_PARTIALS,
+                                           _dense.stream_ptr(x.device))
+            if rc <= 0:
+                _lib.check(rc if rc < 0 else -1, "mixer_token_bwd")
+            calls["token_bwd"] += 1
+            tot = part[:rc].sum(0)                              # fixed order: run-to-run identical bits
+        grads, off = [], 0
+        for i, t in enumerate((gamma, beta, w1, b1, w2, b2)):
+            g = None
+            if ctx.needs_input_grad[1 + i]:
+                g = torch.zeros_like(t) if tot is None else tot[off:off + t.numel()].view(t.shape)
+            grads.append(g)
+            off += t.numel()
+        return (gx, *grads, None, None, None)
+
+
+def token_train(mixer, x, p, key=None):
+    """x + token_feedforward(token_norm(x^T))^T of x [n, K, C] float32 (contiguous, on the Parameters' device) with both dropouts of
+    the token FFN at rate `p` (0 <= p < 1; 0: none), differentiable with respect to x and the six Parameters: one launch forward,
+    one launch backward (+ the sum of at most MAX_PARTIALS partial results), no synchronisation.  `key`: the 64-bit key of this
+    call's dropout draws; None draws one from torch's default CPU generator, so torch.manual_seed makes a run reproducible.  The
+    masks are nn.Dropout's probabilities from the device's counter-based generator (token_masks returns them), NOT torch's
+    dropout stream."""
+    ls = layers_of(mixer)
+    _check_token_input(ls, x, "token_train")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("token_train: 0 <= p < 1")
+    if key is None:
+        key = _new_key() if p > 0.0 else 0
+    return _TokenTrain.apply(x, *_params(ls)[:6], float(ls.token_norm.eps), p, int(key) & (1 << 64) - 1)
+
+
+def token_masks(mixer, n, C, p, key):
+    """The keep masks token_train(mixer, x [n, K, C], p, key) applies, as bool tensors: m1 [n, C, Kh] (behind the GELU) and
+    m2 [n, K, C] (behind the second Linear)."""
+    ls = layers_of(mixer)
+    K, Kh = _dims(ls)[:2]
+    dev = ls.token_norm.weight.device
+    m1 = torch.empty((n, C, Kh), dtype=torch.uint8, device=dev)
+    m2 = torch.empty((n, K, C), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().tpnet_mixer_token_masks(n, K, Kh, C, float(p), int(key) & (1 << 64) - 1, m1.data_ptr(), m2.data_ptr(),
+                                                   _dense.stream_ptr(dev)), "mixer_token_masks")
+    return m1.bool(), m2.bool()
