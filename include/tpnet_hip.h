@@ -885,6 +885,50 @@ int tpnet_mixer_token_bwd(const float* x, const float* gy, int64_t n_nodes, int3
 int tpnet_mixer_token_masks(int64_t n_nodes, int32_t K, int32_t Kh, int32_t C, float p, uint64_t key, uint8_t* m1, uint8_t* m2,
                             void* stream);
 
+/* ---- the channel-mixing half in a training step: forward with dropout, backward (additive to ABI 7; csrc/mixer_channel_train.hip,
+ * DESIGN.md section 3.6) ---------------------------------------------------------------------------------------------------------
+ * Per row v[0 .. C) of x [n_rows][C] f32, with s = 1 / (1 - p) in float and the keep masks m1 [Ch], m2 [C] of the two Dropout(p) of
+ * FeedForwardNet (behind the GELU, behind the second Linear); arguments as tpnet_mixer_channel's, img the image
+ * tpnet_mixer_channel_prepare wrote:
+ *   tpnet_mixer_channel_train:  ln = LN_C(v); a = W1 . ln + b1; h = gelu(a) m1 s; out = (W2 . h + b2) m2 s + v.  ONE launch.  p = 0:
+ *                               nothing is drawn and out has the bits of tpnet_mixer_channel's.
+ *   tpnet_mixer_channel_bwd:    from gy = dL/dout (as x: [n_rows][C], 16-byte aligned), TWO launches that recompute the row's forward
+ *                               from x and the key (the caller saves x alone) and write gx = dL/dx (gx may be NULL: not computed; else as
+ *                               x, and neither x nor gy) and min(n_partial, ceil(n_rows / 32)) partial sums of the six parameter
+ *                               gradients, one per part of the rows.  A partial is tpnet_mixer_channel_bwd_partial_floats(C, Ch) =
+ *                               2 C + 2 C Ch + Ch + C floats (0 for an unserved C / Ch), laid out
+ *                               ggamma [C] | gbeta [C] | gw1 [Ch][C] | gb1 [Ch] | gw2 [C][Ch] | gb2 [C], unpadded, partial i at
+ *                               partial + i * that many floats; `partial` holds n_partial >= 1 of them, those beyond the returned
+ *                               count are not written.  Returns that count (>= 0; 0 for n_rows = 0) or a negative error.  The caller
+ *                               adds the partials in a fixed order; the kernels use no atomics, so two calls give equal bits.
+ *                               bimg: the backward's image, in place of img (tpnet_mixer_channel_bwd_image_bytes;
+ *                               tpnet_mixer_channel_bwd_prepare writes it from w1 [Ch][C], b1 [Ch] and w2 [C][Ch] in ONE launch; again
+ *                               whenever one of the three changed).
+ *                               workspace: tpnet_mixer_channel_bwd_workspace_bytes(n_rows, C, Ch) bytes (0 for an unserved size),
+ *                               16-byte aligned, the call's own: its contents mean nothing before or after the two launches.
+ *   tpnet_mixer_channel_masks:  m1 as bytes [n_rows][Ch] and m2 as bytes [n_rows][C] (1 = kept; p = 0: all 1), for evaluating the same
+ *                               dropout elsewhere.  One thread per block of four draws in one launch: n_rows (ceil(Ch / 4) + C / 4)
+ *                               <= 2^32 - 256, else TPNET_ERR_BAD_ARG.
+ * THE DRAWS.  Row index i = the row's position in x.  Block b of row i is the four words of Philox4x32-10 with counter
+ * (i & 0xffffffff, i >> 32, b, 0x4D584348) and key (key & 0xffffffff, key >> 32).  m1[j] = word j % 4 of block j / 4, m2[c] = word
+ * c % 4 of block ceil(Ch / 4) + c / 4: both masks start on a block boundary.  A unit is kept when its word >= floor(p 2^32) (p the float
+ * argument, the product in double).  A draw depends on (key, row, slot) alone, never on the launch geometry.  These are Dropout(p)'s
+ * probabilities, NOT torch's dropout stream.
+ * Served sizes: tpnet_mixer_supported's C and Ch, n_rows <= 2^31.  0 <= p < 1 (else, as for a null pointer, an array that is not
+ * 16-byte aligned (partial: 4-byte), out == x, gx == x or gy, an unserved size or n_partial < 1: TPNET_ERR_BAD_ARG, nothing launched;
+ * all of these are checked before any GPU call).  n_rows = 0: TPNET_OK / 0, nothing launched.  Every product is the fp32 class on
+ * the matrix cores; LayerNorm, gelu, gelu', the masks and the LayerNorm backward are plain fp32. */
+int tpnet_mixer_channel_train(const float* x, int64_t n_rows, int32_t C, int32_t Ch, const float* gamma, const float* beta, float eps,
+                              const void* img, float p, uint64_t key, float* out, void* stream);
+int64_t tpnet_mixer_channel_bwd_partial_floats(int32_t C, int32_t Ch);
+size_t tpnet_mixer_channel_bwd_image_bytes(int32_t C, int32_t Ch);
+int tpnet_mixer_channel_bwd_prepare(const float* w1, const float* b1, const float* w2, int32_t C, int32_t Ch, void* bimg, void* stream);
+size_t tpnet_mixer_channel_bwd_workspace_bytes(int64_t n_rows, int32_t C, int32_t Ch);
+int tpnet_mixer_channel_bwd(const float* x, const float* gy, int64_t n_rows, int32_t C, int32_t Ch, const float* gamma,
+                            const float* beta, float eps, const void* bimg, float p, uint64_t key, void* workspace, float* gx,
+                            float* partial, int32_t n_partial, void* stream);
+int tpnet_mixer_channel_masks(int64_t n_rows, int32_t C, int32_t Ch, float p, uint64_t key, uint8_t* m1, uint8_t* m2, void* stream);
+
 /* Copies st->err to the host (synchronises the stream): returns TPNET_ERR_INDEX if any bad id was seen since
  * the last call (and clears the words), TPNET_OK otherwise. */
 int tpnet_check_errors(const tpnet_state* st, void* stream);

@@ -167,6 +167,14 @@ SIGNATURES = {
     "tpnet_mixer_token_bwd": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, _P, C.c_int32, _P, _P, C.c_float,
                                         C.c_uint64, _P, _P, C.c_int32, _P]),
     "tpnet_mixer_token_masks": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, _P, _P, _P]),
+    "tpnet_mixer_channel_train": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, C.c_float, C.c_uint64, _P, _P]),
+    "tpnet_mixer_channel_bwd_partial_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "tpnet_mixer_channel_bwd_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tpnet_mixer_channel_bwd_prepare": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "tpnet_mixer_channel_bwd_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "tpnet_mixer_channel_bwd": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_float, _P, C.c_float, C.c_uint64, _P, _P,
+                                          _P, C.c_int32, _P]),
+    "tpnet_mixer_channel_masks": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_uint64, _P, _P, _P]),
     "tpnet_stage_create": (C.c_int, [C.c_int32, C.c_size_t, C.POINTER(_P)]),
     "tpnet_stage_create_ex": (C.c_int, [C.c_int32, C.c_size_t, C.c_int32, C.POINTER(_P)]),
     "tpnet_stage_in_device_memory": (C.c_int, [_P]),

@@ -1,4 +1,5 @@
-// The weight image of dense2.hpp's two layers and its host arithmetic (the kernels that consume it: encoder_input.hip, mixer.hip).
+// The weight image of dense2.hpp's two layers and its host arithmetic (the kernels that consume it: encoder_input.hip, mixer.hip,
+// mixer_channel_train.hip).
 #include "dense2.hpp"
 
 namespace tpnet {

@@ -1,5 +1,6 @@
 // Two dense layers on the matrix cores over rows that are never written as a matrix: out[row] = W2 . act(W1 . x[row] + b1) + b2,
-// once (encoder_input.hip: the gathered concat, ReLU; mixer.hip: the LayerNorm of a row, GELU, + residual).  A kernel gives the
+// once (encoder_input.hip: the gathered concat, ReLU; mixer.hip: the LayerNorm of a row, GELU, + residual; mixer_channel_train.hip:
+// the same with dropout).  A kernel gives the
 // row source -- columns c .. c + 3 of its lane's row -- the activation and what is done with four outputs; everything between is here.
 // Arithmetic: the project's fp32 class (mfma_split.hpp: two-piece operands, three products per term on v_mfma_f32_32x32x16_bf16,
 // fp32 accumulators).  Layer 1 is computed as H^T = W1 . X^T, so a hidden slice's accumulator registers
@@ -42,13 +43,16 @@ size_t d2_image_bytes(const d2_dims& d);
 // ONE launch that writes the image (dense2.hip: the layout) from the four Parameters
 int d2_prepare(const float* w1, const float* b1, const float* w2, const float* b2, const d2_dims& d, void* img, hipStream_t s);
 
+// An activation is an object: split16(a, bias, w, bh, bl) turns the accumulators of hidden slice w (units 32 w + acc_row(q, h) of the
+// lane's row) into layer 2's B operand.  The two stateless ones ignore w; one that needs the row and the units it holds
+// (mixer_channel_train.hip: the dropout mask) carries them as members.
 struct act_relu {
-    static __device__ __forceinline__ void split16(const f32x16& a, const float (&bias)[16], bf16x8 (&bh)[2], bf16x8 (&bl)[2]) {
+    static __device__ __forceinline__ void split16(const f32x16& a, const float (&bias)[16], int, bf16x8 (&bh)[2], bf16x8 (&bl)[2]) {
         relu_split16(a, bias, bh, bl);
     }
 };
 struct act_gelu {
-    static __device__ __forceinline__ void split16(const f32x16& a, const float (&bias)[16], bf16x8 (&bh)[2], bf16x8 (&bl)[2]) {
+    static __device__ __forceinline__ void split16(const f32x16& a, const float (&bias)[16], int, bf16x8 (&bh)[2], bf16x8 (&bl)[2]) {
         gelu_split16(a, bias, bh, bl);
     }
 };
@@ -59,7 +63,7 @@ struct act_gelu {
 // put(o, v) takes outputs o .. o + 3 of a valid row, bias added.
 template <int HG, int OSM, bool MULTI, class ACT, class SRC, class PUT>
 __device__ __forceinline__ void dense2_rows(const d2_dims& d, const uint4* __restrict__ img, const bool valid, const SRC& x4,
-                                            const PUT& put) {
+                                            const PUT& put, const ACT& act = ACT()) {
     constexpr int CH = d2_chunk(HG, OSM), D2_PF = CH / D2_T;
     static_assert(CH >= HG * 128 && CH >= OSM * 256 && CH % D2_T == 0, "a chunk holds a k-step of W1 and a slice of W2");
     __shared__ uint4 buf[2][CH];
@@ -136,7 +140,7 @@ __device__ __forceinline__ void dense2_rows(const d2_dims& d, const uint4* __res
                     bv[4 * q4] = bb.x; bv[4 * q4 + 1] = bb.y; bv[4 * q4 + 2] = bb.z; bv[4 * q4 + 3] = bb.w;
                 }
                 bf16x8 bhh[2], bhl[2];
-                ACT::split16(acc[wl], bv, bhh, bhl);
+                act.split16(acc[wl], bv, w0 + wl, bhh, bhl);
                 const bf16x8* W = reinterpret_cast<const bf16x8*>(buf[cur]) + lane;
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {

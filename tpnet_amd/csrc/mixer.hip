@@ -11,7 +11,7 @@
 // Both LayerNorms: biased variance from the deviations of a first-pass mean m0, corrected by the deviations' own mean
 // (mean = m0 + dl, x - mean = (x - m0) - dl, var = sum (x - m0)^2 / n - dl^2): a row of mean >> spread loses nothing, a constant row
 // normalises to beta exactly as torch's does.
-#include "dense2.hpp"
+#include "mixer_channel.hpp"                     // the row statistics and size checks: shared with mixer_channel_train.hip
 #include "mixer_token.hpp"                       // MX_KMAX, gelu_erf: shared with mixer_token_train.hip
 
 namespace tpnet {
@@ -86,55 +86,13 @@ __global__ __launch_bounds__(D2_T) void k_mixer_channel(const float* __restrict_
     const bool valid = row < n;
     const int C = d.Din;
     const float* xr = x + (valid ? row : 0) * C;
-    // ---- the row's mean and 1 / sqrt(var + eps): the two lanes of a row take every other float4 and add their sums (a + b = b + a:
-    // both hold the same bits)
-    float s = 0.0f;
-    if (valid) {
-        for (int c = 4 * h; c < C; c += 8) {
-            const float4 a = *reinterpret_cast<const float4*>(xr + c);
-            s += (a.x + a.y) + (a.z + a.w);
-        }
-    }
-    s += __shfl_xor(s, 32);
-    const float m0 = s / (float)C;
-    float sd = 0.0f, sq = 0.0f;
-    if (valid) {
-        for (int c = 4 * h; c < C; c += 8) {
-            const float4 a = *reinterpret_cast<const float4*>(xr + c);
-            const float d0 = a.x - m0, d1 = a.y - m0, d2 = a.z - m0, d3 = a.w - m0;
-            sd += (d0 + d1) + (d2 + d3);
-            sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        }
-    }
-    sd += __shfl_xor(sd, 32);
-    sq += __shfl_xor(sq, 32);
-    const float dl = sd / (float)C;
-    const float rstd = 1.0f / sqrtf(fmaxf(sq / (float)C - dl * dl, 0.0f) + eps);
-    // columns c .. c + 3 of the normalised row
-    auto x4 = [&](int c) -> float4 {
-        if (!valid || c >= C) return make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 a = *reinterpret_cast<const float4*>(xr + c), g = *reinterpret_cast<const float4*>(gamma + c),
-                     b = *reinterpret_cast<const float4*>(beta + c);
-        return make_float4(((a.x - m0) - dl) * rstd * g.x + b.x, ((a.y - m0) - dl) * rstd * g.y + b.y,
-                           ((a.z - m0) - dl) * rstd * g.z + b.z, ((a.w - m0) - dl) * rstd * g.w + b.w);
-    };
+    mx_ln_row x4{xr, gamma, beta, C, valid};
+    x4.stats(h, eps);
     float* yo = out + row * C;
     dense2_rows<HG, OSM, MULTI, act_gelu>(d, img, valid, x4, [&](int o, const float4 v) {
         const float4 a = *reinterpret_cast<const float4*>(xr + o);
         *reinterpret_cast<float4*>(yo + o) = make_float4(v.x + a.x, v.y + a.y, v.z + a.z, v.w + a.w);
     });
-}
-
-static bool mx_channel_dims(int32_t C, int32_t Ch, d2_dims& d) {
-    if (C < 4 || C > 256 || (C & 3) || Ch < 1 || Ch > 1024) return false;
-    d2_make_dims(C, Ch, C, true, d);
-    return true;
-}
-
-static bool mx_aligned16(std::initializer_list<const void*> ps) {
-    uintptr_t a = 0;
-    for (const void* p : ps) a |= reinterpret_cast<uintptr_t>(p);
-    return (a & 15) == 0;
 }
 
 }  // namespace tpnet

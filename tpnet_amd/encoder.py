@@ -23,7 +23,13 @@ What differs is where the work runs:
   layer is ONE launch forward and ONE backward in exact fp32 (fused_mixer.token_train, csrc/mixer_token_train.hip); the backward
   recomputes the forward, so the layer's input is the only activation kept.  In train mode its dropout masks follow nn.Dropout's
   probabilities but come from a counter-based generator on the device, keyed from torch's default CPU generator
-  (torch.manual_seed reproduces a run): they are NOT torch's dropout stream.  The channel-mixing half stays stock torch there.
+  (torch.manual_seed reproduces a run): they are NOT torch's dropout stream.
+* with `TPNetEmbedding.fused_channel_training` set (it defaults to False), under the same conditions (the channel FFN's two
+  dropouts at the same p < 1), the channel-mixing half of every layer is ONE launch forward and TWO backward on the matrix
+  cores in the project's fp32 class (fused_mixer.channel_train, csrc/mixer_channel_train.hip); the backward recomputes the forward
+  in a workspace it allocates and frees, so the half's input is the only activation kept.  Its dropout masks are again
+  nn.Dropout's probabilities from the device's generator, NOT torch's dropout stream.  The two switches combine freely: either
+  half of a layer is fused or stock torch.
 * the mean over the K tokens is stock torch.
 """
 import numpy as np
@@ -112,6 +118,9 @@ class TPNetEmbedding(nn.Module):
     # the token-mixing half of every mixer as one launch forward and one backward when a gradient IS recorded: opt-in
     # (profiles/mixer_token_training.md); its dropout masks are the device generator's, not torch's stream
     fused_token_training = False
+    # the channel-mixing half of every mixer as one launch forward and two backward on the matrix cores (fp32 class) when a
+    # gradient IS recorded: opt-in (profiles/mixer_channel_training.md); its dropout masks are the device generator's too
+    fused_channel_training = False
 
     def __init__(self, node_raw_features: torch.Tensor, edge_raw_features: torch.Tensor, neighbor_sampler, time_encoder: nn.Module,
                  node_feat_dim: int, edge_feat_dim: int, time_feat_dim: int, num_layers: int, num_neighbors: int, dropout: float,
@@ -190,16 +199,14 @@ class TPNetEmbedding(nn.Module):
                 return None
         return _fm.prepared(mixer)
 
-    def _fused_token_rate(self, mixer, x):
-        """The dropout rate at which the token-mixing half of `mixer` runs as token_train on `x`, else None: `fused_token_training`
-        set, a gradient recorded, x contiguous float32 on the GPU, a shape tpnet_mixer_supported accepts and both dropouts of the
-        token FFN at the same p < 1.  In eval mode the rate is 0."""
-        if not self.fused_token_training or not torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 \
-                or not x.is_contiguous():
+    def _fused_training_rate(self, switch, ffn, mixer, x):
+        """The dropout rate at which a half of `mixer` (its FeedForwardNet's layers `ffn`) runs as token_train / channel_train on
+        `x`, else None: `switch` set, a gradient recorded, x contiguous float32 on the GPU, a shape tpnet_mixer_supported accepts
+        and both dropouts of `ffn` at the same p < 1.  In eval mode the rate is 0."""
+        if not switch or not torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
             return None
         if _fm.layers_of(mixer) is None:
             return None
-        ffn = mixer.token_feedforward.ffn
         p = float(ffn[2].p)
         if p != float(ffn[4].p) or not 0.0 <= p < 1.0 or not _fm.supported(mixer):
             return None
@@ -231,10 +238,21 @@ class TPNetEmbedding(nn.Module):
             embeddings = self.projection_layer(torch.cat(parts, dim=2))
         # (TPNet.py:332 calls masked_fill out of place and drops the result: pad neighbours are NOT masked)
         for mlp_mixer in self.mlp_mixers:
-            rate = self._fused_token_rate(mlp_mixer, embeddings)
-            if rate is not None:
-                tokens = _fm.token_train(mlp_mixer, embeddings, rate)
-                embeddings = mlp_mixer.channel_feedforward(mlp_mixer.channel_norm(tokens)) + tokens
+            if self.fused_token_training or self.fused_channel_training:
+                rate = self._fused_training_rate(self.fused_token_training, mlp_mixer.token_feedforward.ffn, mlp_mixer, embeddings)
+                crate = self._fused_training_rate(self.fused_channel_training, mlp_mixer.channel_feedforward.ffn, mlp_mixer, embeddings)
+            else:
+                rate = crate = None
+            if rate is not None or crate is not None:
+                if rate is not None:
+                    tokens = _fm.token_train(mlp_mixer, embeddings, rate)
+                else:
+                    hidden = mlp_mixer.token_feedforward(mlp_mixer.token_norm(embeddings.permute(0, 2, 1))).permute(0, 2, 1)
+                    tokens = (hidden + embeddings).contiguous()
+                if crate is not None:
+                    embeddings = _fm.channel_train(mlp_mixer, tokens, crate)
+                else:
+                    embeddings = mlp_mixer.channel_feedforward(mlp_mixer.channel_norm(tokens)) + tokens
                 continue
             prep = self._fused_mixer_prep(mlp_mixer, embeddings)
             embeddings = mlp_mixer(embeddings) if prep is None else _fm.mixer_forward(prep, mlp_mixer, embeddings)

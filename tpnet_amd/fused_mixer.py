@@ -9,6 +9,13 @@ The token-mixing half also runs in a TRAINING step (csrc/mixer_token_train.hip; 
 `token_train` is x + token_feedforward(token_norm(x^T))^T with both dropouts as ONE launch forward and ONE launch backward under
 autograd.  The backward recomputes the forward from x, so x is the only activation saved.  The dropout masks come from a
 counter-based generator on the device, keyed per call (include/tpnet_hip.h): they follow nn.Dropout's probabilities but are NOT
+torch's dropout stream.
+
+So does the channel-mixing half (csrc/mixer_channel_train.hip; opt-in, TPNetEmbedding.fused_channel_training): `channel_train` is
+x + channel_feedforward(channel_norm(x)) with both dropouts as ONE launch forward and TWO backward on the matrix cores, in the
+fp32 class.  Again x is the only activation saved; the backward's transposed operands live in a workspace that is allocated and
+freed inside the backward.  Its second image (W1, W2^T, W1^T) sits in the same per-mixer record and is written with the first once
+a training call has asked for it.  Its masks are again nn.Dropout's probabilities from the device's counter-based generator, NOT
 torch's dropout stream."""
 import weakref
 from typing import NamedTuple
@@ -19,9 +26,13 @@ from . import _dense, _lib
 
 _PREPARED = weakref.WeakKeyDictionary()                 # mixer -> Prepared
 # launches made through this binding (tests assert the dispatch through it)
-calls = {"token": 0, "channel": 0, "prepare": 0, "token_train": 0, "token_bwd": 0}
+calls = {"token": 0, "channel": 0, "prepare": 0, "token_train": 0, "token_bwd": 0, "channel_train": 0, "channel_bwd": 0}
 MAX_PARTIALS = 256                                      # workgroups of a backward launch = partial sums it writes, at most
 _PARTIALS = {}                                          # (device, floats per partial) -> the reused [MAX_PARTIALS, floats] buffer
+# row parts of the channel backward's weight kernel = partial sums it writes, at most: 2 ceil(Ch / 32) waves per part, so 32 parts of
+# the reference's 172 -> 688 -> 172 are 1 408 waves for the 1 024 SIMDs, and 32 partials of 237 876 floats are 30 MB
+# (profiles/mixer_channel_training.md)
+CHANNEL_PARTIALS = 32
 
 layers_of = _dense.mixer_layers                         # the structural test: MixerLayers, or None for another module
 
@@ -31,6 +42,7 @@ class Prepared(NamedTuple):
     dims: tuple         # K, Kh, C, Ch
     img: torch.Tensor   # the channel FFN's weight image (uint8)
     storage: tuple      # device + the Parameters' data_ptr()s + dims: the same storage keeps the image buffer
+    bimg: torch.Tensor = None   # the channel backward's image of (W1, W2^T, W1^T), once a training call asked for it (then kept current)
 
 
 def _dims(ls):
@@ -69,9 +81,10 @@ def cached(mixer):
     return _PREPARED.get(mixer)
 
 
-def prepared(mixer):
+def prepared(mixer, backward=False):
     """The Prepared record of `mixer`, or None where the kernels do not serve it.  The image is rewritten in place, on the current
-    stream, when a Parameter of the channel FFN changed through a versioned op (optimizer step, load_state_dict, copy_())."""
+    stream, when a Parameter of the channel FFN changed through a versioned op (optimizer step, load_state_dict, copy_()).
+    `backward`: the record also holds the channel backward's image; from then on both are rewritten together."""
     ls = layers_of(mixer)
     if ls is None:
         return None
@@ -82,18 +95,28 @@ def prepared(mixer):
         if not supported(mixer):
             return None
         lib = _lib.load()
+        img = bimg = None
         if previous is not None:
-            img = previous.img
+            img, bimg = previous.img, previous.bimg
         else:
             img = torch.empty(int(lib.tpnet_mixer_channel_image_bytes(d[2], d[3])), dtype=torch.uint8, device=w1.device)
         _lib.check(lib.tpnet_mixer_channel_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), d[2], d[3], img.data_ptr(),
                                                    _dense.stream_ptr(w1.device)), "mixer_channel_prepare")
+        if backward or bimg is not None:
+            if bimg is None:
+                bimg = torch.empty(int(lib.tpnet_mixer_channel_bwd_image_bytes(d[2], d[3])), dtype=torch.uint8, device=w1.device)
+            _lib.check(lib.tpnet_mixer_channel_bwd_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), d[2], d[3], bimg.data_ptr(),
+                                                           _dense.stream_ptr(w1.device)), "mixer_channel_bwd_prepare")
         calls["prepare"] += 1
-        return Prepared(key, d, img, storage)
+        return Prepared(key, d, img, storage, bimg)
 
     key = d + _dense.param_key(w1, b1, w2, b2)
     storage = (w1.device, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()) + d
-    return _dense.cached(_PREPARED, mixer, key, storage, build)
+    rec = _dense.cached(_PREPARED, mixer, key, storage, build)
+    if backward and rec is not None and rec.bimg is None:       # (a record an inference call made: both images, once)
+        _PREPARED.pop(mixer)
+        rec = _dense.cached(_PREPARED, mixer, key, storage, build)
+    return rec
 
 
 def mixer_token(mixer, x):
@@ -224,4 +247,101 @@ def token_masks(mixer, n, C, p, key):
     m2 = torch.empty((n, K, C), dtype=torch.uint8, device=dev)
     _lib.check(_lib.load().tpnet_mixer_token_masks(n, K, Kh, C, float(p), int(key) & (1 << 64) - 1, m1.data_ptr(), m2.data_ptr(),
                                                    _dense.stream_ptr(dev)), "mixer_token_masks")
+    return m1.bool(), m2.bool()
+
+
+class _ChannelTrain(torch.autograd.Function):
+    """Forward: tpnet_mixer_channel_train.  Saved: x and the six Parameters (the images are derived from them and looked up again in
+    the backward: an in-place change in between raises as torch does).  Backward: tpnet_mixer_channel_bwd in a workspace of its
+    own + the fixed-order sum of its partials."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, w1, b1, w2, b2, mixer, eps, p, key):
+        Ch, C = w1.shape
+        prep = prepared(mixer, backward=True)
+        out = torch.empty_like(x)
+        if x.numel() > 0:                                       # (an empty tensor has no pointer to give)
+            _lib.check(_lib.load().tpnet_mixer_channel_train(x.data_ptr(), x.numel() // C, C, Ch, gamma.data_ptr(), beta.data_ptr(), eps,
+                                                             prep.img.data_ptr(), p, key, out.data_ptr(), _dense.stream_ptr(x.device)),
+                       "mixer_channel_train")
+            calls["channel_train"] += 1
+        ctx.save_for_backward(x, gamma, beta, w1, b1, w2, b2)
+        ctx.mixer = mixer
+        ctx.consts = (eps, p, key)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, gamma, beta, w1, b1, w2, b2 = ctx.saved_tensors
+        eps, p, key = ctx.consts
+        Ch, C = w1.shape
+        n = x.numel() // C
+        gy = gy.contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        tot = None
+        if n > 0:
+            lib = _lib.load()
+            prep = prepared(ctx.mixer, backward=True)           # (current: the saved Parameters are unchanged, or torch has raised)
+            pf = int(lib.tpnet_mixer_channel_bwd_partial_floats(C, Ch))
+            pkey = (x.device, pf, CHANNEL_PARTIALS)
+            part = _PARTIALS.get(pkey)
+            if part is None:
+                part = _PARTIALS[pkey] = torch.empty((CHANNEL_PARTIALS, pf), dtype=torch.float32, device=x.device)
+            ws = torch.empty(int(lib.tpnet_mixer_channel_bwd_workspace_bytes(n, C, Ch)), dtype=torch.uint8, device=x.device)
+            rc = lib.tpnet_mixer_channel_bwd(x.data_ptr(), gy.data_ptr(), n, C, Ch, gamma.data_ptr(), beta.data_ptr(), eps,
+                                             prep.bimg.data_ptr(), p, key, ws.data_ptr(),
+                                             None if gx is None else gx.data_ptr(), part.data_ptr(), part.shape[0],
+                                             _dense.stream_ptr(x.device))
+            if rc <= 0:
+                _lib.check(rc if rc < 0 else -1, "mixer_channel_bwd")
+            calls["channel_bwd"] += 1
+            tot = part[:rc].sum(0)                              # fixed order: run-to-run identical bits
+            del ws                                              # (the caching allocator keeps it alive for the stream's launches)
+        grads, off = [], 0
+        for i, t in enumerate((gamma, beta, w1, b1, w2, b2)):
+            g = None
+            if ctx.needs_input_grad[1 + i]:
+                g = torch.zeros_like(t) if tot is None else tot[off:off + t.numel()].view(t.shape)
+            grads.append(g)
+            off += t.numel()
+        return (gx, *grads, None, None, None, None)
+
+
+def _channel_params(ls):
+    return _params(ls)[6:]
+
+
+def channel_train(mixer, x, p, key=None):
+    """x + channel_feedforward(channel_norm(x)) of x [..., C] float32 (contiguous, on the Parameters' device) with both dropouts of
+    the channel FFN at rate `p` (0 <= p < 1; 0: none), differentiable with respect to x and the six Parameters: one launch forward,
+    two backward (+ the sum of at most CHANNEL_PARTIALS partial results), no synchronisation, on the matrix cores in the
+    project's fp32 class.  `key`: the 64-bit key of this call's dropout draws; None draws one from torch's default CPU generator,
+    so torch.manual_seed makes a run reproducible.  The masks are nn.Dropout's probabilities from the device's counter-based
+    generator (channel_masks returns them), NOT torch's dropout stream."""
+    ls = layers_of(mixer)
+    C = _dims(ls)[2]
+    if x.dtype != torch.float32 or x.dim() < 1 or x.shape[-1] != C or not x.is_contiguous() \
+            or x.device != ls.channel_norm.weight.device:
+        raise ValueError("channel_train: x must be a contiguous float32 [..., C] on the mixer's device")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("channel_train: 0 <= p < 1")
+    if prepared(mixer, backward=True) is None:
+        raise ValueError("channel_train: the kernels do not serve this mixer")
+    if key is None:
+        key = _new_key() if p > 0.0 else 0
+    return _ChannelTrain.apply(x, *_channel_params(ls), mixer, float(ls.channel_norm.eps), p, int(key) & (1 << 64) - 1)
+
+
+def channel_masks(mixer, n_rows, p, key):
+    """The keep masks channel_train(mixer, x [n_rows, C], p, key) applies, as bool tensors: m1 [n_rows, Ch] (behind the GELU) and
+    m2 [n_rows, C] (behind the second Linear)."""
+    ls = layers_of(mixer)
+    C, Ch = _dims(ls)[2:]
+    dev = ls.channel_norm.weight.device
+    m1 = torch.empty((n_rows, Ch), dtype=torch.uint8, device=dev)
+    m2 = torch.empty((n_rows, C), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().tpnet_mixer_channel_masks(n_rows, C, Ch, float(p), int(key) & (1 << 64) - 1, m1.data_ptr(), m2.data_ptr(),
+                                                     _dense.stream_ptr(dev)), "mixer_channel_masks")
     return m1.bool(), m2.bool()
