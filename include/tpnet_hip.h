@@ -929,6 +929,51 @@ int tpnet_mixer_channel_bwd(const float* x, const float* gy, int64_t n_rows, int
                             float* partial, int32_t n_partial, void* stream);
 int tpnet_mixer_channel_masks(int64_t n_rows, int32_t C, int32_t Ch, float p, uint64_t key, uint8_t* m1, uint8_t* m2, void* stream);
 
+/* ---- the encoder's input stage in a training step: forward that records the ReLU decisions, backward (additive to ABI 7;
+ * csrc/encoder_input_train.hip) ------------------------------------------------------------------------------
+ * Arguments, sources, dims, weight image (img: tpnet_encoder_input_prepare's) and error word as tpnet_encoder_input's; n = n_nodes * K
+ * rows, x[row] the row's concat, Din = Dn + Dt + De + 2 F, NW = ceil(H / 32):
+ *   tpnet_encoder_input_train:  tpnet_encoder_input's launch -- out has its bits -- that also stores relu_bits [n][NW] uint32 (4-byte
+ *                               aligned): bit u % 32 of word u / 32 of a row is (W1 . x + b1)[u] > 0 exactly as this launch decided it;
+ *                               bits of units >= H are 0.  Serves everything tpnet_encoder_input serves.  ONE launch.
+ *   tpnet_encoder_input_bwd:    from gy = dL/dout [n][Dout] (16-byte aligned) and relu_bits = m, TWO launches:
+ *                                 a = W1 . x + b1, h = m ? a : 0, gh = W2^T . gy, ga = m ? gh : 0,
+ *                                 gw1 = sum ga (x) x, gb1 = sum ga, gw2 = sum gy (x) h, gb2 = sum gy,
+ *                                 gxt = W1[:, time columns]^T . ga, gtw = sum gxt (-sin(tw lt + tb)) lt, gtb = sum gxt (-sin(tw lt + tb)),
+ *                                 gfeat[row] | gfeat[n + row] = W1[:, relative-encoding columns]^T . ga       (every sum over the rows)
+ *                               with lt = log(f32(tq - tn) + 1).  The raw tables take no gradient.  gfeat [2 n][F] (16-byte aligned;
+ *                               neither feat nor gy) may be NULL: not computed.  time_grads = 0: gtw and gtb are written as zeros.
+ *                               min(n_partial, ceil(n / 32)) or fewer partial sums of the six parameter gradients are written, one per
+ *                               part of the rows.  A partial is tpnet_encoder_input_bwd_partial_floats(dims) = H Din + H + Dout H +
+ *                               Dout + 2 Dt floats, laid out gw1 [H][Din] | gb1 [H] | gw2 [Dout][H] | gb2 [Dout] | gtw [Dt] | gtb [Dt],
+ *                               unpadded, partial i at partial + i * that many floats; `partial` (4-byte aligned) holds n_partial >= 1
+ *                               of them, those beyond the returned count are not written.  Returns that count (>= 0; 0 for n = 0) or a
+ *                               negative error.  The caller adds the partials in a fixed order; the kernels use no atomics but the
+ *                               error word's, so two calls give equal bits.
+ *                               bimg: the backward's image (tpnet_encoder_input_bwd_image_bytes; tpnet_encoder_input_bwd_prepare writes
+ *                               it from w1 [H][Din], b1 [H] and w2 [Dout][H] in ONE launch; again whenever one of the three changed).
+ *                               workspace: tpnet_encoder_input_bwd_workspace_bytes(n, dims) = ceil(n / 32) 32 (2 pad(H) + pad(Din) +
+ *                               pad(Dout) + pad(Dt) + 1) 4 bytes, pad(v) = 32 ceil(v / 32); 16-byte aligned, the call's own: its contents
+ *                               mean nothing before or after the two launches.
+ * Served by the backward: tpnet_encoder_input_supported's sizes with Dt + 2 F <= 256 and n <= 2^31; the three size entries are host
+ * arithmetic and return 0 for anything else.  An id outside node_raw / edge_raw reads row 0 and sets err[0] in the backward as in the
+ * forward.  Null pointers, misaligned arrays, unserved sizes, n_partial < 1, gfeat == feat or gy: TPNET_ERR_BAD_ARG, nothing launched;
+ * all of these are checked before any GPU call.  n = 0: TPNET_OK / 0, nothing launched.  Every product is the fp32 class on the matrix
+ * cores; sin, the masks and the column sums are plain fp32. */
+int tpnet_encoder_input_train(const float* node_raw, int64_t n_node_rows, const float* edge_raw, int64_t n_edge_rows,
+                              const int64_t* neigh, const int64_t* eid, const double* tn, const double* tq, const float* tw,
+                              const float* tb, const float* feat, int64_t n_nodes, int32_t K, const int32_t* dims, const void* img,
+                              float* out, uint32_t* relu_bits, uint32_t* err, void* stream);
+size_t tpnet_encoder_input_bwd_image_bytes(int32_t Dn, int32_t Dt, int32_t De, int32_t F, int32_t H, int32_t Dout);
+int64_t tpnet_encoder_input_bwd_partial_floats(int32_t Dn, int32_t Dt, int32_t De, int32_t F, int32_t H, int32_t Dout);
+size_t tpnet_encoder_input_bwd_workspace_bytes(int64_t n_rows, int32_t Dn, int32_t Dt, int32_t De, int32_t F, int32_t H, int32_t Dout);
+int tpnet_encoder_input_bwd_prepare(const float* w1, const float* b1, const float* w2, const int32_t* dims, void* bimg, void* stream);
+int tpnet_encoder_input_bwd(const float* node_raw, int64_t n_node_rows, const float* edge_raw, int64_t n_edge_rows, const int64_t* neigh,
+                            const int64_t* eid, const double* tn, const double* tq, const float* tw, const float* tb, const float* feat,
+                            const uint32_t* relu_bits, const float* gy, int64_t n_nodes, int32_t K, const int32_t* dims,
+                            const void* bimg, void* workspace, float* gfeat, int32_t time_grads, float* partial, int32_t n_partial,
+                            uint32_t* err, void* stream);
+
 /* Copies st->err to the host (synchronises the stream): returns TPNET_ERR_INDEX if any bad id was seen since
  * the last call (and clears the words), TPNET_OK otherwise. */
 int tpnet_check_errors(const tpnet_state* st, void* stream);

@@ -156,6 +156,14 @@ SIGNATURES = {
     "tpnet_encoder_input": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32,
                                       C.POINTER(C.c_int32), _P, _P, _P, _P]),
     "tpnet_encoder_input_check": (C.c_int, [_P, _P]),
+    "tpnet_encoder_input_train": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32,
+                                            C.POINTER(C.c_int32), _P, _P, _P, _P, _P]),
+    "tpnet_encoder_input_bwd_image_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "tpnet_encoder_input_bwd_partial_floats": (C.c_int64, [C.c_int32] * 6),
+    "tpnet_encoder_input_bwd_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 6),
+    "tpnet_encoder_input_bwd_prepare": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32), _P, _P]),
+    "tpnet_encoder_input_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32,
+                                          C.POINTER(C.c_int32), _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     "tpnet_mixer_supported": (C.c_int, [C.c_int32] * 4),
     "tpnet_mixer_channel_image_bytes": (C.c_size_t, [C.c_int32] * 2),
     "tpnet_mixer_channel_prepare": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),

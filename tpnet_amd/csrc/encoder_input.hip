@@ -6,27 +6,9 @@
 // dense2.hpp's, in the fp32 class of mfma_split.hpp; this file is the row source.  H <= 352 and Dout <= 192 keep all 11 hidden slices
 // in accumulators; a wider hidden layer or more outputs take passes of 8 slices with 8 output tiles.  313 workgroups at 40 000 rows.
 // Ids outside node_raw / edge_raw read row 0 and set err[0] (tpnet_encoder_input_check reports it); no hand-off between workgroups.
-#include "dense2.hpp"
+#include "encoder_input.hpp"
 
 namespace tpnet {
-
-struct ei_dims {
-    int Dn, Dt, De, F;                           // the segments of a row: node | time | edge | two halves of F relative encodings
-    d2_dims l;                                   // the layers: Din = Dn + Dt + De + 2 F, H, Dout and the variant
-};
-
-static bool ei_make_dims(const int32_t* d, ei_dims& o) {
-    if (!d) return false;
-    o.Dn = d[0]; o.Dt = d[1]; o.De = d[2]; o.F = d[3];
-    const int H = d[4], Dout = d[5];
-    if (o.Dn < 4 || o.Dt < 4 || o.De < 4 || o.F < 4 || H < 1 || Dout < 4) return false;
-    if ((o.Dn | o.Dt | o.De | o.F | Dout) & 3) return false;
-    if (o.Dn > 1024 || o.Dt > 1024 || o.De > 1024 || o.F > 512 || H > 512 || Dout > 256) return false;
-    const int Din = o.Dn + o.Dt + o.De + 2 * o.F;
-    if (Din > 1024) return false;
-    d2_make_dims(Din, H, Dout, false, o.l);
-    return true;
-}
 
 // HG hidden slices per pass, OSM output tiles, MULTI: dense2_rows'
 template <int HG, int OSM, bool MULTI>
@@ -41,35 +23,10 @@ __global__ __launch_bounds__(D2_T) void k_encoder_input(const float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31;
     const int64_t row = ((int64_t)blockIdx.x * 4 + wave) * 32 + r;
-    const bool valid = row < n;
-    // ---- this lane's row: the four sources and the scaled time delta (f64 difference -> f32 -> log(x + 1), TPNet.py:299-301)
-    const float *nrow = node_raw, *erow = edge_raw, *f1 = feat, *f2 = feat;
-    float lt = 0.0f;
-    if (valid) {
-        int64_t ni = neigh[row], ei = eid[row];
-        bool bad = false;
-        if (ni < 0 || ni >= n_node_rows) { ni = 0; bad = true; }
-        if (ei < 0 || ei >= n_edge_rows) { ei = 0; bad = true; }
-        if (bad) atomicOr(err, 1u);
-        nrow = node_raw + ni * d.Dn;
-        erow = edge_raw + ei * d.De;
-        f1 = feat + row * d.F;
-        f2 = feat + (n + row) * d.F;
-        lt = logf((float)(tq[row / K] - tn[row]) + 1.0f);
-    }
-    const int e0 = d.Dn, e1 = e0 + d.Dt, e2 = e1 + d.De, e3 = e2 + d.F, e4 = e3 + d.F;
-    // columns c .. c + 3 of the row's concat (c % 4 == 0: one segment)
-    auto x4 = [&](int c) -> float4 {
-        if (!valid || c >= e4) return make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c < e0) return *reinterpret_cast<const float4*>(nrow + c);
-        if (c < e1) {
-            const float4 a = *reinterpret_cast<const float4*>(tw + (c - e0)), b = *reinterpret_cast<const float4*>(tb + (c - e0));
-            return make_float4(cosf(a.x * lt + b.x), cosf(a.y * lt + b.y), cosf(a.z * lt + b.z), cosf(a.w * lt + b.w));
-        }
-        if (c < e2) return *reinterpret_cast<const float4*>(erow + (c - e1));
-        if (c < e3) return *reinterpret_cast<const float4*>(f1 + (c - e2));
-        return *reinterpret_cast<const float4*>(f2 + (c - e3));
-    };
+    const ei_src src{node_raw, edge_raw, tw, tb, feat, neigh, eid, tn, tq, n_node_rows, n_edge_rows, n, K};
+    ei_row x4;
+    x4.init(src, d, row, err);
+    const bool valid = x4.valid;
     float* yo = out + row * d.l.Dout;
     dense2_rows<HG, OSM, MULTI, act_relu>(d.l, img, valid, x4, [&](int o, const float4 v) { *reinterpret_cast<float4*>(yo + o) = v; });
 }

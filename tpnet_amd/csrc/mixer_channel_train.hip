@@ -41,6 +41,7 @@
 // hidden unit has a = 0 and gh = 0; what is parked for it, and for columns >= C, is again a selected 0.0f.  An accumulator row or column of the
 // padding is never written to a partial.
 #include "mixer_channel.hpp"
+#include "rows_contract.hpp"
 
 namespace tpnet {
 
@@ -478,27 +479,8 @@ __global__ __launch_bounds__(256) void k_mxc_bwd_weights(const mxc_ws ws, int64_
     for (int t = 0; t < MXC_WT; ++t)
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[t][q] = 0.0f;
-    float asum = 0.0f;
-    for (int64_t t = t0; t < t1; ++t) {
-        const float* At = A + ((t * ws.CHS + 32 * slice + r) * 32 + 8 * h);
-        const float* Bt = B + ((t * ws.CS + r) * 32 + 8 * h);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const float4 a0 = *reinterpret_cast<const float4*>(At + 16 * ks), a1 = *reinterpret_cast<const float4*>(At + 16 * ks + 4);
-            asum += ((a0.x + a0.y) + (a0.z + a0.w)) + ((a1.x + a1.y) + (a1.z + a1.w));
-            bf16x8 ah, al;
-            split8(a0, a1, ah, al);
-#pragma unroll
-            for (int tt = 0; tt < MXC_WT; ++tt) {
-                if (tt < nt) {
-                    bf16x8 bh, bl;
-                    load_split8(Bt + (int64_t)tt * 32 * 32 + 16 * ks, bh, bl);
-                    acc[tt] = mm3(ah, al, bh, bl, acc[tt]);
-                }
-            }
-        }
-    }
-    // acc[t][q] = sum over rows of A[unit 32 slice + acc_row(q, h)] B[column 32 t + r]
+    // (rows_contract.hpp) acc[t][q] = sum over rows of A[unit 32 slice + acc_row(q, h)] B[column 32 t + r]
+    float asum = rc_walk(A, ws.CHS, slice, B, ws.CS, 0, nt, t0, t1, r, h, acc);
 #pragma unroll
     for (int tt = 0; tt < MXC_WT; ++tt) {
         const int c = 32 * tt + r;

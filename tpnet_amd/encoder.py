@@ -14,6 +14,13 @@ What differs is where the work runs:
   `torch.no_grad()` / inference mode, with the module on the GPU, `fused_input` set and a served shape, ONE launch on the matrix
   cores (tpnet_amd/fused_input.py, csrc/encoder_input.hip) that never writes the [2B, K, Din] concat.  When gradients are recorded
   the torch layers serve, and autograd reaches `projection_layer`, the time encoder and `rp.mlp` as in the reference.
+* with `TPNetEmbedding.fused_input_training` set (it defaults to False), when a gradient IS recorded, with the module on the GPU,
+  relative encodings present in a served shape (the forward's, with time_feat_dim + random_feature_dim <= 256), contiguous float32
+  Parameters and raw feature tables that take no gradient, the input stage is ONE launch forward and TWO backward on the matrix
+  cores in the project's fp32 class (fused_input.encoder_input_train, csrc/encoder_input_train.hip).  The forward stores one bit
+  per (row, hidden unit), the ReLU's decision; the concat and the hidden layer are not kept, the backward rebuilds the concat from
+  the sources in a workspace it allocates and frees.  Gradients reach `projection_layer`, the time encoder and, through the
+  relative encodings, `rp.mlp`.  It combines freely with the other switches.
 * the MLP-Mixer layers are stock torch unless `TPNetEmbedding.fused_mixer` is set (it defaults to False): then, under
   `torch.no_grad()` / inference mode, on contiguous float32 embeddings on the GPU, with no dropout active (eval mode, or dropout 0)
   and a served shape, every layer is TWO launches (tpnet_amd/fused_mixer.py, csrc/mixer.hip): token mixing in exact fp32, channel
@@ -121,6 +128,10 @@ class TPNetEmbedding(nn.Module):
     # the channel-mixing half of every mixer as one launch forward and two backward on the matrix cores (fp32 class) when a
     # gradient IS recorded: opt-in (profiles/mixer_channel_training.md); its dropout masks are the device generator's too
     fused_channel_training = False
+    # the input stage as one launch forward (that records the ReLU's decisions, one bit per hidden unit) and two backward on the
+    # matrix cores (fp32 class) when a gradient IS recorded: opt-in (profiles/encoder_input_training.md); the concat and the
+    # hidden layer are not kept for the backward
+    fused_input_training = False
 
     def __init__(self, node_raw_features: torch.Tensor, edge_raw_features: torch.Tensor, neighbor_sampler, time_encoder: nn.Module,
                  node_feat_dim: int, edge_feat_dim: int, time_feat_dim: int, num_layers: int, num_neighbors: int, dropout: float,
@@ -187,6 +198,26 @@ class TPNetEmbedding(nn.Module):
             return None
         return _fi.prepared(self.projection_layer, self.node_feat_dim, self.time_feat_dim, self.edge_feat_dim, self.random_feature_dim // 2)
 
+    def _fused_input_training(self, dev, pair_features):
+        """Whether fused_input.encoder_input_train serves this call: `fused_input_training` set, a gradient recorded, module on the
+        GPU, relative encodings present (contiguous float32) in a shape the forward AND the backward serve, the Parameters of
+        projection_layer and of the time encoder contiguous float32, and raw feature tables that take no gradient."""
+        if not self.fused_input_training or not torch.is_grad_enabled() or dev.type != "cuda" or pair_features is None:
+            return False
+        if self.random_feature_dim % 2 or pair_features.shape[1] * 2 != self.random_feature_dim:
+            return False
+        if pair_features.dtype != torch.float32 or not pair_features.is_contiguous():
+            return False
+        if self.node_raw_features.requires_grad or self.edge_raw_features.requires_grad:
+            return False
+        w = getattr(self.time_encoder, "w", None)
+        if not isinstance(w, nn.Linear) or w.bias is None:
+            return False
+        if not all(p.is_cuda and p.is_contiguous() and p.dtype == torch.float32 for p in (w.weight, w.bias)):
+            return False
+        return _fi.prepared(self.projection_layer, self.node_feat_dim, self.time_feat_dim, self.edge_feat_dim,
+                            self.random_feature_dim // 2, backward=True) is not None
+
     def _fused_mixer_prep(self, mixer, x):
         """The prepared channel image if the two-launch layer serves `mixer` on `x`, else None: `fused_mixer` set, no gradient
         recorded, x contiguous float32 on the GPU, no dropout active (eval mode, or every dropout of the mixer 0 -- a no_grad call in
@@ -225,6 +256,9 @@ class TPNetEmbedding(nn.Module):
             w = self.time_encoder.w
             embeddings = _fi.encoder_input(prep, self.node_raw_features, self.edge_raw_features, neigh, eids, tn, tq, w.weight, w.bias,
                                            pair_features)
+        elif self._fused_input_training(dev, pair_features):
+            embeddings = _fi.encoder_input_train(self.projection_layer, self.time_encoder, self.node_raw_features, self.edge_raw_features,
+                                                 neigh, eids, tn, tq, pair_features)
         else:
             neighbor_node_features = self.node_raw_features[neigh]
             # the delta in f64, cast to f32, then log(x + 1) (TPNet.py:299-301)
