@@ -1,5 +1,5 @@
 """tpnet_amd/_dense.py: what the four fused_* modules share -- the Linear -> ReLU -> Linear predicate, the fp32 gradient
-expressions and the cache of derived weight buffers.  No GPU needed."""
+expressions, the cache of derived weight buffers and the Python side of a backward that writes partial sums.  No GPU needed."""
 import copy
 import gc
 import weakref
@@ -150,3 +150,90 @@ def test_layer_grads_match_autograd():
         torch.testing.assert_close(g, w, rtol=1e-12, atol=1e-12)
     for g, w in zip(four, got):
         assert torch.equal(g, w)
+
+
+def test_split_grads_cuts_in_order_and_respects_needs():
+    """One summed partial cut into per-tensor gradients: shapes of several ranks, None where not needed (the offset still moves
+    past it), views of `tot` rather than copies."""
+    tensors = (torch.empty(3), torch.empty(2, 5), torch.empty(()), torch.empty(4, 1, 2), torch.empty(0, 7), torch.empty(6))
+    total = sum(t.numel() for t in tensors)
+    tot = torch.arange(total, dtype=torch.float32)
+    needs = (True, False, True, True, True, True)
+    got = _dense.split_grads(tot, tensors, needs)
+    assert len(got) == len(tensors) and got[1] is None
+    off = 0
+    for t, need, g in zip(tensors, needs, got):
+        if need:
+            assert g.shape == t.shape and g.dtype == tot.dtype
+            assert torch.equal(g.reshape(-1), tot[off:off + t.numel()])
+            assert t.numel() == 0 or g.data_ptr() == tot[off:].data_ptr()
+        off += t.numel()
+    assert off == total
+    assert _dense.split_grads(tot, tensors, (False,) * 6) == [None] * 6
+    assert _dense.split_grads(tot, (), ()) == []
+
+
+def test_split_grads_without_a_total_gives_zeros():
+    tensors = (torch.full((2, 3), 7.0), torch.full((4,), 7.0, dtype=torch.float64), torch.full((1, 1, 5), 7.0))
+    got = _dense.split_grads(None, tensors, (True, False, True))
+    assert got[1] is None
+    for t, g in ((tensors[0], got[0]), (tensors[2], got[2])):
+        assert g.shape == t.shape and g.dtype == t.dtype and g.device == t.device and not g.any()
+    assert tensors[0].eq(7.0).all()                                               # (new tensors: the Parameters are untouched)
+
+
+def test_partial_buffer_is_one_per_device_parts_and_floats():
+    cpu = torch.device("cpu")
+    a = _dense.partial_buffer(cpu, 5, 11)
+    assert tuple(a.shape) == (5, 11) and a.dtype == torch.float32 and a.device == cpu
+    assert _dense.partial_buffer(cpu, 5, 11) is a                                 # the same key: the same tensor
+    b = _dense.partial_buffer(cpu, 6, 11)                                         # another part count: a new buffer of that size
+    assert b is not a and tuple(b.shape) == (6, 11)
+    c = _dense.partial_buffer(cpu, 5, 12)
+    assert c is not a and c is not b and tuple(c.shape) == (5, 12)
+    assert _dense.partial_buffer(cpu, 5, 11) is a and _dense.partial_buffer(cpu, 6, 11) is b
+    assert _dense.partial_buffer(cpu, 5, 11.0) is a                               # (the C calls' sizes arrive as ctypes / int64 values)
+
+
+def test_sum_partials_adds_the_written_partials_and_raises_for_none():
+    part = torch.tensor([[1.0, 2.0], [10.0, 20.0], [float("nan"), float("nan")]])
+    assert torch.equal(_dense.sum_partials(2, part, "t"), torch.tensor([11.0, 22.0]))      # rows >= rc are never read
+    assert torch.equal(_dense.sum_partials(1, part, "t"), part[0])
+    from tpnet_amd import _lib
+    for rc in (0, -1):
+        with pytest.raises(_lib.TPNetHipError, match="some_backward"):
+            _dense.sum_partials(rc, part, "some_backward")
+
+
+class _Two(NamedTuple):
+    key: tuple
+    storage: tuple
+    bimg: object = None
+
+
+def test_cached_images_builds_the_second_image_once_asked_and_keeps_it():
+    cache, log = weakref.WeakKeyDictionary(), []
+    owner = nn.Identity()
+
+    def build(previous, both):
+        log.append((previous, both))
+        bimg = previous.bimg if previous is not None else None
+        if both and bimg is None:
+            bimg = object()
+        return _Two(key[0], ("s",), bimg if both else None)
+
+    key = [("k", 0)]
+    serve = lambda backward: _dense.cached_images(cache, owner, key[0], ("s",), build, backward)
+    first = serve(False)
+    assert first.bimg is None and log == [(None, False)] and serve(False) is first and len(log) == 1
+    second = serve(True)                                                          # a record an inference call made: rebuilt once
+    assert second.bimg is not None and log[-1] == (None, True) and len(log) == 2
+    assert serve(True) is second and serve(False) is second and len(log) == 2
+    key[0] = ("k", 1)                                                             # a Parameter changed: both rewritten, also
+    third = serve(False)                                                          # for an inference call
+    assert log[-1] == (second, True) and third.bimg is second.bimg and len(log) == 3
+    # a build that declines the second image (the backward serves fewer shapes) gives None and keeps the inference record
+    cache2, owner2 = weakref.WeakKeyDictionary(), nn.Identity()
+    decl = lambda previous, both: None if both else _Two(("k",), ("s",))
+    rec = _dense.cached_images(cache2, owner2, ("k",), ("s",), decl, False)
+    assert _dense.cached_images(cache2, owner2, ("k",), ("s",), decl, True) is None and cache2[owner2] is rec

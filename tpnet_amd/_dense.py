@@ -1,6 +1,7 @@
 """What the fused_* modules share: the structural tests of a Linear -> ReLU -> Linear block and of an MLP-Mixer layer, the current
-stream as the C calls take it, the fp32 torch expressions of the two layers' gradients, the launch of the matrix-core weight-gradient kernels, and the
-cache of derived weight buffers."""
+stream as the C calls take it, the fp32 torch expressions of the two layers' gradients, the launch of the matrix-core weight-gradient kernels, the
+Python side of a backward that writes partial sums (their buffer, their sum, the cut into per-Parameter gradients), and the cache of
+derived weight buffers."""
 import ctypes as C
 from typing import NamedTuple
 
@@ -73,6 +74,40 @@ def layer_grads(x, gy, w1, b1, w2, input_grad=False):
     return grads + (gh @ w1,) if input_grad else grads
 
 
+_PARTIALS = {}      # (device, parts, floats per partial) -> the reused [parts, floats] buffer
+
+
+def partial_buffer(device, parts, floats):
+    """The float32 [parts, floats] buffer a backward launch writes its partial sums into: one per (device, parts, floats), reused by
+    every later call (the launches of a stream run in order)."""
+    key = (device, int(parts), int(floats))
+    part = _PARTIALS.get(key)
+    if part is None:
+        part = _PARTIALS[key] = torch.empty(key[1:], dtype=torch.float32, device=device)
+    return part
+
+
+def sum_partials(rc, part, what):
+    """The sum of the first `rc` partials in a fixed order: run-to-run identical bits.  rc = the C call's return value: the number of
+    partials written; <= 0 raises as _lib.check does (0: no partial of a call with rows is an error too)."""
+    if rc <= 0:
+        _lib.check(rc if rc < 0 else -1, what)
+    return part[:rc].sum(0)
+
+
+def split_grads(tot, tensors, needs):
+    """`tot` (one summed partial: the gradients of `tensors`, flat, in order) cut into one gradient per tensor, in its shape; None
+    where `needs` says it is not needed, zeros where tot is None (a call without rows)."""
+    grads, off = [], 0
+    for t, need in zip(tensors, needs):
+        g = None
+        if need:
+            g = torch.zeros_like(t) if tot is None else tot[off:off + t.numel()].view(t.shape)
+        grads.append(g)
+        off += t.numel()
+    return grads
+
+
 def mlp64_bwd(call, x, gy, H=256, F=64, pf=None):
     """One launch of a weight-gradient kernel (tpnet_mlp64_bwd_*; tpnet_mlp_rows_bwd_f32 with its (H, F) and partial size `pf`) +
     the fixed-order sum of its workgroups' partial results (deterministic).  A partial is gW1 [H][F] | gW2 [F][H] | gb1 [H].
@@ -88,7 +123,7 @@ def mlp64_bwd(call, x, gy, H=256, F=64, pf=None):
     rc = call(x.data_ptr(), gy.data_ptr(), n, part.data_ptr(), nblk, stream_ptr(x.device))
     if rc <= 0:
         return rc, None
-    tot = part[:rc].sum(0)
+    tot = sum_partials(rc, part, "mlp64_bwd")
     return rc, (tot[:H * F].view(H, F), tot[2 * H * F:2 * H * F + H], tot[H * F:2 * H * F].view(F, H), gy.sum(0))
 
 
@@ -111,4 +146,16 @@ def cached(cache, owner, key, storage, build):
     rec = build(rec if rec is not None and rec.storage == storage else None)
     if rec is not None:
         cache[owner] = rec
+    return rec
+
+
+def cached_images(cache, owner, key, storage, build, backward):
+    """cached() for a record with a second image `bimg` that only a training call needs: build(previous, both) writes the second one
+    too where `both`.  It is built once a call asks with `backward`, and from then on both are rewritten together; a record an
+    inference call made (bimg None) is rebuilt once, from nothing, and kept where that build declines."""
+    rec = cached(cache, owner, key, storage, lambda prev: build(prev, backward or (prev is not None and prev.bimg is not None)))
+    if backward and rec is not None and rec.bimg is None:
+        rec = build(None, True)
+        if rec is not None:
+            cache[owner] = rec
     return rec

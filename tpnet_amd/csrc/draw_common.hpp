@@ -60,4 +60,9 @@ __device__ __forceinline__ uint4 philox_block(uint32_t c0, uint32_t c1, uint32_t
     return make_uint4(c0, c1, c2, c3);
 }
 
+// a dropout rate the training kernels serve, and its threshold floor(p 2^32): a draw (one 32-bit word) keeps where word >= threshold;
+// 0 = no dropout, nothing is drawn
+static inline bool drop_rate(float p) { return p >= 0.0f && p < 1.0f; }         // (a NaN fails both)
+static inline uint32_t drop_threshold(float p) { return (uint32_t)((double)p * 4294967296.0); }
+
 }  // namespace tpnet

@@ -76,17 +76,11 @@ struct ei_row {
     }
 };
 
-static inline bool ei_aligned16(std::initializer_list<const void*> ps) {
-    uintptr_t a = 0;
-    for (const void* p : ps) a |= reinterpret_cast<uintptr_t>(p);
-    return (a & 15) == 0;
-}
-
 // the host's checks of the arrays every input-stage entry takes
 static inline bool ei_src_ok(const ei_src& s, int64_t n_nodes) {
     if (!s.node_raw || !s.edge_raw || !s.neigh || !s.eid || !s.tn || !s.tq || !s.tw || !s.tb || !s.feat) return false;
     if (s.n_node_rows < 1 || s.n_edge_rows < 1 || n_nodes < 0 || s.K < 1 || n_nodes > (1ll << 31) / s.K) return false;
-    return ei_aligned16({s.node_raw, s.edge_raw, s.tw, s.tb, s.feat});
+    return aligned16({s.node_raw, s.edge_raw, s.tw, s.tb, s.feat});
 }
 
 }  // namespace tpnet

@@ -12,14 +12,12 @@
 //                          The backward is the gradient of the forward that ran: the ReLU's decisions are read, not recomputed
 //                          (mlp_rows_bwd.hip recomputes the pre-activations in exact f32 for that; at Din = 572 that pass would be
 //                          ~8 G vector FMAs per call).  Only G = Dt + 2 F columns of W1^T are multiplied: the raw tables take no gradient.
-// THE BACKWARD'S TWO LAUNCHES follow mixer_channel_train.hip's, with a workspace of the call cut into tiles of 32 rows and held
-// TRANSPOSED (rows_contract.hpp):
-//   k_eib_rows     row-tile parallel like the forward, on an image of its own (W1, W2^T and the G columns of W1^T; k_eib_image).  It
-//                  first parks x, gy and the row's lt -- every lane the columns of x it is layer 1's B operand for, so that the passes
-//                  read x back and hold no gather and no cosf.  Per pass of 4 hidden slices it holds TWO layer-1 accumulators per
-//                  slice, a - b1 = W1 . x and gh = W2^T . gy, forms h and ga in registers from the saved bits, parks both, and feeds ga
-//                  as the B operand of gx += W1[:, G columns]^T . ga.  The epilogue stores gxf into gfeat (may be NULL) and parks gxt,
-//                  which a loop behind the accumulators turns into d = gxt (-sin arg) in place.
+// THE BACKWARD'S TWO LAUNCHES are dense2_bwd.hpp's (the transposed workspace of the call, the image of W1, W2^T and the G columns
+// of W1^T, the row-tile body, the padding rules):
+//   k_eib_rows     first parks x, gy and the row's lt -- every lane the columns of x it is layer 1's B operand for, so that the passes
+//                  read x back and hold no gather and no cosf.  Then dense2_bwd_rows with the parked x and gy as the two row
+//                  sources and the rule of the saved bits; y is gx of the G columns.  The epilogue stores gxf into gfeat (may be
+//                  NULL) and parks gxt, which a loop behind the accumulators turns into d = gxt (-sin arg) in place.
 //   k_eib_weights  the contraction over rows.  A wave owns a 32-unit hidden slice of ONE product and up to 8 column tiles of it --
 //                  gw1[slice, 256 columns of Din] = sum_rows ga^T x, or gw2[:, slice]^T = sum_rows h^T gy -- and a workgroup one part
 //                  of the row tiles; gb1 is the sum of the ga operands a wave of gw1's first column group loads.  The last workgroup of
@@ -30,11 +28,10 @@
 // sources is 8 gathers of one float (and a cosf each in the time columns).  The workspace is 128 (2 ceil(H / 32) + ceil(Din / 32) +
 // ceil(Dout / 32) + ceil(Dt / 32)) + 4 bytes per row for the time of the backward (profiles/encoder_input_training.md).
 // ARITHMETIC.  All products are the fp32 class of mfma_split.hpp; sinf, the masks and the column sums are plain fp32.
-// PADDING (mixer_channel_train.hip's rules).  Rows >= n contribute nothing because the LOADS of x and gy are masked and what is parked
-// for them is a selected 0.0f, never a product with zero.  d and lt of such a row are never read by the column sums (they stop at row n).
-// Columns >= Din / Dout / G and hidden units >= H are zero in the image and have bit 0; what is parked for them is again a selected
-// 0.0f.  An accumulator row or column of the padding is never written to a partial or to gfeat.
+// PADDING.  dense2_bwd.hpp's rules: the row sources return zeros for a row >= n, d and lt of such a row are never read by the column
+// sums, a hidden unit of the padding has bit 0, and an accumulator column of the padding is never written to gfeat.
 #include "encoder_input.hpp"
+#include "dense2_bwd.hpp"
 #include "rows_contract.hpp"
 
 namespace tpnet {
@@ -85,133 +82,58 @@ __global__ __launch_bounds__(D2_T) void k_encoder_input_train(const ei_src src, 
                                                [&](int o, const float4 v) { *reinterpret_cast<float4*>(yo + o) = v; }, act);
 }
 
-// ---- the backward's sizes
-static constexpr int EIB_HG = 4;                 // hidden slices per pass: each holds TWO layer-1 accumulators (a and gh)
+// ---- the backward's sizes: dense2_bwd.hpp's with the G = Dt + 2 F columns of x that take a gradient (the time columns from Dn, the
+// relative encodings from Dn + Dt + De).  It serves the forward's sizes with G <= 256 (8 output tiles of the row-tile kernel)
 static constexpr int EIB_WT = 8;                 // accumulator tiles of a weight wave: 256 columns
-// 16-byte elements of a chunk: the larger of a k-step of W1 and of W2^T for EIB_HG slices each and a slice of W1^T for OS output tiles
-__host__ __device__ constexpr int eib_chunk(int OS) { return OS * 256 > 2 * EIB_HG * 128 ? OS * 256 : 2 * EIB_HG * 128; }
-
-struct eib_dims {
-    int Din, H, Dout, Dt, F;
-    int G, ct, cf;                               // G = Dt + 2 F columns of x take a gradient: W1's columns ct .. and cf ..
-    int KS, NP, OS, CH, NS;                      // k-steps of 16 (of the longer of Din and Dout), passes, output tiles (6: G <= 192, else
-};                                               // 8), elements per chunk, hidden slices with a unit
-
-// the backward serves the forward's sizes with G <= 256 (8 output tiles of the row-tile kernel)
-static bool eib_make_dims(const int32_t* v, ei_dims& e, eib_dims& o) {
-    if (!ei_make_dims(v, e)) return false;
-    o.Din = e.l.Din; o.H = e.l.H; o.Dout = e.l.Dout; o.Dt = e.Dt; o.F = e.F;
-    o.G = e.Dt + 2 * e.F;
-    if (o.G > 32 * D2_OS_WIDE) return false;
-    o.ct = e.Dn;
-    o.cf = e.Dn + e.Dt + e.De;
-    const int big = o.Din > o.Dout ? o.Din : o.Dout;
-    o.KS = (big + 15) / 16;
-    o.NS = (o.H + 31) / 32;
-    o.NP = (o.NS + EIB_HG - 1) / EIB_HG;
-    o.OS = o.G <= 32 * D2_OS ? D2_OS : D2_OS_WIDE;
-    o.CH = eib_chunk(o.OS);
+static bool eib_make_dims(const int32_t* v, ei_dims& e, d2b_dims& o) {
+    if (!ei_make_dims(v, e) || e.Dt + 2 * e.F > 32 * D2_OS_WIDE) return false;
+    d2b_make_dims(e.l.Din, e.l.H, e.l.Dout, e.Dt, e.Dn, 2 * e.F, e.Dn + e.Dt + e.De, o);
     return true;
 }
-static __host__ __device__ inline uint32_t eib_chunk_elems(const eib_dims& d) { return (uint32_t)(d.NP * (d.KS + EIB_HG) * d.CH); }
-static size_t eib_image_bytes(const eib_dims& d) { return (size_t)eib_chunk_elems(d) * 16 + (size_t)d.NP * EIB_HG * 32 * sizeof(float); }
-static int64_t eib_partial_floats(const eib_dims& d) {
-    return (int64_t)d.H * d.Din + d.H + (int64_t)d.Dout * d.H + d.Dout + 2 * (int64_t)d.Dt;
+static int64_t eib_partial_floats(const d2b_dims& d) {
+    return (int64_t)d.H * d.Din + d.H + (int64_t)d.Dout * d.H + d.Dout + 2 * (int64_t)d.Gt;
 }
 
-// ---- the backward's workspace: five transposed arrays, tile by tile, and the rows' lt
-struct eib_ws {
-    int NS, CHS, CSI, CSO, CST;                  // hidden slices with a unit; parked units, columns of x, of gy and time columns per tile
-    int64_t T;                                   // tiles of 32 rows
-    float *hT, *gaT, *xT, *gyT, *dT, *lt;        // hT, gaT [T][CHS][32]; xT [T][CSI][32]; gyT [T][CSO][32]; dT [T][CST][32]; lt [T][32]
+// ---- the backward's workspace: dense2_bwd.hpp's head (hT, gaT), three transposed column arrays, tile by tile, and the rows' lt
+struct eib_ws : d2b_ws {
+    int CSI, CSO, CST;                           // parked columns of x, of gy and time columns per tile (multiples of 32)
+    float *xT, *gyT, *dT, *lt;                   // xT [T][CSI][32]; gyT [T][CSO][32]; dT [T][CST][32]; lt [T][32]
 };
-static inline int eib_pad32(int v) { return (v + 31) / 32 * 32; }
-static int64_t eib_ws_floats(int64_t n, const eib_dims& d) {
-    const int64_t T = (n + 31) / 32;
-    return T * 32 * (2 * (int64_t)eib_pad32(d.H) + eib_pad32(d.Din) + eib_pad32(d.Dout) + eib_pad32(d.Dt) + 1);
+static int64_t eib_ws_floats(int64_t n, const d2b_dims& d) {
+    return d2b_tiles(n) * 32 * (2 * (int64_t)d2b_pad32(d.H) + d2b_pad32(d.Din) + d2b_pad32(d.Dout) + d2b_pad32(d.Gt) + 1);
 }
-static eib_ws eib_make_ws(float* base, int64_t n, const eib_dims& d) {
+static eib_ws eib_make_ws(float* base, int64_t n, const d2b_dims& d) {
     eib_ws w;
-    w.NS = d.NS;
-    w.CHS = 32 * d.NS;
-    w.CSI = eib_pad32(d.Din);
-    w.CSO = eib_pad32(d.Dout);
-    w.CST = eib_pad32(d.Dt);
-    w.T = (n + 31) / 32;
-    w.hT = base;
-    w.gaT = w.hT + w.T * w.CHS * 32;
-    w.xT = w.gaT + w.T * w.CHS * 32;
+    w.xT = d2b_make_ws(w, base, n, d.H);
+    w.CSI = d2b_pad32(d.Din);
+    w.CSO = d2b_pad32(d.Dout);
+    w.CST = d2b_pad32(d.Gt);
     w.gyT = w.xT + w.T * w.CSI * 32;
     w.dT = w.gyT + w.T * w.CSO * 32;
     w.lt = w.dT + w.T * w.CST * 32;
     return w;
 }
 
-// The image, chunks of CH elements in the order k_eib_rows consumes them, per pass p (slices w0 = 4 p .. w0 + 3), in dense2.hip's
-// per-lane operand order (lane = 32 h + r, j = 0..7 the element's eight bf16, piece 0 = hi, 1 = lo):
-//   k-step s = 0..KS-1:  element (v * 2 + piece) * 64 + lane, v = 0..3: W1[32 (w0 + v) + r][16 s + 8 h + j]
-//                                                             v = 4..7: W2^T[32 (w0 + v - 4) + r][16 s + 8 h + j] = W2[16 s + 8 h + j][..]
-//   slice wl = 0..3:     element ((s2 * OS + t) * 2 + piece) * 64 + lane = W1[32 (w0 + wl) + acc_row(8 s2 + j, h)][column of g = 32 t + r]
-//                        with g < Dt the time column ct + g, else the relative-encoding column cf + g - Dt
-// zero beyond Din, Dout, G and H and in the rest of a chunk; then b1 padded to 128 NP floats.
-__global__ __launch_bounds__(256) void k_eib_image(const float* __restrict__ w1, const float* __restrict__ b1,
-                                                   const float* __restrict__ w2, const eib_dims d, uint4* __restrict__ img) {
-    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t total = eib_chunk_elems(d);
-    if (e >= total) {
-        const uint32_t f = (e - total) * 4u;                                   // first of four bias floats
-        if (f >= (uint32_t)(d.NP * EIB_HG * 32)) return;
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = f + j < (uint32_t)d.H ? b1[f + j] : 0.0f;
-        reinterpret_cast<float4*>(img + total)[f / 4u] = make_float4(v[0], v[1], v[2], v[3]);
-        return;
+// ---- the backward's rule (dense2_bwd.hpp): h = m ? a : 0 and ga = m ? gh : 0, m the saved bit of the unit -- the four of a block
+// are bits acc_row(4 q4, h) .. + 3 of the slice's word of the lane's row (act_relu_bits wrote it; 0 for a slice of the padding)
+struct rule_relu_bits {
+    const uint32_t* __restrict__ words;          // relu_bits of the lane's row
+    int NW;                                      // ceil(H / 32) words per row; 0 for a row >= n: nothing is read
+    __device__ __forceinline__ uint32_t block(int slice, int q4) const {
+        return (slice < NW ? words[slice] : 0u) >> acc_row(4 * q4, (threadIdx.x >> 5) & 1);
     }
-    const int chunk = e / (uint32_t)d.CH, el = e % (uint32_t)d.CH;
-    const int w0 = chunk / (d.KS + EIB_HG) * EIB_HG, cj = chunk % (d.KS + EIB_HG);
-    const int lane = el & 63, piece = (el >> 6) & 1, r = lane & 31, h = lane >> 5;
-    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (cj < d.KS) {
-        const int vs = el >> 7;
-        const int unit = 32 * (w0 + (vs & 3)) + r;
-        if (vs < 2 * EIB_HG && unit < d.H) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int col = 16 * cj + 8 * h + j;
-                if (vs < EIB_HG) {
-                    if (col < d.Din) v[j] = w1[(size_t)unit * d.Din + col];
-                } else if (col < d.Dout) {
-                    v[j] = w2[(size_t)col * d.H + unit];
-                }
-            }
-        }
-    } else {
-        const int wl = cj - d.KS;
-        const int s2 = el / (d.OS * 128), t = (el >> 7) % d.OS;
-        const int g = 32 * t + r;
-        if (s2 < 2 && g < d.G) {
-            const int col = g < d.Dt ? d.ct + g : d.cf + (g - d.Dt);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int unit = 32 * (w0 + wl) + acc_row(8 * s2 + j, h);
-                if (unit < d.H) v[j] = w1[(size_t)unit * d.Din + col];
-            }
-        }
+    __device__ __forceinline__ void unit(uint32_t m, int j, bool real, float a, float gh, float& hv, float& gav) const {
+        const bool on = ((m >> j) & 1u) != 0u && real;
+        hv = on ? a : 0.0f;
+        gav = on ? gh : 0.0f;
     }
-    bf16x8 hi, lo;
-    split8(v, hi, lo);
-    *reinterpret_cast<bf16x8*>(img + e) = piece ? lo : hi;
-}
+};
 
-// dense2_rows' mapping and chunk pipeline (a workgroup of 4 waves, one 32-row tile per wave, the image's chunks shared through two LDS
-// buffers, one barrier per chunk) with two row sources and two layer-1 accumulators per hidden slice
+// ---- the backward's row-tile kernel: dense2_bwd_rows on the parked x and gy, gfeat and the time encoder's d behind it
 template <int OSM>
-__global__ __launch_bounds__(D2_T) void k_eib_rows(const ei_src src, const ei_dims ed, const eib_dims d, const float* __restrict__ gy,
+__global__ __launch_bounds__(D2_T) void k_eib_rows(const ei_src src, const ei_dims ed, const d2b_dims d, const float* __restrict__ gy,
                                                    const uint32_t* __restrict__ relu_bits, const uint4* __restrict__ img, const eib_ws ws,
                                                    float* __restrict__ gfeat, int time_grads, uint32_t* __restrict__ err) {
-    constexpr int CH = eib_chunk(OSM), PF = CH / D2_T;
-    static_assert(PF == 6 || PF == 8, "the prefetch registers below");
-    __shared__ uint4 buf[2][CH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
@@ -219,20 +141,19 @@ __global__ __launch_bounds__(D2_T) void k_eib_rows(const ei_src src, const ei_di
     ei_row x4;
     x4.init(src, ed, row, err);
     const bool valid = x4.valid, park = tile < ws.T;
-    const int Dout = d.Dout, H = d.H;
+    const int Dout = d.Dout;
     const float* gr = gy + (valid ? row : 0) * Dout;
-    const uint32_t* bits = relu_bits + (valid ? row : 0) * ws.NS;
+    rule_relu_bits rule;
+    rule.NW = valid ? ws.NS : 0;
+    rule.words = relu_bits + (valid ? row : 0) * ws.NS;
     // columns c .. c + 3 of gy
     auto g4 = [&](int c) -> float4 {
         if (!valid || c >= Dout) return make_float4(0.f, 0.f, 0.f, 0.f);
         return *reinterpret_cast<const float4*>(gr + c);
     };
-    const int64_t tb = park ? tile : 0;
-    float* hT = ws.hT + tb * ws.CHS * 32 + r;
-    float* gaT = ws.gaT + tb * ws.CHS * 32 + r;
     // ---- x and gy of the tile, parked before the accumulators are live.  A lane parks the columns 16 s + 8 h + (0..7) of its row: the
-    // ones it is layer 1's B operand for, so the k-steps below read x back (the lane's own stores) and hold no gather and no cosf
-    float* xT = ws.xT + tb * ws.CSI * 32 + r;
+    // ones it is layer 1's B operand for, so the k-steps read x back (the lane's own stores) and hold no gather and no cosf
+    float* xT = ws.xT + (park ? tile : 0) * ws.CSI * 32 + r;
     if (park) {
         float* gyT = ws.gyT + tile * ws.CSO * 32 + r;
         for (int c = 8 * h; c < ws.CSI; c += 16) {
@@ -251,155 +172,50 @@ __global__ __launch_bounds__(D2_T) void k_eib_rows(const ei_src src, const ei_di
         if (!valid || c >= ws.CSI) return make_float4(0.f, 0.f, 0.f, 0.f);
         return make_float4(xT[c * 32], xT[(c + 1) * 32], xT[(c + 2) * 32], xT[(c + 3) * 32]);
     };
-    // ---- the chunk pipeline (dense2_rows'): fetch(c) reads chunk c into registers, commit(b) writes it to buffer b
-    const uint32_t nchunks = (uint32_t)(d.NP * (d.KS + EIB_HG));
-    uint4 p0, p1, p2, p3, p4, p5, p6, p7;
-    auto fetch = [&](uint32_t c) {
-        const uint4* s = img + (c < nchunks ? c : 0u) * (uint32_t)CH + tid;
-        p0 = s[0]; p1 = s[D2_T]; p2 = s[2 * D2_T]; p3 = s[3 * D2_T]; p4 = s[4 * D2_T]; p5 = s[5 * D2_T];
-        if constexpr (PF == 8) { p6 = s[6 * D2_T]; p7 = s[7 * D2_T]; }
-    };
-    auto commit = [&](int b) {
-        uint4* dst = buf[b] + tid;
-        dst[0] = p0; dst[D2_T] = p1; dst[2 * D2_T] = p2; dst[3 * D2_T] = p3; dst[4 * D2_T] = p4; dst[5 * D2_T] = p5;
-        if constexpr (PF == 8) { dst[6 * D2_T] = p6; dst[7 * D2_T] = p7; }
-        __syncthreads();
-    };
-    const float* bias = reinterpret_cast<const float*>(img + eib_chunk_elems(d));
-    f32x16 y[OSM];                                                              // gx of the G columns
+    dense2_bwd_rows<OSM, true>(d, img, ws, valid, xp4, g4, rule, [&](const f32x16 (&y)[OSM]) {
+        // ---- y = gx of the G columns of row r: time columns first, then f1, then f2
+        if (!valid) return;
+        float* dT = ws.dT + tile * ws.CST * 32 + r;
+        const int Dt = d.Gt, F = ed.F;
 #pragma unroll
-    for (int t = 0; t < OSM; ++t)
+        for (int t = 0; t < OSM; ++t) {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) y[t][q] = 0.0f;
-    uint32_t chunk = 0;
-    int cur = 0;
-    fetch(0);
-    commit(0);
-    for (int p = 0; p < d.NP; ++p) {
-        const int w0 = p * EIB_HG;
-        f32x16 aa[EIB_HG], ag[EIB_HG];                                          // a - b1 = W1 . x and gh = W2^T . gy of the pass's slices
-#pragma unroll
-        for (int wl = 0; wl < EIB_HG; ++wl)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) aa[wl][q] = ag[wl][q] = 0.0f;
-        float4 xa = xp4(8 * h), xb = xp4(8 * h + 4), ga = g4(8 * h), gb = g4(8 * h + 4);
-        for (int ks = 0; ks < d.KS; ++ks) {
-            fetch(chunk + 1);
-            bf16x8 bxh, bxl, bgh, bgl;
-            split8(xa, xb, bxh, bxl);
-            split8(ga, gb, bgh, bgl);
-            xa = xp4(16 * (ks + 1) + 8 * h);                                    // (beyond Din / Dout: zeros)
-            xb = xp4(16 * (ks + 1) + 8 * h + 4);
-            ga = g4(16 * (ks + 1) + 8 * h);
-            gb = g4(16 * (ks + 1) + 8 * h + 4);
-            const bf16x8* W = reinterpret_cast<const bf16x8*>(buf[cur]) + lane;
-            bf16x8 ah[EIB_HG], al[EIB_HG];
-#pragma unroll
-            for (int wl = 0; wl < EIB_HG; ++wl) {
-                ah[wl] = W[(wl * 2) * 64];
-                al[wl] = W[(wl * 2 + 1) * 64];
-            }
-            mm3(ah, al, bxh, bxl, aa);
-            if (16 * ks < Dout) {                                               // (uniform; beyond Dout both operands are zeros)
-#pragma unroll
-                for (int wl = 0; wl < EIB_HG; ++wl) {
-                    ah[wl] = W[((EIB_HG + wl) * 2) * 64];
-                    al[wl] = W[((EIB_HG + wl) * 2 + 1) * 64];
-                }
-                mm3(ah, al, bgh, bgl, ag);
-            }
-            commit(cur ^ 1);
-            cur ^= 1;
-            ++chunk;
-        }
-        // ---- slice by slice: h = m ? a : 0 and ga = m ? gh : 0 of the lane's 16 units (parked for k_eib_weights; a selected 0.0f for
-        // a row or a unit of the padding: their bits are 0), ga the B operand of gx += W1[:, G columns]^T . ga
-#pragma unroll
-        for (int wl = 0; wl < EIB_HG; ++wl) {
-            fetch(chunk + 1);
-            const int slice = w0 + wl;
-            const bool live = park && slice < ws.NS;
-            const uint32_t mw = valid && slice < ws.NS ? bits[slice] : 0u;
-            bf16x8 bhh[2], bhl[2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                float xg[8];
-#pragma unroll
-                for (int q4 = 2 * s2; q4 < 2 * s2 + 2; ++q4) {
-                    const float4 bb = *reinterpret_cast<const float4*>(bias + 32 * slice + 8 * q4 + 4 * h);
-                    const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int q = 4 * q4 + j, ur = acc_row(q, h), u = 32 * slice + ur;
-                        const bool on = ((mw >> ur) & 1u) != 0u && u < H;
-                        const float hv = on ? aa[wl][q] + bv[j] : 0.0f, gav = on ? ag[wl][q] : 0.0f;
-                        if (live) {
-                            hT[u * 32] = hv;
-                            gaT[u * 32] = gav;
-                        }
-                        xg[q - 8 * s2] = gav;
+            for (int i = 0; i < 4; ++i) {
+                const int o = 32 * t + 8 * i + 4 * h;
+                if (o < Dt) {
+                    if (time_grads) {
+                        dT[o * 32] = y[t][4 * i];
+                        dT[(o + 1) * 32] = y[t][4 * i + 1];
+                        dT[(o + 2) * 32] = y[t][4 * i + 2];
+                        dT[(o + 3) * 32] = y[t][4 * i + 3];
                     }
+                } else if (o < d.G && gfeat) {
+                    float* gf = o < Dt + F ? gfeat + row * F + (o - Dt) : gfeat + (src.n + row) * F + (o - Dt - F);
+                    *reinterpret_cast<float4*>(gf) = make_float4(y[t][4 * i], y[t][4 * i + 1], y[t][4 * i + 2], y[t][4 * i + 3]);
                 }
-                split8(xg, bhh[s2], bhl[s2]);
-            }
-            const bf16x8* W = reinterpret_cast<const bf16x8*>(buf[cur]) + lane;
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                bf16x8 ah[OSM], al[OSM];
-#pragma unroll
-                for (int t = 0; t < OSM; ++t) {
-                    ah[t] = W[((s2 * OSM + t) * 2) * 64];
-                    al[t] = W[((s2 * OSM + t) * 2 + 1) * 64];
-                }
-                mm3(ah, al, bhh[s2], bhl[s2], y);
-            }
-            commit(cur ^ 1);
-            cur ^= 1;
-            ++chunk;
-        }
-    }
-    // ---- y[t][4 i .. 4 i + 3] = gx of the G columns 32 t + 8 i + 4 h + (0..3) of row r: time columns first, then f1, then f2
-    if (!valid) return;
-    float* dT = ws.dT + tile * ws.CST * 32 + r;
-    const int Dt = d.Dt, F = d.F;
-#pragma unroll
-    for (int t = 0; t < OSM; ++t) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int o = 32 * t + 8 * i + 4 * h;
-            if (o < Dt) {
-                if (time_grads) {
-                    dT[o * 32] = y[t][4 * i];
-                    dT[(o + 1) * 32] = y[t][4 * i + 1];
-                    dT[(o + 2) * 32] = y[t][4 * i + 2];
-                    dT[(o + 3) * 32] = y[t][4 * i + 3];
-                }
-            } else if (o < d.G && gfeat) {
-                float* gf = o < Dt + F ? gfeat + row * F + (o - Dt) : gfeat + (src.n + row) * F + (o - Dt - F);
-                *reinterpret_cast<float4*>(gf) = make_float4(y[t][4 * i], y[t][4 * i + 1], y[t][4 * i + 2], y[t][4 * i + 3]);
             }
         }
-    }
-    // ---- d = gxt (-sin arg) in place, behind the accumulators (128 inlined sinf among them spilt): the lane's own stores, the time
-    // columns 8 j + 4 h + (0..3)
-    if (!time_grads) return;
+        // ---- d = gxt (-sin arg) in place, behind the accumulators (128 inlined sinf among them spilt): the lane's own stores, the
+        // time columns 8 j + 4 h + (0..3)
+        if (!time_grads) return;
 #pragma unroll 1
-    for (int o = 4 * h; o < Dt; o += 8) {
-        const float4 a = x4.arg4(o);
-        dT[o * 32] *= -sinf(a.x);
-        dT[(o + 1) * 32] *= -sinf(a.y);
-        dT[(o + 2) * 32] *= -sinf(a.z);
-        dT[(o + 3) * 32] *= -sinf(a.w);
-    }
+        for (int o = 4 * h; o < Dt; o += 8) {
+            const float4 a = x4.arg4(o);
+            dT[o * 32] *= -sinf(a.x);
+            dT[(o + 1) * 32] *= -sinf(a.y);
+            dT[(o + 2) * 32] *= -sinf(a.z);
+            dT[(o + 3) * 32] *= -sinf(a.w);
+        }
+    });
 }
 
 // grid (ceil(NS (NG + 1) / 4) + 1, row parts), NG = column groups of gw1.  tpp: tiles per row part (every part holds one)
-__global__ __launch_bounds__(256) void k_eib_weights(const eib_ws ws, int64_t n, const eib_dims d, int64_t tpp, int time_grads,
+__global__ __launch_bounds__(256) void k_eib_weights(const eib_ws ws, int64_t n, const d2b_dims d, int64_t tpp, int time_grads,
                                                      float* __restrict__ partial) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int64_t t0 = (int64_t)blockIdx.y * tpp, t1 = t0 + tpp < ws.T ? t0 + tpp : ws.T;
-    const int Din = d.Din, H = d.H, Dout = d.Dout, Dt = d.Dt;
+    const int Din = d.Din, H = d.H, Dout = d.Dout, Dt = d.Gt;
     float* gw1 = partial + (int64_t)blockIdx.y * ((int64_t)H * Din + H + (int64_t)Dout * H + Dout + 2 * (int64_t)Dt);
     float* gb1 = gw1 + (int64_t)H * Din;
     float* gw2 = gb1 + H;
@@ -411,8 +227,7 @@ __global__ __launch_bounds__(256) void k_eib_weights(const eib_ws ws, int64_t n,
         for (int c = tid; c < Dout; c += 256) {
             float so = 0.0f;
             for (int64_t t = t0; t < t1; ++t) {
-                const int64_t left = n - t * 32;
-                const int nr = left < 32 ? (int)left : 32;
+                const int nr = d2b_tile_rows(n, t);
                 const float* go = ws.gyT + (t * ws.CSO + c) * 32;
                 for (int i = 0; i < nr; ++i) so += go[i];
             }
@@ -422,8 +237,7 @@ __global__ __launch_bounds__(256) void k_eib_weights(const eib_ws ws, int64_t n,
             float sw = 0.0f, sb = 0.0f;
             if (time_grads) {
                 for (int64_t t = t0; t < t1; ++t) {
-                    const int64_t left = n - t * 32;
-                    const int nr = left < 32 ? (int)left : 32;
+                    const int nr = d2b_tile_rows(n, t);
                     const float* dd = ws.dT + (t * ws.CST + c) * 32;
                     const float* lt = ws.lt + t * 32;
                     for (int i = 0; i < nr; ++i) {
@@ -497,7 +311,7 @@ extern "C" int tpnet_encoder_input_train(const float* node_raw, int64_t n_node_r
     ei_dims d;
     ei_src s{node_raw, edge_raw, tw, tb, feat, neigh, eid, tn, tq, n_node_rows, n_edge_rows, 0, K};
     if (!ei_src_ok(s, n_nodes) || !img || !out || !relu_bits || !err || !ei_make_dims(dims, d)) return TPNET_ERR_BAD_ARG;
-    if (!ei_aligned16({img, out}) || (reinterpret_cast<uintptr_t>(relu_bits) & 3)) return TPNET_ERR_BAD_ARG;
+    if (!aligned16({img, out}) || (reinterpret_cast<uintptr_t>(relu_bits) & 3)) return TPNET_ERR_BAD_ARG;
     s.n = n_nodes * K;
     if (s.n == 0) return TPNET_OK;
     if (d.l.HG == D2_HG) ei_launch_train<D2_HG, D2_OS, false>(s, d, img, out, relu_bits, err, (hipStream_t)stream);
@@ -509,14 +323,14 @@ extern "C" int tpnet_encoder_input_train(const float* node_raw, int64_t n_node_r
 extern "C" size_t tpnet_encoder_input_bwd_image_bytes(int32_t Dn, int32_t Dt, int32_t De, int32_t F, int32_t H, int32_t Dout) {
     const int32_t v[6] = {Dn, Dt, De, F, H, Dout};
     ei_dims e;
-    eib_dims b;
-    return eib_make_dims(v, e, b) ? eib_image_bytes(b) : 0;
+    d2b_dims b;
+    return eib_make_dims(v, e, b) ? d2b_image_bytes(b) : 0;
 }
 
 extern "C" int64_t tpnet_encoder_input_bwd_partial_floats(int32_t Dn, int32_t Dt, int32_t De, int32_t F, int32_t H, int32_t Dout) {
     const int32_t v[6] = {Dn, Dt, De, F, H, Dout};
     ei_dims e;
-    eib_dims b;
+    d2b_dims b;
     return eib_make_dims(v, e, b) ? eib_partial_floats(b) : 0;
 }
 
@@ -524,7 +338,7 @@ extern "C" size_t tpnet_encoder_input_bwd_workspace_bytes(int64_t n_rows, int32_
                                                           int32_t Dout) {
     const int32_t v[6] = {Dn, Dt, De, F, H, Dout};
     ei_dims e;
-    eib_dims b;
+    d2b_dims b;
     if (n_rows < 0 || n_rows > (1ll << 31) || !eib_make_dims(v, e, b)) return 0;
     return (size_t)eib_ws_floats(n_rows, b) * sizeof(float);
 }
@@ -532,12 +346,9 @@ extern "C" size_t tpnet_encoder_input_bwd_workspace_bytes(int64_t n_rows, int32_
 extern "C" int tpnet_encoder_input_bwd_prepare(const float* w1, const float* b1, const float* w2, const int32_t* dims, void* bimg,
                                                void* stream) {
     ei_dims e;
-    eib_dims b;
+    d2b_dims b;
     if (!w1 || !b1 || !w2 || !bimg || (reinterpret_cast<uintptr_t>(bimg) & 15) || !eib_make_dims(dims, e, b)) return TPNET_ERR_BAD_ARG;
-    const uint32_t elems = eib_chunk_elems(b) + (uint32_t)(b.NP * EIB_HG) * 8u;
-    hipLaunchKernelGGL(k_eib_image, dim3((elems + 255) / 256), dim3(256), 0, (hipStream_t)stream, w1, b1, w2, b,
-                       reinterpret_cast<uint4*>(bimg));
-    TPNET_HIP_TRY(hipGetLastError());
+    TPNET_HIP_TRY(d2b_prepare(w1, b1, w2, b, bimg, (hipStream_t)stream));
     return TPNET_OK;
 }
 
@@ -547,24 +358,20 @@ extern "C" int tpnet_encoder_input_bwd(const float* node_raw, int64_t n_node_row
                                        int32_t K, const int32_t* dims, const void* bimg, void* workspace, float* gfeat,
                                        int32_t time_grads, float* partial, int32_t n_partial, uint32_t* err, void* stream) {
     ei_dims e;
-    eib_dims b;
+    d2b_dims b;
     ei_src s{node_raw, edge_raw, tw, tb, feat, neigh, eid, tn, tq, n_node_rows, n_edge_rows, 0, K};
     if (!ei_src_ok(s, n_nodes) || !relu_bits || !gy || !bimg || !workspace || !partial || !err) return TPNET_ERR_BAD_ARG;
     if (!eib_make_dims(dims, e, b) || n_partial < 1 || gfeat == feat || gfeat == gy) return TPNET_ERR_BAD_ARG;
-    if (!ei_aligned16({gy, bimg, workspace, gfeat}) || ((reinterpret_cast<uintptr_t>(relu_bits) | reinterpret_cast<uintptr_t>(partial)) & 3))
+    if (!aligned16({gy, bimg, workspace, gfeat}) || ((reinterpret_cast<uintptr_t>(relu_bits) | reinterpret_cast<uintptr_t>(partial)) & 3))
         return TPNET_ERR_BAD_ARG;
     s.n = n_nodes * K;
     if (s.n == 0) return 0;
     const hipStream_t st = (hipStream_t)stream;
     const eib_ws ws = eib_make_ws(static_cast<float*>(workspace), s.n, b);
-    const dim3 grid((unsigned)((s.n + D2_ROWS - 1) / D2_ROWS));
-    const auto rows = b.OS == D2_OS ? k_eib_rows<D2_OS> : k_eib_rows<D2_OS_WIDE>;
-    hipLaunchKernelGGL(rows, grid, dim3(D2_T), 0, st, s, e, b, gy, relu_bits, reinterpret_cast<const uint4*>(bimg), ws, gfeat,
-                       (int)(time_grads != 0), err);
-    TPNET_HIP_TRY(hipGetLastError());
-    // row parts of equal tile counts, none empty
-    const int64_t tpp = (ws.T + n_partial - 1) / n_partial;
-    const int parts = (int)((ws.T + tpp - 1) / tpp);
+    D2B_LAUNCH_ROWS(k_eib_rows, b, s.n, st, s, e, b, gy, relu_bits, reinterpret_cast<const uint4*>(bimg), ws, gfeat, (int)(time_grads != 0),
+                    err);
+    int64_t tpp;
+    const int parts = d2b_row_parts(ws.T, n_partial, tpp);
     const int items = ws.NS * ((ws.CSI / 32 + EIB_WT - 1) / EIB_WT + 1);
     hipLaunchKernelGGL(k_eib_weights, dim3((unsigned)((items + 3) / 4 + 1), (unsigned)parts), dim3(256), 0, st, ws, s.n, b, tpp,
                        (int)(time_grads != 0), partial);

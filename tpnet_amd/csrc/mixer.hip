@@ -121,7 +121,7 @@ extern "C" int tpnet_mixer_token(const float* x, int64_t n_nodes, int32_t K, int
     if (!x || !gamma || !beta || !w1 || !b1 || !w2 || !b2 || !out || out == x) return TPNET_ERR_BAD_ARG;
     if (n_nodes < 0 || K < 2 || K > tpnet::MX_KMAX || Kh < 1 || Kh > tpnet::MX_KMAX || C < 4 || (C & 3)) return TPNET_ERR_BAD_ARG;
     if (n_nodes > (1ll << 31) / K || n_nodes * C > (1ll << 38)) return TPNET_ERR_BAD_ARG;
-    if (!tpnet::mx_aligned16({x, out}) || ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) |
+    if (!tpnet::aligned16({x, out}) || ((reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) |
                                             reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(b1) |
                                             reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(b2)) & 3))
         return TPNET_ERR_BAD_ARG;
@@ -139,7 +139,7 @@ extern "C" int tpnet_mixer_channel(const float* x, int64_t n_rows, int32_t C, in
     tpnet::d2_dims d;
     if (!x || !gamma || !beta || !img || !out || out == x) return TPNET_ERR_BAD_ARG;
     if (n_rows < 0 || n_rows > (1ll << 31) || !tpnet::mx_channel_dims(C, Ch, d)) return TPNET_ERR_BAD_ARG;
-    if (!tpnet::mx_aligned16({x, gamma, beta, img, out})) return TPNET_ERR_BAD_ARG;
+    if (!tpnet::aligned16({x, gamma, beta, img, out})) return TPNET_ERR_BAD_ARG;
     if (n_rows == 0) return TPNET_OK;
     const auto kernel = d.HG == tpnet::D2_HG   ? tpnet::k_mixer_channel<tpnet::D2_HG, tpnet::D2_OS, false>
                         : d.OS == tpnet::D2_OS ? tpnet::k_mixer_channel<tpnet::D2_HG_WIDE, tpnet::D2_OS, true>

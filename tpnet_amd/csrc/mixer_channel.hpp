@@ -12,12 +12,6 @@ static inline bool mx_channel_dims(int32_t C, int32_t Ch, d2_dims& d) {
     return true;
 }
 
-static inline bool mx_aligned16(std::initializer_list<const void*> ps) {
-    uintptr_t a = 0;
-    for (const void* p : ps) a |= reinterpret_cast<uintptr_t>(p);
-    return (a & 15) == 0;
-}
-
 // The first-pass mean m0, the deviations' own mean dl and 1 / sqrt(var + eps) of row xr [C] (mixer.hip's rule): the two lanes of a row
 // (h = 0, 1) take every other float4 and add their sums (a + b = b + a: both hold the same bits).  Every lane of the wave calls it;
 // a row that is not `valid` is not read and gets the statistics of a zero row.

@@ -255,9 +255,6 @@ static bool mxt_aligned(std::initializer_list<const void*> ps, uintptr_t mask) {
     return (a & mask) == 0;
 }
 
-static bool mxt_rate(float p) { return p >= 0.0f && p < 1.0f; }                 // (a NaN fails both)
-static uint32_t mxt_threshold(float p) { return (uint32_t)((double)p * 4294967296.0); }
-
 template <int KC, int KHC>
 static int launch_mixer_token_bwd(const float* x, const float* gy, int64_t total, int32_t K, int32_t Kh, int32_t C, const float* gamma,
                                   const float* beta, float eps, const float* w1, const float* b1, const float* w2, float p, uint64_t key,
@@ -271,7 +268,7 @@ static int launch_mixer_token_bwd(const float* x, const float* gy, int64_t total
     const int64_t nbatch = (total + cols - 1) / cols;
     const int grid = (int)(nbatch < n_partial ? nbatch : n_partial);
     hipLaunchKernelGGL((k_mixer_token_bwd<KC, KHC>), dim3((unsigned)grid), dim3(256), (size_t)cols * mxb_row_floats(K, Kh) * 4, s, x, gy,
-                       total, (int)K, (int)Kh, (int)C, gamma, beta, eps, w1, b1, w2, 1.0f / (1.0f - p), mxt_threshold(p), (uint32_t)key,
+                       total, (int)K, (int)Kh, (int)C, gamma, beta, eps, w1, b1, w2, 1.0f / (1.0f - p), drop_threshold(p), (uint32_t)key,
                        (uint32_t)(key >> 32), gx, partial);
     TPNET_HIP_TRY(hipGetLastError());
     return grid;
@@ -285,13 +282,13 @@ extern "C" int tpnet_mixer_token_train(const float* x, int64_t n_nodes, int32_t 
                                        float eps, const float* w1, const float* b1, int32_t Kh, const float* w2, const float* b2, float p,
                                        uint64_t key, float* out, void* stream) {
     if (!x || !gamma || !beta || !w1 || !b1 || !w2 || !b2 || !out || out == x) return TPNET_ERR_BAD_ARG;
-    if (!mxt_served(n_nodes, K, Kh, C) || !mxt_rate(p)) return TPNET_ERR_BAD_ARG;
+    if (!mxt_served(n_nodes, K, Kh, C) || !drop_rate(p)) return TPNET_ERR_BAD_ARG;
     if (!mxt_aligned({x, out}, 15) || !mxt_aligned({gamma, beta, w1, b1, w2, b2}, 3)) return TPNET_ERR_BAD_ARG;
     const int64_t total = n_nodes * C;
     if (total == 0) return TPNET_OK;
     const auto kernel = K == 20 && Kh == 10 ? k_mixer_token_train<20, 10> : k_mixer_token_train<0, 0>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, total, (int)K, (int)Kh, (int)C,
-                       gamma, beta, eps, w1, b1, w2, b2, 1.0f / (1.0f - p), mxt_threshold(p), (uint32_t)key, (uint32_t)(key >> 32), out);
+                       gamma, beta, eps, w1, b1, w2, b2, 1.0f / (1.0f - p), drop_threshold(p), (uint32_t)key, (uint32_t)(key >> 32), out);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }
@@ -304,7 +301,7 @@ extern "C" int tpnet_mixer_token_bwd(const float* x, const float* gy, int64_t n_
                                      const float* beta, float eps, const float* w1, const float* b1, int32_t Kh, const float* w2,
                                      const float* b2, float p, uint64_t key, float* gx, float* partial, int32_t n_partial, void* stream) {
     if (!x || !gy || !gamma || !beta || !w1 || !b1 || !w2 || !b2 || !partial || gx == x || gx == gy) return TPNET_ERR_BAD_ARG;
-    if (!mxt_served(n_nodes, K, Kh, C) || !mxt_rate(p) || n_partial < 1) return TPNET_ERR_BAD_ARG;
+    if (!mxt_served(n_nodes, K, Kh, C) || !drop_rate(p) || n_partial < 1) return TPNET_ERR_BAD_ARG;
     if (!mxt_aligned({x, gy, gx}, 15) || !mxt_aligned({gamma, beta, w1, b1, w2, b2, partial}, 3)) return TPNET_ERR_BAD_ARG;
     const int64_t total = n_nodes * C;
     if (total == 0) return 0;
@@ -317,11 +314,11 @@ extern "C" int tpnet_mixer_token_bwd(const float* x, const float* gy, int64_t n_
 
 extern "C" int tpnet_mixer_token_masks(int64_t n_nodes, int32_t K, int32_t Kh, int32_t C, float p, uint64_t key, uint8_t* m1, uint8_t* m2,
                                        void* stream) {
-    if (!m1 || !m2 || !mxt_served(n_nodes, K, Kh, C) || !mxt_rate(p)) return TPNET_ERR_BAD_ARG;
+    if (!m1 || !m2 || !mxt_served(n_nodes, K, Kh, C) || !drop_rate(p)) return TPNET_ERR_BAD_ARG;
     const int64_t total = n_nodes * C;
     if (total == 0) return TPNET_OK;
     hipLaunchKernelGGL(k_mixer_token_masks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, total, (int)K,
-                       (int)Kh, (int)C, mxt_threshold(p), (uint32_t)key, (uint32_t)(key >> 32), m1, m2);
+                       (int)Kh, (int)C, drop_threshold(p), (uint32_t)key, (uint32_t)(key >> 32), m1, m2);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }

@@ -424,6 +424,13 @@ int launch_wstep(const tpnet_state& st, const StreamArgs& a, const WPlan& p, int
 // every pointer of the state set, 1 <= N < 2^31, d >= 1, 1 <= L <= TPNET_MAX_LAYERS: what every entry point asks of its tpnet_state
 int check_state(const tpnet_state* st);
 
+// every pointer a multiple of 16 (a null one passes): what the float4 loads and stores of the dense kernels ask of their arrays
+static inline bool aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t a = 0;
+    for (const void* p : ps) a |= reinterpret_cast<uintptr_t>(p);
+    return (a & 15) == 0;
+}
+
 extern thread_local int g_last_hip_error;
 #define TPNET_HIP_TRY(expr)                                   \
     do {                                                      \

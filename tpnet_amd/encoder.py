@@ -189,22 +189,27 @@ class TPNetEmbedding(nn.Module):
                     feats = rp.get_pair_wise_feature(src_node_ids=u.cpu().numpy(), dst_node_ids=v.cpu().numpy())
         return self.embed_from_features(neigh, eids, tn, tq, feats)
 
+    def _input_stage_prepared(self, dev, pair_features, backward=False):
+        """fused_input.prepared of projection_layer where what both routes ask holds -- module on the GPU, relative encodings
+        present, `random_feature_dim` even and twice their width -- else None."""
+        if dev.type != "cuda" or pair_features is None or self.random_feature_dim % 2 \
+                or pair_features.shape[1] * 2 != self.random_feature_dim:
+            return None
+        return _fi.prepared(self.projection_layer, self.node_feat_dim, self.time_feat_dim, self.edge_feat_dim,
+                            self.random_feature_dim // 2, backward=backward)
+
     def _fused_prep(self, dev, pair_features):
         """The prepared weight image if the one-launch input stage serves this call, else None: no gradient recorded, module on
         the GPU, `fused_input` set, relative encodings present and a shape tpnet_encoder_input_supported accepts."""
-        if torch.is_grad_enabled() or not self.fused_input or dev.type != "cuda" or pair_features is None:
+        if torch.is_grad_enabled() or not self.fused_input:
             return None
-        if self.random_feature_dim % 2 or pair_features.shape[1] * 2 != self.random_feature_dim:
-            return None
-        return _fi.prepared(self.projection_layer, self.node_feat_dim, self.time_feat_dim, self.edge_feat_dim, self.random_feature_dim // 2)
+        return self._input_stage_prepared(dev, pair_features)
 
     def _fused_input_training(self, dev, pair_features):
         """Whether fused_input.encoder_input_train serves this call: `fused_input_training` set, a gradient recorded, module on the
         GPU, relative encodings present (contiguous float32) in a shape the forward AND the backward serve, the Parameters of
         projection_layer and of the time encoder contiguous float32, and raw feature tables that take no gradient."""
-        if not self.fused_input_training or not torch.is_grad_enabled() or dev.type != "cuda" or pair_features is None:
-            return False
-        if self.random_feature_dim % 2 or pair_features.shape[1] * 2 != self.random_feature_dim:
+        if not self.fused_input_training or not torch.is_grad_enabled() or pair_features is None:
             return False
         if pair_features.dtype != torch.float32 or not pair_features.is_contiguous():
             return False
@@ -215,8 +220,7 @@ class TPNetEmbedding(nn.Module):
             return False
         if not all(p.is_cuda and p.is_contiguous() and p.dtype == torch.float32 for p in (w.weight, w.bias)):
             return False
-        return _fi.prepared(self.projection_layer, self.node_feat_dim, self.time_feat_dim, self.edge_feat_dim,
-                            self.random_feature_dim // 2, backward=True) is not None
+        return self._input_stage_prepared(dev, pair_features, backward=True) is not None
 
     def _fused_mixer_prep(self, mixer, x):
         """The prepared channel image if the two-launch layer serves `mixer` on `x`, else None: `fused_mixer` set, no gradient

@@ -25,7 +25,6 @@ calls = {"forward": 0, "prepare": 0, "train_forward": 0, "backward": 0}
 # row parts of the backward's weight kernel = partial sums it writes, at most (fused_mixer.CHANNEL_PARTIALS' reasoning: at
 # 572 -> 344 -> 172 a part is 44 waves, so 32 parts are 1 408 waves for the 1 024 SIMDs, and 32 partials of 256 652 floats are 33 MB)
 MAX_PARTIALS = 32
-_PARTIALS = {}                              # (device, floats per partial, parts) -> the reused buffer
 
 
 class Prepared(NamedTuple):
@@ -77,11 +76,11 @@ def prepared(proj, Dn: int, Dt: int, De: int, F: int, backward=False):
     w1, b1, w2, b2 = ls[0].weight, ls[0].bias, ls[1].weight, ls[1].bias
     d = (int(Dn), int(Dt), int(De), int(F), int(ls[0].out_features), int(ls[1].out_features))
 
-    def build(previous):
+    def build(previous, both):
         if not supported(proj, Dn, Dt, De, F) or not all(p.is_contiguous() and p.dtype == torch.float32 for p in (w1, b1, w2, b2)):
             return None
         lib = _lib.load()
-        if backward and int(lib.tpnet_encoder_input_bwd_image_bytes(*d)) == 0:      # (the backward serves fewer shapes: no launch)
+        if both and int(lib.tpnet_encoder_input_bwd_image_bytes(*d)) == 0:          # (the backward serves fewer shapes: no launch)
             return None
         bimg = None
         if previous is not None:
@@ -92,7 +91,7 @@ def prepared(proj, Dn: int, Dt: int, De: int, F: int, backward=False):
             err = torch.zeros(1, dtype=torch.int32, device=w1.device)
         _lib.check(lib.tpnet_encoder_input_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), dims, img.data_ptr(),
                                                    _dense.stream_ptr(w1.device)), "encoder_input_prepare")
-        if backward or bimg is not None:
+        if both:
             if bimg is None:
                 bimg = torch.empty(int(lib.tpnet_encoder_input_bwd_image_bytes(*d)), dtype=torch.uint8, device=w1.device)
             _lib.check(lib.tpnet_encoder_input_bwd_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), dims, bimg.data_ptr(),
@@ -102,13 +101,7 @@ def prepared(proj, Dn: int, Dt: int, De: int, F: int, backward=False):
 
     key = (Dn, Dt, De, F) + _dense.param_key(w1, b1, w2, b2)
     storage = (w1.device, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()) + d
-    rec = _dense.cached(_PREPARED, proj, key, storage, build)
-    if backward and rec is not None and rec.bimg is None:       # (a record an inference call made: both images, once)
-        if int(_lib.load().tpnet_encoder_input_bwd_image_bytes(*d)) == 0:
-            return None
-        _PREPARED.pop(proj)
-        rec = _dense.cached(_PREPARED, proj, key, storage, build)
-    return rec
+    return _dense.cached_images(_PREPARED, proj, key, storage, build, backward)
 
 
 def _sources(prep, node_raw, edge_raw, neigh, eids, tn, tq, tw, tb, feats, what):
@@ -193,31 +186,19 @@ class _InputTrain(torch.autograd.Function):
             prep = prepared(proj, node_raw.shape[1], tw.numel(), edge_raw.shape[1], feats.shape[1], backward=True)
             d = tuple(prep.dims)
             gy = gy.contiguous()
-            pf = int(lib.tpnet_encoder_input_bwd_partial_floats(*d))
-            pkey = (dev, pf, parts)
-            part = _PARTIALS.get(pkey)
-            if part is None:
-                part = _PARTIALS[pkey] = torch.empty((parts, pf), dtype=torch.float32, device=dev)
+            part = _dense.partial_buffer(dev, parts, lib.tpnet_encoder_input_bwd_partial_floats(*d))
             ws = torch.empty(int(lib.tpnet_encoder_input_bwd_workspace_bytes(n * K, *d)), dtype=torch.uint8, device=dev)
             rc = lib.tpnet_encoder_input_bwd(
                 node_raw.data_ptr(), node_raw.shape[0], edge_raw.data_ptr(), edge_raw.shape[0], neigh.data_ptr(), eids.data_ptr(),
                 tn.data_ptr(), tq.data_ptr(), tw.data_ptr(), tb.data_ptr(), feats.data_ptr(), bits.data_ptr(), gy.data_ptr(), n, K,
                 prep.dims, prep.bimg.data_ptr(), ws.data_ptr(), None if gfeat is None else gfeat.data_ptr(), int(time_grads),
                 part.data_ptr(), part.shape[0], prep.err.data_ptr(), _dense.stream_ptr(dev))
-            if rc <= 0:
-                _lib.check(rc if rc < 0 else -1, "encoder_input_bwd")
+            tot = _dense.sum_partials(rc, part, "encoder_input_bwd")
             calls["backward"] += 1
-            tot = part[:rc].sum(0)                              # fixed order: run-to-run identical bits
             del ws                                              # (the caching allocator keeps it alive for the stream's launches)
         elif gfeat is not None:
             gfeat.zero_()
-        grads, off = [], 0
-        for i, t in enumerate((w1, b1, w2, b2, tw, tb)):
-            g = None
-            if ctx.needs_input_grad[i]:
-                g = torch.zeros_like(t) if tot is None else tot[off:off + t.numel()].view(t.shape)
-            grads.append(g)
-            off += t.numel()
+        grads = _dense.split_grads(tot, (w1, b1, w2, b2, tw, tb), ctx.needs_input_grad[:6])
         return (*grads, gfeat, None, None, None, None, None, None, None, None)
 
 

@@ -28,7 +28,6 @@ _PREPARED = weakref.WeakKeyDictionary()                 # mixer -> Prepared
 # launches made through this binding (tests assert the dispatch through it)
 calls = {"token": 0, "channel": 0, "prepare": 0, "token_train": 0, "token_bwd": 0, "channel_train": 0, "channel_bwd": 0}
 MAX_PARTIALS = 256                                      # workgroups of a backward launch = partial sums it writes, at most
-_PARTIALS = {}                                          # (device, floats per partial) -> the reused [MAX_PARTIALS, floats] buffer
 # row parts of the channel backward's weight kernel = partial sums it writes, at most: 2 ceil(Ch / 32) waves per part, so 32 parts of
 # the reference's 172 -> 688 -> 172 are 1 408 waves for the 1 024 SIMDs, and 32 partials of 237 876 floats are 30 MB
 # (profiles/mixer_channel_training.md)
@@ -91,7 +90,7 @@ def prepared(mixer, backward=False):
     w1, b1, w2, b2 = ls.channel[0].weight, ls.channel[0].bias, ls.channel[1].weight, ls.channel[1].bias
     d = _dims(ls)
 
-    def build(previous):
+    def build(previous, both):
         if not supported(mixer):
             return None
         lib = _lib.load()
@@ -102,7 +101,7 @@ def prepared(mixer, backward=False):
             img = torch.empty(int(lib.tpnet_mixer_channel_image_bytes(d[2], d[3])), dtype=torch.uint8, device=w1.device)
         _lib.check(lib.tpnet_mixer_channel_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), d[2], d[3], img.data_ptr(),
                                                    _dense.stream_ptr(w1.device)), "mixer_channel_prepare")
-        if backward or bimg is not None:
+        if both:
             if bimg is None:
                 bimg = torch.empty(int(lib.tpnet_mixer_channel_bwd_image_bytes(d[2], d[3])), dtype=torch.uint8, device=w1.device)
             _lib.check(lib.tpnet_mixer_channel_bwd_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), d[2], d[3], bimg.data_ptr(),
@@ -112,11 +111,7 @@ def prepared(mixer, backward=False):
 
     key = d + _dense.param_key(w1, b1, w2, b2)
     storage = (w1.device, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()) + d
-    rec = _dense.cached(_PREPARED, mixer, key, storage, build)
-    if backward and rec is not None and rec.bimg is None:       # (a record an inference call made: both images, once)
-        _PREPARED.pop(mixer)
-        rec = _dense.cached(_PREPARED, mixer, key, storage, build)
-    return rec
+    return _dense.cached_images(_PREPARED, mixer, key, storage, build, backward)
 
 
 def mixer_token(mixer, x):
@@ -124,9 +119,7 @@ def mixer_token(mixer, x):
     launch on the current stream, no synchronisation."""
     ls = layers_of(mixer)
     K, Kh, C, _ = _dims(ls)
-    if x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape[1:]) != (K, C) or not x.is_contiguous() \
-            or x.device != ls.token_norm.weight.device:
-        raise ValueError("mixer_token: x must be a contiguous float32 [n, K, C] on the mixer's device")
+    _check_token_input(ls, x, "mixer_token")
     out = torch.empty_like(x)
     g, b, w1, b1, w2, b2 = _params(ls)[:6]
     _lib.check(_lib.load().tpnet_mixer_token(x.data_ptr(), x.shape[0], K, C, g.data_ptr(), b.data_ptr(), float(ls.token_norm.eps),
@@ -163,10 +156,18 @@ def _check_token_input(ls, x, what):
         raise ValueError(f"{what}: x must be a contiguous float32 [n, K, C] on the mixer's device")
 
 
-def _new_key():
-    """64 bits from torch's default CPU generator: no device synchronisation, reproducible under torch.manual_seed."""
-    hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
-    return hi << 32 | lo
+def _rate_and_key(p, key, what):
+    """(p, key) as the training calls take them: 0 <= p < 1, and a 64-bit key.  key None: 64 bits from torch's default CPU generator
+    (no device synchronisation, reproducible under torch.manual_seed) -- at p = 0 nothing is drawn from it, the key is 0."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{what}: 0 <= p < 1")
+    if key is None:
+        key = 0
+        if p > 0.0:
+            hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+            key = hi << 32 | lo
+    return p, int(key) & (1 << 64) - 1
 
 
 class _TokenTrain(torch.autograd.Function):
@@ -198,26 +199,14 @@ class _TokenTrain(torch.autograd.Function):
         tot = None
         if n > 0:
             lib = _lib.load()
-            pf = int(lib.tpnet_mixer_token_bwd_partial_floats(K, Kh))
-            part = _PARTIALS.get((x.device, pf))
-            if part is None:
-                part = _PARTIALS[(x.device, pf)] = torch.empty((MAX_PARTIALS, pf), dtype=torch.float32, device=x.device)
+            part = _dense.partial_buffer(x.device, MAX_PARTIALS, lib.tpnet_mixer_token_bwd_partial_floats(K, Kh))
             rc = lib.tpnet_mixer_token_bwd(x.data_ptr(), gy.data_ptr(), n, K, C, gamma.data_ptr(), beta.data_ptr(), eps, w1.data_ptr(),
                                            b1.data_ptr(), Kh, w2.data_ptr(), b2.data_ptr(), p, key,
-                                           None if gx is None else gx.data_ptr(), part.data_ptr(), MAX_PARTIALS,
+                                           None if gx is None else gx.data_ptr(), part.data_ptr(), part.shape[0],
                                            _dense.stream_ptr(x.device))
-            if rc <= 0:
-                _lib.check(rc if rc < 0 else -1, "mixer_token_bwd")
+            tot = _dense.sum_partials(rc, part, "mixer_token_bwd")
             calls["token_bwd"] += 1
-            tot = part[:rc].sum(0)                              # fixed order: run-to-run identical bits
-        grads, off = [], 0
-        for i, t in enumerate((gamma, beta, w1, b1, w2, b2)):
-            g = None
-            if ctx.needs_input_grad[1 + i]:
-                g = torch.zeros_like(t) if tot is None else tot[off:off + t.numel()].view(t.shape)
-            grads.append(g)
-            off += t.numel()
-        return (gx, *grads, None, None, None)
+        return (gx, *_dense.split_grads(tot, (gamma, beta, w1, b1, w2, b2), ctx.needs_input_grad[1:7]), None, None, None)
 
 
 def token_train(mixer, x, p, key=None):
@@ -229,12 +218,8 @@ def token_train(mixer, x, p, key=None):
     dropout stream."""
     ls = layers_of(mixer)
     _check_token_input(ls, x, "token_train")
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError("token_train: 0 <= p < 1")
-    if key is None:
-        key = _new_key() if p > 0.0 else 0
-    return _TokenTrain.apply(x, *_params(ls)[:6], float(ls.token_norm.eps), p, int(key) & (1 << 64) - 1)
+    p, key = _rate_and_key(p, key, "token_train")
+    return _TokenTrain.apply(x, *_params(ls)[:6], float(ls.token_norm.eps), p, key)
 
 
 def token_masks(mixer, n, C, p, key):
@@ -283,33 +268,16 @@ class _ChannelTrain(torch.autograd.Function):
         if n > 0:
             lib = _lib.load()
             prep = prepared(ctx.mixer, backward=True)           # (current: the saved Parameters are unchanged, or torch has raised)
-            pf = int(lib.tpnet_mixer_channel_bwd_partial_floats(C, Ch))
-            pkey = (x.device, pf, CHANNEL_PARTIALS)
-            part = _PARTIALS.get(pkey)
-            if part is None:
-                part = _PARTIALS[pkey] = torch.empty((CHANNEL_PARTIALS, pf), dtype=torch.float32, device=x.device)
+            part = _dense.partial_buffer(x.device, CHANNEL_PARTIALS, lib.tpnet_mixer_channel_bwd_partial_floats(C, Ch))
             ws = torch.empty(int(lib.tpnet_mixer_channel_bwd_workspace_bytes(n, C, Ch)), dtype=torch.uint8, device=x.device)
             rc = lib.tpnet_mixer_channel_bwd(x.data_ptr(), gy.data_ptr(), n, C, Ch, gamma.data_ptr(), beta.data_ptr(), eps,
                                              prep.bimg.data_ptr(), p, key, ws.data_ptr(),
                                              None if gx is None else gx.data_ptr(), part.data_ptr(), part.shape[0],
                                              _dense.stream_ptr(x.device))
-            if rc <= 0:
-                _lib.check(rc if rc < 0 else -1, "mixer_channel_bwd")
+            tot = _dense.sum_partials(rc, part, "mixer_channel_bwd")
             calls["channel_bwd"] += 1
-            tot = part[:rc].sum(0)                              # fixed order: run-to-run identical bits
             del ws                                              # (the caching allocator keeps it alive for the stream's launches)
-        grads, off = [], 0
-        for i, t in enumerate((gamma, beta, w1, b1, w2, b2)):
-            g = None
-            if ctx.needs_input_grad[1 + i]:
-                g = torch.zeros_like(t) if tot is None else tot[off:off + t.numel()].view(t.shape)
-            grads.append(g)
-            off += t.numel()
-        return (gx, *grads, None, None, None, None)
-
-
-def _channel_params(ls):
-    return _params(ls)[6:]
+        return (gx, *_dense.split_grads(tot, (gamma, beta, w1, b1, w2, b2), ctx.needs_input_grad[1:7]), None, None, None, None)
 
 
 def channel_train(mixer, x, p, key=None):
@@ -324,14 +292,10 @@ def channel_train(mixer, x, p, key=None):
     if x.dtype != torch.float32 or x.dim() < 1 or x.shape[-1] != C or not x.is_contiguous() \
             or x.device != ls.channel_norm.weight.device:
         raise ValueError("channel_train: x must be a contiguous float32 [..., C] on the mixer's device")
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError("channel_train: 0 <= p < 1")
+    p, key = _rate_and_key(p, key, "channel_train")
     if prepared(mixer, backward=True) is None:
         raise ValueError("channel_train: the kernels do not serve this mixer")
-    if key is None:
-        key = _new_key() if p > 0.0 else 0
-    return _ChannelTrain.apply(x, *_channel_params(ls), mixer, float(ls.channel_norm.eps), p, int(key) & (1 << 64) - 1)
+    return _ChannelTrain.apply(x, *_params(ls)[6:], mixer, float(ls.channel_norm.eps), p, key)
 
 
 def channel_masks(mixer, n_rows, p, key):
