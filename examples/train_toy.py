@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Toy temporal link prediction with the drop-in pieces, in the reference's batch order
 (train_link_prediction.py:246-386): reset at epoch start; per batch: negatives, encoder readouts (neighbour x src/dst
-relative encodings), decoder readouts, update, then the optimiser step.  The encoder here is a small stand-in for the
-reference's MLP-Mixer (out of scope): mean over the K neighbours of an MLP of their relative encodings.
+relative encodings), decoder readouts, update, the loss, then the optimiser step -- `callers.train_link_prediction_epoch`.  The
+loss is the device meter's (`LinkPredictionMeter.add_training`): every batch's loss, average precision and ROC-AUC are logged on
+the device and read once per epoch; nothing synchronises for them inside the loop.  The encoder here is a small stand-in for
+the reference's MLP-Mixer (out of scope): mean over the K neighbours of an MLP of their relative encodings.
 
     python examples/train_toy.py            # needs a GPU; ~10 s
 """
@@ -11,7 +13,7 @@ import numpy as np, torch
 import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tpnet_amd import RandomProjectionModule
-from tpnet_amd.callers import LinkPredictor_v1, RandomNegativeSampler, run_epoch
+from tpnet_amd.callers import LinkPredictor_v1, RandomNegativeSampler, train_link_prediction_epoch
 from tpnet_amd.sampler import GpuRecentNeighborSampler
 from tpnet_amd.stream import synthetic_stream
 
@@ -30,20 +32,13 @@ opt = torch.optim.Adam([p for p in params if p.requires_grad], lr=2e-3)
 sampler = GpuRecentNeighborSampler(src, dst, t, device=dev)
 negs = RandomNegativeSampler(src, dst)
 encoder = lambda feats, node_ids, times: enc_mlp(feats).mean(dim=1)    # [2B, K, 128] -> [2B, D]
-loss_fn = nn.BCEWithLogitsLoss()
 
 for epoch in range(3):
-    stats = []
-    def on_batch(b, neg, res):
-        _, (pos_logit, neg_logit) = res
-        logits = torch.cat([pos_logit, neg_logit]).squeeze(-1)
-        labels = torch.cat([torch.ones_like(pos_logit), torch.zeros_like(neg_logit)]).squeeze(-1)
-        loss = loss_fn(logits, labels)
-        opt.zero_grad(); loss.backward(); opt.step()
-        stats.append((loss.item(), ((logits > 0).float() == labels).float().mean().item()))
     t0 = time.perf_counter()
-    run_epoch(rp, sampler, negs, src, dst, t, B, K, encoder=encoder, decoder=decoder, on_batch=on_batch)
-    torch.cuda.synchronize()
-    half = len(stats) // 2
-    print(f"epoch {epoch}: loss {np.mean([s[0] for s in stats[half:]]):.4f}  accuracy {np.mean([s[1] for s in stats[half:]]):.3f}"
-          f"  ({E / (time.perf_counter() - t0) / 1e3:.0f} k edges/s end to end, python loop)")
+    losses, metrics = train_link_prediction_epoch(rp, sampler, negs, src, dst, t, B, K, encoder, decoder, opt)   # one read, at the end
+    dt = time.perf_counter() - t0
+    half = len(losses) // 2
+    print(f"epoch {epoch}: loss {np.mean(losses[half:]):.4f}  AP {np.mean([m['average_precision'] for m in metrics[half:]]):.3f}"
+          f"  AUC {np.mean([m['roc_auc'] for m in metrics[half:]]):.3f}  (second half of {len(losses)} batches; first batch: loss "
+          f"{losses[0]:.4f} AP {metrics[0]['average_precision']:.3f} AUC {metrics[0]['roc_auc']:.3f};"
+          f" {E / dt / 1e3:.0f} k edges/s end to end, python loop)")

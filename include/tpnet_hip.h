@@ -46,6 +46,7 @@ extern "C" {
                                     the side-by-side plans of a multi-chunk stream are bounded (TPNET_ARENA_MAX_RATIO);
                                     added since without a new number: tpnet_neg_* (the negative edge sampler's three strategies);
                                     tpnet_lp_metrics* (a batch's BCE loss, average precision and ROC-AUC as one device record);
+                                    tpnet_lp_train_loss (the same record for a training batch, with the loss's gradient by the logits);
                                     tpnet_edgebank_* (the EdgeBank baseline's three memory modes on a prefix of one static stream);
                                     tpnet_mlp_rows_* (self.mlp on the matrix cores for num_layer 1 and 2);
                                     tpnet_mlp_rows_bwd_* (its weight gradients on the matrix cores, same widths) */
@@ -615,6 +616,24 @@ int tpnet_neg_check(void* neg, void* stream);
 size_t tpnet_lp_metrics_scratch_bytes(int64_t n_pos, int64_t n_neg);
 int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
                      const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, void* stream);
+
+/* ---- a TRAINING batch's loss on the device (additive to ABI 7; csrc/metrics.hip) ----------------------------
+ * What the reference's training loop does behind the decoder (train_link_prediction.py:375-386): BCEWithLogitsLoss on
+ * cat(positives, negatives) against labels 1 / 0, loss.item(), get_link_prediction_metrics(predicts.sigmoid(), labels), loss.backward().
+ * tpnet_lp_train_loss is tpnet_lp_metrics -- the same arguments, the same three launches, the same scratch
+ * (tpnet_lp_metrics_scratch_bytes), bit for bit the same record -- and two more outputs:
+ *   pos_grad[n_pos], neg_grad[n_neg]: d(loss) / d(logit) = (sigmoid(x) - y) / (P + N), formed from the fp32 LOGIT in float64 in the
+ *     branch that does not cancel -- a positive: -1 / (1 + exp(x)) / (P + N), a negative: 1 / (1 + exp(-x)) / (P + N) -- and rounded once
+ *     to fp32.  Where an fp32 sigmoid has saturated to 1 or 0, sigmoid(x) - y in fp32 is 0; this gradient keeps its relative accuracy
+ *     down to fp32's subnormals.  A NaN logit gives a NaN gradient for that element only.  They are written, one plain store per
+ *     element, by the workgroups of the counting kernel's first row, which evaluate that logit's loss term anyway.
+ *   loss_out: ONE float, 4-byte aligned: (float)record.loss, written by the finish workgroup.
+ * The logits of every non-empty side are required here (they are optional for tpnet_lp_metrics).  TPNET_ERR_BAD_ARG, nothing
+ * launched: what tpnet_lp_metrics refuses; n_pos + n_neg == 0; a null logit or gradient pointer of a non-empty side (an EMPTY side's
+ * are not looked at); a null or misaligned loss_out. */
+int tpnet_lp_train_loss(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
+                        const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, float* pos_grad, float* neg_grad,
+                        float* loss_out, void* stream);
 
 /* ---- the EdgeBank baseline on the device (additive to ABI 7; csrc/edgebank.hip) ------------------------------
  * models/EdgeBank.py as evaluate_models_utils.py:269-318 drives it: for every test batch the reference builds a memory over

@@ -113,6 +113,7 @@ SIGNATURES = {
     "tpnet_neg_check": (C.c_int, [_P, _P]),
     "tpnet_lp_metrics_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "tpnet_lp_metrics": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P, _P]),
+    "tpnet_lp_train_loss": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P]),
     "tpnet_edgebank_bytes": (C.c_size_t, [C.c_int64]),
     "tpnet_edgebank_build": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
     "tpnet_edgebank_scratch_bytes": (C.c_size_t, [C.c_int64]),

@@ -11,6 +11,8 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `evaluate_edge_bank_link_prediction` -- the EdgeBank baseline's evaluation loop on the device (evaluate_models_utils.py:269-318).
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
+* `train_link_prediction_epoch` -- the same epoch with the loss, the backward and the optimizer step (:375-386), the loss and the
+  per-batch loss / AP / ROC-AUC from the device meter.
 The encoder itself is tpnet_amd/encoder.py (`TPNet`); `encoder` / `decoder` stay plug-in callables here.
 """
 from typing import Callable, Optional
@@ -270,6 +272,35 @@ def run_epoch(rp, neighbor_sampler, negative_sampler, src: np.ndarray, dst: np.n
             on_batch(b0 // batch_size, neg, res)
         results.append(res)
     return results
+
+
+def train_link_prediction_epoch(rp, neighbor_sampler, negative_sampler, src: np.ndarray, dst: np.ndarray, t: np.ndarray,
+                                batch_size: int, num_neighbors: int, encoder: Callable, decoder: Callable, optimizer, meter=None,
+                                on_batch: Optional[Callable] = None):
+    """One training epoch of train_link_prediction.py:246-386 on `link_prediction_batch`: reset of the projections, then per
+    chronological batch (ragged tail included) the negatives, the two encoder readouts, the two decoder calls, the update, the loss,
+    `optimizer.zero_grad()`, `loss.backward()`, `optimizer.step()`.  The loss is `meter.add_training(pos_logits, neg_logits)`
+    (tpnet_amd/metrics.py): a device scalar whose launches also log the batch's loss, average precision and ROC-AUC, so nothing in
+    the loop synchronises for `train_losses` / `train_metrics` -- what `encoder`, `decoder`, the samplers and `optimizer` do is
+    theirs.  `on_batch(index, neg_dst, result, loss)` runs after the step.  -> `meter.results()`, read once after the last batch: the
+    reference's `(train_losses, train_metrics)`, with the records' flags as `.flags`.  meter: None = a new one of one record per
+    batch; a given one is appended to, and everything it holds is returned."""
+    from .metrics import LinkPredictionMeter
+    if meter is None:
+        meter = LinkPredictionMeter(max(1, -(-len(src) // batch_size)), rp.random_projections[0].device)
+    rp.reset_random_projections()                                                     # (:246-248)
+    for b0 in range(0, len(src), batch_size):
+        s = slice(b0, min(b0 + batch_size, len(src)))
+        _, neg = negative_sampler.sample(size=s.stop - s.start)                      # (:259)
+        res = link_prediction_batch(rp, neighbor_sampler, src[s], dst[s], neg, t[s], num_neighbors, encoder, decoder)
+        pos_logits, neg_logits = res[1]
+        loss = meter.add_training(pos_logits, neg_logits)                            # (:375-382)
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        if on_batch is not None:
+            on_batch(b0 // batch_size, neg, res, loss)
+    return meter.results()
 
 
 def evaluate_with_restore(rp, evaluate: Callable):

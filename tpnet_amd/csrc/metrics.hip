@@ -4,6 +4,8 @@
 // negatives equal to it, c_i; AP = mean a_i / (a_i + b_i), AUC = sum(2 (N - b_i) + c_i) / (2 P N).  The rule is spelled out in
 // include/tpnet_hip.h.  Everything that crosses threads out of order is an integer, and the float64 sums are reduced in a fixed
 // order, so a call's record does not depend on scheduling.
+// A training batch (tpnet_lp_train_loss: train_link_prediction.py:375-386) is the same three launches: the workgroups that evaluate
+// a logit's loss term also write d(mean loss) / d(logit), and the finish workgroup the loss as one fp32.
 #include "tpnet_common.h"
 
 #include <math.h>
@@ -33,6 +35,14 @@ __device__ inline double lpm_bce_term(float logit, double y) {
     return fmax(x, 0.0) - x * y + log1p(exp(-fabs(x)));
 }
 
+// d/dx of the mean of the P + N terms, (sigmoid(x) - y) / n, formed from the LOGIT in the branch that does not cancel -- a positive:
+// sigmoid(x) - 1 = -1 / (1 + exp(x)), a negative: sigmoid(x) = 1 / (1 + exp(-x)) -- in float64 and rounded once: where an fp32
+// sigmoid has saturated to 1 or 0 the gradient keeps its relative accuracy.  exp overflows to inf -> 0; NaN -> NaN.
+__device__ inline float lpm_bce_grad(float logit, bool positive, double n) {
+    const double x = (double)logit;
+    return (float)(positive ? -1.0 / (1.0 + exp(x)) / n : 1.0 / (1.0 + exp(-x)) / n);
+}
+
 // the scratch buffer: cnt [3][P] uint32 = a | b | c, then (256-byte aligned) the NaN word, then (256 further on) part double[chunks]
 struct LpmScratch {
     uint32_t* cnt;
@@ -50,12 +60,15 @@ static LpmScratch lpm_carve(void* scratch, uint32_t P) {
 // positives, then the N negatives).  The chunk's positives and its negatives are staged as two runs, each padded with NaN -- which
 // compares false both ways -- to whole float4s: the loops read no labels and no bounds, and every lane reads the same 16 bytes (a
 // broadcast).  The workgroups x = 0 see every score once while staging: they raise the NaN word and sum their chunk's loss terms
-// (thread k: entries k, k + 256, ... of the staged order, then a tree) into part[y].
+// (thread k: entries k, k + 256, ... of the staged order, then a tree) into part[y].  GRAD (a training batch; has_loss holds): they
+// also write each logit's gradient, pos_grad[P] / neg_grad[N], one plain store per element.
+template <bool GRAD>
 __global__ __launch_bounds__(LPM_TILE) void k_lpm_count(const float* __restrict__ pos, uint32_t P, const float* __restrict__ neg,
                                                         uint32_t N, const float* __restrict__ pos_logit,
                                                         const float* __restrict__ neg_logit, int has_loss,
                                                         uint32_t* __restrict__ cnt, uint32_t* __restrict__ nan_word,
-                                                        double* __restrict__ part) {
+                                                        double* __restrict__ part, float* __restrict__ pos_grad,
+                                                        float* __restrict__ neg_grad) {
     __shared__ __attribute__((aligned(16))) float sh[LPM_CHUNK + 8];
     __shared__ double shd[LPM_TILE];
     const uint32_t i = blockIdx.x * LPM_TILE + threadIdx.x;
@@ -66,6 +79,7 @@ __global__ __launch_bounds__(LPM_TILE) void k_lpm_count(const float* __restrict_
     const uint32_t np4 = (np + 3u) & ~3u, nn4 = (nn + 3u) & ~3u;   // np4 + nn4 <= LPM_CHUNK + 6
     const uint32_t n0 = c0 + np - P;                          // first negative of the chunk (nn > 0: c0 + np >= P)
     const bool first = blockIdx.x == 0;
+    const double n = (double)((long long)P + (long long)N);
     double loss = 0.0;
     bool bad = false;
     for (uint32_t k = threadIdx.x; k < np4 + nn4; k += LPM_TILE) {
@@ -73,11 +87,19 @@ __global__ __launch_bounds__(LPM_TILE) void k_lpm_count(const float* __restrict_
         if (k < np) {
             v = pos[c0 + k];
             bad |= isnan(v);
-            if (first && has_loss) loss += lpm_bce_term(pos_logit[c0 + k], 1.0);
+            if (first && has_loss) {
+                const float x = pos_logit[c0 + k];
+                loss += lpm_bce_term(x, 1.0);
+                if constexpr (GRAD) pos_grad[c0 + k] = lpm_bce_grad(x, true, n);
+            }
         } else if (k >= np4 && k - np4 < nn) {
             v = neg[n0 + (k - np4)];
             bad |= isnan(v);
-            if (first && has_loss) loss += lpm_bce_term(neg_logit[n0 + (k - np4)], 0.0);
+            if (first && has_loss) {
+                const float x = neg_logit[n0 + (k - np4)];
+                loss += lpm_bce_term(x, 0.0);
+                if constexpr (GRAD) neg_grad[n0 + (k - np4)] = lpm_bce_grad(x, false, n);
+            }
         }
         sh[k] = v;
     }
@@ -110,10 +132,11 @@ __global__ __launch_bounds__(LPM_TILE) void k_lpm_count(const float* __restrict_
 }
 
 // ONE workgroup: thread k takes entries k, k + 1024, ... of every list in ascending order, the 1024 partial sums meet in the tree.
-// n_part: the counting kernel's chunks (0: no loss).
+// n_part: the counting kernel's chunks (0: no loss).  loss_out (a training batch; else null): the record's loss word once more, as fp32.
 __global__ __launch_bounds__(LPM_FIN) void k_lpm_finish(uint32_t P, uint32_t N, const uint32_t* __restrict__ cnt,
                                                         const uint32_t* __restrict__ nan_word, const double* __restrict__ part,
-                                                        uint32_t n_part, int has_loss, void* __restrict__ record) {
+                                                        uint32_t n_part, int has_loss, void* __restrict__ record,
+                                                        float* __restrict__ loss_out) {
     __shared__ double shd[LPM_FIN];
     __shared__ long long shi[LPM_FIN];
     double ap = 0.0, loss = 0.0;
@@ -133,7 +156,9 @@ __global__ __launch_bounds__(LPM_FIN) void k_lpm_finish(uint32_t P, uint32_t N, 
         const double nan = __builtin_nan("");
         double* rd = reinterpret_cast<double*>(record);
         long long* ri = reinterpret_cast<long long*>(record);
-        rd[0] = has_loss ? loss / (double)((long long)P + (long long)N) : nan;
+        const double mean = has_loss ? loss / (double)((long long)P + (long long)N) : nan;
+        rd[0] = mean;
+        if (loss_out) *loss_out = (float)mean;
         rd[1] = flags ? nan : ap / (double)P;
         rd[2] = flags ? nan : (double)u2 / (double)(2ll * (long long)P * (long long)N);
         ri[3] = u2;
@@ -148,25 +173,22 @@ static bool lpm_sizes_ok(int64_t n_pos, int64_t n_neg) {
     return n_pos >= 0 && n_neg >= 0 && n_pos <= LPM_MAX_SCORES && n_neg <= LPM_MAX_SCORES && n_pos + n_neg <= LPM_MAX_SCORES;
 }
 
-}  // namespace tpnet
-
-using namespace tpnet;
-
-extern "C" {
-
-size_t tpnet_lp_metrics_scratch_bytes(int64_t n_pos, int64_t n_neg) {
+static size_t lpm_scratch_bytes(int64_t n_pos, int64_t n_neg) {
     if (!lpm_sizes_ok(n_pos, n_neg)) return 0;
     const size_t chunks = (size_t)(n_pos + n_neg + LPM_CHUNK - 1) / LPM_CHUNK;
     return lpm_zero_bytes(n_pos) + (chunks * 8 + 255) / 256 * 256;
 }
 
-int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
-                     const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, void* stream) {
+// What tpnet_lp_metrics and tpnet_lp_train_loss share: the checks of the common arguments and the three launches.  train: the
+// counting kernel's first row writes the gradients, the finish workgroup loss_out (the caller has checked those three pointers).
+static int lpm_enqueue(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
+                       const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, bool train, float* pos_grad,
+                       float* neg_grad, float* loss_out, void* stream) {
     if (!lpm_sizes_ok(n_pos, n_neg) || !record || ((size_t)record & 7) || (n_pos > 0 && !pos_score) || (n_neg > 0 && !neg_score))
         return TPNET_ERR_BAD_ARG;
     const bool any = n_pos + n_neg > 0;
     if (any && (!scratch || ((size_t)scratch & 7))) return TPNET_ERR_BAD_ARG;
-    if (any && scratch_bytes < tpnet_lp_metrics_scratch_bytes(n_pos, n_neg)) return TPNET_ERR_WORKSPACE;
+    if (any && scratch_bytes < lpm_scratch_bytes(n_pos, n_neg)) return TPNET_ERR_WORKSPACE;
     // the loss needs the logits of every side that is not empty
     const bool has_loss = (pos_logit || neg_logit) && (n_pos == 0 || pos_logit) && (n_neg == 0 || neg_logit);
     hipStream_t s = (hipStream_t)stream;
@@ -177,13 +199,36 @@ int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_sco
         const uint32_t gx = P ? (P + LPM_TILE - 1) / LPM_TILE : 1u;          // (no positives: one row of workgroups for the loss)
         chunks = (P + N + LPM_CHUNK - 1) / LPM_CHUNK;
         TPNET_HIP_TRY(hipMemsetAsync(scratch, 0, w.zero_bytes, s));
-        hipLaunchKernelGGL(k_lpm_count, dim3(gx, chunks), dim3(LPM_TILE), 0, s, pos_score, P, neg_score, N, pos_logit, neg_logit,
-                           (int)has_loss, w.cnt, w.nan, w.part);
+        hipLaunchKernelGGL(train ? k_lpm_count<true> : k_lpm_count<false>, dim3(gx, chunks), dim3(LPM_TILE), 0, s, pos_score, P,
+                           neg_score, N, pos_logit, neg_logit, (int)has_loss, w.cnt, w.nan, w.part, pos_grad, neg_grad);
     }
     hipLaunchKernelGGL(k_lpm_finish, dim3(1), dim3(LPM_FIN), 0, s, P, N, (const uint32_t*)w.cnt, (const uint32_t*)w.nan,
-                       (const double*)w.part, chunks, (int)has_loss, record);
+                       (const double*)w.part, chunks, (int)has_loss, record, loss_out);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
+}
+
+}  // namespace tpnet
+
+using namespace tpnet;
+
+extern "C" {
+
+size_t tpnet_lp_metrics_scratch_bytes(int64_t n_pos, int64_t n_neg) { return lpm_scratch_bytes(n_pos, n_neg); }
+
+int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
+                     const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, void* stream) {
+    return lpm_enqueue(pos_score, n_pos, neg_score, n_neg, pos_logit, neg_logit, scratch, scratch_bytes, record, false, nullptr,
+                       nullptr, nullptr, stream);
+}
+
+int tpnet_lp_train_loss(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
+                        const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, float* pos_grad, float* neg_grad,
+                        float* loss_out, void* stream) {
+    if (!lpm_sizes_ok(n_pos, n_neg) || n_pos + n_neg == 0 || !loss_out || ((size_t)loss_out & 3)) return TPNET_ERR_BAD_ARG;
+    if ((n_pos > 0 && (!pos_logit || !pos_grad)) || (n_neg > 0 && (!neg_logit || !neg_grad))) return TPNET_ERR_BAD_ARG;
+    return lpm_enqueue(pos_score, n_pos, neg_score, n_neg, pos_logit, neg_logit, scratch, scratch_bytes, record, true, pos_grad,
+                       neg_grad, loss_out, stream);
 }
 
 }  // extern "C"

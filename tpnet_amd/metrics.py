@@ -59,9 +59,13 @@ def link_prediction_metrics_host(pos, neg, pos_logit=None, neg_logit=None):
     return {"loss": loss, "ap": ap, "auc": auc, "u2": u2, "n_pos": P, "n_neg": N, "flags": flags}
 
 
-def _flat_f32(x, device, what):
+def _check_f32(x, device, what):
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != device:
         raise TypeError(f"{what}: an fp32 tensor on {device} is expected")
+
+
+def _flat_f32(x, device, what):
+    _check_f32(x, device, what)
     return x.detach().reshape(-1).contiguous()
 
 
@@ -72,6 +76,34 @@ def _enqueue(pos, neg, pos_logit, neg_logit, scratch, record_ptr, device):
     _lib.check(_lib.load().tpnet_lp_metrics(ptr(pos), pos.numel(), ptr(neg), neg.numel(), ptr(pos_logit), ptr(neg_logit),
                                             ptr(scratch), scratch.numel() if scratch is not None else 0, record_ptr, stream),
                "lp_metrics")
+
+
+class _TrainingLoss(torch.autograd.Function):
+    """tpnet_lp_train_loss as an autograd node: (pos_logits, neg_logits) -> the batch's mean BCE-with-logits loss, a 0-dim fp32 tensor.
+    The forward's launches append the record and write d(loss) / d(logit) of both sides into buffers of this call's own (a later
+    call may run before this one's backward); the backward scales them by grad_output on the device."""
+
+    @staticmethod
+    def forward(ctx, pos_logits, neg_logits, scratch, record_ptr, device):
+        pl, nl = pos_logits.detach().reshape(-1).contiguous(), neg_logits.detach().reshape(-1).contiguous()
+        ps, ns = torch.sigmoid(pl), torch.sigmoid(nl)
+        gp, gn = torch.empty_like(pl), torch.empty_like(nl)
+        loss = torch.empty((), dtype=torch.float32, device=device)
+        ptr = lambda v: v.data_ptr() if v.numel() else None
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _lib.check(_lib.load().tpnet_lp_train_loss(ptr(ps), ps.numel(), ptr(ns), ns.numel(), ptr(pl), ptr(nl), ptr(scratch),
+                                                   scratch.numel(), record_ptr, ptr(gp), ptr(gn), loss.data_ptr(), stream),
+                   "lp_train_loss")
+        ctx.save_for_backward(gp, gn)
+        ctx.shapes = (pos_logits.shape, neg_logits.shape)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        gp, gn = ctx.saved_tensors
+        return ((grad_output * gp).reshape(ctx.shapes[0]) if ctx.needs_input_grad[0] else None,
+                (grad_output * gn).reshape(ctx.shapes[1]) if ctx.needs_input_grad[1] else None, None, None, None)
 
 
 def _scratch_for(P, N, old, device):
@@ -120,8 +152,9 @@ class LinkPredictionMeter:
     """A device-resident log of up to `capacity` batches' loss, average precision and ROC-AUC.
 
     `add` enqueues torch's sigmoid and the three launches of tpnet_lp_metrics on the current stream and returns; it copies nothing to
-    the host and never synchronises.  `results` reads the log with ONE copy.  The scratch buffer is the meter's own: calls belong on
-    one stream."""
+    the host and never synchronises.  `add_training` is `add` for a training batch: the same record, and the loss as a differentiable
+    device scalar whose gradient the same launches write.  `results` reads the log with ONE copy; training and evaluation records
+    share it.  The scratch buffer is the meter's own: calls belong on one stream."""
 
     def __init__(self, capacity: int, device="cuda:0"):
         self.device = torch.device(device)
@@ -154,6 +187,27 @@ class LinkPredictionMeter:
         _enqueue(ps, ns, pl, nl, self._scratch, self._log.data_ptr() + k * _RECORD_WORDS * 8, self.device)
         self._n = k + 1
         return k
+
+    def add_training(self, pos_logits: torch.Tensor, neg_logits: torch.Tensor) -> torch.Tensor:
+        """A TRAINING batch (train_link_prediction.py:375-386): the logits as `add` takes them -> the batch's `BCEWithLogitsLoss`
+        (mean over the P + N logits, labels 1 / 0) as a differentiable 0-dim fp32 tensor on the device.  The same three launches
+        append the record `add` would write for these logits (same scores: torch's `sigmoid`), write the loss and write its gradient
+        by every logit, (sigmoid(x) - y) / (P + N), formed from the logit in float64 (include/tpnet_hip.h: tpnet_lp_train_loss) --
+        `loss.backward()` multiplies it by the incoming gradient and hands it on in the inputs' shapes.  Nothing synchronises, here or
+        in the backward.  Under `no_grad`, or when neither input requires a gradient, the record and the loss are the same and there
+        is no graph.  An empty batch has no mean: ValueError."""
+        if self._n >= self.capacity:
+            raise IndexError(f"LinkPredictionMeter: the log of {self.capacity} records is full (results(), then reset())")
+        _check_f32(pos_logits, self.device, "pos_logits")
+        _check_f32(neg_logits, self.device, "neg_logits")
+        P, N = pos_logits.numel(), neg_logits.numel()
+        if P + N == 0:
+            raise ValueError("LinkPredictionMeter.add_training: an empty batch has no mean loss")
+        self._scratch = _scratch_for(P, N, self._scratch, self.device)
+        k = self._n
+        loss = _TrainingLoss.apply(pos_logits, neg_logits, self._scratch, self._log.data_ptr() + k * _RECORD_WORDS * 8, self.device)
+        self._n = k + 1
+        return loss
 
     def add_probabilities(self, pos_prob: torch.Tensor, neg_prob: torch.Tensor) -> int:
         """Probabilities of a batch's positive and negative pairs (fp32 tensors on the meter's device, any shape: flattened), as a
