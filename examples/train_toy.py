@@ -7,6 +7,7 @@ the device and read once per epoch; nothing synchronises for them inside the loo
 the reference's MLP-Mixer (out of scope): mean over the K neighbours of an MLP of their relative encodings.
 
     python examples/train_toy.py            # needs a GPU; ~10 s
+    python examples/train_toy.py --fused-decoder      # the same with LinkPredictor_v1.fused = "f32"
 """
 import os, sys, time
 import numpy as np, torch
@@ -27,6 +28,8 @@ rp.fused_mlp = True                                   # self.mlp on the bf16 mat
 enc_mlp = nn.Sequential(nn.Linear(2 * 64, D), nn.ReLU(), nn.Linear(D, D)).to(dev)
 decoder = LinkPredictor_v1(input_dim1=D, input_dim2=D, hidden_dim=D, output_dim=1, random_projections=rp,
                            not_encode=False).to(dev)
+if "--fused-decoder" in sys.argv[1:]:                 # opt-in: the decoder's two layers in HIP, fp32 class, forward and backward
+    decoder.fused = "f32"
 params = list(enc_mlp.parameters()) + list(decoder.parameters())       # decoder.parameters() includes rp.mlp
 opt = torch.optim.Adam([p for p in params if p.requires_grad], lr=2e-3)
 sampler = GpuRecentNeighborSampler(src, dst, t, device=dev)

@@ -49,7 +49,8 @@ extern "C" {
                                     tpnet_lp_train_loss (the same record for a training batch, with the loss's gradient by the logits);
                                     tpnet_edgebank_* (the EdgeBank baseline's three memory modes on a prefix of one static stream);
                                     tpnet_mlp_rows_* (self.mlp on the matrix cores for num_layer 1 and 2);
-                                    tpnet_mlp_rows_bwd_* (its weight gradients on the matrix cores, same widths) */
+                                    tpnet_mlp_rows_bwd_* (its weight gradients on the matrix cores, same widths);
+                                    tpnet_decoder_f32* (LinkPredictor_v1 in the fp32 class, forward and backward) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -992,6 +993,40 @@ int tpnet_encoder_input_bwd(const float* node_raw, int64_t n_node_rows, const fl
                             const uint32_t* relu_bits, const float* gy, int64_t n_nodes, int32_t K, const int32_t* dims,
                             const void* bimg, void* workspace, float* gfeat, int32_t time_grads, float* partial, int32_t n_partial,
                             uint32_t* err, void* stream);
+
+/* ---- LinkPredictor_v1 in the fp32 class, forward and backward (additive to ABI 7; csrc/decoder_train.hip) ----
+ * out[p] = fc2(relu(fc1(x[p]))), x[p] = concat[src_emb[p], dst_emb[p], feat[p]] (never written), K = 2 D + F:
+ *   a = W1 . x + b1 on the matrix cores in the fp32 class (two-piece split operands, three products per term, fp32 accumulators),
+ *   logit = sum_u relu(a_u) w2_u + b2 in plain fp32.
+ * src_emb, dst_emb: device f32 [n][D] (both NULL = the reference's not_encode mode: zeros, their k-steps skipped); feat: device f32
+ * [n][F], NULL exactly where F = 0; w1 [H][K], b1 [H], w2 [H], b2 [1]: fc1 / fc2's Parameters as they are, read and split by the kernels
+ * (no image, no prepare call).  src_emb, dst_emb, feat, w1, gsrc, gdst, gfeat and workspace are 16-byte aligned, everything else 4.
+ * Served (tpnet_decoder_f32_supported): D % 4 == 0, 0 <= D <= 256, F % 4 == 0, 0 <= F <= 100, D + F > 0, 1 <= H <= 256; 0 <= n < 2^31.
+ *   tpnet_decoder_f32:      ONE launch.  out [n].  hidden (may be NULL: not written): relu(a) [n][H] as this launch computed it.
+ *   tpnet_decoder_f32_bwd:  from gout = dL/dout [n], TWO launches.  The ReLU's decisions are recomputed: the row-tile kernel runs the
+ *                           forward's instruction sequence on the same operands, so its a has the forward's bits.
+ *                             ga_u = a_u > 0 ? gout w2_u : 0, gw1 = sum ga (x) x, gb1 = sum ga, gw2_u = sum gout relu(a_u), gb2 = sum gout,
+ *                             gsrc | gdst | gfeat = W1^T . ga                                                 (every sum over the rows)
+ *                           gsrc, gdst [n][D], gfeat [n][F]: each may be NULL (not computed; all NULL: the product is skipped); gsrc
+ *                           and gdst must be NULL where src_emb is.  With src_emb NULL the columns [0, 2 D) of gw1 are zeros.
+ *                           min(n_partial, ceil(n / 32)) or fewer partial sums of the four parameter gradients are written, one per
+ *                           part of the rows: tpnet_decoder_f32_partial_floats(D, F, H) = H K + 2 H + 1 floats each, laid out
+ *                           gw1 [H][K] | gb1 [H] | gw2 [H] | gb2 [1], partial i at partial + i * that many floats; those beyond the
+ *                           returned count are not written.  Returns that count (0 for n = 0) or a negative error.  The caller adds
+ *                           the partials in a fixed order; no atomics, two calls give equal bits.
+ *                           workspace: tpnet_decoder_f32_bwd_workspace_bytes(n, D, F, H) = ceil(n / 32) 32 (2 pad(H) + pad(K) + 1) 4
+ *                           bytes, pad(v) = 32 ceil(v / 32); the call's own.  Between the launches it holds, tile by tile of 32 rows,
+ *                           relu(a)^T [T][pad(H)][32] | ga^T [T][pad(H)][32] | x^T [T][pad(K)][32] | gout [T][32].
+ * The three size entries are host arithmetic and return 0 for an unserved shape.  Null pointers, misaligned arrays, unserved sizes,
+ * n < 0, n >= 2^31, n_partial < 1: TPNET_ERR_BAD_ARG, checked before any GPU call.  n = 0: TPNET_OK / 0, nothing launched. */
+int tpnet_decoder_f32_supported(int32_t D, int32_t F, int32_t H);
+int64_t tpnet_decoder_f32_partial_floats(int32_t D, int32_t F, int32_t H);
+size_t tpnet_decoder_f32_bwd_workspace_bytes(int64_t n, int32_t D, int32_t F, int32_t H);
+int tpnet_decoder_f32(const float* src_emb, const float* dst_emb, int32_t D, const float* feat, int32_t F, int64_t n, const float* w1,
+                      const float* b1, const float* w2, const float* b2, int32_t H, float* out, float* hidden, void* stream);
+int tpnet_decoder_f32_bwd(const float* src_emb, const float* dst_emb, int32_t D, const float* feat, int32_t F, int64_t n,
+                          const float* w1, const float* b1, const float* w2, int32_t H, const float* gout, void* workspace, float* gsrc,
+                          float* gdst, float* gfeat, float* partial, int32_t n_partial, void* stream);
 
 /* Copies st->err to the host (synchronises the stream): returns TPNET_ERR_INDEX if any bad id was seen since
  * the last call (and clears the words), TPNET_OK otherwise. */

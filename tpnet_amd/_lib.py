@@ -165,6 +165,12 @@ SIGNATURES = {
     "tpnet_encoder_input_bwd_prepare": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32), _P, _P]),
     "tpnet_encoder_input_bwd": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32,
                                           C.POINTER(C.c_int32), _P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P]),
+    "tpnet_decoder_f32_supported": (C.c_int, [C.c_int32] * 3),
+    "tpnet_decoder_f32_partial_floats": (C.c_int64, [C.c_int32] * 3),
+    "tpnet_decoder_f32_bwd_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 3),
+    "tpnet_decoder_f32": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "tpnet_decoder_f32_bwd": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                        C.c_int32, _P]),
     "tpnet_mixer_supported": (C.c_int, [C.c_int32] * 4),
     "tpnet_mixer_channel_image_bytes": (C.c_size_t, [C.c_int32] * 2),
     "tpnet_mixer_channel_prepare": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),

@@ -35,10 +35,16 @@ class LinkPredictor_v1(nn.Module):
         self.fc1 = nn.Linear(input_dim1 + input_dim2 + self.random_feature_dim, hidden_dim)
         self.fc2 = nn.Linear(hidden_dim, output_dim)
         self.act = nn.ReLU()
-        self.fused = False      # opt-in: both layers in one bf16 matrix-core kernel (tpnet_amd/fused_decoder.py)
+        # opt-in (tpnet_amd/fused_decoder.py): True = both layers in one bf16 matrix-core kernel (~1e-2 relative); "f32" = the fp32
+        # class, forward and backward in HIP, where the kernels serve the call -- else the torch layers below, as with False
+        self.fused = False
 
     def forward(self, src_node_ids: np.ndarray, dst_node_ids: np.ndarray, src_node_embeddings: torch.Tensor,
                 dst_node_embeddings: torch.Tensor):
+        if isinstance(self.fused, str):
+            if self.fused != "f32":
+                raise ValueError(f"LinkPredictor_v1.fused: {self.fused!r} is none of False, True, 'f32'")
+            return self._forward_f32(src_node_ids, dst_node_ids, src_node_embeddings, dst_node_embeddings)
         if self.not_encode:                                        # modules.py:106-108
             src_node_embeddings = torch.zeros_like(src_node_embeddings)
             dst_node_embeddings = torch.zeros_like(dst_node_embeddings)
@@ -52,6 +58,21 @@ class LinkPredictor_v1(nn.Module):
                 return fd.fused_decoder(self, self.fc1, self.fc2, src_node_embeddings, dst_node_embeddings, feat,
                                         self.not_encode)
         parts = [src_node_embeddings, dst_node_embeddings] + ([feat] if feat is not None else [])
+        return self.fc2(self.act(self.fc1(torch.cat(parts, dim=1))))
+
+    def _forward_f32(self, src_node_ids, dst_node_ids, src_emb, dst_emb):
+        """fused == "f32": the fp32-class kernels on the embeddings as they are (with not_encode they are not read: no zeros are
+        made) where they serve the call; anything else -- a CPU module, another dtype, an unserved shape -- is fused = False's path."""
+        feat = None
+        if self.random_projections is not None:                    # modules.py:112-114
+            feat = self.random_projections.get_pair_wise_feature(src_node_ids=src_node_ids, dst_node_ids=dst_node_ids)
+        if src_emb.is_cuda:
+            from . import fused_decoder as fd
+            if fd.serves_f32(self.fc1, self.fc2, src_emb, dst_emb, feat, self.not_encode):
+                return fd.fused_decoder_f32(self.fc1, self.fc2, src_emb, dst_emb, feat, self.not_encode, checked=True)
+        if self.not_encode:                                        # modules.py:106-108
+            src_emb, dst_emb = torch.zeros_like(src_emb), torch.zeros_like(dst_emb)
+        parts = [src_emb, dst_emb] + ([feat] if feat is not None else [])
         return self.fc2(self.act(self.fc1(torch.cat(parts, dim=1))))
 
 
