@@ -50,7 +50,8 @@ extern "C" {
                                     tpnet_edgebank_* (the EdgeBank baseline's three memory modes on a prefix of one static stream);
                                     tpnet_mlp_rows_* (self.mlp on the matrix cores for num_layer 1 and 2);
                                     tpnet_mlp_rows_bwd_* (its weight gradients on the matrix cores, same widths);
-                                    tpnet_decoder_f32* (LinkPredictor_v1 in the fp32 class, forward and backward) */
+                                    tpnet_decoder_f32* (LinkPredictor_v1 in the fp32 class, forward and backward);
+                                    tpnet_mlp_l4_* (self.mlp on the matrix cores for num_layer 4, forward and backward) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -202,7 +203,8 @@ int tpnet_pair_feature(const tpnet_state* st, const int64_t* u, const int64_t* v
 int tpnet_mlp64_f32(const float* x, int64_t n, const tpnet_mlp* mlp, float* y, void* stream);
 
 /* Which (F, H) tpnet_mlp_rows_f32 serves: 1 for (16, 64) and (36, 144) -- num_layer 1 and 2 -- else 0.  (64, 256) is
- * tpnet_mlp64_f32's; (100, 400), num_layer 4, is not served: its split weights (320 KB) do not fit a CU's LDS.  Pure host arithmetic. */
+ * tpnet_mlp64_f32's; (100, 400), num_layer 4, is not served: its split weights (320 KB) do not fit a CU's LDS.  Pure host arithmetic.
+ * (100, 400) has entries of its own that stream the weights: tpnet_mlp_l4_* below. */
 int tpnet_mlp_rows_supported(int32_t F, int32_t H);
 /* self.mlp alone for num_layer 1 and 2 in the fp32 class on the matrix cores: y[n][F] = mlp(x[n][F]) in ONE launch on the caller's
  * stream, no synchronisation (csrc/mlp_rows.hip: two-piece bf16 operands, three products per term, fp32 accumulators; <= 2e-5 of
@@ -993,6 +995,44 @@ int tpnet_encoder_input_bwd(const float* node_raw, int64_t n_node_rows, const fl
                             const uint32_t* relu_bits, const float* gy, int64_t n_nodes, int32_t K, const int32_t* dims,
                             const void* bimg, void* workspace, float* gfeat, int32_t time_grads, float* partial, int32_t n_partial,
                             uint32_t* err, void* stream);
+
+/* ---- self.mlp for num_layer 4, forward and backward (additive to ABI 7; csrc/mlp_l4.hip) --------------------
+ * y[n][100] = W2 . relu(W1 . x[n][100] + b1) + b2 for Linear(100, 400) -> ReLU -> Linear(400, 100) in the fp32 class on the matrix
+ * cores (two-piece bf16 operands, three products per term, fp32 accumulators), the split weights streamed through LDS from an image.
+ * Everything runs on the caller's stream without synchronisation.
+ *   tpnet_mlp_l4_supported:  1 only for (F, H) = (100, 400).  Pure host arithmetic.
+ *   tpnet_mlp_l4_prepare:    ONE launch that writes the forward's image (tpnet_mlp_l4_image_bytes, 16-byte aligned) from w1 [400][100],
+ *                            b1 [400], w2 [100][400], b2 [100]; again whenever one of the four changed.
+ *   tpnet_mlp_l4_f32:        ONE launch.  x and y: device, 16-byte aligned, x read only inside its n * 100 floats, y written only inside
+ *                            its n * 100 floats.  relu_bits (4-byte aligned; NULL: not recorded) [n][13] uint32: bit u % 32 of word
+ *                            u / 32 of a row is (W1 . x + b1)[u] > 0 exactly as this launch decided it; the bits of units 400..415 are 0.
+ *                            y has the same bits with and without relu_bits.
+ *   tpnet_mlp_l4_bwd_f32:    from gy = dL/dy [n][100] (16-byte aligned) and relu_bits = m, TWO launches:
+ *                              a = W1 . x + b1, h = m ? a : 0, gh = W2^T . gy, ga = m ? gh : 0,
+ *                              gw1 = sum ga (x) x, gb1 = sum ga, gw2 = sum gy (x) h, gb2 = sum gy           (every sum over the rows)
+ *                            No gradient by x is formed.  The decisions are the forward's: read, not recomputed.
+ *                            min(n_partial, ceil(n / 32)) or fewer partial sums are written, one per part of the rows.  A partial is
+ *                            tpnet_mlp_l4_bwd_partial_floats() = 80 500 floats, laid out gw1 [400][100] | gb1 [400] | gw2 [100][400] |
+ *                            gb2 [100], partial i at partial + i * that many floats; `partial` (4-byte aligned) holds n_partial >= 1 of
+ *                            them, those beyond the returned count are not written.  Returns that count (>= 0; 0 for n = 0) or a negative
+ *                            error.  The caller adds the partials in a fixed order; the kernels use no atomics: two calls give equal bits.
+ *                            bimg: the backward's image (tpnet_mlp_l4_bwd_image_bytes; tpnet_mlp_l4_bwd_prepare writes it from w1, b1
+ *                            and w2 in ONE launch).  ws: tpnet_mlp_l4_bwd_workspace_bytes(n) = ceil(n / 32) 32 (2 * 416 + 2 * 128) 4 bytes
+ *                            (0 for n < 0 or n > 2^31), 16-byte aligned, the call's own: its contents mean nothing before or after.
+ * n == 0: TPNET_OK / 0, nothing launched.  TPNET_ERR_BAD_ARG, before any HIP call: a null or misaligned x, y, img (gy, bimg, ws,
+ * relu_bits, partial), n < 0 or n > 2^31, n_partial < 1.  A negative code also when the runtime refuses a launch -- the caller then
+ * runs the layers its other way.  A row of x that holds a NaN gives unspecified values in THAT row of y and of relu_bits (a NaN hidden
+ * unit passes the ReLU as 0, bit 0); every other row is unaffected. */
+int tpnet_mlp_l4_supported(int32_t F, int32_t H);
+size_t tpnet_mlp_l4_image_bytes(void);
+int tpnet_mlp_l4_prepare(const float* w1, const float* b1, const float* w2, const float* b2, void* img, void* stream);
+int tpnet_mlp_l4_f32(const float* x, int64_t n, const void* img, float* y, uint32_t* relu_bits, void* stream);
+size_t tpnet_mlp_l4_bwd_image_bytes(void);
+int tpnet_mlp_l4_bwd_prepare(const float* w1, const float* b1, const float* w2, void* bimg, void* stream);
+int64_t tpnet_mlp_l4_bwd_partial_floats(void);
+size_t tpnet_mlp_l4_bwd_workspace_bytes(int64_t n);
+int tpnet_mlp_l4_bwd_f32(const float* x, const uint32_t* relu_bits, const float* gy, int64_t n, const void* bimg, void* ws,
+                         float* partial, int32_t n_partial, void* stream);
 
 /* ---- LinkPredictor_v1 in the fp32 class, forward and backward (additive to ABI 7; csrc/decoder_train.hip) ----
  * out[p] = fc2(relu(fc1(x[p]))), x[p] = concat[src_emb[p], dst_emb[p], feat[p]] (never written), K = 2 D + F:

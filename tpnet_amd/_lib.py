@@ -147,6 +147,15 @@ SIGNATURES = {
     "tpnet_mlp_rows_f32": (C.c_int, [_P, C.c_int64, C.POINTER(Mlp), _P, _P]),
     "tpnet_mlp_rows_bwd_partial_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "tpnet_mlp_rows_bwd_f32": (C.c_int, [_P, _P, C.c_int64, C.POINTER(Mlp), _P, C.c_int32, _P]),
+    "tpnet_mlp_l4_supported": (C.c_int, [C.c_int32, C.c_int32]),
+    "tpnet_mlp_l4_image_bytes": (C.c_size_t, []),
+    "tpnet_mlp_l4_prepare": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "tpnet_mlp_l4_f32": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "tpnet_mlp_l4_bwd_image_bytes": (C.c_size_t, []),
+    "tpnet_mlp_l4_bwd_prepare": (C.c_int, [_P, _P, _P, _P, _P]),
+    "tpnet_mlp_l4_bwd_partial_floats": (C.c_int64, []),
+    "tpnet_mlp_l4_bwd_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "tpnet_mlp_l4_bwd_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     "tpnet_encoder_fused_supported": (C.c_int, [_SP, C.c_int64, C.c_int32, C.POINTER(Mlp)]),
     "tpnet_mlp_image_bytes": (C.c_size_t, []),
     "tpnet_mlp_prepare_image": (C.c_int, [_P, _P, _P, _P, _P, _P]),

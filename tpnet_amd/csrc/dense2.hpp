@@ -73,16 +73,18 @@ __device__ __forceinline__ void dense2_rows(const d2_dims& d, const uint4* __res
     // (every chunk has CH elements and every thread moves D2_PF of them, unconditionally: the registers in between stay registers;
     // behind the last chunk the first one is fetched again and never used)
     const uint32_t nchunks = (uint32_t)(d.NP * (d.KS + HG));
-    static_assert(D2_PF == 6 || D2_PF == 8, "the prefetch registers below");
+    static_assert(D2_PF == 4 || D2_PF == 6 || D2_PF == 8, "the prefetch registers below");
     uint4 p0, p1, p2, p3, p4, p5, p6, p7;      // (named, not an array: an array indexed inside the lambdas ends up in scratch memory)
     auto fetch = [&](uint32_t c) {
         const uint4* src = img + (c < nchunks ? c : 0u) * (uint32_t)CH + tid;
-        p0 = src[0]; p1 = src[D2_T]; p2 = src[2 * D2_T]; p3 = src[3 * D2_T]; p4 = src[4 * D2_T]; p5 = src[5 * D2_T];
+        p0 = src[0]; p1 = src[D2_T]; p2 = src[2 * D2_T]; p3 = src[3 * D2_T];
+        if constexpr (D2_PF >= 6) { p4 = src[4 * D2_T]; p5 = src[5 * D2_T]; }
         if constexpr (D2_PF == 8) { p6 = src[6 * D2_T]; p7 = src[7 * D2_T]; }
     };
     auto commit = [&](int b) {
         uint4* dst = buf[b] + tid;
-        dst[0] = p0; dst[D2_T] = p1; dst[2 * D2_T] = p2; dst[3 * D2_T] = p3; dst[4 * D2_T] = p4; dst[5 * D2_T] = p5;
+        dst[0] = p0; dst[D2_T] = p1; dst[2 * D2_T] = p2; dst[3 * D2_T] = p3;
+        if constexpr (D2_PF >= 6) { dst[4 * D2_T] = p4; dst[5 * D2_T] = p5; }
         if constexpr (D2_PF == 8) { dst[6 * D2_T] = p6; dst[7 * D2_T] = p7; }
         __syncthreads();
     };

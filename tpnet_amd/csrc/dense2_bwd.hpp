@@ -268,6 +268,49 @@ __device__ __forceinline__ void dense2_bwd_rows(const d2b_dims& d, const uint4* 
     epi(y);
 }
 
+// ---- the saved ReLU bits (encoder_input_train.hip, mlp_l4.hip): relu_bits [n][ceil(H / 32)] uint32, bit u % 32 of word u / 32 of a
+// row = the forward's decision about hidden unit u.
+// The forward's activation (dense2.hpp: split16 of slice w; register q of lane half h = hidden unit 32 w + acc_row(q, h)): ReLU,
+// and bit acc_row(q, h) of word w of the lane's row = the decision.  The two lanes of a row hold 16 units each.
+struct act_relu_bits {
+    uint32_t* words;                             // relu_bits of the lane's row
+    int NW;                                      // ceil(H / 32) words per row; 0 for a row >= n: nothing is stored
+    __device__ __forceinline__ void split16(const f32x16& a, const float (&bias)[16], int w, bf16x8 (&bh)[2], bf16x8 (&bl)[2]) const {
+        const int h = (threadIdx.x >> 5) & 1;
+        uint32_t m = 0u;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            float x[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int q = 8 * s2 + j;
+                x[j] = a[q] + bias[q];
+                const bool on = x[j] > 0.0f;
+                m |= on ? 1u << acc_row(q, 0) : 0u;
+                x[j] = on ? x[j] : 0.0f;
+            }
+            split8(x, bh[s2], bl[s2]);
+        }
+        m <<= 4 * h;                                                            // acc_row(q, h) = acc_row(q, 0) + 4 h
+        m |= (uint32_t)__shfl_xor((int)m, 32);
+        if (h == 0 && w < NW) words[w] = m;
+    }
+};
+// The backward's rule: h = m ? a : 0 and ga = m ? gh : 0, m the saved bit of the unit -- the four of a block are bits
+// acc_row(4 q4, h) .. + 3 of the slice's word of the lane's row (act_relu_bits wrote it; 0 for a slice of the padding)
+struct rule_relu_bits {
+    const uint32_t* __restrict__ words;          // relu_bits of the lane's row
+    int NW;                                      // ceil(H / 32) words per row; 0 for a row >= n: nothing is read
+    __device__ __forceinline__ uint32_t block(int slice, int q4) const {
+        return (slice < NW ? words[slice] : 0u) >> acc_row(4 * q4, (threadIdx.x >> 5) & 1);
+    }
+    __device__ __forceinline__ void unit(uint32_t m, int j, bool real, float a, float gh, float& hv, float& gav) const {
+        const bool on = ((m >> j) & 1u) != 0u && real;
+        hv = on ? a : 0.0f;
+        gav = on ? gh : 0.0f;
+    }
+};
+
 // ---- the host's side of the two launches
 // row parts of equal tile counts, none empty: tiles per part, and the parts (= the partials the weight kernel writes)
 static inline int d2b_row_parts(int64_t T, int32_t n_partial, int64_t& tpp) {

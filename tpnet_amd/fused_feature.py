@@ -80,7 +80,9 @@ _declined_once = set()
 # 53.5 / 80.8 against 311 / 516 us; 800 000 rows 236 / 456 against 2 380 / 4 029 us.  Shorter lists were not measured and stay
 # with torch.
 MLP_ROWS_BWD_FROM = {16: 1000, 36: 1000}
-calls = {"rows_bwd": 0}                     # launches of tpnet_mlp_rows_bwd_f32 made from here (tests assert the dispatch through it)
+# launches made from here (tests assert the dispatch through them): of tpnet_mlp_rows_bwd_f32; of tpnet_mlp_l4_f32 (one per call) and
+# tpnet_mlp_l4_bwd_f32 (two per call); "l4_prepare": rebuilds of num_layer 4's weight images
+calls = {"rows_bwd": 0, "l4": 0, "l4_bwd": 0, "l4_prepare": 0}
 
 
 def _bwd_kernel(x, prep, n):
@@ -206,6 +208,130 @@ class _NoCtx:
         pass
 
 
+# ---- num_layer 4 (csrc/mlp_l4.hip): Linear(100, 400) -> ReLU -> Linear(400, 100) with the split weights streamed from an image
+# rows from which tpnet_mlp_l4_f32 takes self.mlp from the torch layers under RandomProjectionModule.mlp_l4, and from which
+# tpnet_mlp_l4_bwd_f32 takes the weight gradients from _dense.layer_grads; None = reachable through the C call, never routed.
+# MLP_ROWS_FROM's rule, measured by tools/mlp_l4_rate.py (profiles/mlp_l4.md): under no_grad one launch takes 27.7 us at 1 000 rows, the
+# smallest size of the protocol, against 48.4 us of the torch layers, 94.4 against 274 us at 80 000 rows and 834 against 2 629 us at
+# 800 000; forward + backward 117 against 158 us, 569 against 1 072 us and 5 007 against 8 452 us.  Shorter lists were not measured
+# and stay with torch.
+MLP_L4_FROM = 1000
+MLP_L4_BWD_FROM = 1000
+L4_PARTIALS = 32                            # row parts of the backward's weight kernel = partial sums it writes, at most
+_L4 = weakref.WeakKeyDictionary()           # mlp module -> L4Images
+
+
+class L4Images(NamedTuple):
+    key: tuple          # (data_ptr, _version) of w1, b1, w2, b2 when the images were last written
+    img: torch.Tensor   # the forward's weight image (uint8)
+    storage: tuple      # device + the Parameters' data_ptr()s: the same storage keeps the image buffers
+    bimg: torch.Tensor = None   # the backward's image, once a training call asked for it (then kept current)
+
+
+def l4_images(mlp, backward=False):
+    """The L4Images record of `mlp`, or None if it is not Linear(100, 400) -> ReLU -> Linear(400, 100) with contiguous float32
+    Parameters on a GPU.  Rewritten in place, on the current stream, when a Parameter changed through a versioned op (prepared()'s
+    contract); `backward`: the record also holds the backward's image, and from then on both are rewritten together."""
+    ls = _dense.linear_relu_linear(mlp)
+    if ls is None or not _lib.load().tpnet_mlp_l4_supported(ls[0].in_features, ls[0].out_features) \
+            or ls[1].out_features != ls[0].in_features:
+        return None
+    w1, b1, w2, b2 = ls[0].weight, ls[0].bias, ls[1].weight, ls[1].bias
+
+    def build(previous, both):
+        if not all(p.is_cuda and p.is_contiguous() and p.dtype == torch.float32 for p in (w1, b1, w2, b2)):
+            return None
+        lib, stream = _lib.load(), _dense.stream_ptr(w1.device)
+        img, bimg = (previous.img, previous.bimg) if previous is not None else (None, None)
+        if img is None:
+            img = torch.empty(int(lib.tpnet_mlp_l4_image_bytes()), dtype=torch.uint8, device=w1.device)
+        _lib.check(lib.tpnet_mlp_l4_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), img.data_ptr(), stream),
+                   "mlp_l4_prepare")
+        if both:
+            if bimg is None:
+                bimg = torch.empty(int(lib.tpnet_mlp_l4_bwd_image_bytes()), dtype=torch.uint8, device=w1.device)
+            _lib.check(lib.tpnet_mlp_l4_bwd_prepare(w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), bimg.data_ptr(), stream),
+                       "mlp_l4_bwd_prepare")
+        calls["l4_prepare"] += 1
+        return L4Images(key, img, storage, bimg)
+
+    key = _dense.param_key(w1, b1, w2, b2)
+    storage = (w1.device, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr())
+    return _dense.cached_images(_L4, mlp, key, storage, build, backward)
+
+
+class _MlpL4(torch.autograd.Function):
+    """Forward: tpnet_mlp_l4_f32; where the backward's kernels will serve (`bits`), it also records the ReLU's decisions.  Saved: x
+    (the features, by reference) and relu_bits, 52 bytes per row; the Parameters stand for their images, which are looked up again
+    in the backward (an in-place change in between raises as torch does).  Backward: tpnet_mlp_l4_bwd_f32 in a workspace of its
+    own + the fixed-order sum of its partials; without bits, or where the C call declines, _dense.layer_grads."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, mlp, rec, bits):
+        n = x.shape[0]
+        y = torch.empty_like(x)
+        relu_bits = torch.empty((n, 13), dtype=torch.int32, device=x.device) if bits else None
+        if _lib.load().tpnet_mlp_l4_f32(x.data_ptr(), n, rec.img.data_ptr(), y.data_ptr(), relu_bits.data_ptr() if bits else None,
+                                        _dense.stream_ptr(x.device)):
+            raise _RowsDeclined()                              # (nothing was launched: mlp_l4 hands the call back to torch)
+        calls["l4"] += 1
+        ctx.save_for_backward(x, w1, b1, w2, b2, relu_bits)
+        ctx.mlp = mlp
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w1, b1, w2, b2, relu_bits = ctx.saved_tensors
+        rec = l4_images(ctx.mlp, backward=True) if relu_bits is not None else None
+        if rec is not None and rec.bimg is not None:
+            lib, n, dev = _lib.load(), x.shape[0], x.device
+            gy = gy.contiguous()
+            part = _dense.partial_buffer(dev, L4_PARTIALS, lib.tpnet_mlp_l4_bwd_partial_floats())
+            ws = torch.empty(int(lib.tpnet_mlp_l4_bwd_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+            rc = lib.tpnet_mlp_l4_bwd_f32(x.data_ptr(), relu_bits.data_ptr(), gy.data_ptr(), n, rec.bimg.data_ptr(), ws.data_ptr(),
+                                          part.data_ptr(), part.shape[0], _dense.stream_ptr(dev))
+            del ws                                              # (the caching allocator keeps it alive for the stream's launches)
+            if rc > 0:
+                calls["l4_bwd"] += 2
+                grads = _dense.split_grads(_dense.sum_partials(rc, part, "mlp_l4_bwd"), (w1, b1, w2, b2), ctx.needs_input_grad[1:5])
+                return (None, *grads, None, None, None)
+            if ("tpnet_mlp_l4_bwd_f32", rc) not in _declined_once:
+                _declined_once.add(("tpnet_mlp_l4_bwd_f32", rc))
+                warnings.warn(f"tpnet_mlp_l4_bwd_f32 declined a call of {n} rows (rc {rc}): weight gradients by the fp32 torch expressions")
+        return (None, *_dense.layer_grads(x, gy, w1, b1, w2), None, None, None)
+
+
+def mlp_l4(mlp, x):
+    """mlp(x) by tpnet_mlp_l4_f32 (one launch, fp32 class), or None where it does not serve the call: `mlp` is not num_layer 4's
+    Linear(100, 400) -> ReLU -> Linear(400, 100) with contiguous float32 Parameters on the GPU of x, fewer rows than MLP_L4_FROM,
+    mlp.mlp_backward = "torch" or an x that requires a gradient while one is recorded (the torch layers serve), a negative return code.
+    Differentiable with respect to the four Parameters: from MLP_L4_BWD_FROM rows the forward records the ReLU's decisions and the
+    backward is two launches (tpnet_mlp_l4_bwd_f32) + the sum of at most L4_PARTIALS partials."""
+    if (MLP_L4_FROM is None or x.dim() != 2 or x.shape[0] < MLP_L4_FROM or x.shape[1] != 100 or x.dtype != torch.float32
+            or not x.is_cuda):
+        return None
+    train = torch.is_grad_enabled()
+    if train and (x.requires_grad or (getattr(mlp, "mlp_backward", None) or mlp_backward) == "torch"):
+        return None
+    ls = _dense.linear_relu_linear(mlp)
+    if ls is None:
+        return None
+    params = (ls[0].weight, ls[0].bias, ls[1].weight, ls[1].bias)
+    grads = train and any(p.requires_grad for p in params)
+    bits = grads and MLP_L4_BWD_FROM is not None and x.shape[0] >= MLP_L4_BWD_FROM
+    rec = l4_images(mlp, backward=bits)
+    if rec is None or rec.img.device != x.device:
+        return None
+    x = x.contiguous()
+    try:
+        if grads:
+            return _MlpL4.apply(x, *params, mlp, rec, bits)
+        return _MlpL4.forward(_NoCtx(), x, None, None, None, None, None, rec, False)
+    except _RowsDeclined:
+        return None
+
+
 def invalidate(mlp=None):
     """Forget the prepared copies of `mlp`'s weights (all modules' if None).  The cache is keyed on (data_ptr, _version) of the
     four tensors; an in-place write THROUGH `.data` (p.data.copy_(), p.data.mul_(): some EMA / weight-averaging helpers) bumps
@@ -213,8 +339,10 @@ def invalidate(mlp=None):
     on the Parameters are seen without it."""
     if mlp is None:
         _PREPARED.clear()
+        _L4.clear()
     else:
         _PREPARED.pop(mlp, None)
+        _L4.pop(mlp, None)
 
 
 def prepared(mlp, F):

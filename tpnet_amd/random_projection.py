@@ -1051,7 +1051,15 @@ class RandomProjectionModule(nn.Module):
         g1, g2 = self.pair_gram_shared(node_ids, first_ids, second_ids)
         return self._apply_mlp(torch.cat([g1, g2], dim=0))
 
+    # extension, opt-in: at num_layer 4 self.mlp runs on the matrix cores in the fp32 class (fused_feature.mlp_l4, csrc/mlp_l4.hip),
+    # forward and weight gradients, for lists of fused_feature.MLP_L4_FROM rows or more; False: the torch layers, bit for bit
+    mlp_l4 = False
+
     def _apply_mlp(self, feats: torch.Tensor) -> torch.Tensor:
+        if self.mlp_l4 and self.num_layer == 4:
+            y = _ff.mlp_l4(self.mlp, feats)
+            if y is not None:
+                return y
         if self.fused_mlp and _fm.supported(self.mlp):
             return _fm.fused_mlp(self.mlp, feats)
         y = _ff.mlp_f32(self.mlp, feats)                   # the fp32 matrix-core kernels where one serves this width and length
