@@ -33,6 +33,19 @@ def _stream(rng, N, B, nb, hubs=True):
     return out
 
 
+def _w2f_index(dev):
+    """The independent reference for tpnet_mlp::w2f (include/tpnet_hip.h): index tensors of the gather
+    w2f[((w*2 + t)*64 + lane)*16 + s] = W2[32 t + (lane & 31)][32 w + (s & 3) + 8 (s >> 2) + 4 (lane >> 5)]
+    (w = 0..7, t = 0..1, lane = 0..63, s = 0..15)."""
+    w = torch.arange(8).view(8, 1, 1, 1)
+    t = torch.arange(2).view(1, 2, 1, 1)
+    lane = torch.arange(64).view(1, 1, 64, 1)
+    s_ = torch.arange(16).view(1, 1, 1, 16)
+    rows = (32 * t + (lane & 31)).expand(8, 2, 64, 16).reshape(-1)
+    cols = (32 * w + (s_ & 3) + 8 * (s_ >> 2) + 4 * (lane >> 5)).expand(8, 2, 64, 16).reshape(-1)
+    return rows.to(dev), cols.to(dev)
+
+
 def _assert_mlp_grads_close(mlp, gram, gy, got, want):
     """Gradients of self.mlp's four tensors from two implementations of the same forward.  The derivative of ReLU at a
     pre-activation that is zero up to GEMM rounding is either 0 or 1, and the two implementations (torch's Linear; the fused
@@ -474,7 +487,7 @@ def test_mlp_prepare_layouts_follow_the_parameters():
     prep = ff.prepared(mlp, 64)
     w1t, w2t, w2f, img = prep[3]
     torch.cuda.synchronize()
-    rows, cols = ff._w2f_index(mlp[2].weight.device)
+    rows, cols = _w2f_index(mlp[2].weight.device)
     assert torch.equal(w1t, mlp[0].weight.detach().t()) and torch.equal(w2t, mlp[2].weight.detach().t())
     assert torch.equal(w2f, mlp[2].weight.detach()[rows, cols])
     assert prep[1].w1 == mlp[0].weight.data_ptr() and prep[1].b1 == mlp[0].bias.data_ptr()
@@ -655,10 +668,12 @@ def test_one_launch_encoder_call_on_random_shapes():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [33, 8192 + 33])
+@pytest.mark.parametrize("n", [33, 8192 + 33, 65536 + 33])
 def test_mlp64_f32_on_both_sides_of_its_switch(n):
     """tpnet_mlp64_f32 through the shared dense-layer route: 33 rows take the tile kernel (one full and one partial tile), 8 225
-    rows the per-wave-tile kernel (from 8 192 rows on; a partial last tile).  Against the torch layers within the fp32-class bound
+    rows the per-wave-tile kernel (from 8 192 rows on; a partial last tile), 65 569 rows are 2 050 tiles for its 256 workgroups of
+    8 waves: two waves walk a second tile (the prefetch and the stride of the tile walk), and the last tile holds one row.
+    Against the torch layers within the fp32-class bound
     of this file (2e-5 of the output scale); on small integers -- every product and partial sum below 2^24, every value the sum
     of two bf16 pieces -- bit for bit, so that a wrong lane or accumulator index cannot hide behind the tolerance."""
     if not torch.cuda.is_available():

@@ -257,6 +257,51 @@ def test_mlp_backward_on_the_matrix_cores_is_exact_on_integers():
 
 
 @pytest.mark.gpu
+def test_mlp_backward_in_the_fp32_class_is_exact_on_integers():
+    """tpnet_mlp64_bwd_f32 on the data of tests/test_mlp_rows_bwd.py::test_exact_on_small_integers at F = 64 (small-integer
+    weights, features and output gradients: every product and partial sum is exact in two bf16 pieces and an fp32 accumulator):
+    the four gradients equal autograd's through the fp32 torch layers bit for bit, around the 32-row tile and beyond one pass of
+    a 256-partial grid (9 000 rows = 282 tiles: 26 workgroups walk two tiles); two calls give equal bits."""
+    if not torch.cuda.is_available():
+        pytest.fail("needs a GPU")
+    from tpnet_amd import _dense, _lib, fused_feature as ff
+    F, H = 64, 256
+    g = torch.Generator().manual_seed(3 + F)
+    mlp = torch.nn.Sequential(torch.nn.Linear(F, H), torch.nn.ReLU(), torch.nn.Linear(H, F)).cuda()
+    with torch.no_grad():
+        mlp[0].weight.copy_(torch.randint(-1, 2, (H, F), generator=g).float())
+        mlp[0].bias.copy_(torch.randint(-8, 9, (H,), generator=g).float())
+        mlp[2].weight.copy_(torch.randint(-2, 3, (F, H), generator=g).float())
+        mlp[2].bias.copy_(torch.randint(-8, 9, (F,), generator=g).float())
+    cpu = [p.detach().cpu() for p in (mlp[0].weight, mlp[0].bias, mlp[2].weight)]
+    lib = _lib.load()
+    pf = int(lib.tpnet_mlp64_bwd_partial_floats())
+    assert pf == 2 * H * F + H
+    for n in (1, 31, 32, 33, 1000, 9000):
+        x = torch.randint(0, 3, (n, F), generator=g).float()
+        x[:, 8:] *= (torch.rand(n, F - 8, generator=g) < 0.2).float()            # sparse: |pre| stays small
+        gy = torch.randint(-1, 2, (n, F), generator=g).float()
+        gy *= (torch.rand(n, F, generator=g) < 0.3).float()
+        # every sum stays an exact integer: the float32 and the float64 expressions agree exactly
+        for a, b in zip(_dense.layer_grads(x, gy, *cpu), _dense.layer_grads(x.double(), gy.double(), *[p.double() for p in cpu])):
+            assert torch.equal(a.double(), b), n
+        x, gy = x.cuda(), gy.cuda()
+        want = torch.autograd.grad(mlp(x), list(mlp.parameters()), gy)
+        ref = ff.prepared(mlp, F)[2]
+        tiles = (n + 31) // 32
+        both = []
+        for _ in range(2):
+            part = torch.full((256, pf), float("nan"), device="cuda")
+            rc = lib.tpnet_mlp64_bwd_f32(x.data_ptr(), gy.data_ptr(), n, ref, part.data_ptr(), 256, _dense.stream_ptr(x.device))
+            assert rc == min(256, tiles)
+            tot = part[:rc].sum(0)
+            both.append((tot[:H * F].view(H, F), tot[2 * H * F:], tot[H * F:2 * H * F].view(F, H), gy.sum(0)))
+        for a, b, c, name in zip(both[0], want, both[1], ("gW1", "gb1", "gW2", "gb2")):
+            assert torch.equal(a, c), name
+            assert torch.equal(a, b), f"{name}, n={n}: max |delta| {(a - b).abs().max().item()}"
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n", [33, 5000, 80000])
 def test_mlp_backward_in_the_fp32_class(n):
     """tpnet_mlp64_bwd_f32 (csrc/mlp_bwd.hip, F32 = true: two-piece bf16 operands, three products, fp32 accumulation; one partial

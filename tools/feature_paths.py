@@ -7,6 +7,7 @@ around it, the kernel names and call counts close the gap.
 
     python tools/feature_paths.py OUT_DIR              # everything (the readout section first: 374 of the files)
     python tools/feature_paths.py OUT_DIR readout      # only the readout kernels' matrix (readout_cases)
+    python tools/feature_paths.py OUT_DIR mlp          # only self.mlp's six C entries, partials included (mlp_cases; not in "everything")
 """
 import os
 import sys
@@ -187,6 +188,37 @@ def dense_cases(rng):
                 case(f"embedding_{tag}_fused_input_{int(fused)}", lambda: emb.embed_from_features(*arrays))
 
 
+def mlp_cases():
+    """The six C entries of self.mlp on rows that exist (csrc/mlp_x3.hip, mlp_rows.hip, mlp_bwd.hip, mlp_rows_bwd.hip) on seeded
+    real-valued data: the forwards around their kernel switch and past one tile per wave, the backwards with every partial of a
+    2-partial and a 256-partial launch."""
+    from tpnet_amd import _dense, _lib, fused_feature as ff, fused_mlp as fm
+    lib = _lib.load()
+    rng = np.random.RandomState(31)
+    rows = lambda n, w, lo=0.0, hi=12.0: torch.from_numpy(rng.uniform(lo, hi, (n, w)).astype(np.float32)).to(DEV)
+    stream = lambda: _dense.stream_ptr(torch.device(DEV))
+    for F, ns in ((64, (33, 8191, 8193, 65569)), (16, (1, 31, 32, 33, 1000, 4099, 140001)), (36, (1, 31, 32, 33, 1000, 4099, 140001))):
+        torch.manual_seed(F)
+        mlp = nn.Sequential(nn.Linear(F, 4 * F), nn.ReLU(), nn.Linear(4 * F, F)).to(DEV)
+        prep = ff.prepared(mlp, F)
+        fwd = lib.tpnet_mlp64_f32 if F == 64 else lib.tpnet_mlp_rows_f32
+        for n in ns:
+            x, y = rows(n, F), torch.empty((n, F), device=DEV)
+            case(f"mlp_fwd_F{F}_n{n}", lambda: (fwd(x.data_ptr(), n, prep.ref, y.data_ptr(), stream()), y))
+        bwds = [("f32", lambda *a: (lib.tpnet_mlp64_bwd_f32 if F == 64 else lib.tpnet_mlp_rows_bwd_f32)(*a[:3], prep.ref, *a[3:]))]
+        if F == 64:
+            p16 = fm._prepared(mlp)
+            bwds.append(("bf16", lambda *a: lib.tpnet_mlp64_bwd_bf16(*a[:3], p16[0].data_ptr(), p16[1].data_ptr(), p16[4].data_ptr(), *a[3:])))
+        pf = 2 * 4 * F * F + 4 * F
+        for n in (33, 1000, 9000, 80000):
+            x, gy = rows(n, F, 0.0, 9.0), rows(n, F, -1.0, 1.0)
+            for tag, call in bwds:
+                for parts in (2, 256):
+                    part = torch.zeros((parts, pf), device=DEV)
+                    case(f"mlp_bwd_{tag}_F{F}_n{n}_p{parts}",
+                         lambda: (call(x.data_ptr(), gy.data_ptr(), n, part.data_ptr(), parts, stream()), part))
+
+
 def readout_cases():
     """The readout kernels by geometry and store path (csrc/readout.hpp): the three standalone readouts at eight row widths x L = 1..4,
     and run_stream's readouts on both schedules and in exact mode."""
@@ -223,7 +255,7 @@ def readout_cases():
 def main():
     if ONLY:
         for name in ONLY:
-            {"readout": readout_cases}[name]()
+            {"readout": readout_cases, "mlp": mlp_cases}[name]()
         print(f"{len(SAVED)} files in {OUT}")
         return
     readout_cases()

@@ -1,5 +1,6 @@
-// The fp32-class arithmetic of the matrix-core kernels, once (mlp.hip, mlp_x3.hip, mlp_bwd.hip, decoder.hip, feature_mfma.hip,
-// encoder_mfma.hip, and through dense2.hpp encoder_input.hip and mixer.hip).  Only the arithmetic atoms live here: every kernel
+// The fp32-class arithmetic of the matrix-core kernels, once (mlp.hip, decoder.hip, feature_mfma.hip, encoder_mfma.hip;
+// through mlp_wave_tile.hpp mlp_x3.hip and mlp_rows.hip; through mlp_wgrad.hpp mlp_bwd.hip and mlp_rows_bwd.hip; through dense2.hpp
+// encoder_input.hip and mixer.hip).  Only the arithmetic atoms live here: every kernel
 // keeps its own mapping, staging, pipelining and scheduling barriers.
 //
 // SPLIT OPERANDS.  Every f32 operand is a sum of bf16 pieces, leading piece first: x = p[0] + p[1] (+ p[2]), p[0] = bf16(x),
@@ -29,7 +30,7 @@ __host__ __device__ constexpr int acc_row(int q, int h) { return (q & 3) + 8 * (
 // The weight image of self.mlp = Linear(64, 256) -> ReLU -> Linear(256, 64) in split pieces, byte offsets: hi / lo planes of W1
 // and W2 (2 048 16-byte elements each, every element the operand of one lane of one matrix instruction), then b1 and b2.  Two
 // element orders use these offsets, each documented where the image is built: k_mlp64_x3's LDS image (32x32x16 operands,
-// mlp_x3.hip) and tpnet_mlp::wimg (16x16x32 operands, k_mlp_image in encoder_mfma.hip).
+// MlpRowsGeo<3> of mlp_wave_tile.hpp, which asserts the equality) and tpnet_mlp::wimg (16x16x32 operands, k_mlp_image in encoder_mfma.hip).
 static constexpr int IMG_W1H = 0, IMG_W1L = 32768, IMG_W2H = 65536, IMG_W2L = 98304, IMG_B1 = 131072, IMG_B2 = IMG_B1 + 1024;
 static constexpr int IMG_BYTES = IMG_B2 + 256;                              // 132 352
 

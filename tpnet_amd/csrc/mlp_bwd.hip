@@ -1,37 +1,21 @@
 // Backward of self.mlp = Linear(64,256) -> ReLU -> Linear(256,64) (models/TPNet.py:64-65) with respect to its four weight
 // tensors, on the bf16 matrix cores ("needs a backward for training (grad w.r.t. weights only -- P has no
-// grad)").  One kernel: per tile of 32 pairs, wave w (of 8) owns hidden units [32w, 32w+32):
-//   pre^T = W1[32w.., :] . X^T + b1,  H^T = relu(pre^T)          (recomputed, as the forward kernel forms it)
-//   gH^T  = (W2^T[32w.., :] . gY^T) * (pre^T > 0)
-//   gW1[32w.., :] += gH^T . X        gW2[:, 32w..] += gY^T . H      (contraction over the 32 pairs: the tiles go through LDS
-//                                                                   transposed, [unit][pair], so that they load as operands)
-//   gb1[32w..]   += sum_pairs gH                                     (fp32, per-lane partial sums, reduced once per workgroup;
-//                                                                    gb2 = sum_pairs gY is a column sum the caller takes)
-// The accumulators live in registers over all tiles of a workgroup; every workgroup writes ONE partial result, and the
-// caller adds the partials (a fixed-order sum: run-to-run identical bits).
+// grad)").  One kernel: per tile of 32 pairs, wave w (of 8) owns hidden units [32w, 32w+32); the mapping, the partial result per
+// workgroup and the phases shared with mlp_rows_bwd.hip (F = 16 and 36) are stated in mlp_wgrad.hpp: the bias staging, the hidden
+// tile's way to LDS, the contraction, the partial store, the launch rule.  pre^T is recomputed as the forward kernel forms it.
 // Two arithmetic classes (template F32): bf16 operands with fp32 accumulation (the opt-in 1e-2 class), and -- round 4 -- the fp32
 // class of the default forward paths: two-piece operands, three products per term (mfma_split.hpp), weights taken from the f32 Parameters (mlp[0].weight [256][64] and the
 // prepared transpose of mlp[2].weight, tpnet_mlp::w2t [256][64]); the four LDS tiles exist twice (hi and lo planes).  What it
 // replaces in a training step at the encoder level: five fp32 torch GEMMs and three elementwise passes over 80 000 x 256 floats
-// per call (~1 ms).
+// per call (~1 ms).  This kernel's own: every wave loads the tile's rows itself, pre^T on the class's operands, the bf16 class.
 #include "tpnet_common.h"
-#include "mfma_split.hpp"
+#include "mlp_wgrad.hpp"
 
 namespace tpnet {
 
 static constexpr int BB = 512;             // 8 waves = the 8 hidden tiles
 static constexpr int BF = 64, BH = 256;
-static constexpr int RS = 40;              // bf16 elements per LDS row of a [unit][32 pairs] tile (80 B: 16-byte aligned, bank spread)
-
-// partial layout per workgroup (floats): gW1 [256][64] | gW2 [64][256] | gb1 [256]
-static constexpr int P_W1 = 0, P_W2 = BH * BF, P_B1 = 2 * BH * BF, P_TOT = 2 * BH * BF + BH;
-
-// c += A B over one 16-deep step; F32: operands in two pieces [0] = hi, [1] = lo
-template <bool F32>
-__device__ __forceinline__ f32x16 mm(const bf16x8* a, const bf16x8* b, f32x16 c) {
-    if constexpr (F32) return mm3(a[0], a[1], b[0], b[1], c);
-    else return mfma(a[0], b[0], c);
-}
+static constexpr int RS = WG_QS;           // bf16 elements per LDS row of a [unit][32 pairs] tile
 
 // W1S / W2S: bf16 [256][64] (F32 = false) or f32 [256][64] (F32 = true: mlp[0].weight, and mlp[2].weight transposed)
 template <bool F32>
@@ -59,15 +43,8 @@ __global__ __launch_bounds__(BB) void k_mlp64_bwd(const float* __restrict__ X, c
             a2[s][0] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const __bf16*>(w2tv) + off);
         }
     }
-    // the bias of this wave's hidden tile in accumulator order, parked in LDS (16 registers the fp32 class does not have):
-    // float 16 * (2 wave + h) + q = b1[32 wave + acc_row(q, h)]
-    float* bias_l = reinterpret_cast<float*>(ght_all + 8 * NP * 32 * RS);
-    if (r == 0) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) bias_l[16 * (2 * wave + h) + q] = b1[wave * 32 + acc_row(q, h)];
-    }
+    const float4* bias4 = wgrad_stage_bias<BH>(reinterpret_cast<float*>(ght_all + 8 * NP * 32 * RS), b1, wave, r, h);
     __syncthreads();
-    const float4* bias4 = reinterpret_cast<const float4*>(bias_l + 16 * (2 * wave + h));
     f32x16 gw1[2], gw2[2];                   // gW1[32w + m][32 nt + r], nt = 0,1;  gW2[32 mt + m][32w + r], mt = 0,1
     float gb1[16];
 #pragma unroll
@@ -114,19 +91,13 @@ __global__ __launch_bounds__(BB) void k_mlp64_bwd(const float* __restrict__ X, c
 #pragma unroll
             for (int q = 0; q < 16; ++q) pre[q] = 0.f;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) pre = mm<F32>(a1[s], bx[s], pre);
+            for (int s = 0; s < 4; ++s) pre = mm<NP>(a1[s], bx[s], pre);
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int hq = acc_row(q, h);
-                const float4 bq = bias4[q >> 2];
-                const float p = pre[q] + ((q & 3) == 0 ? bq.x : (q & 3) == 1 ? bq.y : (q & 3) == 2 ? bq.z : bq.w);
-                const bool on = valid && p > 0.0f;
-                on_mask |= (on ? 1u : 0u) << q;
-                __bf16 hp[NP];
-                split1(on ? p : 0.0f, hp);
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) hrow[pl * 32 * RS + hq * RS + r] = hp[pl];
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float4 bq = bias4[q4];
+                pre[4 * q4] += bq.x; pre[4 * q4 + 1] += bq.y; pre[4 * q4 + 2] += bq.z; pre[4 * q4 + 3] += bq.w;
             }
+            on_mask = wgrad_hidden<NP>(pre, valid, hrow, r, h);
         }
         {
             bf16x8 bg[4][NP];
@@ -135,63 +106,14 @@ __global__ __launch_bounds__(BB) void k_mlp64_bwd(const float* __restrict__ X, c
 #pragma unroll
             for (int q = 0; q < 16; ++q) gh[q] = 0.f;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) gh = mm<F32>(a2[s], bg[s], gh);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int hq = acc_row(q, h);
-                const float gv = ((on_mask >> q) & 1u) ? gh[q] : 0.0f;
-                gb1[q] += gv;
-                __bf16 gp[NP];
-                split1(gv, gp);
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) grow[pl * 32 * RS + hq * RS + r] = gp[pl];
-            }
+            for (int s = 0; s < 4; ++s) gh = mm<NP>(a2[s], bg[s], gh);
+            wgrad_ghidden<NP>(gh, on_mask, gb1, grow, r, h);
         }
         __syncthreads();
-        // gW1[32w + m][32 nt + r] += sum_pairs gH^T[m][pair] X[pair][32 nt + r]:  A = gH^T rows, B[k = pair][n] = X^T[n][pair]
-        // gW2[32 mt + m][32w + r] += sum_pairs gY^T[32 mt + m][pair] H[pair][32w + r]: A = gY^T rows, B = H^T[r][pair]
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int ko = 16 * s + 8 * h;           // 8 consecutive pairs
-            bf16x8 a_gh[NP], b_h[NP];
-#pragma unroll
-            for (int pl = 0; pl < NP; ++pl) {
-                a_gh[pl] = *reinterpret_cast<const bf16x8*>(grow + pl * 32 * RS + r * RS + ko);
-                b_h[pl] = *reinterpret_cast<const bf16x8*>(hrow + pl * 32 * RS + r * RS + ko);
-            }
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) {
-                bf16x8 b_x[NP], a_gy[NP];
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) {
-                    b_x[pl] = *reinterpret_cast<const bf16x8*>(xt + pl * BF * RS + (32 * t2 + r) * RS + ko);
-                    a_gy[pl] = *reinterpret_cast<const bf16x8*>(gyt + pl * BF * RS + (32 * t2 + r) * RS + ko);
-                }
-                gw1[t2] = mm<F32>(a_gh, b_x, gw1[t2]);
-                gw2[t2] = mm<F32>(a_gy, b_h, gw2[t2]);
-            }
-        }
+        wgrad_contract<NP, 2>(xt, gyt, hrow, grow, gw1, gw2, r, h);
         __syncthreads();                          // the tiles are rewritten by the next tile
     }
-    // ---- this workgroup's partial result
-    float* P = partial + (int64_t)blockIdx.x * P_TOT;
-#pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int m = acc_row(q, h);
-            P[P_W1 + (wave * 32 + m) * BF + 32 * t2 + r] = gw1[t2][q];
-            P[P_W2 + (32 * t2 + m) * BH + wave * 32 + r] = gw2[t2][q];
-        }
-    }
-    // gb1: sum over the 32 pairs (lanes r) of each half h; register q <-> hidden acc_row(q, h)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        float v = gb1[q];
-#pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o, 32);
-        if (r == 0) P[P_B1 + wave * 32 + acc_row(q, h)] = v;
-    }
+    wgrad_store_partial<BF, BH, 2>(partial, gw1, gw2, gb1, wave, r, h);
 }
 
 template <bool F32>
@@ -203,14 +125,12 @@ using namespace tpnet;
 
 extern "C" {
 
-int64_t tpnet_mlp64_bwd_partial_floats(void) { return (int64_t)P_TOT; }
+int64_t tpnet_mlp64_bwd_partial_floats(void) { return (int64_t)WgradPartial<BF, BH>::TOT; }
 
 int tpnet_mlp64_bwd_bf16(const float* x, const float* gy, int64_t n, const void* w1_bf16, const float* b1,
                          const void* w2t_bf16, float* partial, int32_t n_partial, void* stream) {
     if (n < 1 || !x || !gy || !w1_bf16 || !b1 || !w2t_bf16 || !partial || n_partial < 1) return TPNET_ERR_BAD_ARG;
-    const int64_t tiles = (n + 31) / 32;
-    const int grid = (int)(tiles < n_partial ? tiles : n_partial);
-    // (workgroups beyond `grid` do not exist: the caller sums only the first min(n_partial, ceil(n / 32)) partials)
+    const int grid = wgrad_grid(n, n_partial);
     hipLaunchKernelGGL(k_mlp64_bwd<false>, dim3((unsigned)grid), dim3(BB), bwd_lds_bytes<false>(), (hipStream_t)stream, x, gy, n,
                        w1_bf16, b1, w2t_bf16, partial);
     TPNET_HIP_TRY(hipGetLastError());
@@ -226,8 +146,7 @@ int tpnet_mlp64_bwd_f32(const float* x, const float* gy, int64_t n, const tpnet_
         return TPNET_ERR_BAD_ARG;
     static LdsOptIn lds;
     if (!lds.granted({reinterpret_cast<const void*>(k_mlp64_bwd<true>)}, bwd_lds_bytes<true>())) return TPNET_ERR_BAD_ARG;
-    const int64_t tiles = (n + 31) / 32;
-    const int grid = (int)(tiles < n_partial ? tiles : n_partial);
+    const int grid = wgrad_grid(n, n_partial);
     hipLaunchKernelGGL(k_mlp64_bwd<true>, dim3((unsigned)grid), dim3(BB), bwd_lds_bytes<true>(), (hipStream_t)stream, x, gy, n,
                        (const void*)mlp->w1, mlp->b1, (const void*)mlp->w2t, partial);
     TPNET_HIP_TRY(hipGetLastError());

@@ -1,17 +1,11 @@
 // Backward of self.mlp = Linear(F, 4F) -> ReLU -> Linear(4F, F) (models/TPNet.py:63-65) with respect to its four weight tensors
-// for rp_num_layer L = 1 and L = 2 (F = 16 and 36, H = 64 and 144), fp32 class only: what mlp_bwd.hip is for L = 3, on the padded
-// geometry of mlp_rows.hip.  Same arithmetic for the three products that carry gradients (two-piece bf16 operands, three products
-// per term in mm3's order on v_mfma_f32_32x32x16_bf16, fp32 accumulators) and mlp_bwd.hip's mapping: per tile of 32 rows, wave w
-// owns hidden units [32 w, 32 w + 32):
-//   pre^T = W1[32w.., :] . X^T + b1,  H^T = relu(pre^T)          (recomputed; in exact f32: PRE-ACTIVATIONS)
-//   gH^T  = (W2^T[32w.., :] . gY^T) * (pre^T > 0)
-//   gW1[32w.., :] += gH^T . X        gW2[:, 32w..] += gY^T . H      (contraction over the 32 rows: the tiles go through LDS
-//                                                                   transposed, [unit][row], so that they load as operands)
-//   gb1[32w..]   += sum_rows gH                                     (gb2 = sum_rows gY is a column sum the caller takes)
-// The accumulators live in registers over all tiles of a workgroup; every workgroup writes ONE partial result
-// (gW1 [H][F] | gW2 [F][H] | gb1 [H], unpadded), and the caller adds the partials in a fixed order: run-to-run identical bits.
+// for rp_num_layer L = 1 and L = 2 (F = 16 and 36, H = 64 and 144), fp32 class only, on the padded geometry of the forward
+// (mlp_wave_tile.hpp).  The mapping, the partial result and the phases shared with mlp_bwd.hip (F = 64) are mlp_wgrad.hpp's: the bias
+// staging, the hidden tile's way to LDS, the contraction, the partial store, the launch rule.  Same arithmetic for the three
+// products that carry gradients (two-piece bf16 operands, three products per term in mm3's order on v_mfma_f32_32x32x16_bf16,
+// fp32 accumulators).  This kernel's own: how the rows arrive (LOADS) and how pre^T is formed (PRE-ACTIVATIONS).
 //
-// GEOMETRY (RowsBwdGeo; F, H and the padded shapes are MlpRowsGeo's of mlp_rows.hip).  One wave per hidden slice:
+// GEOMETRY (RowsBwdGeo; F, H and the padded shapes are MlpRowsGeo's of mlp_wave_tile.hpp).  One wave per hidden slice:
 //   L  F   H    k-steps (features / outputs)   waves = slices   tiles of gW1 columns / gW2 rows   threads   VGPRs   LDS bytes
 //   1  16   64  1                              2                1 (half used)                     128      144      36 096
 //   2  36  144  3 (48 columns)                 5 (160 units)    2 (64)                            320      237      81 536
@@ -28,18 +22,18 @@
 // thread and input, one tile ahead of the matrix work, and parks them in LDS as fp32 rows, from which every wave takes its B
 // operands.  (Every wave loading the rows itself, as mlp_bwd.hip does, measured 6.2 us per tile at L = 2 against 4.3 this way, both
 // with pre^T on split operands: five waves' strided reads of the same rows.)
-// PADDING RULES (mlp_rows.hip's, here for two inputs).  Columns >= F of x AND of gy are zero because the READ of the parked row is
+// PADDING RULES (the forward's, mlp_wave_tile.hpp, here for two inputs).  Columns >= F of x AND of gy are zero because the READ of the parked row is
 // masked in whole float4s (F % 4 == 0), never because a zero weight multiplies them: it would take the next row's values.  Rows >= n
 // of the last tile are zero because the global load is masked, in float4s that lie wholly inside or wholly outside n * F floats:
 // the contraction runs over the rows, so a row read past the list would add into every gradient (and NaN * 0 = NaN).  Padded
 // hidden units have zero weights and a zero bias: pre = 0 is "off", H = gH = 0.  Rows >= 16 * k-steps of the transposed X / gY
 // tiles are zeroed once and never rewritten.  Nothing of the padding is written into a partial.
 #include "tpnet_common.h"
-#include "mfma_split.hpp"
+#include "mlp_wgrad.hpp"
 
 namespace tpnet {
 
-static constexpr int QS = 40;              // bf16 elements per LDS row of a [unit][32 rows] tile (80 B: 16-byte aligned, bank spread)
+static constexpr int QS = WG_QS;           // bf16 elements per LDS row of a [unit][32 rows] tile
 
 template <int L>
 struct RowsBwdGeo {
@@ -55,8 +49,6 @@ struct RowsBwdGeo {
     static constexpr int RS = (F / 4) % 2 ? F : F + 4;
     static constexpr int BIAS = END * 2, XS = BIAS + NS * 32 * 4, GS = XS + 32 * RS * 4, BYTES = GS + 32 * RS * 4;
     static constexpr int V4 = 32 * F / 4, NLD = (V4 + BLOCK - 1) / BLOCK;   // float4s of a tile of one input; per thread
-    // partial layout per workgroup (floats)
-    static constexpr int P_W1 = 0, P_W2 = H * F, P_B1 = 2 * H * F, P_TOT = 2 * H * F + H;
     static_assert(F % 4 == 0 && KS * 16 <= FT, "rows are whole float4s; the loaded columns fit the transposed tiles");
     static_assert((F / 2) % 2 == 0 && (RS * 4) % 8 == 0, "a lane's half of a parked row is read in 8-byte vectors");
     static_assert((END * 2) % 16 == 0 && (NS * 32 * 4) % 16 == 0 && (RS * 4) % 16 == 0, "the float tiles are read in 16-byte vectors");
@@ -98,20 +90,11 @@ void k_mlp_rows_bwd(const float* __restrict__ X, const float* __restrict__ GY, i
     }
     // the X^T and gY^T tiles start as zeros (PADDING RULES: their rows >= 16 KS stay so)
     for (int i = tid; i < G::HT; i += G::BLOCK) lds[i] = (__bf16)0.0f;
-    // the bias of this wave's slice in accumulator order: float 16 * (2 wave + h) + q = b1[32 wave + acc_row(q, h)]
     char* smem = reinterpret_cast<char*>(lds);
-    float* bias_l = reinterpret_cast<float*>(smem + G::BIAS);
     float* xs = reinterpret_cast<float*>(smem + G::XS);                   // x  [row][RS]
     float* gs = reinterpret_cast<float*>(smem + G::GS);                   // gy [row][RS]
-    if (r == 0) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int hid = 32 * wave + acc_row(q, h);
-            bias_l[16 * (2 * wave + h) + q] = hid < H ? b1[hid] : 0.0f;
-        }
-    }
+    const float4* bias4 = wgrad_stage_bias<H>(reinterpret_cast<float*>(smem + G::BIAS), b1, wave, r, h);
     __syncthreads();
-    const float4* bias4 = reinterpret_cast<const float4*>(bias_l + 16 * (2 * wave + h));
     f32x16 gw1[NT], gw2[NT];                 // gW1[32w + m][32 t + r];  gW2[32 t + m][32w + r]
     float gb1[16];
 #pragma unroll
@@ -192,16 +175,7 @@ void k_mlp_rows_bwd(const float* __restrict__ X, const float* __restrict__ GY, i
                 pre = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[2 * i2], v.x, pre, 0, 0, 0);
                 pre = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[2 * i2 + 1], v.y, pre, 0, 0, 0);
             }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int hq = acc_row(q, h);
-                const bool on = valid && pre[q] > 0.0f;
-                on_mask |= (on ? 1u : 0u) << q;
-                __bf16 hp[2];
-                split1(on ? pre[q] : 0.0f, hp);
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) hrow[pl * 32 * QS + hq * QS + r] = hp[pl];
-            }
+            on_mask = wgrad_hidden<2>(pre, valid, hrow, r, h);
         }
         {
             bf16x8 bg[KS][2];
@@ -211,64 +185,14 @@ void k_mlp_rows_bwd(const float* __restrict__ X, const float* __restrict__ GY, i
             for (int q = 0; q < 16; ++q) gh[q] = 0.f;
 #pragma unroll
             for (int s = 0; s < KS; ++s) gh = mm3(a2[s][0], a2[s][1], bg[s][0], bg[s][1], gh);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int hq = acc_row(q, h);
-                const float gv = ((on_mask >> q) & 1u) ? gh[q] : 0.0f;
-                gb1[q] += gv;
-                __bf16 gp[2];
-                split1(gv, gp);
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) grow[pl * 32 * QS + hq * QS + r] = gp[pl];
-            }
+            wgrad_ghidden<2>(gh, on_mask, gb1, grow, r, h);
         }
         __syncthreads();
-        // gW1[32w + m][32 t + r] += sum_rows gH^T[m][row] X[row][32 t + r]:  A = gH^T rows, B[k = row][n] = X^T[n][row]
-        // gW2[32 t + m][32w + r] += sum_rows gY^T[32 t + m][row] H[row][32w + r]: A = gY^T rows, B = H^T[r][row]
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int ko = 16 * s + 8 * h;           // 8 consecutive rows of the tile
-            bf16x8 a_gh[2], b_h[2];
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                a_gh[pl] = *reinterpret_cast<const bf16x8*>(grow + pl * 32 * QS + r * QS + ko);
-                b_h[pl] = *reinterpret_cast<const bf16x8*>(hrow + pl * 32 * QS + r * QS + ko);
-            }
-#pragma unroll
-            for (int t2 = 0; t2 < NT; ++t2) {
-                bf16x8 b_x[2], a_gy[2];
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    b_x[pl] = *reinterpret_cast<const bf16x8*>(xt + pl * FT * QS + (32 * t2 + r) * QS + ko);
-                    a_gy[pl] = *reinterpret_cast<const bf16x8*>(gyt + pl * FT * QS + (32 * t2 + r) * QS + ko);
-                }
-                gw1[t2] = mm3(a_gh[0], a_gh[1], b_x[0], b_x[1], gw1[t2]);
-                gw2[t2] = mm3(a_gy[0], a_gy[1], b_h[0], b_h[1], gw2[t2]);
-            }
-        }
+        wgrad_contract<2, NT>(xt, gyt, hrow, grow, gw1, gw2, r, h);
         // (no barrier here: the next tile's rows go to xs / gs, which nobody reads after the barrier above, and the transposed
         // tiles are rewritten only behind the next tile's first barrier)
     }
-    // ---- this workgroup's partial result: the unpadded entries only
-    float* P = partial + (int64_t)blockIdx.x * G::P_TOT;
-#pragma unroll
-    for (int t2 = 0; t2 < NT; ++t2) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int m = acc_row(q, h);
-            if (wave * 32 + m < H && 32 * t2 + r < F) P[G::P_W1 + (wave * 32 + m) * F + 32 * t2 + r] = gw1[t2][q];
-            if (32 * t2 + m < F && wave * 32 + r < H) P[G::P_W2 + (32 * t2 + m) * H + wave * 32 + r] = gw2[t2][q];
-        }
-    }
-    // gb1: sum over the 32 rows (lanes r) of each half h; register q <-> hidden unit acc_row(q, h)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        float v = gb1[q];
-#pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o, 32);
-        const int hid = wave * 32 + acc_row(q, h);
-        if (r == 0 && hid < H) P[G::P_B1 + hid] = v;
-    }
+    wgrad_store_partial<F, H, NT>(partial, gw1, gw2, gb1, wave, r, h);
 }
 
 template <int L>
@@ -277,9 +201,7 @@ static int launch_mlp_rows_bwd_l(const float* x, const float* gy, int64_t n, con
     using G = RowsBwdGeo<L>;
     static LdsOptIn lds;                               // L = 2: 81 536 bytes of dynamic LDS need the opt-in
     if (!lds.granted({reinterpret_cast<const void*>(k_mlp_rows_bwd<L>)}, G::BYTES)) return TPNET_ERR_BAD_ARG;
-    const int64_t tiles = (n + 31) / 32;
-    const int grid = (int)(tiles < n_partial ? tiles : n_partial);
-    // (workgroups beyond `grid` do not exist: the caller sums only the first min(n_partial, ceil(n / 32)) partials)
+    const int grid = wgrad_grid(n, n_partial);
     hipLaunchKernelGGL(k_mlp_rows_bwd<L>, dim3((unsigned)grid), dim3(G::BLOCK), G::BYTES, s, x, gy, n, mlp->w1t, mlp->b1, mlp->w2t,
                        partial);
     TPNET_HIP_TRY(hipGetLastError());
@@ -292,7 +214,7 @@ using namespace tpnet;
 
 extern "C" int64_t tpnet_mlp_rows_bwd_partial_floats(int32_t F, int32_t H) {
     if (!tpnet_mlp_rows_supported(F, H)) return 0;
-    return F == RowsBwdGeo<1>::F ? RowsBwdGeo<1>::P_TOT : RowsBwdGeo<2>::P_TOT;
+    return F == RowsBwdGeo<1>::F ? WgradPartial<RowsBwdGeo<1>::F, RowsBwdGeo<1>::H>::TOT : WgradPartial<RowsBwdGeo<2>::F, RowsBwdGeo<2>::H>::TOT;
 }
 
 extern "C" int tpnet_mlp_rows_bwd_f32(const float* x, const float* gy, int64_t n, const tpnet_mlp* mlp, float* partial,

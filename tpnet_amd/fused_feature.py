@@ -38,32 +38,6 @@ def supported(mlp: torch.nn.Module, F: int) -> bool:
             and ls[0].weight.dtype == torch.float32 and ls[0].weight.is_cuda)
 
 
-_W2F_IDX = {}
-
-
-def _w2f_index(dev):
-    """Index tensors of the gather w2f[((w*2 + t)*64 + lane)*16 + s] = W2[32 t + (lane & 31)][32 w + (s & 3) + 8 (s >> 2) +
-    4 (lane >> 5)] (w = 0..7, t = 0..1, lane = 0..63, s = 0..15), cached per device."""
-    key = str(dev)
-    if key not in _W2F_IDX:
-        w = torch.arange(8).view(8, 1, 1, 1)
-        t = torch.arange(2).view(1, 2, 1, 1)
-        lane = torch.arange(64).view(1, 1, 64, 1)
-        s_ = torch.arange(16).view(1, 1, 1, 16)
-        rows = (32 * t + (lane & 31)).expand(8, 2, 64, 16).reshape(-1)
-        cols = (32 * w + (s_ & 3) + 8 * (s_ >> 2) + 4 * (lane >> 5)).expand(8, 2, 64, 16).reshape(-1)
-        _W2F_IDX[key] = (rows.to(dev), cols.to(dev))
-    return _W2F_IDX[key]
-
-
-def _w2f_rows(dev):
-    return _w2f_index(dev)[0]
-
-
-def _w2f_cols(dev):
-    return _w2f_index(dev)[1]
-
-
 # rows from which the matrix-core backward serves a call: one launch + a sum of partials against ten small torch launches -- at the
 # decoder's 1 000 rows per call a training step went 704 -> 520-570 us (bench.py, dropin.train); below, the torch expressions
 MFMA_BWD_FROM = 512
