@@ -8,6 +8,8 @@ around it, the kernel names and call counts close the gap.
     python tools/feature_paths.py OUT_DIR              # everything (the readout section first: 374 of the files)
     python tools/feature_paths.py OUT_DIR readout      # only the readout kernels' matrix (readout_cases)
     python tools/feature_paths.py OUT_DIR mlp          # only self.mlp's six C entries, partials included (mlp_cases; not in "everything")
+    python tools/feature_paths.py OUT_DIR sizes        # only the size exports of the C ABI over a grid -> OUT_DIR/sizes.json (sizes_cases;
+                                                       # not in "everything"; needs no GPU -- without one rocPRIM's size queries answer 0)
 """
 import os
 import sys
@@ -252,10 +254,67 @@ def readout_cases():
                          lambda: list(rp.run_stream(src, dst, neg, t, B, packed=packed, schedule=sched)) + list(rp.backup_random_projections()[1]))
 
 
+def sizes_cases():
+    """Every export that sizes a caller-owned buffer, and tpnet_stream_schedule (which decides on such sizes), over a grid of shapes
+    around the tile, batch-size and chunk thresholds: {export: [[arguments..., result], ...]} in sizes.json.  Sizes decide how a
+    stream is cut into chunks, so two builds lay buffers out alike only if their files are EQUAL."""
+    import json
+    from tpnet_amd import _lib
+    lib = _lib.load()
+    EB = (1, 255, 256, 257, 1000, 4096, 4097, 100000, 5000000)      # edges / list lengths
+    BATCH = (200, 1000, 1024, 1025, 4096, 4097)
+    DS, LS, GS, NS = (16, 64, 128, 172, 512), (1, 2, 3, 4), (1, 2, 8), (2, 300, 5000, 100000)
+    out = {}
+
+    def grid(name, *axes):
+        fn, rows = getattr(lib, name), []
+
+        def walk(prefix, rest):
+            if not rest:
+                rows.append(list(prefix) + [int(fn(*prefix))])
+                return
+            for x in rest[0]:
+                walk(prefix + (x,), rest[1:])
+        walk((), axes)
+        out.setdefault(name, []).extend(rows)
+
+    grid("tpnet_sampler_bytes", EB, NS)
+    for name in ("tpnet_sampler_weights_bytes", "tpnet_neg_bytes", "tpnet_edgebank_bytes", "tpnet_edgebank_scratch_bytes"):
+        grid(name, (0,) + EB)
+    grid("tpnet_neg_scratch_bytes", EB, (0, 5) + BATCH, (0, 5) + BATCH)
+    grid("tpnet_lp_metrics_scratch_bytes", (0,) + EB, (0,) + EB)
+    grid("tpnet_xplan_large_bytes", EB, BATCH, GS)
+    grid("tpnet_workspace_bytes", EB, (1,) + BATCH)
+    for G in GS:
+        for n_owned in (1, 150, 2500):
+            grid("tpnet_wshard_workspace_bytes", (n_owned + 1, 2 * n_owned + 7), DS, LS, EB, BATCH, (G,), (n_owned,))
+    grid("tpnet_stream_workspace_bytes", NS, DS, LS, EB, BATCH)
+    flags = (0, _lib.FLAG_SCHED_WINDOWED, _lib.FLAG_SCHED_BATCH, _lib.FLAG_PLAN_SORTED, _lib.FLAG_PLAN_HASHED)
+    for N in NS:
+        for d in DS:
+            for L in LS:
+                for E in EB:
+                    for B in BATCH:
+                        unit = 2 * L * d * 4 * B                    # version-log bytes of one batch: a cap cuts chunks at whole batches
+                        nb = (E + B - 1) // B
+                        caps = sorted({0, 1} | {k * unit + o for k in (3, 4, 5, nb - 1, nb, nb + 1) if k > 0 for o in (-1, 0, 1)})
+                        grid("tpnet_stream_workspace_bytes_capped", (N,), (d,), (L,), (E,), (B,), caps)
+                        # either side of every size the schedule can turn on: the whole stream's workspace, a capped one's, the
+                        # per-batch plan's
+                        turn = {int(lib.tpnet_stream_workspace_bytes(N, d, L, E, B)), int(lib.tpnet_workspace_bytes(E, B)),
+                                int(lib.tpnet_stream_workspace_bytes_capped(N, d, L, E, B, 4 * unit)),
+                                int(lib.tpnet_stream_workspace_bytes_capped(N, d, L, E, B, max(nb // 2, 1) * unit))}
+                        ws = sorted({0} | {w + o for w in turn for o in (-1, 0, 1) if w + o >= 0} | {w // 2 for w in turn})
+                        grid("tpnet_stream_schedule", (N,), (d,), (L,), (E,), (B,), flags, ws)
+    with open(os.path.join(OUT, "sizes.json"), "w") as f:
+        json.dump(out, f, sort_keys=True, separators=(",", ":"))
+    SAVED.append("sizes")
+
+
 def main():
     if ONLY:
         for name in ONLY:
-            {"readout": readout_cases, "mlp": mlp_cases}[name]()
+            {"readout": readout_cases, "mlp": mlp_cases, "sizes": sizes_cases}[name]()
         print(f"{len(SAVED)} files in {OUT}")
         return
     readout_cases()

@@ -7,12 +7,10 @@
 // in a fixed order, so a call gives the same bits every time.
 #include "tpnet_common.h"
 #include "scan_common.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "arena.hpp"
+#include "sort_tmp.hpp"
 
 namespace tpnet {
-
-static inline size_t eb_al(size_t x) { return (x + 255) / 256 * 256; }
 
 static constexpr int EB_STAT_WGS = 256;              // workgroups of k_eb_stats at most: one partial each, folded by 256 threads
 
@@ -188,40 +186,37 @@ __global__ __launch_bounds__(256) void k_eb_predict(EbTable tb, uint32_t h, int 
 // ---- layout ----------------------------------------------------------------------------------------------------------------------
 struct EbView {
     uint32_t* hdr; uint64_t* ukey; uint32_t* ustart; uint32_t* pos; double* t; uint32_t* present;
-    uint64_t* k_a; uint64_t* k_b; uint32_t* ix_a; uint8_t* first; uint32_t* blk; void* tmp;       // build only
+    uint64_t* k_a; uint64_t* k_b; uint32_t* ix_a; uint8_t* first; uint32_t* blk; Arena::Span tmp;       // build only
 };
-static EbView eb_carve(void* buf, int64_t E) {
+static void eb_layout(Arena& a, EbView& v, int64_t E) {
     const size_t n = (size_t)(E < 1 ? 1 : E);
-    char* p = (char*)(((size_t)buf + 255) / 256 * 256);
-    auto take = [&](size_t b) { void* r = p; p += eb_al(b); return r; };
+    a.head();
+    v.hdr = a.take<uint32_t>(64);
+    v.ukey = a.take<uint64_t>(n);
+    v.ustart = a.take<uint32_t>(n + 1);
+    v.pos = a.take<uint32_t>(n);
+    v.t = a.take<double>(n);
+    v.present = a.take<uint32_t>(n + 1);
+    v.k_a = a.take<uint64_t>(n);
+    v.k_b = a.take<uint64_t>(n);
+    v.ix_a = a.take<uint32_t>(n);
+    v.first = a.take<uint8_t>(n);
+    v.blk = a.take<uint32_t>(n / 256 + 2);
+    v.tmp = a.rest();
+    a.skip(sort_pairs_tmp<uint64_t, uint32_t>(n));
+    a.skip(256);                                     // tail slack
+}
+static EbView eb_view(const void* eb, size_t bytes, int64_t E) {
+    Arena a(const_cast<void*>(eb), bytes);
     EbView v;
-    v.hdr = (uint32_t*)take(256);
-    v.ukey = (uint64_t*)take(n * 8);
-    v.ustart = (uint32_t*)take((n + 1) * 4);
-    v.pos = (uint32_t*)take(n * 4);
-    v.t = (double*)take(n * 8);
-    v.present = (uint32_t*)take((n + 1) * 4);
-    v.k_a = (uint64_t*)take(n * 8);
-    v.k_b = (uint64_t*)take(n * 8);
-    v.ix_a = (uint32_t*)take(n * 4);
-    v.first = (uint8_t*)take(n);
-    v.blk = (uint32_t*)take((n / 256 + 2) * 4);
-    v.tmp = p;
+    eb_layout(a, v, E);
     return v;
 }
-static size_t eb_sort_tmp(size_t n) {
-    size_t t = 0;
-    uint64_t* k64 = nullptr;
-    uint32_t* k32 = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, t, k64, k64, k32, k32, n, 0, 64, (hipStream_t)0, false);
-    return t;
-}
 static EbTable eb_table(const EbView& v) { return {v.hdr, v.ukey, v.ustart, v.pos, v.t, v.present}; }
-
-static int eb_grid(int64_t n, int cap) {
-    int64_t g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
+// the scratch of the repeat-interval statistics: one partial sum per workgroup of k_eb_stats
+static double* eb_scratch_layout(Arena& a) {
+    a.head();
+    return a.take<double>(EB_STAT_WGS);
 }
 
 }  // namespace tpnet
@@ -232,9 +227,7 @@ extern "C" {
 
 size_t tpnet_edgebank_bytes(int64_t E) {
     if (E < 1 || E >= (1ll << 30)) return 0;
-    const size_t n = (size_t)E;
-    return 256 + eb_al(256) + eb_al(n * 8) * 4 + eb_al((n + 1) * 4) * 2 + eb_al(n * 4) * 2 + eb_al(n) + eb_al((n / 256 + 2) * 4) +
-           eb_al(eb_sort_tmp(n)) + 256;
+    return measured([&](Arena& a) { EbView v; eb_layout(a, v, E); });
 }
 
 int tpnet_edgebank_build(void* eb, size_t bytes, const int64_t* src, const int64_t* dst, const double* t, int64_t E, int64_t* counts,
@@ -242,24 +235,18 @@ int tpnet_edgebank_build(void* eb, size_t bytes, const int64_t* src, const int64
     if (!eb || !src || !dst || !t || !counts || E < 1 || E >= (1ll << 30)) return TPNET_ERR_BAD_ARG;
     if (bytes < tpnet_edgebank_bytes(E)) return TPNET_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    EbView v = eb_carve(eb, E);
+    EbView v = eb_view(eb, bytes, E);
     const size_t n = (size_t)E;
     const uint32_t n32 = (uint32_t)E;
-    const int grid = eb_grid(E, 4096);
+    const int grid = grid_1d(E, 4096);
     TPNET_HIP_TRY(hipMemsetAsync(v.hdr, 0, 256, s));
     TPNET_HIP_TRY(hipMemsetAsync(v.first, 0, n, s));
     hipLaunchKernelGGL(k_eb_keys, dim3(grid), dim3(256), 0, s, src, dst, t, E, v.k_a, v.ix_a, v.t, v.hdr);
     // ONE stable sort by (src, dst) with the position as payload: positions come out ascending inside each key
-    size_t tmp = bytes - (size_t)((char*)v.tmp - (char*)eb);
-    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp, tmp, v.k_a, v.k_b, v.ix_a, v.pos, n, 0u, 64u, s, false));
+    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp.ptr, v.tmp.bytes, v.k_a, v.k_b, v.ix_a, v.pos, n, 0u, 64u, s, false));
     // the unique edges (head flags in key order), then the distinct edges per prefix (first occurrences in position order)
-    const EbHead he{v.k_b};
-    hipLaunchKernelGGL(k_scan_count<EbHead>, dim3(grid), dim3(256), 0, s, he, (const uint32_t*)nullptr, n32, v.blk);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, v.blk, (const uint32_t*)nullptr, n32, v.hdr + EB_U);
-    hipLaunchKernelGGL((k_scan_emit<EbHead, EbEmit>), dim3(grid), dim3(256), 0, s, he, EbEmit{v.k_b, v.pos, v.ukey, v.ustart, v.first},
-                       (const uint32_t*)nullptr, n32, v.blk);
-    hipLaunchKernelGGL(k_scan_count<EbFirst>, dim3(grid), dim3(256), 0, s, EbFirst{v.first}, (const uint32_t*)nullptr, n32, v.blk);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, v.blk, (const uint32_t*)nullptr, n32, v.hdr + EB_FIRSTS);
+    scan_compact(EbHead{v.k_b}, EbEmit{v.k_b, v.pos, v.ukey, v.ustart, v.first}, nullptr, n32, v.blk, v.hdr + EB_U, grid, s);
+    scan_count(EbFirst{v.first}, nullptr, n32, v.blk, v.hdr + EB_FIRSTS, grid, s);
     hipLaunchKernelGGL(k_eb_present, dim3(grid), dim3(256), 0, s, (const uint8_t*)v.first, n32, (const uint32_t*)v.blk,
                        (const uint32_t*)v.hdr, v.present, v.ustart);
     TPNET_HIP_TRY(hipGetLastError());
@@ -274,7 +261,7 @@ int tpnet_edgebank_build(void* eb, size_t bytes, const int64_t* src, const int64
 
 size_t tpnet_edgebank_scratch_bytes(int64_t E) {
     if (E < 1 || E >= (1ll << 30)) return 0;
-    return 256 + (size_t)EB_STAT_WGS * 8;
+    return measured([](Arena& a) { (void)eb_scratch_layout(a); });
 }
 
 int tpnet_edgebank_predict(const void* eb, int64_t E, int32_t memory_mode, int32_t window_mode, double proportion, int64_t h,
@@ -290,12 +277,13 @@ int tpnet_edgebank_predict(const void* eb, int64_t E, int32_t memory_mode, int32
     if (stats && scratch_bytes < tpnet_edgebank_scratch_bytes(E)) return TPNET_ERR_WORKSPACE;
     if (Q0 + Q1 == 0) return TPNET_OK;
     hipStream_t s = (hipStream_t)stream;
-    const EbTable tb = eb_table(eb_carve(const_cast<void*>(eb), E));
+    const EbTable tb = eb_table(eb_view(eb, 0, E));
     double* part = nullptr;
     uint32_t n_part = 0;
     if (stats) {
-        part = (double*)(((size_t)scratch + 255) / 256 * 256);
-        n_part = (uint32_t)eb_grid(E, EB_STAT_WGS);
+        Arena a(scratch, scratch_bytes);
+        part = eb_scratch_layout(a);
+        n_part = (uint32_t)grid_1d(E, EB_STAT_WGS);
         hipLaunchKernelGGL(k_eb_stats, dim3(n_part), dim3(256), 0, s, tb, (uint32_t)h, part);
     }
     hipLaunchKernelGGL(k_eb_predict, dim3((unsigned)((Q0 + Q1 + 255) / 256)), dim3(256), 0, s, tb, (uint32_t)h, (int)memory_mode,

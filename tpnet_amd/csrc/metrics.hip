@@ -7,6 +7,7 @@
 // A training batch (tpnet_lp_train_loss: train_link_prediction.py:375-386) is the same three launches: the workgroups that evaluate
 // a logit's loss term also write d(mean loss) / d(logit), and the finish workgroup the loss as one fp32.
 #include "tpnet_common.h"
+#include "arena.hpp"
 
 #include <math.h>
 
@@ -43,17 +44,15 @@ __device__ inline float lpm_bce_grad(float logit, bool positive, double n) {
     return (float)(positive ? -1.0 / (1.0 + exp(x)) / n : 1.0 / (1.0 + exp(-x)) / n);
 }
 
-// the scratch buffer: cnt [3][P] uint32 = a | b | c, then (256-byte aligned) the NaN word, then (256 further on) part double[chunks]
-struct LpmScratch {
-    uint32_t* cnt;
-    uint32_t* nan;
-    double* part;
-    size_t zero_bytes;   // cnt and the NaN word are zeroed by one fill before the counting kernel; part is written whole
-};
-static size_t lpm_zero_bytes(int64_t P) { return ((size_t)P * 12 + 255) / 256 * 256 + 256; }
-static LpmScratch lpm_carve(void* scratch, uint32_t P) {
-    const size_t z = lpm_zero_bytes(P);
-    return {(uint32_t*)scratch, (uint32_t*)((char*)scratch + z - 256), (double*)((char*)scratch + z), z};
+// the scratch buffer (8-byte aligned by the caller, laid out from where it starts): cnt [3][P] uint32 = a | b | c, the NaN word in a
+// 256-byte slot of its own, then part double[chunks].  zero_bytes: cnt and the NaN word are zeroed by one fill before the counting
+// kernel; part is written whole
+struct LpmScratch { uint32_t* cnt; uint32_t* nan; double* part; size_t zero_bytes; };
+static void lpm_layout(Arena& a, LpmScratch& w, int64_t n_pos, int64_t n_neg) {
+    w.cnt = a.take<uint32_t>(3 * (size_t)n_pos);
+    w.nan = a.take<uint32_t>(64);
+    w.zero_bytes = a.off;
+    w.part = a.take<double>((size_t)(n_pos + n_neg + LPM_CHUNK - 1) / LPM_CHUNK);
 }
 
 // Workgroup (x, y): positives [256 x, 256 x + 256) against scores [256 y, 256 y + 256) of the concatenated axis (the P
@@ -175,8 +174,7 @@ static bool lpm_sizes_ok(int64_t n_pos, int64_t n_neg) {
 
 static size_t lpm_scratch_bytes(int64_t n_pos, int64_t n_neg) {
     if (!lpm_sizes_ok(n_pos, n_neg)) return 0;
-    const size_t chunks = (size_t)(n_pos + n_neg + LPM_CHUNK - 1) / LPM_CHUNK;
-    return lpm_zero_bytes(n_pos) + (chunks * 8 + 255) / 256 * 256;
+    return measured([&](Arena& a) { LpmScratch w; lpm_layout(a, w, n_pos, n_neg); });
 }
 
 // What tpnet_lp_metrics and tpnet_lp_train_loss share: the checks of the common arguments and the three launches.  train: the
@@ -193,7 +191,9 @@ static int lpm_enqueue(const float* pos_score, int64_t n_pos, const float* neg_s
     const bool has_loss = (pos_logit || neg_logit) && (n_pos == 0 || pos_logit) && (n_neg == 0 || neg_logit);
     hipStream_t s = (hipStream_t)stream;
     const uint32_t P = (uint32_t)n_pos, N = (uint32_t)n_neg;
-    const LpmScratch w = any ? lpm_carve(scratch, P) : LpmScratch{nullptr, nullptr, nullptr, 0};
+    Arena wa(any ? scratch : nullptr, scratch_bytes);
+    LpmScratch w;
+    lpm_layout(wa, w, n_pos, n_neg);
     uint32_t chunks = 0;
     if (any) {
         const uint32_t gx = P ? (P + LPM_TILE - 1) / LPM_TILE : 1u;          // (no positives: one row of workgroups for the loss)

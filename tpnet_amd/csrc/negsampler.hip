@@ -7,12 +7,10 @@
 #include "tpnet_common.h"
 #include "draw_common.hpp"
 #include "scan_common.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "arena.hpp"
+#include "sort_tmp.hpp"
 
 namespace tpnet {
-
-static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
 static constexpr int NEG_HASH_SLOTS = 2048;          // LDS table of the batch's pairs: batches of up to NEG_HASH_MAX_B
 static constexpr int64_t NEG_HASH_MAX_B = 1024;      // (load <= 1/2); larger batches are sorted and searched
@@ -261,71 +259,55 @@ __global__ __launch_bounds__(256) void k_neg_pick(uint32_t* __restrict__ hdr, co
 // ---- layouts ---------------------------------------------------------------------------------------------------------------------
 struct NegView {
     uint32_t* hdr; uint64_t* ukey; double* ufirst; uint32_t* ustart; uint8_t* uobs; double* times; int64_t* us; int64_t* ud;
-    uint64_t* k_a; uint64_t* k_b; uint32_t* ix_a; uint32_t* ix_b; uint32_t* d_a; uint32_t* d_b; uint32_t* blk; void* tmp;
+    uint64_t* k_a; uint64_t* k_b; uint32_t* ix_a; uint32_t* ix_b; uint32_t* d_a; uint32_t* d_b; uint32_t* blk; Arena::Span tmp;
 };
-static NegView neg_carve(void* buf, int64_t E) {
+static void neg_layout(Arena& a, NegView& v, int64_t E) {
     const size_t n = (size_t)(E < 1 ? 1 : E);
-    char* p = (char*)(((size_t)buf + 255) / 256 * 256);
-    auto take = [&](size_t b) { void* r = p; p += al(b); return r; };
-    NegView v;
-    v.hdr = (uint32_t*)take(256);
-    v.ukey = (uint64_t*)take(n * 8);
-    v.ufirst = (double*)take(n * 8);
-    v.ustart = (uint32_t*)take(n * 4);
-    v.uobs = (uint8_t*)take(n);
-    v.times = (double*)take(n * 8);
-    v.us = (int64_t*)take(n * 8);
-    v.ud = (int64_t*)take(n * 8);
-    v.k_a = (uint64_t*)take(n * 8);
-    v.k_b = (uint64_t*)take(n * 8);
-    v.ix_a = (uint32_t*)take(n * 4);
-    v.ix_b = (uint32_t*)take(n * 4);
-    v.d_a = (uint32_t*)take(n * 4);
-    v.d_b = (uint32_t*)take(n * 4);
-    v.blk = (uint32_t*)take((n / 256 + 2) * 4);
-    v.tmp = p;
-    return v;
+    a.head();
+    v.hdr = a.take<uint32_t>(64);
+    v.ukey = a.take<uint64_t>(n);
+    v.ufirst = a.take<double>(n);
+    v.ustart = a.take<uint32_t>(n);
+    v.uobs = a.take<uint8_t>(n);
+    v.times = a.take<double>(n);
+    v.us = a.take<int64_t>(n);
+    v.ud = a.take<int64_t>(n);
+    v.k_a = a.take<uint64_t>(n);
+    v.k_b = a.take<uint64_t>(n);
+    v.ix_a = a.take<uint32_t>(n);
+    v.ix_b = a.take<uint32_t>(n);
+    v.d_a = a.take<uint32_t>(n);
+    v.d_b = a.take<uint32_t>(n);
+    v.blk = a.take<uint32_t>(n / 256 + 2);
+    v.tmp = a.rest();
+    const size_t t1 = sort_pairs_tmp<uint64_t, uint32_t>(n), t2 = sort_keys_tmp<uint32_t>(n);
+    a.skip(t1 > t2 ? t1 : t2);
+    a.skip(256);                                     // tail slack
 }
-static size_t neg_sort_tmp(size_t n) {
-    size_t t1 = 0, t2 = 0;
-    uint64_t* k64 = nullptr;
-    uint32_t* k32 = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, t1, k64, k64, k32, k32, n, 0, 64, (hipStream_t)0, false);
-    (void)rocprim::radix_sort_keys(nullptr, t2, k32, k32, n, 0, 32, (hipStream_t)0, false);
-    return t1 > t2 ? t1 : t2;
+static NegView neg_view(const void* neg, size_t bytes, int64_t E) {
+    Arena a(const_cast<void*>(neg), bytes);
+    NegView v;
+    neg_layout(a, v, E);
+    return v;
 }
 
 struct NegScratch {
-    uint32_t* words; uint8_t* flag; uint32_t* blk; uint32_t* cand; uint64_t* valid; uint64_t* b_a; uint64_t* b_b; void* tmp;
+    uint32_t* words; uint8_t* flag; uint32_t* blk; uint32_t* cand; uint64_t* valid; uint64_t* b_a; uint64_t* b_b; Arena::Span tmp;
 };
-static NegScratch scratch_carve(void* buf, int64_t E, int64_t size, int64_t B) {
+static void scratch_layout(Arena& a, NegScratch& v, int64_t E, int64_t size, int64_t B) {
     const size_t n = (size_t)(E < 1 ? 1 : E);
-    char* p = (char*)(((size_t)buf + 255) / 256 * 256);
-    auto take = [&](size_t b) { void* r = p; p += al(b); return r; };
-    NegScratch v;
-    v.words = (uint32_t*)take(256);
-    v.flag = (uint8_t*)take(n);
-    v.blk = (uint32_t*)take((n / 256 + 2) * 4);
-    v.cand = (uint32_t*)take(n * 4);
-    v.valid = (uint64_t*)take((size_t)(size < 1 ? 1 : size) * 8);
-    const size_t nb = B > NEG_HASH_MAX_B ? (size_t)B : 1;
-    v.b_a = (uint64_t*)take(nb * 8);
-    v.b_b = (uint64_t*)take(nb * 8);
-    v.tmp = p;
-    return v;
-}
-static size_t batch_sort_tmp(int64_t B) {
-    if (B <= NEG_HASH_MAX_B) return 0;
-    size_t t = 0;
-    uint64_t* k64 = nullptr;
-    (void)rocprim::radix_sort_keys(nullptr, t, k64, k64, (size_t)B, 0, 64, (hipStream_t)0, false);
-    return t;
-}
-
-static int grid_for(int64_t n, int cap) {
-    int64_t g = (n + 255) / 256;
-    if (g < 1) g = 1;
-    return (int)(g > cap ? cap : g);
+    const size_t nb = B > NEG_HASH_MAX_B ? (size_t)B : 1;         // the batch's keys are sorted only beyond the LDS hash table
+    a.head();
+    v.words = a.take<uint32_t>(64);
+    v.flag = a.take<uint8_t>(n);
+    v.blk = a.take<uint32_t>(n / 256 + 2);
+    v.cand = a.take<uint32_t>(n);
+    v.valid = a.take<uint64_t>((size_t)(size < 1 ? 1 : size));
+    v.b_a = a.take<uint64_t>(nb);
+    v.b_b = a.take<uint64_t>(nb);
+    v.tmp = a.rest();
+    a.skip(B > NEG_HASH_MAX_B ? sort_keys_tmp<uint64_t>((size_t)B) : 0);
+    a.skip(256);                                     // tail slack
 }
 
 }  // namespace tpnet
@@ -336,8 +318,7 @@ extern "C" {
 
 size_t tpnet_neg_bytes(int64_t E) {
     if (E < 1 || E >= (1ll << 30)) return 0;
-    const size_t n = (size_t)E;
-    return 256 + al(256) + al(n * 8) * 7 + al(n * 4) * 5 + al(n) + al((n / 256 + 2) * 4) + al(neg_sort_tmp(n)) + 256;
+    return measured([&](Arena& a) { NegView v; neg_layout(a, v, E); });
 }
 
 int tpnet_neg_build(void* neg, size_t neg_bytes, const int64_t* src, const int64_t* dst, const double* t, int64_t E,
@@ -345,38 +326,23 @@ int tpnet_neg_build(void* neg, size_t neg_bytes, const int64_t* src, const int64
     if (!neg || !src || !dst || !counts || E < 1 || E >= (1ll << 30)) return TPNET_ERR_BAD_ARG;
     if (neg_bytes < tpnet_neg_bytes(E)) return TPNET_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    NegView v = neg_carve(neg, E);
+    NegView v = neg_view(neg, neg_bytes, E);
     const size_t n = (size_t)E;
     const uint32_t n32 = (uint32_t)E;
-    const int grid = grid_for(E, 4096);
+    const int grid = grid_1d(E, 4096);
     TPNET_HIP_TRY(hipMemsetAsync(v.hdr, 0, 256, s));
     // stable sort by time, then stable sort by (src, dst)  ==  sort by (edge, time)
     hipLaunchKernelGGL(k_neg_keys, dim3(grid), dim3(256), 0, s, src, dst, t, E, v.k_a, v.ix_a, v.hdr);
-    size_t tmp = neg_bytes - (size_t)((char*)v.tmp - (char*)neg);
-    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp, tmp, v.k_a, v.k_b, v.ix_a, v.ix_b, n, 0u, 64u, s, false));
+    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp.ptr, v.tmp.bytes, v.k_a, v.k_b, v.ix_a, v.ix_b, n, 0u, 64u, s, false));
     hipLaunchKernelGGL(k_neg_edgekeys, dim3(grid), dim3(256), 0, s, src, dst, E, v.ix_b, v.k_a);
-    tmp = neg_bytes - (size_t)((char*)v.tmp - (char*)neg);
-    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp, tmp, v.k_a, v.k_b, v.ix_b, v.ix_a, n, 0u, 64u, s, false));
+    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp.ptr, v.tmp.bytes, v.k_a, v.k_b, v.ix_b, v.ix_a, n, 0u, 64u, s, false));
     hipLaunchKernelGGL(k_neg_times, dim3(grid), dim3(256), 0, s, t, E, v.ix_a, v.k_b, v.times, v.d_a);
-    tmp = neg_bytes - (size_t)((char*)v.tmp - (char*)neg);
-    TPNET_HIP_TRY(rocprim::radix_sort_keys(v.tmp, tmp, v.d_a, v.d_b, n, 0u, 32u, s, false));
+    TPNET_HIP_TRY(rocprim::radix_sort_keys(v.tmp.ptr, v.tmp.bytes, v.d_a, v.d_b, n, 0u, 32u, s, false));
     // the table of unique edges, then the sorted unique src and dst ids: three scans over the same tile sums
-    const HeadEdge he{v.k_b};
-    hipLaunchKernelGGL(k_scan_count<HeadEdge>, dim3(grid), dim3(256), 0, s, he, (const uint32_t*)nullptr, n32, v.blk);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, v.blk, (const uint32_t*)nullptr, n32, v.hdr + NEG_U);
-    hipLaunchKernelGGL((k_scan_emit<HeadEdge, EmitEdge>), dim3(grid), dim3(256), 0, s, he,
-                       EmitEdge{v.k_b, v.times, v.ukey, v.ustart, v.ufirst, v.uobs, last_observed_time, (int)has_observed},
-                       (const uint32_t*)nullptr, n32, v.blk);
-    const HeadSrc hs{v.k_b};
-    hipLaunchKernelGGL(k_scan_count<HeadSrc>, dim3(grid), dim3(256), 0, s, hs, (const uint32_t*)nullptr, n32, v.blk);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, v.blk, (const uint32_t*)nullptr, n32, v.hdr + NEG_NUS);
-    hipLaunchKernelGGL((k_scan_emit<HeadSrc, EmitSrc>), dim3(grid), dim3(256), 0, s, hs, EmitSrc{v.k_b, v.us},
-                       (const uint32_t*)nullptr, n32, v.blk);
-    const HeadDst hd{v.d_b};
-    hipLaunchKernelGGL(k_scan_count<HeadDst>, dim3(grid), dim3(256), 0, s, hd, (const uint32_t*)nullptr, n32, v.blk);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, v.blk, (const uint32_t*)nullptr, n32, v.hdr + NEG_NUD);
-    hipLaunchKernelGGL((k_scan_emit<HeadDst, EmitDst>), dim3(grid), dim3(256), 0, s, hd, EmitDst{v.d_b, v.ud},
-                       (const uint32_t*)nullptr, n32, v.blk);
+    scan_compact(HeadEdge{v.k_b}, EmitEdge{v.k_b, v.times, v.ukey, v.ustart, v.ufirst, v.uobs, last_observed_time, (int)has_observed},
+                 nullptr, n32, v.blk, v.hdr + NEG_U, grid, s);
+    scan_compact(HeadSrc{v.k_b}, EmitSrc{v.k_b, v.us}, nullptr, n32, v.blk, v.hdr + NEG_NUS, grid, s);
+    scan_compact(HeadDst{v.d_b}, EmitDst{v.d_b, v.ud}, nullptr, n32, v.blk, v.hdr + NEG_NUD, grid, s);
     TPNET_HIP_TRY(hipGetLastError());
     uint32_t h[8] = {0};
     TPNET_HIP_TRY(hipMemcpyAsync(h, v.hdr, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -393,7 +359,7 @@ int tpnet_neg_uniques(const void* neg, int64_t E, int64_t n_src, int64_t n_dst, 
     if (!neg || E < 1 || E >= (1ll << 30) || n_src < 0 || n_dst < 0 || n_src > E || n_dst > E || (n_src > 0 && !unique_src) ||
         (n_dst > 0 && !unique_dst))
         return TPNET_ERR_BAD_ARG;
-    NegView v = neg_carve(const_cast<void*>(neg), E);
+    NegView v = neg_view(neg, 0, E);
     if (n_src) TPNET_HIP_TRY(hipMemcpyAsync(unique_src, v.us, (size_t)n_src * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (n_dst) TPNET_HIP_TRY(hipMemcpyAsync(unique_dst, v.ud, (size_t)n_dst * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return TPNET_OK;
@@ -401,10 +367,7 @@ int tpnet_neg_uniques(const void* neg, int64_t E, int64_t n_src, int64_t n_dst, 
 
 size_t tpnet_neg_scratch_bytes(int64_t E, int64_t size, int64_t B) {
     if (E < 1 || E >= (1ll << 30) || size < 0 || size >= (1ll << 31) || B < 0 || B >= (1ll << 31)) return 0;
-    const size_t n = (size_t)E;
-    const size_t nb = B > NEG_HASH_MAX_B ? (size_t)B : 1;
-    return 256 + al(256) + al(n) + al((n / 256 + 2) * 4) + al(n * 4) + al((size_t)(size < 1 ? 1 : size) * 8) + al(nb * 8) * 2 +
-           al(batch_sort_tmp(B)) + 256;
+    return measured([&](Arena& a) { NegScratch w; scratch_layout(a, w, E, size, B); });
 }
 
 int tpnet_neg_sample(void* neg, int64_t E, int32_t strategy, int64_t size, const int64_t* batch_src, const int64_t* batch_dst,
@@ -416,30 +379,30 @@ int tpnet_neg_sample(void* neg, int64_t E, int32_t strategy, int64_t size, const
     if (strategy != TPNET_NEG_RANDOM && (!scratch || (B > 0 && (!batch_src || !batch_dst)))) return TPNET_ERR_BAD_ARG;
     if (size == 0) return TPNET_OK;
     hipStream_t s = (hipStream_t)stream;
-    NegView v = neg_carve(neg, E);
+    NegView v = neg_view(neg, 0, E);
     const NegKey key{(uint32_t)seed, (uint32_t)(seed >> 32), call_index};
     if (strategy == TPNET_NEG_RANDOM) {
-        hipLaunchKernelGGL(k_neg_random, dim3(grid_for(size, 1024)), dim3(256), 0, s, v.us, v.ud, v.hdr, size, key, out_src, out_dst);
+        hipLaunchKernelGGL(k_neg_random, dim3(grid_1d(size, 1024)), dim3(256), 0, s, v.us, v.ud, v.hdr, size, key, out_src, out_dst);
         TPNET_HIP_TRY(hipGetLastError());
         return TPNET_OK;
     }
     if (scratch_bytes < tpnet_neg_scratch_bytes(E, size, B)) return TPNET_ERR_WORKSPACE;
-    NegScratch w = scratch_carve(scratch, E, size, B);
-    const int grid = grid_for(E, 1024);
+    Arena wa(scratch, scratch_bytes);
+    NegScratch w;
+    scratch_layout(wa, w, E, size, B);
+    const int grid = grid_1d(E, 1024);
     const uint32_t* U = v.hdr + NEG_U;
     const CandFlag cf{v.ufirst, v.ustart, v.uobs, v.times, v.hdr, (uint32_t)E, t0, t1, strategy == TPNET_NEG_INDUCTIVE, w.flag};
-    hipLaunchKernelGGL(k_scan_count<CandFlag>, dim3(grid), dim3(256), 0, s, cf, U, 0u, w.blk);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, w.blk, U, 0u, w.words);
+    scan_count(cf, U, 0u, w.blk, w.words, grid, s);
     hipLaunchKernelGGL((k_scan_emit<ByteFlag, EmitCand>), dim3(grid), dim3(256), 0, s, ByteFlag{w.flag}, EmitCand{w.cand}, U, 0u,
-                       (const uint32_t*)w.blk);
+                       (const uint32_t*)w.blk);                 // (the flags the count pass left, not the search again)
     const uint64_t* bsorted = nullptr;
     if (B > NEG_HASH_MAX_B) {
-        hipLaunchKernelGGL(k_neg_bkeys, dim3(grid_for(B, 1024)), dim3(256), 0, s, batch_src, batch_dst, B, w.b_a);
-        size_t tmp = scratch_bytes - (size_t)((char*)w.tmp - (char*)scratch);
-        TPNET_HIP_TRY(rocprim::radix_sort_keys(w.tmp, tmp, w.b_a, w.b_b, (size_t)B, 0u, 64u, s, false));
+        hipLaunchKernelGGL(k_neg_bkeys, dim3(grid_1d(B, 1024)), dim3(256), 0, s, batch_src, batch_dst, B, w.b_a);
+        TPNET_HIP_TRY(rocprim::radix_sort_keys(w.tmp.ptr, w.tmp.bytes, w.b_a, w.b_b, (size_t)B, 0u, 64u, s, false));
         bsorted = w.b_b;
     }
-    hipLaunchKernelGGL(k_neg_pick, dim3(grid_for(size, 1024)), dim3(256), 0, s, v.hdr, v.us, v.ud, v.ukey, w.cand, w.words, size,
+    hipLaunchKernelGGL(k_neg_pick, dim3(grid_1d(size, 1024)), dim3(256), 0, s, v.hdr, v.us, v.ud, v.ukey, w.cand, w.words, size,
                        batch_src, batch_dst, B, bsorted, w.valid, key, out_src, out_dst);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
@@ -447,7 +410,7 @@ int tpnet_neg_sample(void* neg, int64_t E, int32_t strategy, int64_t size, const
 
 int tpnet_neg_check(void* neg, void* stream) {
     if (!neg) return TPNET_ERR_BAD_ARG;
-    uint32_t* err = (uint32_t*)(((size_t)neg + 255) / 256 * 256) + NEG_ERR;
+    uint32_t* err = (uint32_t*)align256((size_t)neg) + NEG_ERR;      // (the header leads the layout)
     uint32_t h = 0;
     TPNET_HIP_TRY(hipMemcpyAsync(&h, err, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
     TPNET_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));

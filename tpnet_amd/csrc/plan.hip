@@ -3,6 +3,8 @@
 // order, then all dst-side ones).  Done for a whole chunk of the stream at once (one stable device radix sort over
 // (batch, target) keys), so the per-batch step kernels find ready-made item lists and the cost is amortised.
 #include "wplan_common.hpp"
+#include "arena.hpp"
+#include "sort_tmp.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -35,8 +37,6 @@ static inline int ceil_log2_u64(uint64_t x) {
     return b;
 }
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // A batch's 2*B keys are contiguous (k_make_keys), so grouping by target is a SEGMENTED sort on the node bits alone, one
 // segment per batch: rocPRIM sorts a segment of a few thousand keys inside one workgroup's LDS, all batches in one
 // launch, instead of several device-wide passes over (batch, node) keys.  Very long segments (one workgroup would walk
@@ -63,14 +63,12 @@ static size_t sort_tmp_bytes(size_t n, int64_t batch) {
     static thread_local int memo_next = 0;
     for (int i = 0; i < 4; ++i)
         if (memo_v[i] && memo_n[i] == n && memo_b[i] == batch) return memo_v[i];
-    size_t bytes = 0, bytes32 = 0, bytes_seg = 0;
-    uint64_t* kn64 = nullptr;
+    // size queries only: no kernel is launched (keys are 32-bit whenever (batch, node) fits, else 64-bit: plan_build)
+    size_t bytes = sort_pairs_tmp<uint64_t, uint32_t>(n), bytes_seg = 0;
+    const size_t bytes32 = sort_pairs_tmp<uint32_t, uint32_t>(n);
+    if (bytes32 > bytes) bytes = bytes32;
     uint32_t* kn = nullptr;
     uint32_t* vn = nullptr;
-    // size queries only: no kernel is launched (keys are 32-bit whenever (batch, node) fits, else 64-bit: plan_build)
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, kn64, kn64, vn, vn, n, 0, 64, (hipStream_t)0, false);
-    (void)rocprim::radix_sort_pairs(nullptr, bytes32, kn, kn, vn, vn, n, 0, 32, (hipStream_t)0, false);
-    if (bytes32 > bytes) bytes = bytes32;
     if (n < (1ull << 32)) {
         const unsigned nseg = (unsigned)((n + 2 * (size_t)batch - 1) / (2 * (size_t)batch));
         auto cnt = rocprim::counting_iterator<unsigned>(0);
@@ -85,49 +83,37 @@ static size_t sort_tmp_bytes(size_t n, int64_t batch) {
     return res;
 }
 
+// the workspace of the per-batch schedule
+static void plan_layout(Arena& a, Plan& p, int64_t Ec, int64_t batch) {
+    const size_t nc = 2 * (size_t)Ec;
+    const size_t nb = (size_t)((Ec + batch - 1) / batch);
+    a.head();
+    p.dbg = a.take<unsigned long long>(TPNET_DBG_BYTES / 8);
+    p.keys_in = a.take<uint64_t>(nc);
+    p.keys_out = a.take<uint64_t>(nc);
+    p.vals_in = a.take<uint32_t>(nc);
+    p.vals_out = a.take<uint32_t>(nc);
+    p.s_partner = a.take<int32_t>(nc);
+    p.s_target = a.take<int32_t>(nc);
+    p.s_coef = a.take<float>(nc);
+    p.light = a.take<Item>(nc);
+    p.heavy = a.take<Item>(nc);
+    p.desc = a.take<BatchDesc>(nb);
+    p.sort_tmp_bytes = sort_tmp_bytes(nc, batch);
+    p.sort_tmp = a.take<char>(p.sort_tmp_bytes);
+}
+
 size_t plan_bytes(int64_t max_edges, int64_t batch) {
-    if (max_edges < 1) max_edges = 1;
-    if (batch < 1) batch = 1;
-    const size_t nc = 2 * (size_t)max_edges;
-    const size_t nb = (size_t)((max_edges + batch - 1) / batch);
-    size_t tot = TPNET_DBG_BYTES;
-    tot += align_up(nc * sizeof(uint64_t), 256) * 2;   // keys in/out
-    tot += align_up(nc * sizeof(uint32_t), 256) * 2;   // vals in/out
-    tot += align_up(nc * sizeof(int32_t), 256) * 2;    // s_partner, s_target
-    tot += align_up(nc * sizeof(float), 256);          // s_coef
-    tot += align_up(nc * sizeof(Item), 256) * 2;       // light, heavy
-    tot += align_up(nb * sizeof(BatchDesc), 256);
-    tot += align_up(sort_tmp_bytes(nc, batch), 256) + 256;
-    return tot;
+    return measured([&](Arena& a) { Plan p; plan_layout(a, p, max_edges < 1 ? 1 : max_edges, batch < 1 ? 1 : batch); });
 }
 
 int plan_carve(void* ws, size_t ws_bytes, int64_t Ec, int64_t batch, Plan* out) {
     if (!ws) return TPNET_ERR_WORKSPACE;
+    Arena a(ws, ws_bytes);
+    plan_layout(a, *out, Ec, batch);
     const size_t nc = 2 * (size_t)Ec;
-    const size_t nb = (size_t)((Ec + batch - 1) / batch);
-    char* p = reinterpret_cast<char*>(ws);
-    char* const end = p + ws_bytes;
-    p = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(p), 256));
-    auto take = [&](size_t bytes) -> void* {
-        void* r = p;
-        p += align_up(bytes, 256);
-        return r;
-    };
-    out->dbg = (unsigned long long*)take(TPNET_DBG_BYTES);
-    out->keys_in = (uint64_t*)take(nc * sizeof(uint64_t));
-    out->keys_out = (uint64_t*)take(nc * sizeof(uint64_t));
-    out->vals_in = (uint32_t*)take(nc * sizeof(uint32_t));
-    out->vals_out = (uint32_t*)take(nc * sizeof(uint32_t));
-    out->s_partner = (int32_t*)take(nc * sizeof(int32_t));
-    out->s_target = (int32_t*)take(nc * sizeof(int32_t));
-    out->s_coef = (float*)take(nc * sizeof(float));
-    out->light = (Item*)take(nc * sizeof(Item));
-    out->heavy = (Item*)take(nc * sizeof(Item));
-    out->desc = (BatchDesc*)take(nb * sizeof(BatchDesc));
-    out->sort_tmp_bytes = sort_tmp_bytes(nc, batch);
-    out->sort_tmp = take(out->sort_tmp_bytes);
     // edge-fused update flags alias keys_in (dead after the sort): 2*Ec bytes + Ec floats <= 16*Ec bytes for Ec >= 26
-    const size_t fw_off = align_up(2 * (size_t)Ec, 256);
+    const size_t fw_off = align256(2 * (size_t)Ec);
     if (fw_off + 4 * (size_t)Ec <= nc * sizeof(uint64_t)) {
         out->fuse_src = reinterpret_cast<uint8_t*>(out->keys_in);
         out->fuse_dst = out->fuse_src + Ec;
@@ -136,8 +122,7 @@ int plan_carve(void* ws, size_t ws_bytes, int64_t Ec, int64_t batch, Plan* out) 
         out->fuse_src = out->fuse_dst = nullptr;
         out->fuse_w = nullptr;
     }
-    if (p > end) return TPNET_ERR_WORKSPACE;
-    return TPNET_OK;
+    return a.fits() ? TPNET_OK : TPNET_ERR_WORKSPACE;
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------
@@ -639,9 +624,7 @@ int plan_build(const tpnet_state& st, const Plan& p, const int64_t* src, const i
     if (batch <= plan_one_max_batch() && !(flags & PLAN_FUSE) && node_bits <= 31)
         return plan_blocks(st, p, src, dst, t, Ec, batch, now_time, t_prev_dev, lambda, flags, s);
 
-    int grid = (int)((nc + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    const int dgrid = (int)((nb + 255) / 256) > 64 ? 64 : (int)((nb + 255) / 256);
+    const int grid = grid_1d(nc, 4096), dgrid = grid_1d(nb, 64);
     const DescArgs da{p.desc, t, nb, now_time, t_prev_dev, lambda, (int)st.L, (uint32_t)grid};
     const bool seg = use_segmented_sort(batch, (size_t)nc);
     const bool narrow = seg || node_bits + batch_bits <= 32;
@@ -781,86 +764,62 @@ int64_t wplan_max_chunk_edges(int64_t batch, int d, int L) {
     return e < batch ? batch : e;
 }
 
-static size_t wplan_extra_bytes(int64_t Ec, int64_t batch, int64_t N, int d, int L, int K) {
+// The workspace of a windowed chunk: the per-batch schedule's, then what the windows add (room for windows of ONE batch: the window
+// length is chosen per chunk).  own_log = false: the version log lives outside the region -- the plans of the chunks of a multi-chunk
+// stream each keep a region of their own (so that every one of them can be replayed, api.hip) and share ONE log.
+static void wplan_layout(Arena& a, WPlan& p, int64_t Ec, int64_t batch, int64_t N, int d, int L, bool own_log) {
     const size_t nc = 2 * (size_t)Ec;
-    (void)K;
-    const size_t nw = (size_t)((Ec + batch - 1) / batch);       // (room for windows of ONE batch: the window length is chosen per chunk)
-    size_t tot = 0;
-    tot += align_up(nc * 4, 256) * 3;                           // wscr: bsb, bri, rprevb of the planners that sort every batch
-    tot += align_up(nc * 2, 256);                               // (spare: the workspace's size is what it was with one array per field)
-    tot += align_up(nw * sizeof(WinDesc), 256) + 256;           // wdesc, wb_count
-    tot += align_up(3 * (size_t)Ec * 4, 256) * 2;               // e_ref, e_g
-    tot += align_up(nc * (size_t)L * (size_t)d * 4, 256);       // version log
-    tot += align_up((size_t)N * 4, 256) * 2;                    // node_lo, node_hi
-    tot += align_up(nc * 4, 256) * 2;                           // inv, rhead
-    tot += align_up((size_t)N * 8, 256) + align_up((2 * WIN_MAX_WINDOWS * 8 + WIN_MAX_WINDOWS) * 4, 256) +
-           align_up(wplan3_table_bytes(Ec, batch), 256) + align_up(wplan3_blk_bytes(Ec, batch), 256);   // wmask, wcls, wtab, wblk (hashed planner, wplan3.hip)
-    tot += align_up(wplan_dense_bytes(Ec, batch, N, d, L), 256);       // the dense planner's matrices (wplan_dense.hip; 0: not eligible)
-    return tot + 256;
+    const size_t nw = (size_t)((Ec + batch - 1) / batch);
+    plan_layout(a, p.base, Ec, batch);
+    a.skip(256);                                                  // slack, where it has been: plan_bytes (its own slack included)
+                                                                  // lie between the aligned base and what the windows add
+    p.wscr = a.take<uint32_t>(3 * align256(nc * 4) / 4);          // [3][nc] words, with the room of three aligned arrays
+    a.skip(nc * 2);                                               // spare: the size is what it was with one array per field
+    p.wdesc = a.take<WinDesc>(nw);
+    a.skip(256);                                                  // spare: the slot of a write-back counter that is gone
+    p.e_ref = a.take<uint32_t>(3 * (size_t)Ec);
+    p.e_g = a.take<float>(3 * (size_t)Ec);
+    p.log = own_log ? a.take<float>(nc * (size_t)L * (size_t)d) : nullptr;
+    p.node_lo = a.take<uint32_t>((size_t)N);
+    p.node_hi = a.take<uint32_t>((size_t)N);
+    p.inv = a.take<uint32_t>(nc);
+    p.rhead = a.take<uint32_t>(nc);
+    const size_t zero0 = a.off;
+    p.wmask = a.take<unsigned long long>((size_t)N);
+    p.wcls = a.take<uint32_t>(2 * WIN_MAX_WINDOWS * 8 + WIN_MAX_WINDOWS);
+    p.wzero_bytes = a.off - zero0;                                // (+ the chain table's share of wtab: wplan3_build)
+    p.wtab = a.take<char>(wplan3_table_bytes(Ec, batch));         // the hashed planner's (wplan3.hip)
+    p.wblk = (uint32_t*)a.take<char>(wplan3_blk_bytes(Ec, batch));
+    const size_t db = wplan_dense_bytes(Ec, batch, N, d, L);      // the dense planner's matrices (wplan_dense.hip; 0: not eligible)
+    p.dense = db ? a.take<char>(db) : nullptr;
+}
+static size_t wplan_measure(int64_t Ec, int64_t batch, int64_t N, int d, int L, bool own_log) {
+    return measured([&](Arena& a) { WPlan p; wplan_layout(a, p, Ec < 1 ? 1 : Ec, batch < 1 ? 1 : batch, N, d, L, own_log); });
 }
 
 size_t wplan_bytes(int64_t max_edges, int64_t batch, int64_t N, int d, int L) {
-    if (max_edges < 1) max_edges = 1;
-    if (batch < 1) batch = 1;
-    const int K = wplan_window_batches(batch, d, L);
-    if (K == 0) return plan_bytes(max_edges, batch);
-    return plan_bytes(max_edges, batch) + wplan_extra_bytes(max_edges, batch, N, d, L, K);
+    if (wplan_window_batches(batch < 1 ? 1 : batch, d, L) == 0) return plan_bytes(max_edges, batch);
+    return wplan_measure(max_edges, batch, N, d, L, true);
 }
 
 size_t wplan_log_bytes(int64_t max_edges, int d, int L) {
-    if (max_edges < 1) max_edges = 1;
-    return align_up(2 * (size_t)max_edges * (size_t)L * (size_t)d * 4, 256);
+    return align256(2 * (size_t)(max_edges < 1 ? 1 : max_edges) * (size_t)L * (size_t)d * 4);
 }
 
-// `shared_log` (may be null): the version log lives there instead of inside [ws, ws + ws_bytes) -- the plans of the chunks of a
-// multi-chunk stream each keep a region of their own (so that every one of them can be replayed, api.hip) and share ONE log
 // (the plan of a row shard's chunk, wshard.hip: global batches beyond 4096 edges, of which a rank computes its share -- the window
 // length is chosen there)
-size_t wplan_bytes_shard(int64_t max_edges, int64_t batch, int64_t N, int d, int L) {
-    if (max_edges < 1) max_edges = 1;
-    if (batch < 1) batch = 1;
-    return plan_bytes(max_edges, batch) + wplan_extra_bytes(max_edges, batch, N, d, L, 2);
-}
+size_t wplan_bytes_shard(int64_t max_edges, int64_t batch, int64_t N, int d, int L) { return wplan_measure(max_edges, batch, N, d, L, true); }
 
 int wplan_carve(void* ws, size_t ws_bytes, int64_t Ec, int64_t batch, int64_t N, int d, int L, int K, WPlan* out, float* shared_log,
                 bool shard) {
     if (K < 1 || K > WIN_MAX_BATCHES || (!shard && K > wplan_window_batches(batch, d, L))) return TPNET_ERR_BAD_ARG;
     if (Ec > wplan_max_chunk_edges(batch, d, L)) return TPNET_ERR_BAD_ARG;
-    int rc = plan_carve(ws, ws_bytes, Ec, batch, &out->base);
-    if (rc) return rc;
-    const size_t base_bytes = plan_bytes(Ec, batch);
-    if (base_bytes + wplan_extra_bytes(Ec, batch, N, d, L, K) - (shared_log ? wplan_log_bytes(Ec, d, L) : 0) > ws_bytes)
-        return TPNET_ERR_WORKSPACE;
-    char* p = reinterpret_cast<char*>(align_up(reinterpret_cast<size_t>(ws), 256)) + align_up(base_bytes, 256);
-    // (plan_carve aligned the base the same way; plan_bytes includes its slack)
-    auto take = [&](size_t bytes) -> void* {
-        void* r = p;
-        p += align_up(bytes, 256);
-        return r;
-    };
+    if (!ws || wplan_measure(Ec, batch, N, d, L, !shared_log) > ws_bytes) return TPNET_ERR_WORKSPACE;
+    Arena a(ws, ws_bytes);
+    wplan_layout(a, *out, Ec, batch, N, d, L, !shared_log);
+    if (!a.fits()) return TPNET_ERR_WORKSPACE;
+    if (shared_log) out->log = shared_log;
     const size_t nc = 2 * (size_t)Ec;
-    const int64_t Ew = (int64_t)K * batch;
-    const size_t nw = (size_t)((Ec + batch - 1) / batch);
-    out->wscr = (uint32_t*)take(3 * align_up(nc * 4, 256));     // (3 * nc words)
-    (void)take(nc * 2);
-    out->wdesc = (WinDesc*)take(nw * sizeof(WinDesc));
-    (void)take(256);
-    out->e_ref = (uint32_t*)take(3 * (size_t)Ec * 4);
-    out->e_g = (float*)take(3 * (size_t)Ec * 4);
-    out->log = shared_log ? shared_log : (float*)take(nc * (size_t)L * (size_t)d * 4);
-    out->node_lo = (uint32_t*)take((size_t)N * 4);
-    out->node_hi = (uint32_t*)take((size_t)N * 4);
-    out->inv = (uint32_t*)take(nc * 4);
-    out->rhead = (uint32_t*)take(nc * 4);
-    out->wmask = (unsigned long long*)take((size_t)N * 8);
-    out->wcls = (uint32_t*)take((2 * WIN_MAX_WINDOWS * 8 + WIN_MAX_WINDOWS) * 4);
-    out->wzero_bytes = (size_t)(p - reinterpret_cast<char*>(out->wmask));      // (+ the chain table's share of wtab: wplan3_build)
-    out->wtab = take(wplan3_table_bytes(Ec, batch));
-    out->wblk = (uint32_t*)take(wplan3_blk_bytes(Ec, batch));
-    {
-        const size_t db = wplan_dense_bytes(Ec, batch, N, d, L);
-        out->dense = db ? take(db) : nullptr;
-    }
     out->heavy_thr = wplan_heavy_threshold(K, batch, d);
     out->chains = reinterpret_cast<Chain*>(out->base.light);
     // the records live where the per-batch schedule keeps its heavy items (32 bytes per contribution both, 256-byte aligned).  What
@@ -877,8 +836,7 @@ int wplan_carve(void* ws, size_t ws_bytes, int64_t Ec, int64_t batch, int64_t N,
     out->lv_in = out->base.vals_in;
     out->lv_out = out->base.vals_out;
     out->K = K;
-    out->Ew = Ew;
-    if (p > reinterpret_cast<char*>(ws) + ws_bytes) return TPNET_ERR_WORKSPACE;
+    out->Ew = (int64_t)K * batch;
     return TPNET_OK;
 }
 
@@ -1208,9 +1166,7 @@ int wplan_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipSt
     const int batch_bits = ceil_log2_u64((uint64_t)nb + 1) < 1 ? 1 : ceil_log2_u64((uint64_t)nb + 1);
     const int key_bits = node_bits + batch_bits;
     if (key_bits > 63 || nb > 65535) return TPNET_ERR_BAD_ARG;
-    int grid = (int)((nc + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    const int dgrid = (int)((nb + 255) / 256) > 64 ? 64 : (int)((nb + 255) / 256);
+    const int grid = grid_1d(nc, 4096), dgrid = grid_1d(nb, 64);
     const DescArgs da{p.base.desc, t, nb, now_time, t_prev_dev, lambda, (int)st.L, (uint32_t)grid};
     const bool narrow = key_bits <= 31;       // (the chain-end bound (node + 1) << batch_bits must not wrap)
     uint32_t* k32_in = reinterpret_cast<uint32_t*>(p.base.keys_in);

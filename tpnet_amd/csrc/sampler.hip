@@ -5,13 +5,12 @@
 // ('uniform', 'time_interval_aware') draw from the same CSR with a counter-based generator: k_sampler_weights / k_sample_random.
 #include "tpnet_common.h"
 #include "draw_common.hpp"
+#include "arena.hpp"
+#include "sort_tmp.hpp"
 
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace tpnet {
-
-static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
 // entry 2e = (node src[e] -> neighbour dst[e]), entry 2e+1 = (node dst[e] -> neighbour src[e]): the reference's
 // append order (utils/utils.py:307-309)
@@ -280,41 +279,47 @@ bool tpnet::encoder_generic_readout(const tpnet_state& st) {
 
 extern "C" {
 
-size_t tpnet_sampler_bytes(int64_t E, int64_t num_nodes) {
-    const size_t n2 = 2 * (size_t)(E < 1 ? 1 : E);
-    size_t tmp1 = 0, tmp2 = 0;
-    uint64_t* k64 = nullptr;
-    uint32_t* k32 = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, tmp1, k64, k64, k32, k32, n2, 0, 64, (hipStream_t)0, false);
-    (void)rocprim::radix_sort_pairs(nullptr, tmp2, k32, k32, k32, k32, n2, 0, 32, (hipStream_t)0, false);
-    const size_t tmp = tmp1 > tmp2 ? tmp1 : tmp2;
-    return al((size_t)(num_nodes + 1) * 8) + al(n2 * 4) + al(n2 * 8) * 2          // CSR
-           + al(n2 * 8) * 2 + al(n2 * 4) * 4 + al(tmp) + 256;                      // build scratch
-}
-
-// Layout of the sampler buffer (caller-owned device memory of tpnet_sampler_bytes): CSR first, scratch behind it.
+// Layout of the sampler buffer (caller-owned device memory of tpnet_sampler_bytes): the CSR, which is all a sampling call reads,
+// and the scratch of the build behind it.
 struct SamplerView {
     int64_t* row_start; int32_t* nbr; int64_t* nbr_eid; double* nbr_t;
-    uint64_t* tk_a; uint64_t* tk_b; uint32_t* ix_a; uint32_t* ix_b; uint32_t* nk_a; uint32_t* nk_b; void* tmp; size_t tmp_bytes;
+    uint64_t* tk_a; uint64_t* tk_b; uint32_t* ix_a; uint32_t* ix_b; uint32_t* nk_a; uint32_t* nk_b; Arena::Span tmp;
 };
-static SamplerView carve(void* buf, int64_t E, int64_t num_nodes) {
+static void csr_layout(Arena& a, SamplerView& v, int64_t E, int64_t num_nodes) {
     const size_t n2 = 2 * (size_t)(E < 1 ? 1 : E);
-    char* p = (char*)(((size_t)buf + 255) / 256 * 256);
-    SamplerView v;
-    auto take = [&](size_t b) { void* r = p; p += al(b); return r; };
-    v.row_start = (int64_t*)take((size_t)(num_nodes + 1) * 8);
-    v.nbr = (int32_t*)take(n2 * 4);
-    v.nbr_eid = (int64_t*)take(n2 * 8);
-    v.nbr_t = (double*)take(n2 * 8);
-    v.tk_a = (uint64_t*)take(n2 * 8);
-    v.tk_b = (uint64_t*)take(n2 * 8);
-    v.ix_a = (uint32_t*)take(n2 * 4);
-    v.ix_b = (uint32_t*)take(n2 * 4);
-    v.nk_a = (uint32_t*)take(n2 * 4);
-    v.nk_b = (uint32_t*)take(n2 * 4);
-    v.tmp = p;
-    v.tmp_bytes = 0;
+    a.head();
+    v.row_start = a.take<int64_t>((size_t)(num_nodes + 1));
+    v.nbr = a.take<int32_t>(n2);
+    v.nbr_eid = a.take<int64_t>(n2);
+    v.nbr_t = a.take<double>(n2);
+}
+static void sampler_layout(Arena& a, SamplerView& v, int64_t E, int64_t num_nodes) {
+    const size_t n2 = 2 * (size_t)(E < 1 ? 1 : E);
+    csr_layout(a, v, E, num_nodes);
+    v.tk_a = a.take<uint64_t>(n2);
+    v.tk_b = a.take<uint64_t>(n2);
+    v.ix_a = a.take<uint32_t>(n2);
+    v.ix_b = a.take<uint32_t>(n2);
+    v.nk_a = a.take<uint32_t>(n2);
+    v.nk_b = a.take<uint32_t>(n2);
+    v.tmp = a.rest();
+    const size_t t1 = sort_pairs_tmp<uint64_t, uint32_t>(n2), t2 = sort_pairs_tmp<uint32_t, uint32_t>(n2);
+    a.skip(t1 > t2 ? t1 : t2);
+}
+static SamplerView csr_view(const void* sampler, int64_t E, int64_t num_nodes) {
+    Arena a(const_cast<void*>(sampler), 0);
+    SamplerView v{};
+    csr_layout(a, v, E, num_nodes);
     return v;
+}
+// W[2E] doubles (the scan keeps its carries in registers)
+static double* weights_layout(Arena& a, int64_t E) {
+    a.head();
+    return a.take<double>(2 * (size_t)(E < 1 ? 1 : E));
+}
+
+size_t tpnet_sampler_bytes(int64_t E, int64_t num_nodes) {
+    return measured([&](Arena& a) { SamplerView v; sampler_layout(a, v, E, num_nodes); });
 }
 
 int tpnet_sampler_build(void* sampler, size_t sampler_bytes, const int64_t* src, const int64_t* dst, const double* t,
@@ -324,24 +329,23 @@ int tpnet_sampler_build(void* sampler, size_t sampler_bytes, const int64_t* src,
     if (E >= (1ll << 30)) return TPNET_ERR_BAD_ARG;
     if (sampler_bytes < tpnet_sampler_bytes(E, num_nodes)) return TPNET_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    SamplerView v = carve(sampler, E, num_nodes);
+    Arena a(sampler, sampler_bytes);
+    SamplerView v;
+    sampler_layout(a, v, E, num_nodes);
     if (E == 0) {
         hipLaunchKernelGGL(k_adj_empty, dim3(64), dim3(256), 0, s, num_nodes, v.row_start);
         TPNET_HIP_TRY(hipGetLastError());
         return TPNET_OK;
     }
     const size_t n2 = 2 * (size_t)E;
-    int grid = (int)((n2 + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const int grid = grid_1d((int64_t)n2, 4096);
     // stable sort by time, then stable sort by node  ==  sort by (node, time) with ties in append order
     hipLaunchKernelGGL(k_adj_keys, dim3(grid), dim3(256), 0, s, src, dst, t, E, v.tk_a, v.ix_a);
-    size_t tmp = sampler_bytes - (size_t)((char*)v.tmp - (char*)sampler);
-    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp, tmp, v.tk_a, v.tk_b, v.ix_a, v.ix_b, n2, 0u, 64u, s, false));
+    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp.ptr, v.tmp.bytes, v.tk_a, v.tk_b, v.ix_a, v.ix_b, n2, 0u, 64u, s, false));
     hipLaunchKernelGGL(k_adj_nodekeys, dim3(grid), dim3(256), 0, s, src, dst, E, v.ix_b, v.nk_a);
     int bits = 1;
     while ((1ll << bits) < num_nodes && bits < 32) ++bits;
-    tmp = sampler_bytes - (size_t)((char*)v.tmp - (char*)sampler);
-    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp, tmp, v.nk_a, v.nk_b, v.ix_b, v.ix_a, n2, 0u, (unsigned)bits, s, false));
+    TPNET_HIP_TRY(rocprim::radix_sort_pairs(v.tmp.ptr, v.tmp.bytes, v.nk_a, v.nk_b, v.ix_b, v.ix_a, n2, 0u, (unsigned)bits, s, false));
     hipLaunchKernelGGL(k_adj_fill, dim3(grid), dim3(256), 0, s, src, dst, t, edge_ids, E, v.nk_b, v.ix_a, num_nodes,
                        v.row_start, v.nbr, v.nbr_eid, v.nbr_t);
     TPNET_HIP_TRY(hipGetLastError());
@@ -353,10 +357,8 @@ int tpnet_sample_recent(const void* sampler, int64_t E, int64_t num_nodes, const
     if (!sampler || n < 0 || K < 1 || num_nodes < 1 || (n > 0 && (!node_ids || !times || !out_ids)))
         return TPNET_ERR_BAD_ARG;
     if (n == 0) return TPNET_OK;
-    SamplerView v = carve(const_cast<void*>(sampler), E, num_nodes);
-    int64_t tot = n * (int64_t)K;
-    int grid = (int)((tot + 255) / 256);
-    if (grid > 8192) grid = 8192;
+    SamplerView v = csr_view(sampler, E, num_nodes);
+    const int grid = grid_1d(n * (int64_t)K, 8192);
     hipLaunchKernelGGL(k_sample_recent, dim3(grid), dim3(256), 0, (hipStream_t)stream, v.row_start, v.nbr, v.nbr_eid,
                        v.nbr_t, num_nodes, node_ids, times, n, (int)K, out_ids, out_eids, out_times);
     TPNET_HIP_TRY(hipGetLastError());
@@ -364,7 +366,7 @@ int tpnet_sample_recent(const void* sampler, int64_t E, int64_t num_nodes, const
 }
 
 size_t tpnet_sampler_weights_bytes(int64_t E) {
-    return al(2 * (size_t)(E < 1 ? 1 : E) * 8) + 256;           // W[2E] doubles; the scan keeps its carries in registers
+    return measured([&](Arena& a) { (void)weights_layout(a, E); });
 }
 
 int tpnet_sampler_build_weights(const void* sampler, int64_t E, int64_t num_nodes, double time_scaling_factor, void* weights,
@@ -372,8 +374,9 @@ int tpnet_sampler_build_weights(const void* sampler, int64_t E, int64_t num_node
     if (!sampler || !weights || E < 0 || E >= (1ll << 30) || num_nodes < 1 || num_nodes >= (1ll << 31)) return TPNET_ERR_BAD_ARG;
     if (weights_bytes < tpnet_sampler_weights_bytes(E)) return TPNET_ERR_WORKSPACE;
     if (E == 0) return TPNET_OK;
-    SamplerView v = carve(const_cast<void*>(sampler), E, num_nodes);
-    double* W = (double*)(((size_t)weights + 255) / 256 * 256);
+    SamplerView v = csr_view(sampler, E, num_nodes);
+    Arena wa(weights, weights_bytes);
+    double* W = weights_layout(wa, E);
     const int grid = (int)(num_nodes < 8192 ? num_nodes : 8192);
     hipLaunchKernelGGL(k_sampler_weights, dim3(grid), dim3(256), 0, (hipStream_t)stream, v.row_start, v.nbr_t, num_nodes,
                        time_scaling_factor, W);
@@ -390,8 +393,9 @@ int tpnet_sample_random(const void* sampler, const void* weights, int64_t E, int
     const int rows_per_wg = 256 / K;                             // whole rows per workgroup (K > 128: one)
     const int64_t grid = (n + rows_per_wg - 1) / rows_per_wg;
     if (grid > 0x7fffffffll) return TPNET_ERR_BAD_ARG;
-    SamplerView v = carve(const_cast<void*>(sampler), E, num_nodes);
-    const double* W = (weights && E > 0) ? (const double*)(((size_t)weights + 255) / 256 * 256) : nullptr;
+    SamplerView v = csr_view(sampler, E, num_nodes);
+    Arena wa(const_cast<void*>(weights), 0);
+    const double* W = (weights && E > 0) ? weights_layout(wa, E) : nullptr;
     hipLaunchKernelGGL(k_sample_random, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, v.row_start, v.nbr, v.nbr_eid,
                        v.nbr_t, W, num_nodes, node_ids, times, n, (int)K, rows_per_wg, (uint32_t)seed, (uint32_t)(seed >> 32),
                        call_index, out_ids, out_eids, out_times);
@@ -412,22 +416,18 @@ int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, in
     if (B == 0) return TPNET_OK;
     if (scratch_bytes < tpnet_encoder_scratch_bytes(B, K)) return TPNET_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    int64_t* nodes = (int64_t*)(((size_t)scratch + 255) / 256 * 256);
+    int64_t* nodes = (int64_t*)align256((size_t)scratch);
     double* t2 = (double*)(nodes + 2 * B);
     int64_t* a1 = (int64_t*)(t2 + 2 * B);
     int64_t* a2 = a1 + 2 * B;
     int64_t* neigh = a2 + 2 * B;
     static const int two = TPNET_DEV_INT(ENCODER_TWO_LAUNCHES, 0);     // developer override: row set-up and sampler apart
     if (two) {
-        int g0 = (int)((2 * B + 255) / 256);
-        if (g0 > 1024) g0 = 1024;
-        hipLaunchKernelGGL(k_encoder_rows, dim3(g0), dim3(256), 0, s, src, other, t, B, nodes, t2, a1, a2);
+        hipLaunchKernelGGL(k_encoder_rows, dim3(grid_1d(2 * B, 1024)), dim3(256), 0, s, src, other, t, B, nodes, t2, a1, a2);
         return tpnet_sample_recent(sampler, E, num_nodes, nodes, t2, 2 * B, K, neigh, nullptr, nullptr, stream);
     }
-    SamplerView v = carve(const_cast<void*>(sampler), E, num_nodes);
-    const int64_t tot = 2 * B * (int64_t)K;
-    int grid = (int)((tot + 255) / 256);
-    if (grid > 8192) grid = 8192;
+    SamplerView v = csr_view(sampler, E, num_nodes);
+    const int grid = grid_1d(2 * B * (int64_t)K, 8192);
     int64_t* pu = (encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K)) ? neigh + 2 * B * (int64_t)K : nullptr;
     hipLaunchKernelGGL(k_encoder_sample, dim3(grid), dim3(256), 0, s, v.row_start, v.nbr, v.nbr_t, num_nodes, src, other, t, B, (int)K,
                        nodes, t2, a1, a2, neigh, pu, pu ? pu + 4 * B * (int64_t)K : nullptr);
@@ -444,7 +444,7 @@ int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, in
     if (!tpnet_pair_gram_anchored_supported(st)) return TPNET_ERR_BAD_ARG;
     int rc = tpnet_encoder_rows(st, sampler, E, num_nodes, src, other, t, B, K, scratch, scratch_bytes, stream);
     if (rc) return rc;
-    int64_t* nodes = (int64_t*)(((size_t)scratch + 255) / 256 * 256);
+    int64_t* nodes = (int64_t*)align256((size_t)scratch);
     int64_t* a1 = nodes + 4 * B;
     int64_t* a2 = a1 + 2 * B;
     int64_t* neigh = a2 + 2 * B;

@@ -56,4 +56,18 @@ __global__ __launch_bounds__(256) void k_scan_emit(Flag f, Emit e, const uint32_
     }
 }
 
+// Host side, on stream s.  scan_count: the two launches that leave the exclusive tile sums in blk and the number of set flags in
+// *total; scan_compact: those and k_scan_emit on the same flag.
+template <class Flag>
+static void scan_count(Flag f, const uint32_t* n_dev, uint32_t n_host, uint32_t* blk, uint32_t* total, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_scan_count<Flag>, dim3(grid), dim3(256), 0, s, f, n_dev, n_host, blk);
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, blk, n_dev, n_host, total);
+}
+template <class Flag, class Emit>
+static void scan_compact(Flag f, Emit e, const uint32_t* n_dev, uint32_t n_host, uint32_t* blk, uint32_t* total, int grid,
+                         hipStream_t s) {
+    scan_count(f, n_dev, n_host, blk, total, grid, s);
+    hipLaunchKernelGGL((k_scan_emit<Flag, Emit>), dim3(grid), dim3(256), 0, s, f, e, n_dev, n_host, (const uint32_t*)blk);
+}
+
 }  // namespace tpnet

@@ -33,14 +33,7 @@ bool wplan_dense_eligible(int64_t N, int d, int L, int64_t batch) {
 
 size_t wplan_dense_bytes(int64_t Ec, int64_t batch, int64_t N, int d, int L) {
     if (!wplan_dense_eligible(N, d, L, batch)) return 0;
-    const size_t nb = (size_t)((Ec + batch - 1) / batch);
-    const size_t Ns = (size_t)dense_ns(N);
-    size_t nw = (nb + 1) / 2 + 1;
-    if (nw > (size_t)DENSE_MAX_WINDOWS) nw = DENSE_MAX_WINDOWS;
-    const size_t nchunks = (Ns + 255) / 256;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    return al(nb * Ns * 2) + al(nb * Ns * 8) + al(nw * Ns * 4) + al(nw * Ns * 8) + 4 * al(Ns * 4) + al(nchunks * 4) +
-           2 * al(nchunks * nw * 8 * 4) + al(nw * 8 * 4) + 256;
+    return measured([&](Arena& a) { DView v; dense_layout(a, v, Ec, batch, N); });
 }
 
 struct DArgs {
@@ -657,9 +650,7 @@ int wplan_dense_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& pa
     a.status = pa.status;
     if (replay) {
         if (a.nwhich == 3) {
-            int g = (int)((Ec + 255) / 256);
-            if (g > 2048) g = 2048;
-            hipLaunchKernelGGL(k_wplan_dense_negs, dim3(g), dim3(256), 0, s, p, D, a);
+            hipLaunchKernelGGL(k_wplan_dense_negs, dim3(grid_1d(Ec, 2048)), dim3(256), 0, s, p, D, a);
             TPNET_HIP_TRY(hipGetLastError());
         }
         return TPNET_OK;
@@ -675,9 +666,8 @@ int wplan_dense_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& pa
     const unsigned bgrid = (unsigned)((int64_t)a.nchunks * a.nw);
     hipLaunchKernelGGL(k_dense_win, dim3(bgrid), dim3(DCH), 0, s, p, D, a);
     hipLaunchKernelGGL(k_dense_pre, dim3(bgrid), dim3(DCH), 0, s, p, D, a);
-    int64_t cgrid = (3 * Ec + DCH - 1) / DCH;
-    if (cgrid > 4096) cgrid = 4096;
-    hipLaunchKernelGGL(k_dense_place, dim3((unsigned)cgrid), dim3(DCH), 0, s, p, q, D, a);
+    static_assert(DCH == 256, "grid_1d counts workgroups of 256");
+    hipLaunchKernelGGL(k_dense_place, dim3(grid_1d(3 * Ec, 4096)), dim3(DCH), 0, s, p, q, D, a);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }

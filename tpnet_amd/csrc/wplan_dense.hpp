@@ -2,6 +2,7 @@
 // the lookup "version of node v before batch b".
 #pragma once
 #include "wplan_common.hpp"
+#include "arena.hpp"
 
 namespace tpnet {
 
@@ -28,28 +29,32 @@ struct DView {                 // the dense planner's arrays (WPlan::dense, carv
 
 static inline int64_t dense_ns(int64_t N) { return (N + 63) / 64 * 64; }
 
-static inline DView dview_of(const WPlan& p, int64_t Ec, int64_t batch, int64_t N) {
-    DView v;
+// the layout of WPlan::dense (256-byte aligned by wplan_carve)
+static inline void dense_layout(Arena& a, DView& v, int64_t Ec, int64_t batch, int64_t N) {
     const size_t nb = (size_t)((Ec + batch - 1) / batch);
     const size_t Ns = (size_t)dense_ns(N);
     size_t nw = (nb + 1) / 2 + 1;
     if (nw > (size_t)DENSE_MAX_WINDOWS) nw = DENSE_MAX_WINDOWS;
     const size_t nchunks = (Ns + 255) / 256;
-    char* c = reinterpret_cast<char*>(p.dense);
-    auto take = [&](size_t bytes) { void* r = c; c += (bytes + 255) / 256 * 256; return r; };
-    v.len = (uint16_t*)take(nb * Ns * 2);
-    v.m = (uint2*)take(nb * Ns * 8);
-    v.crank = (uint32_t*)take(nw * Ns * 4);
-    v.wsl = (uint2*)take(nw * Ns * 8);
-    v.tot = (uint32_t*)take(Ns * 4);
-    v.lastb = (uint32_t*)take(Ns * 4);
-    v.base = (uint32_t*)take(Ns * 4);
-    v.basef = (uint32_t*)take(Ns * 4);
-    v.ctot = (uint32_t*)take(nchunks * 4);
-    v.ccnt = (uint32_t*)take(nchunks * nw * 8 * 4);
-    v.cpre = (uint32_t*)take(nchunks * nw * 8 * 4);
-    v.ptot = (uint32_t*)take(nw * 8 * 4);
+    v.len = a.take<uint16_t>(nb * Ns);
+    v.m = a.take<uint2>(nb * Ns);
+    v.crank = a.take<uint32_t>(nw * Ns);
+    v.wsl = a.take<uint2>(nw * Ns);
+    v.tot = a.take<uint32_t>(Ns);
+    v.lastb = a.take<uint32_t>(Ns);
+    v.base = a.take<uint32_t>(Ns);
+    v.basef = a.take<uint32_t>(Ns);
+    v.ctot = a.take<uint32_t>(nchunks);
+    v.ccnt = a.take<uint32_t>(nchunks * nw * 8);
+    v.cpre = a.take<uint32_t>(nchunks * nw * 8);
+    v.ptot = a.take<uint32_t>(nw * 8);
+    a.skip(256);                                     // tail slack
     v.Ns = (int64_t)Ns;
+}
+static inline DView dview_of(const WPlan& p, int64_t Ec, int64_t batch, int64_t N) {
+    Arena a(p.dense, 0);
+    DView v;
+    dense_layout(a, v, Ec, batch, N);
     return v;
 }
 

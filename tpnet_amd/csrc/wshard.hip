@@ -19,6 +19,8 @@
 // schedule -- bit for bit where the chunk's halo rows need no decay (a table just reset or imported), else up to the one extra f32
 // rounding of tpnet_pack_split's decay, as on the per-batch shard.
 #include "wplan_dense.hpp"
+#include "arena.hpp"
+#include "sort_tmp.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -358,25 +360,51 @@ struct tpnet_wshard {
     double now_time;
 };
 
-static size_t ws_al(size_t x) { return (x + 255) / 256 * 256; }
-static size_t ws_sort_tmp(size_t cap, size_t nq) {
-    size_t b1 = 0, b2 = 0;
-    unsigned long long* k = nullptr;
-    (void)rocprim::radix_sort_keys(nullptr, b1, k, k, cap, 0u, 64u, (hipStream_t)0, false);
+// The workspace of a plan: the chunk's WPlan region (wplan_carve lays it out), the scratch of tpnet_wshard_plan behind it.  nw, nsteps:
+// the chunk's windows and pipeline steps -- measured for the most a chunk of nb batches can have (nb and nb + L + 1).
+struct WsView {
+    char* plan; size_t plan_bytes;
+    uint8_t* mark; uint32_t* rank; int64_t *lsrc, *ldst, *lneg, *pack_ids; uint8_t *fa, *fb, *wa, *wb; uint16_t* ww;
+    unsigned long long *keys, *sorted; uint32_t *off, *pbase, *ent[2]; int64_t* cnt_dev; uint32_t *status, *own_list, *erank, *own_start;
+    Arena::Span tmp;
+};
+static void ws_layout(Arena& a, WsView& v, int64_t n_local, int d, int L, int64_t E, int64_t batch, int32_t G, int64_t n_cap, int64_t nw,
+                      int64_t nsteps) {
+    const size_t nq = (size_t)G * (size_t)n_cap + 1, cap = 6 * (size_t)E, e = (size_t)E;
+    a.head();
+    v.plan_bytes = align256(wplan_bytes_shard(E, batch, n_local, d, L));
+    v.plan = a.take<char>(v.plan_bytes);
+    v.mark = a.take<uint8_t>(nq);
+    v.rank = a.take<uint32_t>(nq);
+    v.lsrc = a.take<int64_t>(e);
+    v.ldst = a.take<int64_t>(e);
+    v.lneg = a.take<int64_t>(e);
+    v.pack_ids = a.take<int64_t>((size_t)n_cap);
+    v.fa = a.take<uint8_t>(2 * e * G);                            // (fa .. wb are contiguous: one fill)
+    v.fb = a.take<uint8_t>(2 * e * G);
+    v.wa = a.take<uint8_t>(2 * e);
+    v.wb = a.take<uint8_t>(2 * e);
+    v.ww = a.take<uint16_t>(2 * e);
+    v.keys = a.take<unsigned long long>(cap);
+    v.sorted = a.take<unsigned long long>(cap);
+    v.off = a.take<uint32_t>(4 * (size_t)nw * G + 1);
+    v.pbase = a.take<uint32_t>(2 * (size_t)nsteps * G);
+    v.ent[0] = a.take<uint32_t>(cap * 3);
+    v.ent[1] = a.take<uint32_t>(cap * 3);
+    v.cnt_dev = a.take<int64_t>((size_t)(G + 2));
+    v.status = a.take<uint32_t>(4);
+    v.own_list = a.take<uint32_t>(e + 1);
+    v.erank = a.take<uint32_t>(e + 1);
+    v.own_start = a.take<uint32_t>((size_t)nw + 2);
+    v.tmp = a.rest();                                             // of the sort of the items and of the two scans
+    size_t scan = 0;
     uint8_t* m = nullptr;
     uint32_t* r = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, b2, rocprim::make_transform_iterator(m, WsFlag()), r, 0u, nq, rocprim::plus<uint32_t>(),
-                                  (hipStream_t)0, false);
-    return ws_al(b1 > b2 ? b1 : b2);
-}
-static size_t ws_scratch_bytes(int64_t n_cap, int32_t G, int64_t E, int64_t nb, int L) {
-    const size_t nq = (size_t)G * (size_t)n_cap + 1;
-    const size_t cap = 6 * (size_t)E;
-    const size_t nsteps = (size_t)nb + (size_t)L + 1;
-    return ws_al(nq) + ws_al(nq * 4) + 3 * ws_al((size_t)E * 8) + ws_al((size_t)n_cap * 8) + 2 * ws_al(2 * (size_t)E * G) +
-           2 * ws_al(2 * (size_t)E) + ws_al(4 * (size_t)E) + 2 * ws_al(cap * 8) + ws_al((4 * (size_t)nb * G + 1) * 4) + ws_al(2 * nsteps * G * 4) +
-           2 * ws_al(cap * 3 * 4) + ws_al((size_t)(G + 2) * 8) + ws_al(16) + ws_sort_tmp(cap, nq > (size_t)E + 1 ? nq : (size_t)E + 1) +
-           2 * ws_al(((size_t)E + 1) * 4) + ws_al(((size_t)nb + 2) * 4) + 1024;
+    (void)rocprim::exclusive_scan(nullptr, scan, rocprim::make_transform_iterator(m, WsFlag()), r, 0u, nq > e + 1 ? nq : e + 1,
+                                  rocprim::plus<uint32_t>(), (hipStream_t)0, false);
+    const size_t sort = sort_keys_tmp<unsigned long long>(cap);
+    a.skip(sort > scan ? sort : scan);
+    a.skip(1024 + 256);                                           // tail slack
 }
 
 extern "C" {
@@ -384,7 +412,7 @@ extern "C" {
 size_t tpnet_wshard_workspace_bytes(int64_t n_local, int32_t d, int32_t L, int64_t E, int64_t batch, int32_t G, int32_t n_owned) {
     if (n_local < 1 || d < 1 || L < 1 || L > TPNET_MAX_LAYERS || E < 1 || batch < 1 || G < 1 || G > WS_MAXG || n_owned < 1) return 0;
     const int64_t nb = (E + batch - 1) / batch;
-    return ws_al(wplan_bytes_shard(E, batch, n_local, d, L)) + ws_scratch_bytes(n_owned, G, E, nb, L) + 512;
+    return measured([&](Arena& a) { WsView v; ws_layout(a, v, n_local, d, L, E, batch, G, n_owned, nb, nb + L + 1); });
 }
 
 void tpnet_wshard_destroy(tpnet_wshard* w) { delete w; }
@@ -422,62 +450,36 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
     w->have_readout = want_pos || want_neg;
     w->nsteps = nw + (w->have_readout ? L : L - 1);
     auto fail = [&](int rc) { return rc; };
-    const size_t plan_b = ws_al(wplan_bytes_shard(E, batch, st->N, d, L));
-    char* base = reinterpret_cast<char*>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
-    rc = wplan_carve(base, plan_b, E, batch, st->N, d, L, K, &w->p, nullptr, true);
-    if (rc) return fail(rc == TPNET_ERR_BAD_ARG ? 1 : rc);
-    if (!wplan_dense_applies_shard(*st, w->p, E, batch, K)) return fail(1);
-    char* c = base + plan_b;
-    auto take = [&](size_t bytes) { void* r = c; c += ws_al(bytes); return r; };
     const int64_t n_cap = n_owned;
     const size_t nq = (size_t)G * (size_t)n_cap + 1;
     const size_t cap = 6 * (size_t)E;
-    uint8_t* mark = (uint8_t*)take(nq);
-    uint32_t* rank = (uint32_t*)take(nq * 4);
-    int64_t* lsrc = (int64_t*)take((size_t)E * 8);
-    int64_t* ldst = (int64_t*)take((size_t)E * 8);
-    int64_t* lneg = (int64_t*)take((size_t)E * 8);
-    w->pack_ids = (int64_t*)take((size_t)n_cap * 8);
-    uint8_t* fa = (uint8_t*)take(2 * (size_t)E * G);
-    uint8_t* fb = (uint8_t*)take(2 * (size_t)E * G);
-    uint8_t* wa = (uint8_t*)take(2 * (size_t)E);
-    uint8_t* wb = (uint8_t*)take(2 * (size_t)E);
-    uint16_t* ww = (uint16_t*)take(4 * (size_t)E);
-    unsigned long long* keys = (unsigned long long*)take(cap * 8);
-    unsigned long long* sorted = (unsigned long long*)take(cap * 8);
-    uint32_t* off = (uint32_t*)take((4 * (size_t)nw * G + 1) * 4);
-    uint32_t* pbase = (uint32_t*)take(2 * (size_t)w->nsteps * G * 4);
-    w->ent[0] = (uint32_t*)take(cap * 3 * 4);
-    w->ent[1] = (uint32_t*)take(cap * 3 * 4);
-    int64_t* cnt_dev = (int64_t*)take((size_t)(G + 2) * 8);
-    uint32_t* status = (uint32_t*)take(16);
-    uint32_t* own_list = (uint32_t*)take(((size_t)E + 1) * 4);
-    uint32_t* erank = (uint32_t*)take(((size_t)E + 1) * 4);
-    uint32_t* own_start = (uint32_t*)take(((size_t)nw + 2) * 4);
-    void* tmp = c;
-    size_t tmp_bytes = ws_sort_tmp(cap, nq > (size_t)E + 1 ? nq : (size_t)E + 1);
-    if ((size_t)(c + tmp_bytes - reinterpret_cast<char*>(workspace)) > ws_bytes) return fail(TPNET_ERR_WORKSPACE);
+    Arena ar(workspace, ws_bytes);
+    WsView v;
+    ws_layout(ar, v, st->N, d, L, E, batch, G, n_cap, nw, w->nsteps);
+    if (!ar.fits()) return fail(TPNET_ERR_WORKSPACE);
+    rc = wplan_carve(v.plan, v.plan_bytes, E, batch, st->N, d, L, K, &w->p, nullptr, true);
+    if (rc) return fail(rc == TPNET_ERR_BAD_ARG ? 1 : rc);
+    if (!wplan_dense_applies_shard(*st, w->p, E, batch, K)) return fail(1);
+    w->pack_ids = v.pack_ids;
+    w->ent[0] = v.ent[0];
+    w->ent[1] = v.ent[1];
 
     // ---- relabel: the chunk's touched nodes, one local id each
-    TPNET_HIP_TRY(hipMemsetAsync(mark, 0, nq, s));
-    TPNET_HIP_TRY(hipMemsetAsync(status, 0, 16, s));
+    TPNET_HIP_TRY(hipMemsetAsync(v.mark, 0, nq, s));
+    TPNET_HIP_TRY(hipMemsetAsync(v.status, 0, 16, s));
     const int64_t items = (neg ? 3 : 2) * E;
-    int grid = (int)((items + 255) / 256);
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(k_ws_mark, dim3(grid), dim3(256), 0, s, src, dst, neg, E, N_global, G, n_cap, mark, status);
-    {
-        size_t tb = tmp_bytes;
-        if (rocprim::exclusive_scan(tmp, tb, rocprim::make_transform_iterator(mark, WsFlag()), rank, 0u, nq, rocprim::plus<uint32_t>(), s,
-                                    false) != hipSuccess)
-            return fail(TPNET_ERR_HIP);
-    }
-    hipLaunchKernelGGL(k_ws_counts, dim3((unsigned)((n_cap + 255) / 256)), dim3(256), 0, s, rank, mark, G, me, n_cap, cnt_dev, w->pack_ids);
-    hipLaunchKernelGGL(k_ws_relabel, dim3(grid), dim3(256), 0, s, src, dst, neg, E, N_global, G, me, n_cap, rank, lsrc, ldst,
-                       neg ? lneg : nullptr);
+    const int grid = grid_1d(items, 8192);
+    hipLaunchKernelGGL(k_ws_mark, dim3(grid), dim3(256), 0, s, src, dst, neg, E, N_global, G, n_cap, v.mark, v.status);
+    if (rocprim::exclusive_scan(v.tmp.ptr, v.tmp.bytes, rocprim::make_transform_iterator(v.mark, WsFlag()), v.rank, 0u, nq,
+                                rocprim::plus<uint32_t>(), s, false) != hipSuccess)
+        return fail(TPNET_ERR_HIP);
+    hipLaunchKernelGGL(k_ws_counts, dim3((unsigned)((n_cap + 255) / 256)), dim3(256), 0, s, v.rank, v.mark, G, me, n_cap, v.cnt_dev, w->pack_ids);
+    hipLaunchKernelGGL(k_ws_relabel, dim3(grid), dim3(256), 0, s, src, dst, neg, E, N_global, G, me, n_cap, v.rank, v.lsrc, v.ldst,
+                       neg ? v.lneg : nullptr);
     std::vector<int64_t> hc((size_t)G + 1);
     uint32_t hstat[4] = {0, 0, 0, 0};
-    if (hipMemcpyAsync(hc.data(), cnt_dev, (size_t)(G + 1) * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    if (hipMemcpyAsync(hc.data(), v.cnt_dev, (size_t)(G + 1) * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(hstat, v.status, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return fail(TPNET_ERR_HIP);
     if (hstat[0]) return fail(TPNET_ERR_INDEX);
     w->chunk_cnt.assign(hc.begin(), hc.begin() + G);
@@ -491,26 +493,22 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
     if (rc) return fail(rc);
     // ---- the plan of the pipeline on the local ids, owned targets only
     StreamArgs& a = w->a;
-    a = stream_args_at(lsrc, ldst, neg ? lneg : nullptr, t, nullptr, nullptr, 0, 0, 0, n_owned);      // (local ids: the rank owns those < n_owned)
-    rc = wplan_dense_build(*st, w->p, {a.src, a.dst, a.neg, t, E, batch, now_time, nullptr, lambda, w->have_readout, false, n_owned, status + 1}, s);
+    a = stream_args_at(v.lsrc, v.ldst, neg ? v.lneg : nullptr, t, nullptr, nullptr, 0, 0, 0, n_owned);      // (local ids: the rank owns those < n_owned)
+    rc = wplan_dense_build(*st, w->p, {a.src, a.dst, a.neg, t, E, batch, now_time, nullptr, lambda, w->have_readout, false, n_owned, v.status + 1}, s);
     if (rc) return fail(rc);
     {
         // the rank's own edges (src node owned), in order, and every window's slice of them
-        size_t tb = tmp_bytes;
-        auto flags_it = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), WsOwnFlag{lsrc, (int64_t)n_owned});
-        if (rocprim::exclusive_scan(tmp, tb, flags_it, erank, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), s, false) != hipSuccess)
+        auto flags_it = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), WsOwnFlag{v.lsrc, (int64_t)n_owned});
+        if (rocprim::exclusive_scan(v.tmp.ptr, v.tmp.bytes, flags_it, v.erank, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), s, false) != hipSuccess)
             return fail(TPNET_ERR_HIP);
-        int g1 = (int)((E + 255) / 256);
-        if (g1 > 4096) g1 = 4096;
-        hipLaunchKernelGGL(k_ws_ownlist, dim3(g1), dim3(256), 0, s, lsrc, (int64_t)n_owned, E, w->p.Ew, nw, erank, own_list, own_start);
-        a.own_list = own_list;
-        a.own_start = own_start;
+        hipLaunchKernelGGL(k_ws_ownlist, dim3(grid_1d(E, 4096)), dim3(256), 0, s, v.lsrc, (int64_t)n_owned, E, w->p.Ew, nw, v.erank, v.own_list, v.own_start);
+        a.own_list = v.own_list;
+        a.own_start = v.own_start;
     }
 
     // ---- what travels after every step: items, sorted; counts per (list, kind, window, peer)
-    // (fa .. wb are contiguous in the workspace: one fill)
-    TPNET_HIP_TRY(hipMemsetAsync(fa, 0, (size_t)(reinterpret_cast<char*>(ww) - reinterpret_cast<char*>(fa)), s));
-    TPNET_HIP_TRY(hipMemsetAsync(status + 2, 0, 4, s));
+    TPNET_HIP_TRY(hipMemsetAsync(v.fa, 0, (size_t)(reinterpret_cast<char*>(v.ww) - reinterpret_cast<char*>(v.fa)), s));
+    TPNET_HIP_TRY(hipMemsetAsync(v.status + 2, 0, 4, s));
     WsOwners ow{};
     ow.G = G; ow.me = me; ow.n_owned = n_owned;
     for (int o = 0; o <= G; ++o) ow.hstart[o] = w->hstart[o];
@@ -518,34 +516,29 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
     if (G > 1) {
         WsNeed nd{};
         nd.gsrc = src; nd.gdst = dst; nd.gneg = neg;
-        nd.lsrc = lsrc; nd.ldst = ldst; nd.lneg = neg ? lneg : nullptr;
+        nd.lsrc = v.lsrc; nd.ldst = v.ldst; nd.lneg = neg ? v.lneg : nullptr;
             nd.E = E; nd.B = batch; nd.K = K; nd.have_pos = want_pos ? 1 : 0; nd.have_neg = want_neg ? 1 : 0; nd.G = G;
-        nd.fa = fa; nd.fb = fb; nd.wa = wa; nd.wb = wb; nd.ww = ww; nd.keys = keys; nd.counter = status + 2;
-        int g2 = (int)((E + 255) / 256);
-        if (g2 > 4096) g2 = 4096;
-        hipLaunchKernelGGL(k_ws_needs, dim3(g2), dim3(256), 0, s, nd, ow, D);
-        int64_t gi = ((2 * E * (G + 1) + 31) / 16 + 255) / 256;
-        if (gi > 8192) gi = 8192;
-        hipLaunchKernelGGL(k_ws_items, dim3((unsigned)gi), dim3(256), 0, s, nd);
+        nd.fa = v.fa; nd.fb = v.fb; nd.wa = v.wa; nd.wb = v.wb; nd.ww = v.ww; nd.keys = v.keys; nd.counter = v.status + 2;
+        hipLaunchKernelGGL(k_ws_needs, dim3(grid_1d(E, 4096)), dim3(256), 0, s, nd, ow, D);
+        hipLaunchKernelGGL(k_ws_items, dim3(grid_1d((2 * E * (G + 1) + 31) / 16, 8192)), dim3(256), 0, s, nd);
         // how many items there are sizes the sort (a sort of the 6 E slots the array has room for was 8 x the work at G = 8)
-        if (hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        if (hipMemcpyAsync(hstat, v.status, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return fail(TPNET_ERR_HIP);
         if (hstat[1]) return fail(1);                                // a batch's owned contributions exceeded the sort: per batch
         const uint32_t n_items = hstat[2];
         if (n_items > cap) return fail(TPNET_ERR_WORKSPACE);
         if (n_items > 0) {
-            size_t tb = tmp_bytes;
-            if (rocprim::radix_sort_keys(tmp, tb, keys, sorted, (size_t)n_items, 0u, (unsigned)(2 + WS_WIN_BITS + WS_PEER_BITS + WS_SLOT_BITS), s,
+            if (rocprim::radix_sort_keys(v.tmp.ptr, v.tmp.bytes, v.keys, v.sorted, (size_t)n_items, 0u, (unsigned)(2 + WS_WIN_BITS + WS_PEER_BITS + WS_SLOT_BITS), s,
                                          false) != hipSuccess)
                 return fail(TPNET_ERR_HIP);
         }
-        hipLaunchKernelGGL(k_ws_offsets, dim3((unsigned)((4 * nw * G + 256) / 256)), dim3(256), 0, s, sorted, n_items, nw, G, off);
+        hipLaunchKernelGGL(k_ws_offsets, dim3((unsigned)((4 * nw * G + 256) / 256)), dim3(256), 0, s, v.sorted, n_items, nw, G, v.off);
     } else {
-        TPNET_HIP_TRY(hipMemsetAsync(off, 0, (4 * (size_t)nw * G + 1) * 4, s));
+        TPNET_HIP_TRY(hipMemsetAsync(v.off, 0, (4 * (size_t)nw * G + 1) * 4, s));
     }
     std::vector<uint32_t> hoff(4 * (size_t)nw * G + 1);
-    if (hipMemcpyAsync(hoff.data(), off, hoff.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    if (hipMemcpyAsync(hoff.data(), v.off, hoff.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(hstat, v.status, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return fail(TPNET_ERR_HIP);
     if (hstat[1]) return fail(1);                                    // a batch's owned contributions exceeded the sort: per batch
     auto cnt_of = [&](int list, int kind, int64_t ww, int peer) -> int64_t {
@@ -579,13 +572,11 @@ int tpnet_wshard_plan(const tpnet_state* st, const int64_t* src, const int64_t* 
         if ((size_t)run > cap * 3) return fail(TPNET_ERR_WORKSPACE);
     }
     if (G > 1 && hoff.back() > 0) {
-        TPNET_HIP_TRY(hipMemcpyAsync(pbase, hpb.data(), hpb.size() * 4, hipMemcpyHostToDevice, s));
+        TPNET_HIP_TRY(hipMemcpyAsync(v.pbase, hpb.data(), hpb.size() * 4, hipMemcpyHostToDevice, s));
         WsEnt ea{};
-        ea.sorted = sorted; ea.off = off; ea.pbase = pbase; ea.ent[0] = w->ent[0]; ea.ent[1] = w->ent[1];
+        ea.sorted = v.sorted; ea.off = v.off; ea.pbase = v.pbase; ea.ent[0] = w->ent[0]; ea.ent[1] = w->ent[1];
         ea.nw = nw; ea.G = G; ea.L = L; ea.nsteps = (int32_t)ns;
-        int g3 = (int)((hoff.back() + 255) / 256);
-        if (g3 > 4096) g3 = 4096;
-        hipLaunchKernelGGL(k_ws_entries, dim3(g3), dim3(256), 0, s, ea);
+        hipLaunchKernelGGL(k_ws_entries, dim3(grid_1d(hoff.back(), 4096)), dim3(256), 0, s, ea);
         TPNET_HIP_TRY(hipStreamSynchronize(s));                      // (hpb leaves scope)
     }
     TPNET_HIP_TRY(hipGetLastError());

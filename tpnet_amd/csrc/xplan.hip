@@ -11,6 +11,8 @@
 //               batch's receive list); anything else -> the first halo row (never dereferenced by a unit this rank computes).
 // The host reads back 2 * G counts per batch (the message sizes of the grouped ncclSend / ncclRecv) and two status words.
 #include "tpnet_common.h"
+#include "arena.hpp"
+#include "sort_tmp.hpp"
 
 #include <rocprim/block/block_radix_sort.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -287,15 +289,24 @@ __global__ __launch_bounds__(256) void k_xl_finish(XLArgs a, int32_t n_cap, int6
     }
 }
 
-static size_t xl_align(size_t x) { return (x + 255) / 256 * 256; }
-static size_t xl_sort_tmp(size_t cap) {
-    size_t bytes = 0;
-    unsigned long long* k = nullptr;
-    (void)rocprim::radix_sort_keys(nullptr, bytes, k, k, cap, 0u, 64u, (hipStream_t)0, false);
-    size_t b2 = 0;
+// the scratch of tpnet_xplan_targeted_large; returns what its sort and its scan share as temporary storage
+static Arena::Span xl_layout(Arena& a, XLArgs& x, int64_t E, int64_t batch, int32_t G) {
+    const size_t cap = 6 * (size_t)E;                           // (an item is at most one key of each list)
+    const size_t nb = (size_t)((E + batch - 1) / batch);
+    a.head();
+    x.keys = a.take<unsigned long long>(cap);
+    x.sorted = a.take<unsigned long long>(cap);
+    x.uniq = a.take<unsigned long long>(cap);
+    x.heads = a.take<uint32_t>(cap);
+    x.off = a.take<uint32_t>(2 * nb * (size_t)G + 1);
+    x.counter = a.take<uint32_t>(2);
+    const Arena::Span tmp = a.rest();
+    size_t scan = 0;
     uint32_t* h = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, b2, h, h, 0u, cap, rocprim::plus<uint32_t>(), (hipStream_t)0, false);
-    return xl_align(bytes > b2 ? bytes : b2);
+    (void)rocprim::exclusive_scan(nullptr, scan, h, h, 0u, cap, rocprim::plus<uint32_t>(), (hipStream_t)0, false);
+    const size_t sort = sort_keys_tmp<unsigned long long>(cap);
+    a.skip(sort > scan ? sort : scan);
+    return tmp;
 }
 
 }  // namespace tpnet
@@ -323,8 +334,7 @@ int tpnet_xplan_targeted(const int64_t* src, const int64_t* dst, const int64_t* 
     XArgs a{src, dst, neg, E, batch, N, G, me, nbits, nbits + gbits, recv_keys, pack_ids, cnt, status};
     hipLaunchKernelGGL(k_xplan, dim3((unsigned)nb), dim3(XBS), 0, s, a);
     const int64_t items = (neg ? 3 : 2) * E;
-    int grid = (int)((items + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const int grid = grid_1d(items, 4096);
     hipLaunchKernelGGL(k_xrelabel, dim3(grid), dim3(256), 0, s, a, n_owned, local_src, local_dst, local_neg);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
@@ -332,9 +342,7 @@ int tpnet_xplan_targeted(const int64_t* src, const int64_t* dst, const int64_t* 
 
 size_t tpnet_xplan_large_bytes(int64_t E, int64_t batch, int32_t G) {
     if (E < 1 || batch < 1 || G < 1) return 0;
-    const size_t cap = 6 * (size_t)E;                           // (an item is at most one key of each list)
-    const size_t nb = (size_t)((E + batch - 1) / batch);
-    return 3 * xl_align(cap * 8) + xl_align(cap * 4) + xl_align((2 * nb * (size_t)G + 1) * 4) + 256 + xl_sort_tmp(cap) + 256;
+    return measured([&](Arena& a) { XLArgs x{}; (void)xl_layout(a, x, E, batch, G); });
 }
 
 int tpnet_xplan_targeted_large(const int64_t* src, const int64_t* dst, const int64_t* neg, int64_t E, int64_t batch, int64_t N,
@@ -354,25 +362,16 @@ int tpnet_xplan_targeted_large(const int64_t* src, const int64_t* dst, const int
     if (nbits + gbits + bbits + 1 > 63) return TPNET_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const size_t cap = 6 * (size_t)E;
-    char* c = reinterpret_cast<char*>((reinterpret_cast<size_t>(scratch) + 255) / 256 * 256);
-    auto take = [&](size_t bytes) { void* r = c; c += xl_align(bytes); return r; };
     XLArgs a{};
+    Arena ar(scratch, scratch_bytes);
+    Arena::Span tmp = xl_layout(ar, a, E, batch, G);
     a.src = src; a.dst = dst; a.neg = neg; a.E = E; a.B = batch; a.N = N; a.nb = nb;
     a.G = G; a.me = me; a.nbits = nbits; a.gbits = gbits; a.bbits = bbits;
-    a.keys = (unsigned long long*)take(cap * 8);
-    a.sorted = (unsigned long long*)take(cap * 8);
-    a.uniq = (unsigned long long*)take(cap * 8);
-    a.heads = (uint32_t*)take(cap * 4);
-    a.off = (uint32_t*)take((2 * (size_t)nb * (size_t)G + 1) * 4);
-    a.counter = (uint32_t*)take(8);
     a.status = status;
-    void* tmp = c;
-    size_t tmp_bytes = xl_sort_tmp(cap);
     TPNET_HIP_TRY(hipMemsetAsync(status, 0, 2 * sizeof(uint32_t), s));
     TPNET_HIP_TRY(hipMemsetAsync(a.counter, 0, 8, s));
     const int64_t items = (neg ? 3 : 2) * E;
-    int grid = (int)((items + 255) / 256);
-    if (grid > 8192) grid = 8192;
+    const int grid = grid_1d(items, 8192);
     hipLaunchKernelGGL(k_xl_keys, dim3(grid), dim3(256), 0, s, a);
     // how many keys there are decides the size of the sort: ONE small read-back (the caller reads the counts back afterwards anyway)
     uint32_t n_keys = 0;
@@ -380,19 +379,13 @@ int tpnet_xplan_targeted_large(const int64_t* src, const int64_t* dst, const int
     TPNET_HIP_TRY(hipStreamSynchronize(s));
     if (n_keys > cap) return TPNET_ERR_WORKSPACE;
     if (n_keys > 0) {
-        size_t tb = tmp_bytes;
-        TPNET_HIP_TRY(rocprim::radix_sort_keys(tmp, tb, a.keys, a.sorted, (size_t)n_keys, 0u, (unsigned)(nbits + gbits + bbits + 1), s, false));
-        int g2 = (int)((n_keys + 255) / 256);
-        if (g2 > 8192) g2 = 8192;
+        TPNET_HIP_TRY(rocprim::radix_sort_keys(tmp.ptr, tmp.bytes, a.keys, a.sorted, (size_t)n_keys, 0u, (unsigned)(nbits + gbits + bbits + 1), s, false));
+        const int g2 = grid_1d(n_keys, 8192);
         hipLaunchKernelGGL(k_xl_heads, dim3(g2), dim3(256), 0, s, a, n_keys);
-        tb = tmp_bytes;
-        TPNET_HIP_TRY(rocprim::exclusive_scan(tmp, tb, a.heads, a.heads, 0u, (size_t)n_keys, rocprim::plus<uint32_t>(), s, false));
+        TPNET_HIP_TRY(rocprim::exclusive_scan(tmp.ptr, tmp.bytes, a.heads, a.heads, 0u, (size_t)n_keys, rocprim::plus<uint32_t>(), s, false));
         hipLaunchKernelGGL(k_xl_compact, dim3(g2), dim3(256), 0, s, a, n_keys);
     }
-    const int64_t nq = 2 * nb * G + 1;
-    int g3 = (int)((nq + 255) / 256);
-    if (g3 > 4096) g3 = 4096;
-    hipLaunchKernelGGL(k_xl_offsets, dim3(g3), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_xl_offsets, dim3(grid_1d(2 * nb * G + 1, 4096)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_xl_finish, dim3(grid), dim3(256), 0, s, a, n_owned, cnt, pack_ids, local_src, local_dst, local_neg);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
