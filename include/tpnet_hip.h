@@ -51,7 +51,8 @@ extern "C" {
                                     tpnet_mlp_rows_* (self.mlp on the matrix cores for num_layer 1 and 2);
                                     tpnet_mlp_rows_bwd_* (its weight gradients on the matrix cores, same widths);
                                     tpnet_decoder_f32* (LinkPredictor_v1 in the fp32 class, forward and backward);
-                                    tpnet_mlp_l4_* (self.mlp on the matrix cores for num_layer 4, forward and backward) */
+                                    tpnet_mlp_l4_* (self.mlp on the matrix cores for num_layer 4, forward and backward);
+                                    TPNET_FLAG_ROWS8 / tpnet_encoder_rows8_supported (the encoder's matrix-core calls on rows of d % 4 == 2) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -112,6 +113,13 @@ typedef struct tpnet_state {
 #define TPNET_FLAG_NO_MFMA_READOUT 256u /* tpnet_pair_gram_anchored and the encoder calls built on it: keep the vector-ALU readout where
                                        the matrix-core one applies (rows of 36..160 floats, d % 4 == 0, L = 3, K >= 4: split-bf16 operands,
                                        three pieces per value, fp32 accumulation -- fp32 class, other summation order) */
+#define TPNET_FLAG_ROWS8 512u         /* tpnet_pair_gram_anchored, tpnet_anchored_features, tpnet_encoder_gram, tpnet_encoder_features,
+                                       tpnet_host_encoder_features, tpnet_host_anchored_features: serve rows that are only 8-byte
+                                       aligned (d % 4 == 2, 38 <= d <= 158 -- the reference's default widths 110 / 130 / 150 --, L = 3,
+                                       K >= 4) on the matrix cores, every 16-byte piece of a row fetched as two 8-byte halves
+                                       (tpnet_encoder_rows8_supported).  No effect where d % 4 == 0.  With d % 4 == 2 only the
+                                       matrix-core kernels serve the call: TPNET_ERR_BAD_ARG for K < 4, L != 3, d outside 38..158,
+                                       outputs that are not 16-byte aligned, or TPNET_FLAG_NO_MFMA_READOUT beside it */
 
 const char* tpnet_strerror(int status);
 int tpnet_abi_version(void);
@@ -272,7 +280,9 @@ int tpnet_host_update(const tpnet_state* st, tpnet_stage* stage, const int64_t* 
  * zeros past its end); other shapes take tpnet_pair_gram_shared / tpnet_pair_gram.  Rows of 36..160 floats with L = 3 and
  * K >= 4 are served by the matrix cores (csrc/encoder_mfma.hip: 16 x 16 x 32 bf16 products on operands split into three bf16
  * pieces, fp32 accumulation over d inside the pipe -- no cross-lane reduction; d = 64 / 128 in whole 32-deep steps, every other
- * width with the last step masked; TPNET_FLAG_NO_MFMA_READOUT keeps the vector-ALU walk). */
+ * width with the last step masked; TPNET_FLAG_NO_MFMA_READOUT keeps the vector-ALU walk).  Rows of d % 4 == 2 floats are
+ * refused unless TPNET_FLAG_ROWS8 is set and tpnet_encoder_rows8_supported(st, n_rows, K, NULL): then the matrix cores serve
+ * them too (no vector-ALU walk exists at those widths). */
 int tpnet_pair_gram_anchored(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
                              int64_t n_rows, int32_t K, double now_time, double lambda, uint32_t flags, float* out1,
                              float* out2, void* stream);
@@ -706,7 +716,8 @@ int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, in
 
 /* The first half of tpnet_encoder_gram alone: the rows [src; other] at tile(t, 2), their anchors and their K sampled neighbours,
  * laid out in `scratch` (rounded up to 256): nodes int64[2B] | times double[2B] | a1 int64[2B] | a2 int64[2B] | neigh int64[2B][K]
- * | (rows of <= 128 floats that the matrix-core readout does not serve: the call's pairs spelled out for the generic readout) u int64[4BK] | v int64[4BK]. */
+ * | (rows of <= 128 floats that the matrix-core readout does not serve: the call's pairs spelled out for the generic readout) u int64[4BK] | v int64[4BK].
+ * (tpnet_encoder_gram / tpnet_encoder_features with TPNET_FLAG_ROWS8 on rows of d % 4 == 2 take the matrix cores and leave the pair lists out.) */
 int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src,
                        const int64_t* other, const double* t, int64_t B, int32_t K, void* scratch, size_t scratch_bytes,
                        void* stream);
@@ -720,6 +731,11 @@ int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, in
  * of csrc/anchored_feature.hip -- a class is routed only where that kernel was measured faster than the two launches
  * (profiles/encoder_wide.md: at present neither); TPNET_FLAG_NO_MFMA_READOUT selects the two launches at every width. */
 int tpnet_encoder_fused_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp);
+/* Rows that are only 8-byte aligned (d % 4 == 2): does TPNET_FLAG_ROWS8 make the matrix-core kernels serve this shape
+ * (38 <= d <= 158, L = 3, K >= 4)?  mlp == NULL: the readout alone (tpnet_pair_gram_anchored, tpnet_encoder_gram); mlp given:
+ * readout and self.mlp as ONE launch (tpnet_anchored_features and the calls built on it; gram may then be NULL).  0 for every
+ * d % 4 != 2: tpnet_pair_gram_anchored_supported / tpnet_encoder_fused_supported answer for those, and never count this flag. */
+int tpnet_encoder_rows8_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp);
 int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                             int32_t K, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram,
                             float* out, void* stream);

@@ -7,7 +7,14 @@ pairs per call) and C3's (B = 10 000), every route the build under `--tree` has 
   host_uv    get_pair_wise_feature(u, v) on host arrays, as the reference's encoder issues it (pattern recognised where served)
   wide       tpnet_anchored_features_wide on device ids, no feature buffer: the one-launch kernel for rows of 164..512 floats
              (csrc/anchored_feature.hip) whatever the default route of `anchored` is
+  rows8      `anchored` with RandomProjectionModule.rows8_readout set: rows of dim % 4 == 2 (110 / 130 / 150) on the matrix cores,
+             one launch (at dim % 4 == 0 the switch changes nothing)
+  fallback   what TPNetEmbedding.compute_node_temporal_embeddings does where the anchored call does not serve the width: the
+             u / v index lists spelled out with torch on the device, the general pair kernel, self.mlp as the torch layers
+  tpnet_off / tpnet_on   one encoder-level batch: tpnet_amd.TPNet.compute_src_dst_node_temporal_embeddings (device sampler, raw
+             features of 172 / 172 floats, time encoding of 100, two mixers) with rows8_readout off / on
 
+    tools/encoder_width_rate.py --dim 110 112 --routes rows8 fallback dev_uv anchored tpnet_off tpnet_on --shapes C2
     tools/encoder_width_rate.py --dim 120 128 140 160 [--shapes C2 C3] [--reps 11] [--inner 10] [--tree OTHER_CHECKOUT] [--json OUT]
 
 One repeat = HIP events around `inner` calls, then a synchronise; per (shape, width, route) the median and the range over the
@@ -81,17 +88,44 @@ for cfg in args.shapes:
                 "anchored_features_wide")
             return out
 
+        def switched(fn, rp=rp):
+            def call():
+                rp.rows8_readout = True
+                try:
+                    return fn()
+                finally:
+                    rp.rows8_readout = False
+            return call
+
+        def fallback(rp=rp):
+            uu = neigh_d.reshape(-1).repeat(2)
+            vv = torch.cat([a1_d.repeat_interleave(K), a2_d.repeat_interleave(K)])
+            return rp.mlp(rp.pair_gram(uu, vv))
+
+        def tpnet_batch(rp=rp, model=[]):
+            if not model:
+                from tpnet_amd.sampler import GpuRecentNeighborSampler
+                g = np.random.RandomState(d)
+                model.append(tpnet_amd.TPNet(node_raw_features=g.randn(N, 172).astype(np.float32),
+                                             edge_raw_features=g.randn(E + 1, 172).astype(np.float32),
+                                             neighbor_sampler=GpuRecentNeighborSampler(src, dst, t, device="cuda:0", num_nodes=N),
+                                             time_feat_dim=100, dropout=0.1, random_projections=rp, num_layers=2, num_neighbors=K,
+                                             device="cuda:0").to(dev).eval())
+            es, ed = model[0].compute_src_dst_node_temporal_embeddings(src[-B:], dst[-B:], t[-B:])
+            return torch.cat([es, ed])
+
         routes = {"anchored": lambda rp=rp: rp.get_pair_wise_feature_anchored(neigh_d, a1_d, a2_d),
                   "dev_uv": lambda rp=rp: rp.get_pair_wise_feature(u_d, v_d),
-                  "host_uv": lambda rp=rp: rp.get_pair_wise_feature(u, v), "wide": wide}
-        ref = None
+                  "host_uv": lambda rp=rp: rp.get_pair_wise_feature(u, v), "wide": wide,
+                  "rows8": switched(lambda rp=rp: rp.get_pair_wise_feature_anchored(neigh_d, a1_d, a2_d)),
+                  "fallback": fallback, "tpnet_off": tpnet_batch, "tpnet_on": switched(tpnet_batch)}
+        refs = {}                                                   # (pair features; the tpnet_* routes: embeddings)
         for name in args.routes:
             try:
                 with torch.no_grad():
                     y = routes[name]()                              # warm-up (and: does the build have this route here?)
                     torch.cuda.synchronize()
-                    if ref is None:
-                        ref = y
+                    ref = refs.setdefault(name.startswith("tpnet"), y)
                     checks[(d, name)] = float((y - ref).abs().max() / ref.abs().max())
                 calls[(d, name)] = routes[name]
             except Exception as e:                                  # noqa: BLE001

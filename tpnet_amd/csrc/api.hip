@@ -402,6 +402,11 @@ int tpnet_pair_gram_anchored(const tpnet_state* st, const int64_t* neigh, const 
     if (rc) return rc;
     if (n_rows < 0 || K < 0 || (n_rows > 0 && K > 0 && (!neigh || !a1 || !a2 || !out1 || !out2))) return TPNET_ERR_BAD_ARG;
     if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;
+    if (n_rows > 0 && K > 0 && rows8_asked(*st, flags)) {
+        // rows of d % 4 == 2 with TPNET_FLAG_ROWS8: the matrix cores (8-byte loads) or nothing -- no vector-ALU walk reads such rows
+        if (!encoder_mfma_supported(*st, n_rows, K, flags)) return TPNET_ERR_BAD_ARG;
+        return launch_encoder_gram_mfma(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
+    }
     if (n_rows > 0 && K > 0 && !pair_gram_anchored_supported(*st)) {
         // rows that are not whole 16-byte vectors (d % 4 != 0: 110, 130, 150 ...), narrower than 36 or wider than 512 floats: the
         // generic kernel, one launch per anchor side, on index arrays the caller would otherwise build -- not available without

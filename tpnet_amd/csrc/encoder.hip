@@ -26,6 +26,12 @@ int tpnet_encoder_fused_supported(const tpnet_state* st, int64_t n_rows, int32_t
     return (encoder_fused_supported(*st, n_rows, K, mlp) || encoder_wide_routed(*st, n_rows, K, mlp)) ? 1 : 0;
 }
 
+int tpnet_encoder_rows8_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp) {
+    if (!st || !st->p0 || !st->q || !st->meta || st->N < 1 || st->d < 1 || st->d % 4 != 2) return 0;
+    if (!mlp) return encoder_mfma_supported(*st, n_rows, K, TPNET_FLAG_ROWS8) ? 1 : 0;
+    return encoder_fused_supported(*st, n_rows, K, mlp, TPNET_FLAG_ROWS8) ? 1 : 0;
+}
+
 int tpnet_encoder_wide_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp) {
     if (!st || !st->p0 || !st->q || !st->meta || st->N < 1 || st->d < 1) return 0;
     return encoder_wide_supported(*st, n_rows, K, mlp) ? 1 : 0;
@@ -49,15 +55,18 @@ int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const i
     if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;
     if (mlp->F != 64 || mlp->H != 256 || !mlp->w1 || !mlp->w2f || !mlp->b1 || !mlp->b2) return TPNET_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(gram) | reinterpret_cast<uintptr_t>(out)) & 15) return TPNET_ERR_BAD_ARG;
+    // rows of d % 4 == 2 with TPNET_FLAG_ROWS8: the matrix-core kernels (one launch, or readout + dense layers) or nothing
+    const bool r8 = rows8_asked(*st, flags);
+    if (r8 && !encoder_mfma_supported(*st, n_rows, K, flags)) return TPNET_ERR_BAD_ARG;
     // readout + dense layers in ONE launch on the matrix cores (encoder_mfma.hip); a runtime that refuses it: two launches below
-    if (!(flags & TPNET_FLAG_NO_MFMA_READOUT) && encoder_fused_supported(*st, n_rows, K, mlp) &&
+    if (!(flags & TPNET_FLAG_NO_MFMA_READOUT) && encoder_fused_supported(*st, n_rows, K, mlp, flags) &&
         launch_encoder_fused(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, mlp, gram, out, (hipStream_t)stream) == TPNET_OK)
         return TPNET_OK;
     // wide rows: the vector-ALU walk with the dense layers inside (anchored_feature.hip), where that is the class's route
     if (!(flags & TPNET_FLAG_NO_MFMA_READOUT) && encoder_wide_routed(*st, n_rows, K, mlp))
         return launch_anchored_feature(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, mlp, gram, out, (hipStream_t)stream);
     if (!gram) return TPNET_ERR_NEED_GRAM;             // (the fused launch was refused after the caller had been told it may pass NULL)
-    if (!pair_gram_anchored_supported(*st)) return TPNET_ERR_BAD_ARG;
+    if (!r8 && !pair_gram_anchored_supported(*st)) return TPNET_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t F = 64;
     const int64_t half = n_rows * (int64_t)K;                // pairs per anchor side
@@ -75,14 +84,15 @@ int tpnet_encoder_features(const tpnet_state* st, const void* sampler, int64_t E
     if (!st || !sampler || B < 0 || K < 1 || (B > 0 && (!src || !other || !t || !scratch || !out || !mlp)))
         return TPNET_ERR_BAD_ARG;
     if (B == 0) return TPNET_OK;
+    if (rows8_asked(*st, flags) && !encoder_mfma_supported(*st, 2 * B, K, flags)) return TPNET_ERR_BAD_ARG;
     // rows + neighbours exactly as tpnet_encoder_gram lays them out in `scratch`
-    int rc = tpnet_encoder_rows(st, sampler, E, num_nodes, src, other, t, B, K, scratch, scratch_bytes, stream);
+    int rc = encoder_rows(st, sampler, E, num_nodes, src, other, t, B, K, flags, scratch, scratch_bytes, stream);
     if (rc) return rc;
     int64_t* nodes = (int64_t*)(((size_t)scratch + 255) / 256 * 256);
     int64_t* a1 = nodes + 4 * B;
     int64_t* a2 = a1 + 2 * B;
     int64_t* neigh = a2 + 2 * B;
-    if (gram && encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K) && st->L == 3 && !(flags & TPNET_FLAG_PACKED) && mlp->F == 64 && mlp->H == 256 && mlp->w1 &&
+    if (gram && encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K, flags) && st->L == 3 && !(flags & TPNET_FLAG_PACKED) && mlp->F == 64 && mlp->H == 256 && mlp->w1 &&
         mlp->w2f && mlp->b1 && mlp->b2 && !((reinterpret_cast<uintptr_t>(gram) | reinterpret_cast<uintptr_t>(out)) & 15)) {
         // narrow rows: the generic readout on the pair lists the sampler kernel wrote behind the neighbour ids, then the dense layers
         const int64_t half = 2 * B * (int64_t)K;

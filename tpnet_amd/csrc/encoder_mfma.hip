@@ -21,6 +21,8 @@
 // Row widths: d % 4 == 0, 36 <= d <= 160, in KS = ceil(d / 32) steps.  d = 64 / 128 fill their steps (FULL); every other width --
 // the reference's default rule gives 120 / 140 / 160 (models/TPNet.py:30-33) -- runs its last step with the pieces past the row's
 // end supplied as zeros (load_rows); nothing behind the accumulators depends on d.
+// Rows that are only 8-byte aligned (d % 4 == 2, 38 <= d <= 158: the default rule's 110 / 130 / 150), behind TPNET_FLAG_ROWS8: the
+// same kernels with every 16-byte piece fetched as two 8-byte halves (R8 below), a half past the row's end supplied as zeros.
 #include "device_common.hpp"
 #include "mfma_split.hpp"
 
@@ -71,15 +73,38 @@ __device__ unsigned long long g_em_stamps[4096 * 64];
 // FULL: a row is exactly 32 KS floats.  !FULL: a row is d floats, 32 (KS - 1) < d <= 32 KS, d % 4 == 0: a piece is loaded only if
 // it lies inside the row (`left` = d - 4 p, the floats from the lane's first piece to the row's end) and is zero otherwise -- a
 // zero k-position adds exactly 0 to every product, and what follows a row in memory (the next node's row) is never read.
-template <int KS, bool FULL>
+// R8 (with !FULL): d % 4 == 2 -- a row starts at 0 or 8 mod 16 bytes, by the parity of its index, so a piece is only 8-byte
+// aligned and is fetched as two 8-byte halves; d - 4 p is even, not a multiple of 4: a row ends with a HALF piece, and each half is
+// loaded only if it lies inside the row (`left` compared in steps of 2 floats), zero otherwise -- the same guarantee as above.
+template <int KS, bool FULL, bool R8 = false>
 __device__ __forceinline__ void load_rows(const float* __restrict__ rp, int left, float (&raw)[KS][8]) {
+    static_assert(!(FULL && R8), "load_rows: a full row is a row of whole 16-byte pieces");
+    // R8: the second halves through a pointer the compiler cannot relate to `rp` -- where both halves of a piece are loaded
+    // unconditionally it would otherwise fuse them into ONE 16-byte load of an address that is only 8-byte aligned
+    // (the OFFSET is what is hidden: the pointer keeps its provenance, the loads stay global loads)
+    int two = 2;
+    if constexpr (R8) asm volatile("" : "+v"(two));
+    const float* rp2 = rp + two;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
-        float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-        if (FULL || 32 * s + 4 <= left) x = *reinterpret_cast<const float4*>(rp + 32 * s);
-        if (FULL || 32 * s + 20 <= left) y = *reinterpret_cast<const float4*>(rp + 32 * s + 16);
-        raw[s][0] = x.x; raw[s][1] = x.y; raw[s][2] = x.z; raw[s][3] = x.w;
-        raw[s][4] = y.x; raw[s][5] = y.y; raw[s][6] = y.z; raw[s][7] = y.w;
+        if constexpr (R8) {
+            float2 h[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {          // halves at floats 32 s + {0, 2, 16, 18} of the lane's pointer
+                const int o = 32 * s + 16 * (k >> 1) + 2 * (k & 1);
+                h[k] = make_float2(0.f, 0.f);
+                // (d > 32 (KS - 1): every step but the last lies inside the row for every lane -- 4 lane masks to keep, not 4 KS)
+                if (s + 1 < KS || o + 2 <= left) h[k] = *reinterpret_cast<const float2*>((k & 1) ? rp2 + (o - 2) : rp + o);
+            }
+            raw[s][0] = h[0].x; raw[s][1] = h[0].y; raw[s][2] = h[1].x; raw[s][3] = h[1].y;
+            raw[s][4] = h[2].x; raw[s][5] = h[2].y; raw[s][6] = h[3].x; raw[s][7] = h[3].y;
+        } else {
+            float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
+            if (FULL || 32 * s + 4 <= left) x = *reinterpret_cast<const float4*>(rp + 32 * s);
+            if (FULL || 32 * s + 20 <= left) y = *reinterpret_cast<const float4*>(rp + 32 * s + 16);
+            raw[s][0] = x.x; raw[s][1] = x.y; raw[s][2] = x.z; raw[s][3] = x.w;
+            raw[s][4] = y.x; raw[s][5] = y.y; raw[s][6] = y.z; raw[s][7] = y.w;
+        }
     }
 }
 
@@ -110,7 +135,7 @@ __device__ __forceinline__ void to_operands(const float (&raw)[KS][8], float rs,
 // in one of two LDS tiles for the consumer wave (sync[0] = tiles published, sync[1] = tiles taken, sync[2 + 2 b] / [3 + 2 b] =
 // first slot / validity of the tile in buffer b) and are stored only if out1 is given.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int KS, bool FULL, int SPLIT, bool HANDOFF>
+template <int KS, bool FULL, int SPLIT, bool HANDOFF, bool R8 = false>
 __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* __restrict__ neigh, const int64_t* __restrict__ a1,
                                            const int64_t* __restrict__ a2, int n_rows, int K, int T, int slot_begin, int slot_end,
                                            double now, double lambda, uint32_t flags, float* __restrict__ out1,
@@ -177,14 +202,14 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
         auto issue_tile = [&](int t) {             // rows of tile t of the group (load layout: neighbour g of the tile)
             const int sl = 4 * t + g;
             const int wv = __shfl(w, sl), cp = __shfl(mv.copy, sl);
-            load_rows<KS, FULL>(row_ptr(wv, cp, l_layer), left, raw);
+            load_rows<KS, FULL, R8>(row_ptr(wv, cp, l_layer), left, raw);
         };
         auto issue_anchors = [&](int n0) {         // the 16 anchor rows of nodes n0, n0 + 1 (load layout: anchor index g)
             int al = 2 * (n0 - nfirst) + g;        // lane that holds anchor (n0 + (g >> 1), side g & 1)
             al = al > 63 ? 63 : al;
             const int id = __shfl(aid, al), cp = __shfl(am.copy, al);
             pre_g = __shfl(am.g, al);
-            load_rows<KS, FULL>(row_ptr(id, cp, l_layer), left, ra);
+            load_rows<KS, FULL, R8>(row_ptr(id, cp, l_layer), left, ra);
             pre_n0 = n0;
         };
         issue_tile(0);
@@ -335,7 +360,8 @@ __device__ __forceinline__ int walk_tiles(const tpnet_state& S, const int64_t* _
 
 // out1 / out2: the pre-mlp features of the two anchor sides, rows [slot][64]
 // (SPLIT = 3: the pieces per operand; part of the kernels' names in the profiles)
-template <int KS, bool FULL, int SPLIT>
+// (R8: rows of d % 4 == 2 floats -- the kernels' names say so: k_encoder_gram_mfma<KS, false, 3, true>)
+template <int KS, bool FULL, int SPLIT, bool R8 = false>
 __global__ __launch_bounds__(EMB) void k_encoder_gram_mfma(tpnet_state S, const int64_t* __restrict__ neigh,
                                                            const int64_t* __restrict__ a1, const int64_t* __restrict__ a2,
                                                            int n_rows, int K, int T, int tpw, double now, double lambda,
@@ -345,8 +371,8 @@ __global__ __launch_bounds__(EMB) void k_encoder_gram_mfma(tpnet_state S, const 
     const int wid = blockIdx.x * (EMB / 64) + wave;
     const int slot_begin = wid * tpw * 4;
     const int slot_end = (slot_begin + tpw * 4 < T) ? slot_begin + tpw * 4 : T;
-    (void)walk_tiles<KS, FULL, SPLIT, false>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags, out1, out2,
-                                             stg_all + wave * (8 * EM_RS), nullptr);
+    (void)walk_tiles<KS, FULL, SPLIT, false, R8>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags, out1, out2,
+                                                 stg_all + wave * (8 * EM_RS), nullptr);
 }
 
 // ReLU in ONE instruction: the signed-integer maximum of the bits and 0 (fmaxf / med3 cost a canonicalising v_max first; inline
@@ -452,7 +478,7 @@ __device__ __forceinline__ void dense_consumer(const char* smem, const float* st
 }
 
 // gram (may be null): the pre-mlp features [2][T][64]; y = self.mlp(features), rows [side * T + slot]
-template <int KS, bool FULL, int SPLIT>
+template <int KS, bool FULL, int SPLIT, bool R8 = false>
 __global__ __launch_bounds__(EMF_B) void k_encoder_fused(tpnet_state S, const int64_t* __restrict__ neigh, const int64_t* __restrict__ a1,
                                                          const int64_t* __restrict__ a2, int n_rows, int K, int T, int tpw, double now,
                                                          double lambda, uint32_t flags, float* __restrict__ gram,
@@ -491,8 +517,8 @@ __global__ __launch_bounds__(EMF_B) void k_encoder_fused(tpnet_state S, const in
     float* stg = reinterpret_cast<float*>(smem + EMF_STG + p * EMF_PP);
     int* sync = reinterpret_cast<int*>(smem + EMF_SYNC) + p * 8;
     if (wave < EMF_NP) {
-        const int done = walk_tiles<KS, FULL, SPLIT, true>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags,
-                                                           gram, gram ? gram + (int64_t)T * 64 : nullptr, stg, sync);
+        const int done = walk_tiles<KS, FULL, SPLIT, true, R8>(S, neigh, a1, a2, n_rows, K, T, slot_begin, slot_end, now, lambda, flags,
+                                                               gram, gram ? gram + (int64_t)T * 64 : nullptr, stg, sync);
         if (done == 0) __syncthreads();            // (a producer without tiles still owes the workgroup its barrier)
     } else
         dense_consumer(smem, stg, sync, (slot_end - slot_begin + 3) >> 2, T, slot_end, y);
@@ -500,17 +526,20 @@ __global__ __launch_bounds__(EMF_B) void k_encoder_fused(tpnet_state S, const in
 
 static inline int encoder_steps(int d) { return (d + 31) / 32; }      // KS: 32-deep steps of a row of d floats
 
-bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K) {
+bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K, uint32_t flags) {
     static const int off = TPNET_DEV_INT(NO_ENCODER_MFMA, 0);
-    // rows of whole 16-byte vectors, 2..5 steps of 32: d = 64 / 128 unmasked, every other width with a masked last step
-    return !off && st.L == 3 && st.d % 4 == 0 && st.d >= 36 && st.d <= 160 && K >= 4 && st.N < (int64_t)1 << 31 && n_rows > 0 &&
+    // rows of whole 16-byte vectors, 2..5 steps of 32: d = 64 / 128 unmasked, every other width with a masked last step; rows of
+    // d % 4 == 2 floats (8-byte aligned) in the same steps, only where the caller asks (TPNET_FLAG_ROWS8) and does not take it back
+    const bool rows16 = st.d % 4 == 0 && st.d >= 36 && st.d <= 160;
+    const bool rows8 = st.d % 4 == 2 && st.d >= 38 && st.d <= 158 && (flags & TPNET_FLAG_ROWS8) && !(flags & TPNET_FLAG_NO_MFMA_READOUT);
+    return !off && st.L == 3 && (rows16 || rows8) && K >= 4 && st.N < (int64_t)1 << 31 && n_rows > 0 &&
            n_rows * (int64_t)K < ((int64_t)1 << 31) / 64;
 }
 
 int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                              int K, double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s) {
     if (n_rows == 0 || K == 0) return TPNET_OK;
-    if (!encoder_mfma_supported(st, n_rows, K) || (flags & TPNET_FLAG_PACKED)) return TPNET_ERR_BAD_ARG;
+    if (!encoder_mfma_supported(st, n_rows, K, flags) || (flags & TPNET_FLAG_PACKED)) return TPNET_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15) return TPNET_ERR_BAD_ARG;
     const int T = (int)(n_rows * K);
     const int ntiles = (T + 3) / 4;
@@ -520,17 +549,24 @@ int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const 
     if (tpw < 2) tpw = 2;
     const int nwaves = (ntiles + tpw - 1) / tpw;
     const int grid = (nwaves + EMB / 64 - 1) / (EMB / 64);
-#define TPNET_EM_LAUNCH(KS_, FULL_)                                                                                             \
-    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, FULL_, 3>), dim3(grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+#define TPNET_EM_LAUNCH(KS_, FULL_, R8_)                                                                                             \
+    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, FULL_, 3, R8_>), dim3(grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
                        tpw, now, lambda, flags, out1, out2)
-    if (st.d == 128) TPNET_EM_LAUNCH(4, true);
-    else if (st.d == 64) TPNET_EM_LAUNCH(2, true);
-    else
+    if (st.d == 128) TPNET_EM_LAUNCH(4, true, false);
+    else if (st.d == 64) TPNET_EM_LAUNCH(2, true, false);
+    else if (st.d % 4 == 0)
         switch (encoder_steps(st.d)) {
-            case 2: TPNET_EM_LAUNCH(2, false); break;
-            case 3: TPNET_EM_LAUNCH(3, false); break;
-            case 4: TPNET_EM_LAUNCH(4, false); break;
-            default: TPNET_EM_LAUNCH(5, false); break;
+            case 2: TPNET_EM_LAUNCH(2, false, false); break;
+            case 3: TPNET_EM_LAUNCH(3, false, false); break;
+            case 4: TPNET_EM_LAUNCH(4, false, false); break;
+            default: TPNET_EM_LAUNCH(5, false, false); break;
+        }
+    else
+        switch (encoder_steps(st.d)) {                 // d % 4 == 2 (encoder_mfma_supported): 8-byte halves
+            case 2: TPNET_EM_LAUNCH(2, false, true); break;
+            case 3: TPNET_EM_LAUNCH(3, false, true); break;
+            case 4: TPNET_EM_LAUNCH(4, false, true); break;
+            default: TPNET_EM_LAUNCH(5, false, true); break;
         }
 #undef TPNET_EM_LAUNCH
     TPNET_HIP_TRY(hipGetLastError());
@@ -547,18 +583,22 @@ static bool encoder_fused_available() {
                                       reinterpret_cast<const void*>(k_encoder_fused<2, false, 3>),
                                       reinterpret_cast<const void*>(k_encoder_fused<3, false, 3>),
                                       reinterpret_cast<const void*>(k_encoder_fused<4, false, 3>),
-                                      reinterpret_cast<const void*>(k_encoder_fused<5, false, 3>)},
+                                      reinterpret_cast<const void*>(k_encoder_fused<5, false, 3>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<2, false, 3, true>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<3, false, 3, true>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<4, false, 3, true>),
+                                      reinterpret_cast<const void*>(k_encoder_fused<5, false, 3, true>)},
                                      EMF_LDS, off != 0);
 }
 
-bool encoder_fused_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp) {
-    return mlp && mlp->wimg && mlp->F == 64 && mlp->H == 256 && encoder_mfma_supported(st, n_rows, K) && encoder_fused_available();
+bool encoder_fused_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp, uint32_t flags) {
+    return mlp && mlp->wimg && mlp->F == 64 && mlp->H == 256 && encoder_mfma_supported(st, n_rows, K, flags) && encoder_fused_available();
 }
 
 int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows, int K,
                          double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram, float* out, hipStream_t s) {
     if (n_rows == 0 || K == 0) return TPNET_OK;
-    if (!encoder_fused_supported(st, n_rows, K, mlp) || (flags & TPNET_FLAG_PACKED)) return TPNET_ERR_BAD_ARG;
+    if (!encoder_fused_supported(st, n_rows, K, mlp, flags) || (flags & TPNET_FLAG_PACKED)) return TPNET_ERR_BAD_ARG;
     if ((reinterpret_cast<uintptr_t>(gram) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(mlp->wimg)) & 15)
         return TPNET_ERR_BAD_ARG;
     const int T = (int)(n_rows * K);
@@ -569,17 +609,24 @@ int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int6
     if (tpw < 2) tpw = 2;
     const int nprod = (ntiles + tpw - 1) / tpw;
     const int grid = (nprod + EMF_NP - 1) / EMF_NP;
-#define TPNET_EMF_LAUNCH(KS_, FULL_)                                                                                              \
-    hipLaunchKernelGGL((k_encoder_fused<KS_, FULL_, 3>), dim3(grid), dim3(EMF_B), EMF_LDS, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+#define TPNET_EMF_LAUNCH(KS_, FULL_, R8_)                                                                                              \
+    hipLaunchKernelGGL((k_encoder_fused<KS_, FULL_, 3, R8_>), dim3(grid), dim3(EMF_B), EMF_LDS, s, st, neigh, a1, a2, (int)n_rows, K, T, \
                        tpw, now, lambda, flags, gram, reinterpret_cast<const float4*>(mlp->wimg), out)
-    if (st.d == 128) TPNET_EMF_LAUNCH(4, true);
-    else if (st.d == 64) TPNET_EMF_LAUNCH(2, true);
-    else
+    if (st.d == 128) TPNET_EMF_LAUNCH(4, true, false);
+    else if (st.d == 64) TPNET_EMF_LAUNCH(2, true, false);
+    else if (st.d % 4 == 0)
         switch (encoder_steps(st.d)) {
-            case 2: TPNET_EMF_LAUNCH(2, false); break;
-            case 3: TPNET_EMF_LAUNCH(3, false); break;
-            case 4: TPNET_EMF_LAUNCH(4, false); break;
-            default: TPNET_EMF_LAUNCH(5, false); break;
+            case 2: TPNET_EMF_LAUNCH(2, false, false); break;
+            case 3: TPNET_EMF_LAUNCH(3, false, false); break;
+            case 4: TPNET_EMF_LAUNCH(4, false, false); break;
+            default: TPNET_EMF_LAUNCH(5, false, false); break;
+        }
+    else
+        switch (encoder_steps(st.d)) {                 // d % 4 == 2 (encoder_mfma_supported): 8-byte halves
+            case 2: TPNET_EMF_LAUNCH(2, false, true); break;
+            case 3: TPNET_EMF_LAUNCH(3, false, true); break;
+            case 4: TPNET_EMF_LAUNCH(4, false, true); break;
+            default: TPNET_EMF_LAUNCH(5, false, true); break;
         }
 #undef TPNET_EMF_LAUNCH
     if (hipGetLastError() != hipSuccess) {             // (a runtime that refuses the launch: the callers fall back for good)

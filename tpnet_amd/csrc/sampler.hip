@@ -412,6 +412,14 @@ size_t tpnet_encoder_scratch_bytes(int64_t B, int32_t K) {
 int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src,
                        const int64_t* other, const double* t, int64_t B, int32_t K, void* scratch, size_t scratch_bytes,
                        void* stream) {
+    return encoder_rows(st, sampler, E, num_nodes, src, other, t, B, K, 0, scratch, scratch_bytes, stream);
+}
+
+}  // extern "C"
+
+int tpnet::encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src,
+                        const int64_t* other, const double* t, int64_t B, int32_t K, uint32_t flags, void* scratch,
+                        size_t scratch_bytes, void* stream) {
     if (!st || !sampler || B < 0 || K < 1 || num_nodes < 1 || (B > 0 && (!src || !other || !t || !scratch))) return TPNET_ERR_BAD_ARG;
     if (B == 0) return TPNET_OK;
     if (scratch_bytes < tpnet_encoder_scratch_bytes(B, K)) return TPNET_ERR_WORKSPACE;
@@ -428,12 +436,14 @@ int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, in
     }
     SamplerView v = csr_view(sampler, E, num_nodes);
     const int grid = grid_1d(2 * B * (int64_t)K, 8192);
-    int64_t* pu = (encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K)) ? neigh + 2 * B * (int64_t)K : nullptr;
+    int64_t* pu = (encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K, flags)) ? neigh + 2 * B * (int64_t)K : nullptr;
     hipLaunchKernelGGL(k_encoder_sample, dim3(grid), dim3(256), 0, s, v.row_start, v.nbr, v.nbr_t, num_nodes, src, other, t, B, (int)K,
                        nodes, t2, a1, a2, neigh, pu, pu ? pu + 4 * B * (int64_t)K : nullptr);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }
+
+extern "C" {
 
 int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src,
                        const int64_t* other, const double* t, int64_t B, int32_t K, double now_time, double lambda,
@@ -441,15 +451,17 @@ int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, in
     if (!st || !out) return TPNET_ERR_BAD_ARG;
     if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;
     if (B == 0) return TPNET_OK;
-    if (!tpnet_pair_gram_anchored_supported(st)) return TPNET_ERR_BAD_ARG;
-    int rc = tpnet_encoder_rows(st, sampler, E, num_nodes, src, other, t, B, K, scratch, scratch_bytes, stream);
+    if (check_state(st)) return TPNET_ERR_BAD_ARG;
+    // rows of d % 4 == 2 with TPNET_FLAG_ROWS8: the matrix-core readout or nothing
+    if (rows8_asked(*st, flags) ? !encoder_mfma_supported(*st, 2 * B, K, flags) : !pair_gram_anchored_supported(*st)) return TPNET_ERR_BAD_ARG;
+    int rc = encoder_rows(st, sampler, E, num_nodes, src, other, t, B, K, flags, scratch, scratch_bytes, stream);
     if (rc) return rc;
     int64_t* nodes = (int64_t*)align256((size_t)scratch);
     int64_t* a1 = nodes + 4 * B;
     int64_t* a2 = a1 + 2 * B;
     int64_t* neigh = a2 + 2 * B;
     const int NN = 2 * st->L + 2;
-    if (encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K)) {
+    if (encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K, flags)) {
         const int64_t half = 2 * B * (int64_t)K;
         return tpnet_pair_gram(st, neigh + half, neigh + 3 * half, 2 * half, now_time, lambda, flags, out, stream);
     }

@@ -162,12 +162,15 @@ bool pair_gram_anchored_supported(const tpnet_state& st);
 int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
                               int64_t n_rows, int K, double now, double lambda, uint32_t flags, float* out1, float* out2,
                               hipStream_t s);
-// encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 36..160 floats (d % 4 == 0), L = 3, K >= 4
-bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K);
+// encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 36..160 floats (d % 4 == 0), L = 3, K >= 4;
+// with TPNET_FLAG_ROWS8 (and without TPNET_FLAG_NO_MFMA_READOUT) in `flags` also for rows of 38..158 floats with d % 4 == 2, which no
+// other anchored kernel reads: rows8_asked = the flag on such a row -- served there, or the call is refused
+bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K, uint32_t flags = 0);
+inline bool rows8_asked(const tpnet_state& st, uint32_t flags) { return (flags & TPNET_FLAG_ROWS8) && st.d % 4 == 2; }
 int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                              int K, double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s);
 // the same + self.mlp in ONE launch (gram: optional copy of the pre-mlp features [2][n_rows * K][64]; out [2 * n_rows * K][64])
-bool encoder_fused_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp);
+bool encoder_fused_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp, uint32_t flags = 0);
 int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows, int K,
                          double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram, float* out, hipStream_t s);
 // anchored_feature.hip: the vector-ALU anchored walk + self.mlp in ONE launch for rows of 164..512 floats (d % 4 == 0), L = 3,
@@ -233,6 +236,10 @@ struct LdsOptIn {
 // the plan of ONE batch by one workgroup (plan.hip, k_plan_one): same Plan contents as plan_build for batch 0 of a chunk
 static constexpr int64_t PLAN_ONE_MAX = 2048;
 bool encoder_generic_readout(const tpnet_state& st);   // sampler.hip: the encoder's calls on rows of <= 128 floats
+// sampler.hip: tpnet_encoder_rows for a readout that runs with `flags` (the spelled-out pair lists are written only where the
+// generic readout will take the call: not where TPNET_FLAG_ROWS8 sends it to the matrix cores)
+int encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src, const int64_t* other,
+                 const double* t, int64_t B, int32_t K, uint32_t flags, void* scratch, size_t scratch_bytes, void* stream);
 int64_t plan_one_max_batch();      // PLAN_ONE_MAX (0 with the developer override TPNET_DEV_NO_PLAN_ONE)
 int plan_one(const tpnet_state& st, const Plan& p, const int64_t* src, const int64_t* dst, const double* t, int64_t B,
              double now_time, double lambda, uint32_t flags, hipStream_t s);

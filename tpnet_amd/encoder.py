@@ -175,7 +175,11 @@ class TPNetEmbedding(nn.Module):
         rp = self.random_projections
         if rp is not None:
             # TPNet.py:313-316, [2 n K, F]: every neighbour against the row's two anchors
-            if dev.type == "cuda" and hasattr(rp, "get_pair_wise_feature_anchored") and rp.dim % 4 == 0 and 36 <= rp.dim <= 512:
+            # (the module says which widths its anchored call serves: dim % 4 == 0 in 36..512, and with its `rows8_readout` set the
+            # default rule's 110 / 130 / 150)
+            if dev.type == "cuda" and hasattr(rp, "get_pair_wise_feature_anchored") and (
+                    rp.anchored_call_served(neigh.shape[0], K) if hasattr(rp, "anchored_call_served")
+                    else rp.dim % 4 == 0 and 36 <= rp.dim <= 512):
                 feats = rp.get_pair_wise_feature_anchored(neigh, src_node_ids, dst_node_ids)
             else:
                 # row widths the anchored readout does not serve (or another module): the general pair readout, then self.mlp as

@@ -818,7 +818,8 @@ class RandomProjectionModule(nn.Module):
         if _ff.needs_grad(prep.params):
             return _ff.apply_with_grad(self.mlp, launch, n, NG)
         gram = None
-        if rows_k is not None and not _lib.load().tpnet_encoder_fused_supported(self._st_ref(), rows_k[0], rows_k[1], prep.ref):
+        if rows_k is not None and not (_lib.load().tpnet_encoder_fused_supported(self._st_ref(), rows_k[0], rows_k[1], prep.ref)
+                                       or self._rows8(rows_k[0], rows_k[1], prep.ref)):
             gram = torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
         try:
             return launch(gram)
@@ -837,10 +838,10 @@ class RandomProjectionModule(nn.Module):
             return out
         return launch
 
-    def _anchored_launch(self, wd, a1, a2, rows, K, prep):
+    def _anchored_launch(self, wd, a1, a2, rows, K, prep, rows8=0):
         """The launch (for _feature_call) of tpnet_anchored_features: `rows` x K neighbour ids `wd` and two anchors per row, all on
-        the device -> [2 * rows * K, (2L+2)^2] features, self.mlp applied."""
-        lib, flags, dev = _lib.load(), self._readout_flags(), self._eng["dev"]
+        the device -> [2 * rows * K, (2L+2)^2] features, self.mlp applied.  `rows8`: what _rows8 said for this call."""
+        lib, flags, dev = _lib.load(), self._readout_flags() | rows8, self._eng["dev"]
 
         def launch(gram):
             out = torch.empty((2 * rows * K, self.pair_wise_feature_dim), dtype=torch.float32, device=dev)
@@ -863,7 +864,10 @@ class RandomProjectionModule(nn.Module):
             return None
         self._ensure_engine()
         lib = _lib.load()
-        if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
+        anchored = bool(lib.tpnet_pair_gram_anchored_supported(self._st_ref()))
+        # (rows of dim % 4 == 2 with `rows8_readout`: the pattern's K is the C call's to find -- it declines what the flag does not serve)
+        rows8 = 0 if anchored else self._rows8(1, 4, prep.ref)
+        if not anchored and not rows8:
             return None
         if _ff.needs_grad(prep.params) and int(lib.tpnet_host_encoder_pattern(src.ctypes.data, dst.ctypes.data, n, self.node_num)) < 4:
             # (training: the cheap host check FIRST -- a declined call would already have allocated an n x 64 feature buffer and an
@@ -878,7 +882,7 @@ class RandomProjectionModule(nn.Module):
             if eng.get("stage_big") is None:
                 eng["stage_big"] = _Stage(lib, eng["dev"], slots=4, slot_bytes=_BIG_SLOT_BYTES)
             served = C.c_int32(0)
-            flags = self._readout_flags()
+            flags = self._readout_flags() | rows8
 
             def launch_host(gram):
                 out = torch.empty((n, self.pair_wise_feature_dim), dtype=torch.float32, device=eng["dev"])
@@ -896,8 +900,12 @@ class RandomProjectionModule(nn.Module):
         if K < 4:
             return None
         h = n // 2
+        if not anchored:
+            rows8 = self._rows8(h // K, K, prep.ref)
+            if not rows8:
+                return None
         wd, a1, a2 = self._to_device(src[:h], np.ascontiguousarray(dst[:h:K]), np.ascontiguousarray(dst[h::K]))
-        return self._feature_call(prep, n, self._anchored_launch(wd, a1, a2, h // K, K, prep), (h // K, K))
+        return self._feature_call(prep, n, self._anchored_launch(wd, a1, a2, h // K, K, prep, rows8), (h // K, K))
 
     def pair_gram_anchored(self, neighbor_ids, first_anchor_ids, second_anchor_ids, matrix_cores=True):
         """The encoder's readout before self.mlp (models/TPNet.py:311-324): neighbor_ids [n, K] (the sampled neighbours of n
@@ -906,7 +914,8 @@ class RandomProjectionModule(nn.Module):
         get_pair_wise_feature(tile(neighbours, 2), concat(repeat(first, K), repeat(second, K))) pair order.  One lane group per
         row keeps both anchors' rows in registers for its K neighbours (tpnet_pair_gram_anchored).  Served: rows of whole 16-byte
         vectors, dim % 4 == 0 and 36 <= dim <= 512 (the reference's default widths 120, 140, 160 among them); rows of 36..160
-        floats with L = 3 and K >= 4 take the matrix cores (csrc/encoder_mfma.hip) unless matrix_cores=False."""
+        floats with L = 3 and K >= 4 take the matrix cores (csrc/encoder_mfma.hip) unless matrix_cores=False.  With
+        `rows8_readout` set, rows of dim % 4 == 2 (38 <= dim <= 158, L = 3, K >= 4) are served too, on the matrix cores only."""
         self._ensure_engine()
         nb = neighbor_ids if isinstance(neighbor_ids, torch.Tensor) else np.asarray(neighbor_ids)
         if nb.ndim != 2:
@@ -916,18 +925,45 @@ class RandomProjectionModule(nn.Module):
         if len(first_anchor_ids) != n or len(second_anchor_ids) != n:
             raise ValueError("one first and one second anchor per row of neighbor_ids")
         lib = _lib.load()
+        rows8 = 0
         if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
-            raise _lib.TPNetHipError(f"pair_gram_anchored needs dim % 4 == 0 and 36 <= dim <= 512, not {self.dim}: "
-                                     "use pair_gram_shared")
+            rows8 = self._rows8(n, K) if matrix_cores else 0
+            if not rows8:
+                raise _lib.TPNetHipError(f"pair_gram_anchored needs dim % 4 == 0 and 36 <= dim <= 512, not {self.dim}: "
+                                         "use pair_gram_shared")
         wd = self._to_device(self._ids(w, "neighbor_ids"))[0]
         a1, a2 = self._to_device(self._ids(first_anchor_ids, "first_anchor_ids"),
                                  self._ids(second_anchor_ids, "second_anchor_ids"))
         out = torch.empty((2, n * K, self.pair_wise_feature_dim), dtype=torch.float32, device=self._dev())
-        flags = self._readout_flags(matrix_cores=matrix_cores)
+        flags = self._readout_flags(matrix_cores=matrix_cores) | rows8
         _lib.check(lib.tpnet_pair_gram_anchored(self._st_ref(), wd.data_ptr(), a1.data_ptr(), a2.data_ptr(), n, K,
                                                 self._now_host, float(self.time_decay_weight), flags, out[0].data_ptr(),
                                                 out[1].data_ptr(), self._stream()), "pair_gram_anchored")
         return out
+
+    # extension, opt-in: rows that are only 8-byte aligned -- dim % 4 == 2, 38 <= dim <= 158: the default rule's 110 / 130 / 150
+    # (models/TPNet.py:30-33) -- take the encoder's readout on the matrix cores and readout + self.mlp as one launch, L = 3 and
+    # K >= 4 (TPNET_FLAG_ROWS8, csrc/encoder_mfma.hip; profiles/encoder_even_widths.md).  False: at these widths the encoder's calls keep
+    # the general pair kernel and the torch layers, bit for bit.  `update`, pair_gram and the decoder-level readouts run on the
+    # scalar geometry at these widths either way
+    rows8_readout = False
+
+    def _rows8(self, rows, K, mlp_ref=None) -> int:
+        """_lib.FLAG_ROWS8 if `rows8_readout` is set and tpnet_encoder_rows8_supported answers 1 for `rows` x K neighbours (with
+        `mlp_ref`: for readout + self.mlp in one launch), else 0."""
+        if not self.rows8_readout or self.dim % 4 != 2:
+            return 0
+        return _lib.FLAG_ROWS8 if _lib.load().tpnet_encoder_rows8_supported(self._st_ref(), rows, K, mlp_ref) else 0
+
+    def anchored_call_served(self, rows, K) -> bool:
+        """Whether get_pair_wise_feature_anchored serves `rows` x K neighbours at this module's width: dim % 4 == 0 and
+        36 <= dim <= 512, or -- `rows8_readout` -- what tpnet_encoder_rows8_supported accepts."""
+        if self.dim % 4 == 0 and 36 <= self.dim <= 512:
+            return True
+        if not self.rows8_readout or self._plist()[0].device.type != "cuda":
+            return False
+        self._ensure_engine()
+        return bool(self._rows8(rows, K))
 
     def _overlapped_mlp(self):
         """The prepared fp32 weights of self.mlp if the encoder's one-call path applies (readout chunks and their dense layers side
@@ -942,17 +978,19 @@ class RandomProjectionModule(nn.Module):
         reference's row order, self.mlp applied.  Needs what pair_gram_anchored needs (dim % 4 == 0, 36 <= dim <= 512).  Device
         ids, L = 3, K >= 4: one launch on rows of 36..160 floats (csrc/encoder_mfma.hip); on rows of 164..512 floats one launch
         (csrc/anchored_feature.hip) where that kernel is the route of the width's geometry class, else the anchored walk and the
-        dense layers as two launches (tpnet_encoder_fused_supported tells which)."""
+        dense layers as two launches (tpnet_encoder_fused_supported tells which).  With `rows8_readout` set, rows of
+        dim % 4 == 2 (38 <= dim <= 158) take the same one launch (tpnet_encoder_rows8_supported)."""
         prep = self._overlapped_mlp() if self._plist()[0].device.type == "cuda" else None
         if prep is not None and isinstance(neighbor_ids, torch.Tensor) and neighbor_ids.is_cuda:
             self._ensure_engine()
             lib = _lib.load()
-            if lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
-                n, K = neighbor_ids.shape
+            n, K = neighbor_ids.shape
+            rows8 = 0
+            if lib.tpnet_pair_gram_anchored_supported(self._st_ref()) or (rows8 := self._rows8(n, K, prep.ref)):
                 wd = self._ids(neighbor_ids.reshape(-1), "neighbor_ids")
                 a1, a2 = self._to_device(self._ids(first_anchor_ids, "first_anchor_ids"),
                                          self._ids(second_anchor_ids, "second_anchor_ids"))
-                return self._feature_call(prep, 2 * n * K, self._anchored_launch(wd, a1, a2, n, K, prep), (n, K))
+                return self._feature_call(prep, 2 * n * K, self._anchored_launch(wd, a1, a2, n, K, prep, rows8), (n, K))
         g = self.pair_gram_anchored(neighbor_ids, first_anchor_ids, second_anchor_ids)
         return self._apply_mlp(g.view(-1, self.pair_wise_feature_dim))
 
@@ -1003,7 +1041,10 @@ class RandomProjectionModule(nn.Module):
         off = (-scratch.data_ptr()) % 256 + 64 * B
         neigh = scratch[off: off + 16 * B * K].view(torch.int64).view(2 * B, K)
         prep = self._overlapped_mlp()
-        if prep is not None and lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
+        anchored = bool(lib.tpnet_pair_gram_anchored_supported(self._st_ref()))
+        if not anchored:
+            flags |= (prep is not None and self._rows8(2 * B, K, prep.ref)) or self._rows8(2 * B, K)
+        if prep is not None and (anchored or flags & _lib.FLAG_ROWS8):
             # ONE call, self.mlp included: the dense layers of a chunk of rows run beside the readout of the next one
             def launch(gram):
                 out = torch.empty((4 * B * K, NG), dtype=torch.float32, device=dev)
