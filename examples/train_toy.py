@@ -8,6 +8,7 @@ the reference's MLP-Mixer (out of scope): mean over the K neighbours of an MLP o
 
     python examples/train_toy.py            # needs a GPU; ~10 s
     python examples/train_toy.py --fused-decoder      # the same with LinkPredictor_v1.fused = "f32"
+    python examples/train_toy.py --device-optimizer   # the same with Adam's step in one launch (tpnet_amd.DeviceAdam)
 """
 import os, sys, time
 import numpy as np, torch
@@ -31,7 +32,10 @@ decoder = LinkPredictor_v1(input_dim1=D, input_dim2=D, hidden_dim=D, output_dim=
 if "--fused-decoder" in sys.argv[1:]:                 # opt-in: the decoder's two layers in HIP, fp32 class, forward and backward
     decoder.fused = "f32"
 params = list(enc_mlp.parameters()) + list(decoder.parameters())       # decoder.parameters() includes rp.mlp
-opt = torch.optim.Adam([p for p in params if p.requires_grad], lr=2e-3)
+Adam = torch.optim.Adam
+if "--device-optimizer" in sys.argv[1:]:              # opt-in: every tensor's Adam step in one launch, same state_dict as torch's
+    from tpnet_amd import DeviceAdam as Adam
+opt = Adam([p for p in params if p.requires_grad], lr=2e-3)
 sampler = GpuRecentNeighborSampler(src, dst, t, device=dev)
 negs = RandomNegativeSampler(src, dst)
 encoder = lambda feats, node_ids, times: enc_mlp(feats).mean(dim=1)    # [2B, K, 128] -> [2B, D]

@@ -1084,6 +1084,43 @@ int tpnet_decoder_f32_bwd(const float* src_emb, const float* dst_emb, int32_t D,
                           const float* w1, const float* b1, const float* w2, int32_t H, const float* gout, void* workspace, float* gsrc,
                           float* gdst, float* gfeat, float* partial, int32_t n_partial, void* stream);
 
+/* ---- the optimizer step on the device (additive to ABI 7; csrc/optimizer.hip) --------------------------------
+ * What utils.create_optimizer builds (utils/utils.py:61-79: Adam, SGD or RMSprop with an L2 weight_decay; no amsgrad, momentum 0, not
+ * centered) and train_link_prediction.py:386 steps once per batch, for any number of tensors per call: every
+ * tpnet_optim_max_tensors() non-empty tensors are ONE launch, a workgroup per tpnet_optim_chunk() elements of a tensor.
+ * An entry: p [n] the parameter, g [n] its gradient, s1 / s2 [n] the rule's state, c[8] the rule's scalars, which the caller forms in
+ * double and rounds once to fp32 -- so tensors of one call may be at different step counts and carry different hyperparameters:
+ *   TPNET_OPTIM_ADAM     s1 = exp_avg, s2 = exp_avg_sq;  c = { lr / (1 - beta1^t), weight_decay, beta1, 1 - beta1, beta2, 1 - beta2,
+ *                                                              sqrt(1 - beta2^t), eps }, t = the step being taken (1, 2, ...)
+ *   TPNET_OPTIM_SGD      no state (s1, s2 not looked at); c = { lr, weight_decay }
+ *   TPNET_OPTIM_RMSPROP  s1 = square_avg (s2 not looked at); c = { lr, weight_decay, alpha, 1 - alpha, eps }
+ * Per element, fp32, one rounding per operation, in exactly this order (no fused multiply-add; IEEE division and square root):
+ *   g1 = c[1] != 0 ? g + c[1] * p : g
+ *   Adam:     s1 = c[2] * s1 + c[3] * g1;  s2 = c[4] * s2 + (c[5] * g1) * g1;  p = p - c[0] * (s1 / (sqrt(s2) / c[6] + c[7]))
+ *   SGD:      p = p - c[0] * g1
+ *   RMSprop:  s1 = c[2] * s1 + (c[3] * g1) * g1;  p = p - c[0] * (g1 / (sqrt(s1) + c[4]))
+ * p, s1 and s2 are updated in place; nothing else is written.  Arrays need 4-byte alignment only: an entry whose arrays are all
+ * 16-byte aligned moves 16 bytes per load and store, any other one 4, with the same bits.  The arrays of one call must not overlap.
+ * flags and reserved are the library's (a caller's values are not looked at).  All launches go to `stream`; no copy, no
+ * synchronisation.  TPNET_ERR_BAD_ARG, before any launch: an unknown rule, count < 0, a null table with count > 0, a null p or g, a
+ * null state array that the rule reads, an array that is not 4-byte aligned, n < 0 or n > 2^41.  Entries with n == 0 are skipped. */
+#define TPNET_OPTIM_ADAM 0
+#define TPNET_OPTIM_SGD 1
+#define TPNET_OPTIM_RMSPROP 2
+typedef struct tpnet_optim_tensor {
+    float* p;
+    const float* g;
+    float* s1;
+    float* s2;
+    int64_t n;
+    float c[8];
+    uint32_t flags;
+    uint32_t reserved;
+} tpnet_optim_tensor; /* 80 bytes */
+int tpnet_optim_max_tensors(void);
+int tpnet_optim_chunk(void);
+int tpnet_optim_step(int rule, const tpnet_optim_tensor* tensors, int32_t count, void* stream);
+
 /* Copies st->err to the host (synchronises the stream): returns TPNET_ERR_INDEX if any bad id was seen since
  * the last call (and clears the words), TPNET_OK otherwise. */
 int tpnet_check_errors(const tpnet_state* st, void* stream);

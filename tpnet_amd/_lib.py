@@ -45,6 +45,15 @@ class Mlp(C.Structure):
                 ("H", C.c_int32), ("w1", C.c_void_p), ("w2f", C.c_void_p), ("wimg", C.c_void_p)]
 
 
+OPTIM_ADAM, OPTIM_SGD, OPTIM_RMSPROP = 0, 1, 2
+
+
+class OptimTensor(C.Structure):
+    """tpnet_optim_tensor: one tensor of tpnet_optim_step (include/tpnet_hip.h)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("n", C.c_int64),
+                ("c", C.c_float * 8), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/tpnet_hip.h declares (tests check this)
 _P = C.c_void_p
 _SP = C.POINTER(State)
@@ -182,6 +191,9 @@ SIGNATURES = {
     "tpnet_decoder_f32": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "tpnet_decoder_f32_bwd": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P,
                                         C.c_int32, _P]),
+    "tpnet_optim_max_tensors": (C.c_int, []),
+    "tpnet_optim_chunk": (C.c_int, []),
+    "tpnet_optim_step": (C.c_int, [C.c_int, _P, C.c_int32, _P]),
     "tpnet_mixer_supported": (C.c_int, [C.c_int32] * 4),
     "tpnet_mixer_channel_image_bytes": (C.c_size_t, [C.c_int32] * 2),
     "tpnet_mixer_channel_prepare": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P]),

@@ -13,6 +13,7 @@ G8 -- without the reference's files (they never travel to the GPU box).
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
 * `train_link_prediction_epoch` -- the same epoch with the loss, the backward and the optimizer step (:375-386), the loss and the
   per-batch loss / AP / ROC-AUC from the device meter.
+* `create_optimizer`        -- utils.create_optimizer (utils/utils.py:61-79), by default with the step on the device.
 The encoder itself is tpnet_amd/encoder.py (`TPNet`); `encoder` / `decoder` stay plug-in callables here.
 """
 from typing import Callable, Optional
@@ -322,6 +323,20 @@ def train_link_prediction_epoch(rp, neighbor_sampler, negative_sampler, src: np.
         if on_batch is not None:
             on_batch(b0 // batch_size, neg, res, loss)
     return meter.results()
+
+
+def create_optimizer(model: nn.Module, optimizer_name: str, learning_rate: float, weight_decay: float = 0.0, device_step: bool = True):
+    """utils.create_optimizer (utils/utils.py:61-79): 'Adam', 'SGD' or 'RMSprop' over `model.parameters()`.  device_step: the step of
+    every fp32 tensor on a GPU is one launch (tpnet_amd/optimizer.py; same state_dict as torch's classes, and a model that is moved to
+    the GPU after this call, as train_link_prediction.py:220-223 does, is served from its first step); False: exactly the reference's
+    torch.optim objects."""
+    from . import optimizer as O
+    classes = {"Adam": (O.DeviceAdam, torch.optim.Adam), "SGD": (O.DeviceSGD, torch.optim.SGD),
+               "RMSprop": (O.DeviceRMSprop, torch.optim.RMSprop)}
+    if optimizer_name not in classes:
+        raise ValueError(f"Wrong value for optimizer {optimizer_name}!")
+    cls = classes[optimizer_name][0 if device_step else 1]
+    return cls(params=model.parameters(), lr=learning_rate, weight_decay=weight_decay)
 
 
 def evaluate_with_restore(rp, evaluate: Callable):
