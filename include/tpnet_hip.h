@@ -52,7 +52,9 @@ extern "C" {
                                     tpnet_mlp_rows_bwd_* (its weight gradients on the matrix cores, same widths);
                                     tpnet_decoder_f32* (LinkPredictor_v1 in the fp32 class, forward and backward);
                                     tpnet_mlp_l4_* (self.mlp on the matrix cores for num_layer 4, forward and backward);
-                                    TPNET_FLAG_ROWS8 / tpnet_encoder_rows8_supported (the encoder's matrix-core calls on rows of d % 4 == 2) */
+                                    TPNET_FLAG_ROWS8 / tpnet_encoder_rows8_supported (the encoder's matrix-core calls on rows of d % 4 == 2);
+                                    tpnet_import_layers_ld / tpnet_export_layers_ld / tpnet_pad_rows / tpnet_gather_rows_ld (a table whose rows
+                                    are kept wider than the caller's, pad columns zero) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -157,6 +159,25 @@ int tpnet_decay(const tpnet_state* st, const float* factors, double t_new, void*
 /* get_random_projections (models/TPNet.py:101-110): out[(i*n + k)*d + :] = P[i][ids[k]] at now_time, i = 0..L. */
 int tpnet_gather_rows(const tpnet_state* st, const int64_t* ids, int64_t n, double now_time, double lambda,
                       float* out, void* stream);
+
+/* A table kept wider than the caller's tensors (RandomProjectionModule.padded_rows): the engine's rows are st->d floats, the
+ * caller's rows `ld` floats, 1 <= ld <= st->d; columns ld..st->d-1 of the engine's rows ("pad columns") hold +0.0 -- a zero column adds
+ * exactly 0 to every inner product and stays 0 under every update.  The wide side (st->q, st->p0, the mirror) is read and written
+ * in 16-byte vectors: it must be 16-byte aligned, with st->d % 4 == 0 (ld == st->d is allowed: the plain entry points' result); the
+ * narrow side in 8-byte vectors when ld is even (rows then 8-byte aligned: the base must be), else float by float.
+ * TPNET_ERR_BAD_ARG, before anything is launched, for a null pointer, ld outside its range, or a wide side that is not aligned.
+ *
+ * tpnet_import_layers_ld: tpnet_import_layers from layers of [N][ld]; the pad columns of copy 0 AND copy 1 of every bundle are
+ * written as +0.0 (copy 1's other columns are left as they are: nothing reads them before a launch has written them). */
+int tpnet_import_layers_ld(const tpnet_state* st, const float* const* layers, int32_t ld, double now_time, void* stream);
+/* tpnet_export_layers_ld: tpnet_export_layers into layers of [N][ld]: the first ld columns of every row, never a float past them. */
+int tpnet_export_layers_ld(const tpnet_state* st, float* const* layers, int32_t ld, double now_time, double lambda, void* stream);
+/* dst[n][0..ld_src-1] = src[n][0..ld_src-1], dst[n][ld_src..ld_dst-1] = +0.0 for n < N: the wide copy of P[0] that st->p0 points at.
+ * 1 <= ld_src <= ld_dst; dst is the wide side (16-byte aligned, ld_dst % 4 == 0). */
+int tpnet_pad_rows(const float* src, int32_t ld_src, float* dst, int32_t ld_dst, int64_t N, void* stream);
+/* tpnet_gather_rows with output rows of ld_out floats: out[(i*n + k)*ld_out + c] = P[i][ids[k]][c], c < ld_out <= st->d. */
+int tpnet_gather_rows_ld(const tpnet_state* st, const int64_t* ids, int64_t n, double now_time, double lambda, int32_t ld_out,
+                         float* out, void* stream);
 
 /* Single elements of every layer: out[k][i] = P[i][rows[k]][cols[k]] at now_time, i = 0..L (out: device float[n][L+1]).
  * With a square table (d = N) this is the readout of the reference's sibling walk-matrix state, PINT's

@@ -70,6 +70,10 @@ SIGNATURES = {
     "tpnet_export_layers": (C.c_int, [_SP, C.POINTER(_P), C.c_double, C.c_double, _P]),
     "tpnet_decay": (C.c_int, [_SP, C.POINTER(C.c_float), C.c_double, _P]),
     "tpnet_gather_rows": (C.c_int, [_SP, _P, C.c_int64, C.c_double, C.c_double, _P, _P]),
+    "tpnet_import_layers_ld": (C.c_int, [_SP, C.POINTER(_P), C.c_int32, C.c_double, _P]),
+    "tpnet_export_layers_ld": (C.c_int, [_SP, C.POINTER(_P), C.c_int32, C.c_double, C.c_double, _P]),
+    "tpnet_pad_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, _P]),
+    "tpnet_gather_rows_ld": (C.c_int, [_SP, _P, C.c_int64, C.c_double, C.c_double, C.c_int32, _P, _P]),
     "tpnet_pair_gram": (C.c_int, [_SP, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_uint32, _P, _P]),
     "tpnet_pair_gram_shared": (C.c_int, [_SP, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_uint32, _P, _P, _P]),
     "tpnet_pair_gram_anchored": (C.c_int, [_SP, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P, _P,

@@ -370,6 +370,41 @@ int tpnet_gather_rows(const tpnet_state* st, const int64_t* ids, int64_t n, doub
     return launch_gather_rows(*st, ids, n, now_time, lambda, out, (hipStream_t)stream);
 }
 
+// the wide side of the *_ld entry points: whole 16-byte vectors at 16-byte aligned addresses
+static bool wide_ok(const void* p, int32_t d) { return p && d >= 4 && d % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int tpnet_import_layers_ld(const tpnet_state* st, const float* const* layers, int32_t ld, double now_time, void* stream) {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (!layers || ld < 1 || ld > st->d || !wide_ok(st->q, st->d)) return TPNET_ERR_BAD_ARG;
+    for (int i = 0; i < st->L; ++i)
+        if (!layers[i]) return TPNET_ERR_BAD_ARG;
+    return launch_import_ld(*st, layers, ld, now_time, (hipStream_t)stream);
+}
+
+int tpnet_export_layers_ld(const tpnet_state* st, float* const* layers, int32_t ld, double now_time, double lambda, void* stream) {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (!layers || ld < 1 || ld > st->d || !wide_ok(st->q, st->d)) return TPNET_ERR_BAD_ARG;
+    for (int i = 0; i < st->L; ++i)
+        if (!layers[i]) return TPNET_ERR_BAD_ARG;
+    return launch_export_ld(*st, layers, ld, now_time, lambda, (hipStream_t)stream);
+}
+
+int tpnet_pad_rows(const float* src, int32_t ld_src, float* dst, int32_t ld_dst, int64_t N, void* stream) {
+    if (!src || ld_src < 1 || ld_src > ld_dst || !wide_ok(dst, ld_dst) || N < 0 || N >= (1ll << 31)) return TPNET_ERR_BAD_ARG;
+    return launch_pad_rows(src, ld_src, dst, ld_dst, N, (hipStream_t)stream);
+}
+
+int tpnet_gather_rows_ld(const tpnet_state* st, const int64_t* ids, int64_t n, double now_time, double lambda, int32_t ld_out,
+                         float* out, void* stream) {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (n < 0 || !ids || !out || ld_out < 1 || ld_out > st->d || !wide_ok(st->q, st->d) || !wide_ok(st->p0, st->d))
+        return TPNET_ERR_BAD_ARG;
+    return launch_gather_rows_ld(*st, ids, n, now_time, lambda, ld_out, out, (hipStream_t)stream);
+}
+
 int tpnet_gather_elems(const tpnet_state* st, const int64_t* rows, const int64_t* cols, int64_t n, double now_time,
                        double lambda, float* out, void* stream) {
     int rc = check_state(st);

@@ -64,6 +64,140 @@ __global__ void k_export(tpnet_state S, LayerPtrs lp, double now, double lambda)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// a table kept wider than the caller's rows (RandomProjectionModule.padded_rows): the wide side (S.q, S.p0: rows of S.d floats,
+// S.d % 4 == 0, 16-byte aligned) moves as 16-byte vectors, one per thread; the narrow side (rows of ld <= S.d floats) as two
+// 8-byte halves when EVEN (ld even and the base 8-byte aligned: every row start and every column c % 4 == 0 is then 8-byte
+// aligned), else float by float -- a row of odd ld starts on any 4-byte boundary.  Columns ld.. of the wide side are +0.0.
+// ---------------------------------------------------------------------------------------------------------------
+// columns c..c+3 (c % 4 == 0) of a narrow row, +0.0 from column ld on; never reads past the row's ld floats
+template <bool EVEN> __device__ __forceinline__ float4 load_narrow4(const float* __restrict__ row, int c, int ld) {
+    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (EVEN) {
+        if (c < ld) { const float2 a = *reinterpret_cast<const float2*>(row + c); v.x = a.x; v.y = a.y; }
+        if (c + 2 < ld) { const float2 b = *reinterpret_cast<const float2*>(row + c + 2); v.z = b.x; v.w = b.y; }
+    } else {
+        if (c < ld) v.x = row[c];
+        if (c + 1 < ld) v.y = row[c + 1];
+        if (c + 2 < ld) v.z = row[c + 2];
+        if (c + 3 < ld) v.w = row[c + 3];
+    }
+    return v;
+}
+
+// the inverse: those of v's four columns that lie below ld; never writes past the row's ld floats
+template <bool EVEN> __device__ __forceinline__ void store_narrow4(float* __restrict__ row, int c, int ld, const float4 v) {
+    if constexpr (EVEN) {
+        if (c < ld) *reinterpret_cast<float2*>(row + c) = make_float2(v.x, v.y);
+        if (c + 2 < ld) *reinterpret_cast<float2*>(row + c + 2) = make_float2(v.z, v.w);
+    } else {
+        if (c < ld) row[c] = v.x;
+        if (c + 1 < ld) row[c + 1] = v.y;
+        if (c + 2 < ld) row[c + 2] = v.z;
+        if (c + 3 < ld) row[c + 3] = v.w;
+    }
+}
+
+// k_import from layers of [N][ld]: copy 0 bundles with their pad columns +0.0, the pad columns of copy 1 +0.0 as well (the update
+// kernels keep a zero column zero; here it is established); meta = {0, now}
+template <bool EVEN> __global__ void k_import_ld(tpnet_state S, LayerPtrs lp, int ld, double now) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t nv = S.d / 4, L = S.L;
+    const int64_t tot = S.N * L * nv;                      // 16-byte vectors of one copy
+    float4* q0 = reinterpret_cast<float4*>(S.q);
+    float* q1 = S.q + S.N * L * (int64_t)S.d;
+    for (int64_t x = tid; x < tot; x += stride) {
+        const int64_t n = x / (L * nv);
+        const int64_t r = x - n * (L * nv);
+        const int64_t i = r / nv;
+        const int c = (int)(r - i * nv) * 4;
+        q0[x] = load_narrow4<EVEN>(lp.p[i] + n * ld, c, ld);
+        if (c + 4 > ld) {
+            if (c >= ld) {
+                reinterpret_cast<float4*>(q1)[x] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            } else {
+                for (int k = ld - c; k < 4; ++k) q1[x * 4 + k] = 0.0f;
+            }
+        }
+    }
+    NodeMeta* meta = reinterpret_cast<NodeMeta*>(S.meta);
+    for (int64_t n = tid; n < S.N; n += stride) {
+        NodeMeta m;
+        m.ver = 0; m.pad0 = 0; m.tref[0] = now; m.tref[1] = now; m.pad1 = 0;
+        meta[n] = m;
+    }
+}
+
+// k_export into layers of [N][ld]: the first ld columns of the current bundles, pending decay applied as k_export applies it
+template <bool EVEN> __global__ void k_export_ld(tpnet_state S, LayerPtrs lp, int ld, double now, double lambda) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t nv = S.d / 4, L = S.L;
+    const int64_t tot = S.N * L * nv;
+    const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
+    const float4* q = reinterpret_cast<const float4*>(S.q);
+    for (int64_t x = tid; x < tot; x += stride) {
+        const int64_t n = x / (L * nv);
+        const int64_t r = x - n * (L * nv);
+        const int64_t i = r / nv;
+        const int c = (int)(r - i * nv) * 4;
+        if (c >= ld) continue;
+        const MetaView m = read_meta(meta, n, READER_BID, now, lambda);
+        float g = m.g;
+        for (int64_t z = 0; z < i; ++z) g *= m.g;
+        float4 v = q[(int64_t)m.copy * tot + x];
+        v.x *= g; v.y *= g; v.z *= g; v.w *= g;
+        store_narrow4<EVEN>(lp.p[i] + n * ld, c, ld, v);
+    }
+}
+
+// dst [N][ld_dst] <- src [N][ld_src], columns ld_src.. +0.0: the wide copy of P[0]
+template <bool EVEN> __global__ void k_pad_rows(const float* __restrict__ src, int ld_src, float4* __restrict__ dst, int ld_dst,
+                                                int64_t N) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t nv = ld_dst / 4;
+    const int64_t tot = N * nv;
+    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < tot; x += stride) {
+        const int64_t n = x / nv;
+        const int c = (int)(x - n * nv) * 4;
+        dst[x] = load_narrow4<EVEN>(src + n * ld_src, c, ld_src);
+    }
+}
+
+// k_gather_rows with output rows of ld_out floats: out[(i*n + k)*ld_out + c] = P[i][ids[k]][c], c < ld_out
+template <bool EVEN> __global__ void k_gather_rows_ld(tpnet_state S, const int64_t* __restrict__ ids, int64_t n, double now,
+                                                      double lambda, int ld, float* __restrict__ out) {
+    const int64_t d = S.d, L = S.L;
+    const int nv = S.d / 4;
+    const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
+    for (int64_t k = blockIdx.x; k < n; k += gridDim.x) {
+        int64_t id = ids[k];
+        const bool ok = (uint64_t)id < (uint64_t)S.N;
+        if (!ok) {
+            if (threadIdx.x == 0) atomicAdd(S.err, 1u);
+            id = 0;
+        }
+        const MetaView m = read_meta(meta, id, READER_BID, now, lambda);
+        const float* qb = S.q + ((int64_t)m.copy * S.N + id) * (L * d);
+        for (int r = threadIdx.x; r < (int)(L + 1) * nv; r += blockDim.x) {
+            const int i = r / nv, c = (r - i * nv) * 4;
+            if (c >= ld) continue;
+            float4 v;
+            if (i == 0) {
+                v = *reinterpret_cast<const float4*>(S.p0 + id * d + c);
+            } else {
+                float g = m.g;
+                for (int z = 1; z < i; ++z) g *= m.g;
+                v = *reinterpret_cast<const float4*>(qb + (i - 1) * d + c);
+                v.x *= g; v.y *= g; v.z *= g; v.w *= g;
+            }
+            if (!ok) v.x = v.y = v.z = v.w = __builtin_nanf("");
+            store_narrow4<EVEN>(out + (i * n + k) * ld, c, ld, v);
+        }
+    }
+}
+
 struct DecayFactors {
     float f[TPNET_MAX_LAYERS];
 };
@@ -396,6 +530,57 @@ int launch_export(const tpnet_state& st, float* const* layers, double now, doubl
     for (int i = 0; i < st.L; ++i) lp.p[i] = layers[i];
     hipLaunchKernelGGL(k_export, dim3(grid_for(st.N * (int64_t)st.L * st.d, 256 * 4, 4096)), dim3(256), 0, s, st, lp,
                        now, lambda);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+// whether a narrow side of rows of ld floats at `base` takes the 8-byte halves
+static inline bool narrow_even(const void* base, int ld) { return ld % 2 == 0 && (reinterpret_cast<uintptr_t>(base) & 7) == 0; }
+
+int launch_import_ld(const tpnet_state& st, const float* const* layers, int ld, double now, hipStream_t s) {
+    LayerPtrs lp{};
+    bool even = true;
+    for (int i = 0; i < st.L; ++i) {
+        lp.p[i] = const_cast<float*>(layers[i]);
+        even = even && narrow_even(layers[i], ld);
+    }
+    const dim3 grid(grid_for(st.N * (int64_t)st.L * (st.d / 4), 256, 4096));
+    if (even) hipLaunchKernelGGL(k_import_ld<true>, grid, dim3(256), 0, s, st, lp, ld, now);
+    else hipLaunchKernelGGL(k_import_ld<false>, grid, dim3(256), 0, s, st, lp, ld, now);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+int launch_export_ld(const tpnet_state& st, float* const* layers, int ld, double now, double lambda, hipStream_t s) {
+    LayerPtrs lp{};
+    bool even = true;
+    for (int i = 0; i < st.L; ++i) {
+        lp.p[i] = layers[i];
+        even = even && narrow_even(layers[i], ld);
+    }
+    const dim3 grid(grid_for(st.N * (int64_t)st.L * (st.d / 4), 256, 4096));
+    if (even) hipLaunchKernelGGL(k_export_ld<true>, grid, dim3(256), 0, s, st, lp, ld, now, lambda);
+    else hipLaunchKernelGGL(k_export_ld<false>, grid, dim3(256), 0, s, st, lp, ld, now, lambda);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+int launch_pad_rows(const float* src, int ld_src, float* dst, int ld_dst, int64_t N, hipStream_t s) {
+    if (N == 0) return TPNET_OK;
+    const dim3 grid(grid_for(N * (ld_dst / 4), 256, 4096));
+    float4* d4 = reinterpret_cast<float4*>(dst);
+    if (narrow_even(src, ld_src)) hipLaunchKernelGGL(k_pad_rows<true>, grid, dim3(256), 0, s, src, ld_src, d4, ld_dst, N);
+    else hipLaunchKernelGGL(k_pad_rows<false>, grid, dim3(256), 0, s, src, ld_src, d4, ld_dst, N);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+int launch_gather_rows_ld(const tpnet_state& st, const int64_t* ids, int64_t n, double now, double lambda, int ld_out, float* out,
+                          hipStream_t s) {
+    if (n == 0) return TPNET_OK;
+    const dim3 grid(grid_for(n, 1, 8192));
+    if (narrow_even(out, ld_out)) hipLaunchKernelGGL(k_gather_rows_ld<true>, grid, dim3(256), 0, s, st, ids, n, now, lambda, ld_out, out);
+    else hipLaunchKernelGGL(k_gather_rows_ld<false>, grid, dim3(256), 0, s, st, ids, n, now, lambda, ld_out, out);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }

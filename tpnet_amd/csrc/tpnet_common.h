@@ -147,6 +147,12 @@ inline Geom pick_geom(int d, bool many = false) {
 int launch_state_init(const tpnet_state& st, double t0, hipStream_t s);
 int launch_import(const tpnet_state& st, const float* const* layers_dev, double now, hipStream_t s);
 int launch_export(const tpnet_state& st, float* const* layers_dev, double now, double lambda, hipStream_t s);
+// a table kept wider than the caller's rows (tables.hip): st.d % 4 == 0, rows of the caller's side `ld` floats, 1 <= ld <= st.d
+int launch_import_ld(const tpnet_state& st, const float* const* layers_dev, int ld, double now, hipStream_t s);
+int launch_export_ld(const tpnet_state& st, float* const* layers_dev, int ld, double now, double lambda, hipStream_t s);
+int launch_pad_rows(const float* src, int ld_src, float* dst, int ld_dst, int64_t N, hipStream_t s);
+int launch_gather_rows_ld(const tpnet_state& st, const int64_t* ids, int64_t n, double now, double lambda, int ld_out, float* out,
+                          hipStream_t s);
 int launch_decay(const tpnet_state& st, const float* factors_host, double t_new, hipStream_t s);
 int launch_gather_elems(const tpnet_state& st, const int64_t* rows, const int64_t* cols, int64_t n, double now,
                         double lambda, float* out, hipStream_t s);

@@ -179,7 +179,7 @@ class TPNetEmbedding(nn.Module):
             # default rule's 110 / 130 / 150)
             if dev.type == "cuda" and hasattr(rp, "get_pair_wise_feature_anchored") and (
                     rp.anchored_call_served(neigh.shape[0], K) if hasattr(rp, "anchored_call_served")
-                    else rp.dim % 4 == 0 and 36 <= rp.dim <= 512):
+                    else getattr(rp, "engine_dim", rp.dim) % 4 == 0 and 36 <= getattr(rp, "engine_dim", rp.dim) <= 512):
                 feats = rp.get_pair_wise_feature_anchored(neigh, src_node_ids, dst_node_ids)
             else:
                 # row widths the anchored readout does not serve (or another module): the general pair readout, then self.mlp as

@@ -122,7 +122,8 @@ class _FusedReadoutMLP(torch.autograd.Function):
 
 def readout_supported(rp) -> bool:
     """tpnet_pair_feature_bf16 serves L = 3 and rows of whole 16-byte vectors from 64 floats (16, 32 or 64 lanes per pair)."""
-    return rp.num_layer == 3 and rp.dim % 4 == 0 and rp.dim >= 36 and not rp.use_matrix and supported(rp.mlp)
+    d = getattr(rp, "engine_dim", rp.dim)        # (the width of the rows the kernel reads: padded_rows)
+    return rp.num_layer == 3 and d % 4 == 0 and d >= 36 and not rp.use_matrix and supported(rp.mlp)
 
 
 def fused_readout_mlp(rp, u_dev: torch.Tensor, v_dev: torch.Tensor) -> torch.Tensor:

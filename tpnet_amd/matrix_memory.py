@@ -174,4 +174,5 @@ def _bare_table(rp: RandomProjectionModule, N: int, H: int, device):
     rp.pair_wise_feature_dim = (2 * H + 2) ** 2
     rp.mlp = nn.Identity()
     rp._init_engine_side(0.0)
+    rp.padded_rows = False                     # (a square table addressed by element: never a padded one, whatever the class says)
     rp.to(device)

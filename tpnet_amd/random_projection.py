@@ -7,7 +7,8 @@ models/modules.py:112) work unchanged.  There is no CPU fallback: every compute 
 and a GPU-resident module, and raises otherwise.
 
 How the state is held:
-  * `random_projections[0]` (P[0]) IS the kernels' layer-0 buffer (no copy).
+  * `random_projections[0]` (P[0]) IS the kernels' layer-0 buffer (no copy) -- except with `padded_rows` in effect
+    (engine_dim != dim): the kernels then read an engine-owned copy of it with rows of engine_dim floats, pad columns +0.0.
   * layers 1..L live in the engine's own layout (`_q`: ping-pong per-node bundles + `_meta`), where the
     reference's dense per-batch decay (TPNet.py:83-85) is carried lazily per row.  The `random_projections[1..L]`
     Parameters are materialised from it (one export pass, decay applied) whenever somebody looks at them
@@ -84,11 +85,18 @@ class _LazyLayers(nn.ParameterList):
         return _OWNERS.get(self.__dict__.get("_tp_owner_key"))
 
     def _tp_touch(self, idx):
-        if isinstance(idx, int) and (idx == 0 or idx == -len(self)):
-            return                                   # layer 0 IS the kernels' buffer: always current
         o = self._tp_owner()
-        if o is not None:
-            o._layers_read()
+        if o is None:
+            return
+        if isinstance(idx, int) and (idx == 0 or idx == -len(self)):
+            # layer 0 IS the kernels' buffer: always current.  (With padded rows the kernels read a wide copy of it: whoever got the
+            # entry may write it through `.data`, so the copy is rebuilt before the next kernel reads it.)
+            if o.padded_rows:
+                o.__dict__["_p0_exposed"] = True
+            return
+        if o.padded_rows:
+            o.__dict__["_p0_exposed"] = True         # (iteration, slices: entry 0 may be among them)
+        o._layers_read()
 
     def __getitem__(self, idx):
         self._tp_touch(idx)
@@ -154,7 +162,7 @@ class PreparedStream:
     it runs the stream.  Attributes: the tensors it reads (`src`, `dst`, `neg`, `t`: their contents are read at every call) and
     writes (`out_pos`, `out_neg`: what the call returns)."""
     __slots__ = ("rp", "src", "dst", "neg", "t", "E", "batch_size", "nb", "want_pos", "want_neg", "out_pos", "out_neg", "t_end",
-                 "flags", "replay", "exact", "dev", "ptrs", "owners", "ws_need", "ws_cap")
+                 "flags", "replay", "exact", "dev", "ptrs", "owners", "ws_need", "ws_cap", "width_gen")
 
     def __call__(self):
         return self.rp._run_prepared(self)
@@ -249,20 +257,62 @@ class RandomProjectionModule(nn.Module):
         # looked up once: nn.ParameterList.__getitem__ costs microseconds and the hot methods need them every call
         refs = self.__dict__.get("_param_refs")
         if refs is None or len(refs) != self.num_layer + 1:
-            refs = list(nn.ParameterList.__iter__(self._modules["random_projections"]))   # (not the lazy list's own iterator)
+            pl = self._modules["random_projections"]
+            refs = [getattr(pl, str(i)) for i in range(len(pl))]     # (not through the lazy list's __getitem__ / __iter__: no hand-out)
             self.__dict__["_param_refs"] = refs
         return refs
 
     # bookkeeping attributes of the hot methods (plain Python values, never Parameters / Modules / buffers): stored without
     # nn.Module.__setattr__'s type checks -- six assignments per update() call, ~0.7 us each, in a loop the host bounds
     _PLAIN_ATTRS = frozenset(("_engine_valid", "_params_valid", "_now_host", "_now_dirty", "_param_sig", "_launch_id", "_table_sig",
-                              "_params_exposed", "_sig_counter", "last_stream_replayed"))
+                              "_params_exposed", "_sig_counter", "last_stream_replayed", "last_stream_schedule", "_p0_exposed"))
 
     def __setattr__(self, name, value):
         if name in RandomProjectionModule._PLAIN_ATTRS:
             self.__dict__[name] = value
+        elif name == "padded_rows":
+            self._set_padded_rows(value)
         else:
             super().__setattr__(name, value)
+
+    # extension, opt-in: widths that are no multiple of 4 floats -- the default rule's 110 / 130 / 150 (models/TPNet.py:30-33), odd
+    # widths of tiny graphs -- run on the scalar geometry: one float per lane, one launch per batch of a stream, no anchored readout.
+    # True: the ENGINE keeps its table (layers 1..L, the workspaces, a copy of P[0]) at the next multiple of 4 floats with the pad
+    # columns +0.0 -- a zero column adds exactly 0 to every inner product and stays 0 under every update -- so every call takes the
+    # kernels of that width (112 / 132 / 152: the windowed pipeline, the 16-byte readouts), while `random_projections`, state_dict,
+    # backup / reload, get_random_projections and copies keep the reference's [N, dim].  Costs N * engine_dim * 4 bytes for the copy
+    # of P[0].  No effect where dim % 4 == 0 or use_matrix.  Set it on the class before modules are built, or on an instance at any
+    # time (the state is kept: the engine is rebuilt at the other width on the next call; profiles/padded_rows.md)
+    padded_rows = False
+    _p0_exposed = False      # entry 0 of the ParameterList was handed out since the wide copy of P[0] was built
+    _width_gen = 0           # counts the changes of engine_dim (`padded_rows` toggled): prepared streams carry it
+
+    @property
+    def engine_dim(self) -> int:
+        """Floats per row of the engine's table: `dim`, or with `padded_rows` in effect `dim` rounded up to a multiple of 4."""
+        d = self.dim
+        return (d + 3) // 4 * 4 if (d % 4 and self.padded_rows and not self.use_matrix) else d
+
+    def _set_padded_rows(self, value):
+        """Assignment of `padded_rows` on an instance.  Where it changes engine_dim on a live engine nothing is lost: the Parameters are
+        brought up to date, then the engine, its plan and the cached state struct are dropped -- the next call builds them at the new
+        width and imports the Parameters.  Streams prepared before are refused from then on."""
+        d = self.__dict__
+        ready = "_eng" in d and "dim" in d and "use_matrix" in d
+        before = self.engine_dim if ready else None
+        d["padded_rows"] = bool(value)
+        if ready and self.engine_dim != before:
+            if d["_eng"] is not None and not d["_params_valid"]:
+                self._materialize()                 # (reads the engine at the width it was built with: _eng["d"])
+            self._drop_plan()
+            d["_plan_tag"] = None
+            d["_eng"] = None
+            d["_st_cache"] = None
+            d["_ws_need"] = {}
+            d["_engine_valid"] = False
+            d["_params_valid"] = True
+            d["_param_sig"] = None
+            d["_width_gen"] = self._width_gen + 1
 
     def __getattr__(self, name):
         # external readers of `random_projections` / `now_time` see the reference's eager values
@@ -273,6 +323,8 @@ class RandomProjectionModule(nn.Module):
                 pl.__dict__["_tp_owner_key"] = id(self)
                 _OWNERS[id(self)] = self
             else:                                    # (a plain list put there by somebody else: the eager behaviour)
+                if self.padded_rows:
+                    self.__dict__["_p0_exposed"] = True
                 self._layers_read()
         elif name == "now_time" and self.__dict__.get("_now_dirty", False):     # (.get: nn.Module.__init__ and the constructor
             self._sync_now_time()                                               #  read attributes before _init_engine_side has run)
@@ -313,14 +365,16 @@ class RandomProjectionModule(nn.Module):
         dev = self._dev()
         lib = _lib.load()
         if self._eng is None or self._eng["dev"] != dev:
-            N, d, L = self.node_num, self.dim, self.num_layer
+            N, d, L = self.node_num, self.engine_dim, self.num_layer
             with torch.cuda.device(dev):
                 q = torch.empty(lib.tpnet_q_bytes(N, d, L) // 4, dtype=torch.float32, device=dev)
                 meta = torch.empty(lib.tpnet_meta_bytes(N), dtype=torch.uint8, device=dev)
                 err = torch.zeros(4, dtype=torch.int32, device=dev)
+                # padded rows: the wide copy of P[0] that the kernels read (filled by _p0_wide before the first of them does)
+                p0w = torch.empty((N, d), dtype=torch.float32, device=dev) if d != self.dim else None
             # (the per-batch ring in device memory behind the large BAR where there is one: STAGE_MODE, tpnet_stage_create_ex)
             self._eng = dict(dev=dev, dev_index=dev.index if dev.index is not None else torch.cuda.current_device(), q=q,
-                             meta=meta, err=err, ws=None, stage=_Stage(lib, dev, mode=STAGE_MODE))
+                             meta=meta, err=err, ws=None, stage=_Stage(lib, dev, mode=STAGE_MODE), d=d, p0w=p0w, p0sig=None)
             if dev not in _WARMED:
                 # once per process and device: the HIP runtime's first-use costs are paid here, not inside the first long
                 # call -- a burst of launches behind a busy kernel, then ONE synchronise (tools/first_call.py, first 20-batch
@@ -337,12 +391,28 @@ class RandomProjectionModule(nn.Module):
 
     def _st_ref(self):
         """byref of the tpnet_state struct, rebuilt only when P[0]'s storage or the engine buffers changed."""
-        ptr = self._plist()[0].data_ptr()
+        p0 = self._plist()[0]
+        ptr = p0.data_ptr()
         c = self.__dict__.get("_st_cache")
         if c is None or c.p0 != ptr or c.eng is not self._eng:
             st = self._state()
             c = self.__dict__["_st_cache"] = _StateRef(ptr, self._eng, st, C.byref(st), C.addressof(st))
+        elif c.eng["p0w"] is not None and (c.eng["p0sig"][1] != p0._version or self._p0_exposed):
+            self._p0_wide(c.eng, p0)               # (padded rows: the struct points at the wide copy, which is stale)
         return c.ref
+
+    def _p0_wide(self, eng, p0):
+        """Padded rows: the engine's copy of P[0] with rows of engine_dim floats, pad columns +0.0 (what tpnet_state.p0 points at),
+        brought up to date if P[0] may have changed since it was built: another storage or version counter (reset, load_state_dict,
+        `.data = ...`, copy_), or entry 0 of the list handed out -- a write through its `.data` shows in neither (the rule of
+        _params_exposed).  One pass over N * engine_dim floats, before the kernel that reads it, on the same stream."""
+        sig = (p0.data_ptr(), p0._version)
+        if eng["p0sig"] != sig or self._p0_exposed:
+            _lib.check(_lib.load().tpnet_pad_rows(p0.data_ptr(), self.dim, eng["p0w"].data_ptr(), eng["d"], self.node_num,
+                                                  _raw_stream(eng["dev_index"])), "pad_rows")
+            eng["p0sig"] = sig
+            self._p0_exposed = False
+        return eng["p0w"]
 
     def _ids(self, ids, what, staged=False):
         """Node ids in the form a call needs.  `staged` (the C calls that stage host ids themselves, and check their range and wrap
@@ -399,8 +469,10 @@ class RandomProjectionModule(nn.Module):
         p0 = self._plist()[0]
         if not p0.is_contiguous() or p0.dtype != torch.float32:
             raise _lib.TPNetHipError("random_projections[0] must be a contiguous float32 tensor")
+        if eng["p0w"] is not None:
+            p0 = self._p0_wide(eng, p0)
         return _lib.State(p0=p0.data_ptr(), q=eng["q"].data_ptr(), meta=eng["meta"].data_ptr(), N=self.node_num,
-                          d=self.dim, L=self.num_layer, err=eng["err"].data_ptr())
+                          d=eng["d"], L=self.num_layer, err=eng["err"].data_ptr())
 
     def _workspace(self, max_edges: int, batch: int, stream: bool = False, tail: int = 0, keep_plan: bool = False):
         """Plan workspace.  `stream`: sized for tpnet_run_stream (the windowed schedule's plan + version log where it applies),
@@ -413,9 +485,9 @@ class RandomProjectionModule(nn.Module):
         need = cache.get((max_edges, batch, stream, tail, cap))
         if need is None:
             if stream and cap:
-                need = _lib.load().tpnet_stream_workspace_bytes_capped(self.node_num, self.dim, self.num_layer, max_edges, batch, cap)
+                need = _lib.load().tpnet_stream_workspace_bytes_capped(self.node_num, eng["d"], self.num_layer, max_edges, batch, cap)
             elif stream:
-                need = _lib.load().tpnet_stream_workspace_bytes(self.node_num, self.dim, self.num_layer, max_edges, batch)
+                need = _lib.load().tpnet_stream_workspace_bytes(self.node_num, eng["d"], self.num_layer, max_edges, batch)
             else:
                 need = _lib.load().tpnet_workspace_bytes(max_edges, batch)
             need = (need + 255) // 256 * 256 + tail
@@ -431,10 +503,10 @@ class RandomProjectionModule(nn.Module):
                 # a GPU short of memory: halve the version log's cap (shorter chunks, more pipeline fills and drains, and beyond
                 # TPNET_ARENA_MAX_RATIO no replay) until the workspace fits -- the C side takes whatever chunk it is given
                 eng["ws"] = None
-                lib, row = _lib.load(), 2 * self.num_layer * self.dim * 4
+                lib, row = _lib.load(), 2 * self.num_layer * eng["d"] * 4
                 cap_try = (cap or (16 << 30)) // 2
                 while True:
-                    need = (lib.tpnet_stream_workspace_bytes_capped(self.node_num, self.dim, self.num_layer, max_edges, batch,
+                    need = (lib.tpnet_stream_workspace_bytes_capped(self.node_num, eng["d"], self.num_layer, max_edges, batch,
                                                                     cap_try) + 255) // 256 * 256 + tail
                     try:
                         eng["ws"] = torch.empty(need, dtype=torch.uint8, device=eng["dev"])
@@ -498,8 +570,12 @@ class RandomProjectionModule(nn.Module):
                 raise _lib.TPNetHipError("internal error: neither the engine nor the Parameters hold the state")
             self._now_host = float(self._parameters["now_time"].item())   # the Parameters are the truth here
             st = self._state()
-            _lib.check(_lib.load().tpnet_import_layers(C.byref(st), self._layer_ptrs(), self._now_host, self._stream()),
-                       "import_layers")
+            if st.d != self.dim:                # (padded rows: the pad columns of both copies of every bundle become +0.0)
+                _lib.check(_lib.load().tpnet_import_layers_ld(C.byref(st), self._layer_ptrs(), self.dim, self._now_host,
+                                                              self._stream()), "import_layers_ld")
+            else:
+                _lib.check(_lib.load().tpnet_import_layers(C.byref(st), self._layer_ptrs(), self._now_host, self._stream()),
+                           "import_layers")
             self._engine_valid = True
             self._param_sig = self._sig()
             self._params_exposed = False
@@ -512,8 +588,12 @@ class RandomProjectionModule(nn.Module):
         if self._params_valid:
             return
         st = self._state()
-        _lib.check(_lib.load().tpnet_export_layers(C.byref(st), self._layer_ptrs(), self._now_host,
-                                                   float(self.time_decay_weight), self._stream()), "export_layers")
+        if st.d != self.dim:
+            _lib.check(_lib.load().tpnet_export_layers_ld(C.byref(st), self._layer_ptrs(), self.dim, self._now_host,
+                                                          float(self.time_decay_weight), self._stream()), "export_layers_ld")
+        else:
+            _lib.check(_lib.load().tpnet_export_layers(C.byref(st), self._layer_ptrs(), self._now_host,
+                                                       float(self.time_decay_weight), self._stream()), "export_layers")
         self._params_valid = True
         self._param_sig = self._sig()
 
@@ -582,6 +662,8 @@ class RandomProjectionModule(nn.Module):
     def state_dict(self, *args, **kwargs):
         self._materialize()
         self._params_exposed = True            # the returned tensors alias the Parameters' storage
+        if self.padded_rows:
+            self._p0_exposed = True
         return super().state_dict(*args, **kwargs)
 
     def _load_from_state_dict(self, *args, **kwargs):
@@ -659,9 +741,13 @@ class RandomProjectionModule(nn.Module):
         n = ids.numel()
         out = torch.empty((self.num_layer + 1, n, self.dim), dtype=torch.float32, device=self._dev())
         st = self._state()
-        _lib.check(_lib.load().tpnet_gather_rows(C.byref(st), ids.data_ptr(), n, self._now_host,
-                                                 float(self.time_decay_weight), out.data_ptr(), self._stream()),
-                   "gather_rows")
+        if st.d != self.dim:
+            _lib.check(_lib.load().tpnet_gather_rows_ld(C.byref(st), ids.data_ptr(), n, self._now_host, float(self.time_decay_weight),
+                                                        self.dim, out.data_ptr(), self._stream()), "gather_rows_ld")
+        else:
+            _lib.check(_lib.load().tpnet_gather_rows(C.byref(st), ids.data_ptr(), n, self._now_host,
+                                                     float(self.time_decay_weight), out.data_ptr(), self._stream()),
+                       "gather_rows")
         return [out[i] for i in range(self.num_layer + 1)]
 
     def _readout_flags(self, raw: bool = False, packed: bool = False, matrix_cores: bool = True) -> int:
@@ -730,7 +816,7 @@ class RandomProjectionModule(nn.Module):
         #    Not for rows of < 256 floats on long lists: the 512-thread workgroups of the one-kernel version cost the readout its
         #    occupancy -- 80 000 pairs at d=128: 87..89 us against 42 + 34 us for readout kernel + dense-layer kernel
         #    (tools/feature_rate.py); the same holds for the fp32 kernel of route 4
-        if self.fused_mlp and cuda and _fm.readout_supported(self) and (self.dim >= 256 or len(src_node_ids) <= 16384):
+        if self.fused_mlp and cuda and _fm.readout_supported(self) and (self.engine_dim >= 256 or len(src_node_ids) <= 16384):
             if len(src_node_ids) != len(dst_node_ids):
                 raise ValueError("src_node_ids and dst_node_ids must have the same length")
             self._ensure_engine()
@@ -753,7 +839,7 @@ class RandomProjectionModule(nn.Module):
             self._ensure_engine()
             # (the fp32 matrix-core kernel serves L = 3 and rows of >= 36 floats in 16-byte vectors: lists up to the staging ring's
             # length; the plain one up to _ff.MAX_PAIRS)
-            mfma = bool(prep.st.w1) and self.dim % 4 == 0 and self.dim >= 36 and not self.use_matrix
+            mfma = bool(prep.st.w1) and self._eng["d"] % 4 == 0 and self._eng["d"] >= 36 and not self.use_matrix
             if n <= (self._eng["stage"].max_pairs if mfma else _ff.MAX_PAIRS):
                 # 3. the decoder's call (models/modules.py:112: n = batch size) from host arrays: ids checked and staged, readout
                 #    AND self.mlp in one launch (tpnet_host_pair_feature), fp32.  (Flags and the no-grad branch are
@@ -766,7 +852,7 @@ class RandomProjectionModule(nn.Module):
         # ---- long lists (and whatever the routes above do not serve).  `tiled`: src = tile(x, 2) on rows wide enough for fetching
         # x's rows once to pay (_tiled) -- one pass over the ids, made when the first route asks and at most once
         tiled = None
-        if mfma and self.dim > 128:
+        if mfma and self._eng["d"] > 128:
             tiled = self._tiled(src, n)
             if not tiled:
                 # 4. wide rows, not the encoder's pattern: still one launch on the fp32 matrix cores, from a device copy of the ids
@@ -806,7 +892,7 @@ class RandomProjectionModule(nn.Module):
     def _tiled(self, src, n) -> bool:
         """src = tile(x, 2), on rows of more than 128 floats.  (Rows of <= 128 floats: the generic kernel's 16-lane geometry is as
         fast on long lists as the kernels that fetch x's rows once -- measured, tools/encoder_readout.py.)"""
-        return self.dim > 128 and n >= 2 and n % 2 == 0 and np.array_equal(src[: n // 2], src[n // 2:])
+        return self.engine_dim > 128 and n >= 2 and n % 2 == 0 and np.array_equal(src[: n // 2], src[n // 2:])
 
     def _feature_call(self, prep, n, launch, rows_k=None):
         """A readout + self.mlp call, `launch(gram)` -> the [n, (2L+2)^2] features, `gram` = where the kernel leaves the pre-mlp
@@ -929,7 +1015,7 @@ class RandomProjectionModule(nn.Module):
         if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
             rows8 = self._rows8(n, K) if matrix_cores else 0
             if not rows8:
-                raise _lib.TPNetHipError(f"pair_gram_anchored needs dim % 4 == 0 and 36 <= dim <= 512, not {self.dim}: "
+                raise _lib.TPNetHipError(f"pair_gram_anchored needs rows of dim % 4 == 0 and 36 <= dim <= 512 floats, not {self.engine_dim}: "
                                          "use pair_gram_shared")
         wd = self._to_device(self._ids(w, "neighbor_ids"))[0]
         a1, a2 = self._to_device(self._ids(first_anchor_ids, "first_anchor_ids"),
@@ -951,14 +1037,14 @@ class RandomProjectionModule(nn.Module):
     def _rows8(self, rows, K, mlp_ref=None) -> int:
         """_lib.FLAG_ROWS8 if `rows8_readout` is set and tpnet_encoder_rows8_supported answers 1 for `rows` x K neighbours (with
         `mlp_ref`: for readout + self.mlp in one launch), else 0."""
-        if not self.rows8_readout or self.dim % 4 != 2:
+        if not self.rows8_readout or self.engine_dim % 4 != 2:
             return 0
         return _lib.FLAG_ROWS8 if _lib.load().tpnet_encoder_rows8_supported(self._st_ref(), rows, K, mlp_ref) else 0
 
     def anchored_call_served(self, rows, K) -> bool:
         """Whether get_pair_wise_feature_anchored serves `rows` x K neighbours at this module's width: dim % 4 == 0 and
         36 <= dim <= 512, or -- `rows8_readout` -- what tpnet_encoder_rows8_supported accepts."""
-        if self.dim % 4 == 0 and 36 <= self.dim <= 512:
+        if self.engine_dim % 4 == 0 and 36 <= self.engine_dim <= 512:
             return True
         if not self.rows8_readout or self._plist()[0].device.type != "cuda":
             return False
@@ -1147,6 +1233,7 @@ class RandomProjectionModule(nn.Module):
     default_schedule = "auto"      # run_stream: "auto" | "windowed" | "batch" (see include/tpnet_hip.h, TPNET_FLAG_SCHED_*)
     plan_replay = True             # run_stream: replay the plan of a stream that is run again on the same table state
     last_stream_replayed = False
+    last_stream_schedule = None    # "windowed" | "batch": what the last run_stream call took (tpnet_stream_schedule on its arguments)
 
     def reserve_stream(self, max_edges: int, batch_size: int):
         """Extension: size the stream workspace for run_stream calls of up to `max_edges` edges in batches of `batch_size` now, so
@@ -1219,6 +1306,7 @@ class RandomProjectionModule(nn.Module):
                   out_pos.data_ptr() if want_pos else 0, out_neg.data_ptr() if want_neg else 0)
         p.owners = _owners(src, dst, t)
         p.ws_cap = self.stream_log_cap_bytes
+        p.width_gen = self._width_gen
         need = 0
         if E > 0:
             w0 = self._workspace(E, batch_size, stream=True, keep_plan=True)
@@ -1232,6 +1320,8 @@ class RandomProjectionModule(nn.Module):
         self._ensure_engine()
         if p.exact != self.exact or p.dev != self._dev():
             raise RuntimeError("this prepared stream was made for another mode / device of the module: prepare it again")
+        if p.width_gen != self._width_gen:
+            raise RuntimeError("this prepared stream was made before `padded_rows` changed the engine's row width: prepare it again")
         E, batch_size = p.E, p.batch_size
         src, dst, t = p.src, p.dst, p.t
         ws = self._eng["ws"]                             # (the stream's workspace: sized when the call was prepared; looked up again
@@ -1276,6 +1366,14 @@ class RandomProjectionModule(nn.Module):
                 pop or None, pon or None, ws.data_ptr(), ws.numel(), None if t_end is not None else C.byref(t_out), stream,
                 C.byref(tag) if tag is not None else None), "run_stream")
         self.last_stream_replayed = bool(tag is not None and tag.replayed)
+        # which schedule the call took: the library's answer for the very (N, d, L, E, batch, flags, workspace) it ran with -- asked
+        # once per distinct call, it depends on nothing else
+        key = (st.d, E, batch_size, flags, ws.numel())
+        sc = self.__dict__.get("_sched_seen")
+        if sc is None or sc[0] != key:
+            sc = self.__dict__["_sched_seen"] = (key, "windowed" if _lib.load().tpnet_stream_schedule(
+                self.node_num, st.d, self.num_layer, E, batch_size, flags, ws.numel()) == 1 else "batch")
+        self.last_stream_schedule = sc[1]
         self._advanced(t_end if t_end is not None else float(t_out.value))
         return p.out_pos, p.out_neg
 

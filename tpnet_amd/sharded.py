@@ -228,6 +228,7 @@ class ShardedStreamRunner:
 
     def __init__(self, rp_local, node_num: int, halo_rows: int, group=None, world=None, rank=None):
         self.rp = rp_local
+        rp_local.padded_rows = False              # (the runner addresses the table's rows itself: a request for padded rows is ignored)
         self.group = group
         # world / rank given: a shard with no process group behind it (several shards in ONE process: the loopback test of the
         # RCCL branch, tests/loopback) -- whoever drives it moves the rows and merges the outputs
@@ -1111,6 +1112,7 @@ class ColumnShardedRunner:
 
     def __init__(self, rp_local, full_dim: int, group=None):
         self.rp = rp_local
+        rp_local.padded_rows = False              # (column shards are the caller's widths: a request for padded rows is ignored)
         self.group = group
         self.G = dist.get_world_size(group)
         self.me = dist.get_rank(group)
