@@ -54,7 +54,8 @@ extern "C" {
                                     tpnet_mlp_l4_* (self.mlp on the matrix cores for num_layer 4, forward and backward);
                                     TPNET_FLAG_ROWS8 / tpnet_encoder_rows8_supported (the encoder's matrix-core calls on rows of d % 4 == 2);
                                     tpnet_import_layers_ld / tpnet_export_layers_ld / tpnet_pad_rows / tpnet_gather_rows_ld (a table whose rows
-                                    are kept wider than the caller's, pad columns zero) */
+                                    are kept wider than the caller's, pad columns zero);
+                                    TPNET_FLAG_LAYERS_MFMA / tpnet_encoder_layers_* (the encoder's matrix-core readout for num_layer 1, 2, 4) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -122,6 +123,11 @@ typedef struct tpnet_state {
                                        (tpnet_encoder_rows8_supported).  No effect where d % 4 == 0.  With d % 4 == 2 only the
                                        matrix-core kernels serve the call: TPNET_ERR_BAD_ARG for K < 4, L != 3, d outside 38..158,
                                        outputs that are not 16-byte aligned, or TPNET_FLAG_NO_MFMA_READOUT beside it */
+#define TPNET_FLAG_LAYERS_MFMA 1024u  /* tpnet_pair_gram_anchored, tpnet_encoder_gram: a state with L = 1, 2 or 4 takes the anchored
+                                       readout on the matrix cores (csrc/encoder_layers.hip, fp32 class as at L = 3) where
+                                       tpnet_encoder_layers_supported answers 1 and the outputs are 16-byte aligned.  Every other call
+                                       with the flag -- L = 3, a shape the query declines, TPNET_FLAG_NO_MFMA_READOUT beside it --
+                                       is the call without it, bit for bit: never an error */
 
 const char* tpnet_strerror(int status);
 int tpnet_abi_version(void);
@@ -757,6 +763,14 @@ int tpnet_encoder_fused_supported(const tpnet_state* st, int64_t n_rows, int32_t
  * readout and self.mlp as ONE launch (tpnet_anchored_features and the calls built on it; gram may then be NULL).  0 for every
  * d % 4 != 2: tpnet_pair_gram_anchored_supported / tpnet_encoder_fused_supported answer for those, and never count this flag. */
 int tpnet_encoder_rows8_supported(const tpnet_state* st, int64_t n_rows, int32_t K, const tpnet_mlp* mlp);
+/* Does TPNET_FLAG_LAYERS_MFMA send the anchored readout of this shape to the matrix cores?  1 for L = 1, 2, 4 on rows of 36..160
+ * floats with d % 4 == 0 (a table padded to such a width included), K >= 4, N < 2^31; 0 otherwise -- L = 3 among them: that is
+ * tpnet_pair_gram_anchored's own route and needs no flag. */
+int tpnet_encoder_layers_supported(const tpnet_state* st, int64_t n_rows, int32_t K);
+/* The tiles that kernel cuts the flat [n_rows * K] neighbour list into, on the host (tests): their number (0: not a served L /
+ * K), and tile t's first slot and slot count.  L = 1, 2: 8 resp. 5 consecutive slots; L = 4: <= 3 slots, never across a row's end. */
+int64_t tpnet_encoder_layers_tiles(int32_t L, int64_t n_rows, int32_t K);
+int tpnet_encoder_layers_tile(int32_t L, int64_t n_rows, int32_t K, int64_t t, int64_t* first_slot, int32_t* count);
 int tpnet_anchored_features(const tpnet_state* st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                             int32_t K, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, float* gram,
                             float* out, void* stream);

@@ -20,6 +20,7 @@ FLAG_PLAN_SORTED = 64
 FLAG_PLAN_HASHED = 128
 FLAG_NO_MFMA_READOUT = 256
 FLAG_ROWS8 = 512
+FLAG_LAYERS_MFMA = 1024
 
 ERR_INDEX = -4
 ERR_NEED_GRAM = -6
@@ -172,6 +173,9 @@ SIGNATURES = {
     "tpnet_mlp_l4_bwd_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     "tpnet_encoder_fused_supported": (C.c_int, [_SP, C.c_int64, C.c_int32, C.POINTER(Mlp)]),
     "tpnet_encoder_rows8_supported": (C.c_int, [_SP, C.c_int64, C.c_int32, C.POINTER(Mlp)]),
+    "tpnet_encoder_layers_supported": (C.c_int, [_SP, C.c_int64, C.c_int32]),
+    "tpnet_encoder_layers_tiles": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32]),
+    "tpnet_encoder_layers_tile": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "tpnet_mlp_image_bytes": (C.c_size_t, []),
     "tpnet_mlp_prepare_image": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "tpnet_mlp_prepare": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),

@@ -452,6 +452,9 @@ int tpnet_pair_gram_anchored(const tpnet_state* st, const int64_t* neigh, const 
     // supported (K < 4, unaligned outputs, wider rows, the flag): the vector-ALU walk
     if ((flags & TPNET_FLAG_NO_MFMA_READOUT) == 0 && encoder_mfma_supported(*st, n_rows, K) && !((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15))
         return launch_encoder_gram_mfma(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
+    // L = 1, 2, 4 on the matrix cores (encoder_layers.hip): only with TPNET_FLAG_LAYERS_MFMA, same shapes otherwise
+    if (layers_asked(*st, n_rows, K, flags) && !((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15))
+        return launch_encoder_gram_layers(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
     return launch_pair_gram_anchored(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
 }
 

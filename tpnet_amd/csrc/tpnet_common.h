@@ -175,6 +175,16 @@ bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K, uint32
 inline bool rows8_asked(const tpnet_state& st, uint32_t flags) { return (flags & TPNET_FLAG_ROWS8) && st.d % 4 == 2; }
 int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                              int K, double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s);
+// encoder_layers.hip: the matrix-core readout for L = 1, 2, 4 (rows of 36..160 floats, d % 4 == 0, K >= 4), taken only where the
+// caller asks: layers_asked = TPNET_FLAG_LAYERS_MFMA on a shape it serves, not taken back by TPNET_FLAG_NO_MFMA_READOUT -- every
+// other call with the flag keeps the route it has without it
+bool encoder_layers_supported(const tpnet_state& st, int64_t n_rows, int K);
+inline bool layers_asked(const tpnet_state& st, int64_t n_rows, int K, uint32_t flags) {
+    return (flags & TPNET_FLAG_LAYERS_MFMA) && !(flags & (TPNET_FLAG_NO_MFMA_READOUT | TPNET_FLAG_PACKED)) &&
+           encoder_layers_supported(st, n_rows, K);
+}
+int launch_encoder_gram_layers(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
+                               int K, double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s);
 // the same + self.mlp in ONE launch (gram: optional copy of the pre-mlp features [2][n_rows * K][64]; out [2 * n_rows * K][64])
 bool encoder_fused_supported(const tpnet_state& st, int64_t n_rows, int K, const tpnet_mlp* mlp, uint32_t flags = 0);
 int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows, int K,

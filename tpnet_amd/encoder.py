@@ -176,7 +176,8 @@ class TPNetEmbedding(nn.Module):
         if rp is not None:
             # TPNet.py:313-316, [2 n K, F]: every neighbour against the row's two anchors
             # (the module says which widths its anchored call serves: dim % 4 == 0 in 36..512, and with its `rows8_readout` set the
-            # default rule's 110 / 130 / 150)
+            # default rule's 110 / 130 / 150; at num_layer 1, 2, 4 its `layers_readout` puts the readout of rows of 36..160 floats on
+            # the matrix cores, K >= 4)
             if dev.type == "cuda" and hasattr(rp, "get_pair_wise_feature_anchored") and (
                     rp.anchored_call_served(neigh.shape[0], K) if hasattr(rp, "anchored_call_served")
                     else getattr(rp, "engine_dim", rp.dim) % 4 == 0 and 36 <= getattr(rp, "engine_dim", rp.dim) <= 512):

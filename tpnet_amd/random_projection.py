@@ -752,11 +752,14 @@ class RandomProjectionModule(nn.Module):
 
     def _readout_flags(self, raw: bool = False, packed: bool = False, matrix_cores: bool = True) -> int:
         """The TPNET_FLAG_* word of a readout: `raw` / `packed` as in pair_gram (both leave out the log tail, as not_scale does),
-        `matrix_cores=False` keeps the anchored readout off the matrix cores."""
+        `matrix_cores=False` keeps the anchored readout off the matrix cores.  With `layers_readout` set and num_layer != 3 the word
+        carries TPNET_FLAG_LAYERS_MFMA (only the anchored readout reads it)."""
         flags = _lib.FLAG_NOT_SCALE if (self.not_scale or raw or packed) else 0
         if packed:
             flags |= _lib.FLAG_PACKED
-        return flags if matrix_cores else flags | _lib.FLAG_NO_MFMA_READOUT
+        if not matrix_cores:
+            return flags | _lib.FLAG_NO_MFMA_READOUT
+        return flags | _lib.FLAG_LAYERS_MFMA if (self.layers_readout and self.num_layer != 3) else flags
 
     @property
     def packed_feature_dim(self) -> int:
@@ -945,6 +948,20 @@ class RandomProjectionModule(nn.Module):
         if src.dtype != np.int64 or dst.dtype != np.int64 or not src.flags.c_contiguous or not dst.flags.c_contiguous \
                 or src.ndim != 1 or dst.ndim != 1:
             return None
+        if self.layers_readout and self.num_layer != 3 and not self.fused_mlp:
+            # num_layer 1, 2, 4 with `layers_readout`: the pattern's n / 2 neighbours and 2 n / (2 K) anchors go up, the anchored
+            # readout runs on the matrix cores where tpnet_encoder_layers_supported (else on the walk), self.mlp behind it
+            self._ensure_engine()
+            lib = _lib.load()
+            if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
+                return None
+            K = int(lib.tpnet_host_encoder_pattern(src.ctypes.data, dst.ctypes.data, n, self.node_num))
+            if K < 4:
+                return None
+            h = n // 2
+            wd, a1, a2 = self._to_device(src[:h], np.ascontiguousarray(dst[:h:K]), np.ascontiguousarray(dst[h::K]))
+            g = self.pair_gram_anchored(wd.view(h // K, K), a1, a2)
+            return self._apply_mlp(g.view(-1, self.pair_wise_feature_dim))
         prep = self._overlapped_mlp()
         if prep is None:
             return None
@@ -1001,7 +1018,9 @@ class RandomProjectionModule(nn.Module):
         row keeps both anchors' rows in registers for its K neighbours (tpnet_pair_gram_anchored).  Served: rows of whole 16-byte
         vectors, dim % 4 == 0 and 36 <= dim <= 512 (the reference's default widths 120, 140, 160 among them); rows of 36..160
         floats with L = 3 and K >= 4 take the matrix cores (csrc/encoder_mfma.hip) unless matrix_cores=False.  With
-        `rows8_readout` set, rows of dim % 4 == 2 (38 <= dim <= 158, L = 3, K >= 4) are served too, on the matrix cores only."""
+        `rows8_readout` set, rows of dim % 4 == 2 (38 <= dim <= 158, L = 3, K >= 4) are served too, on the matrix cores only.
+        With `layers_readout` set, L = 1, 2 and 4 take the matrix cores on the same rows of 36..160 floats (dim % 4 == 0, K >= 4:
+        csrc/encoder_layers.hip) unless matrix_cores=False; without it they keep the vector-ALU walk."""
         self._ensure_engine()
         nb = neighbor_ids if isinstance(neighbor_ids, torch.Tensor) else np.asarray(neighbor_ids)
         if nb.ndim != 2:
@@ -1034,6 +1053,13 @@ class RandomProjectionModule(nn.Module):
     # scalar geometry at these widths either way
     rows8_readout = False
 
+    # extension, opt-in: num_layer 1, 2 or 4 -- the encoder's anchored readout (pair_gram_anchored and what is built on it:
+    # get_pair_wise_feature_anchored, encoder_pair_features, get_pair_wise_feature on the encoder's host pattern) on the matrix
+    # cores, rows of 36..160 floats with dim % 4 == 0 and K >= 4 (TPNET_FLAG_LAYERS_MFMA, csrc/encoder_layers.hip;
+    # profiles/encoder_layers.md); every other shape keeps its route.  False: the vector-ALU walk resp. the general pair kernel,
+    # bit for bit.  No effect at num_layer 3.  self.mlp behind the readout is what _apply_mlp picks either way
+    layers_readout = False
+
     def _rows8(self, rows, K, mlp_ref=None) -> int:
         """_lib.FLAG_ROWS8 if `rows8_readout` is set and tpnet_encoder_rows8_supported answers 1 for `rows` x K neighbours (with
         `mlp_ref`: for readout + self.mlp in one launch), else 0."""
@@ -1065,7 +1091,8 @@ class RandomProjectionModule(nn.Module):
         ids, L = 3, K >= 4: one launch on rows of 36..160 floats (csrc/encoder_mfma.hip); on rows of 164..512 floats one launch
         (csrc/anchored_feature.hip) where that kernel is the route of the width's geometry class, else the anchored walk and the
         dense layers as two launches (tpnet_encoder_fused_supported tells which).  With `rows8_readout` set, rows of
-        dim % 4 == 2 (38 <= dim <= 158) take the same one launch (tpnet_encoder_rows8_supported)."""
+        dim % 4 == 2 (38 <= dim <= 158) take the same one launch (tpnet_encoder_rows8_supported).  L != 3: pair_gram_anchored, then
+        self.mlp -- with `layers_readout` set the readout on the matrix cores (tpnet_encoder_layers_supported), else the walk."""
         prep = self._overlapped_mlp() if self._plist()[0].device.type == "cuda" else None
         if prep is not None and isinstance(neighbor_ids, torch.Tensor) and neighbor_ids.is_cuda:
             self._ensure_engine()
