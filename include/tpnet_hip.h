@@ -55,7 +55,9 @@ extern "C" {
                                     TPNET_FLAG_ROWS8 / tpnet_encoder_rows8_supported (the encoder's matrix-core calls on rows of d % 4 == 2);
                                     tpnet_import_layers_ld / tpnet_export_layers_ld / tpnet_pad_rows / tpnet_gather_rows_ld (a table whose rows
                                     are kept wider than the caller's, pad columns zero);
-                                    TPNET_FLAG_LAYERS_MFMA / tpnet_encoder_layers_* (the encoder's matrix-core readout for num_layer 1, 2, 4) */
+                                    TPNET_FLAG_LAYERS_MFMA / tpnet_encoder_layers_* (the encoder's matrix-core readout for num_layer 1, 2, 4);
+                                    tpnet_pair_gram_fanout* (one source against C candidates), tpnet_neg_sample_many (per-query candidates),
+                                    tpnet_lp_ranking* (a batch's MRR and Hits@k as one device record) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -314,6 +316,24 @@ int tpnet_pair_gram_anchored(const tpnet_state* st, const int64_t* neigh, const 
                              int64_t n_rows, int32_t K, double now_time, double lambda, uint32_t flags, float* out1,
                              float* out2, void* stream);
 int tpnet_pair_gram_anchored_supported(const tpnet_state* st);
+
+/* The one-vs-many readout of the ranking protocol: row i has ONE source src[i] and C candidate destinations cand[i*C .. i*C+C);
+ * out[(i*C + c)] = G(src[i], cand[i*C + c]), rows of (2L+2)^2 floats laid out and scaled like tpnet_pair_gram's, with the SOURCE's
+ * layers first -- rows stacked [src 0..L ; cand 0..L], the decoder's order (models/modules.py:112; NOT the anchored readout's, where
+ * the neighbour comes first): this IS tpnet_pair_gram(repeat(src, C), cand) before self.mlp.  One lane group walks a unit = (row,
+ * chunk of candidates; chunks as tpnet_pair_gram_anchored cuts them): the source's L+1 rows are fetched and decayed once per unit
+ * and stay in registers, its own Gram block is reduced once per unit; per candidate only its L+1 rows are loaded and (L+1)^2 cross
+ * products + (L+1)(L+2)/2 self products are formed (26 at L = 3; the anchored walk forms 42), candidate k+1's rows in flight while
+ * candidate k is reduced.  Every row goes through the same lazy per-row decay as every other readout, and a pair's row depends on
+ * its two nodes alone: the same (src, cand) gives the same bits whatever n_rows, C and its position.
+ * Geometry: the anchored walk's class, d % 4 == 0, 36 <= d <= 512, L = 1..4 (tpnet_pair_gram_fanout_supported returns 1); other
+ * states: TPNET_ERR_BAD_ARG -- the caller expands the ids and takes tpnet_pair_gram.  TPNET_FLAG_NOT_SCALE is honoured,
+ * TPNET_FLAG_PACKED is refused.  Null pointers, C <= 0, n_rows < 0, n_rows * C >= 2^31 or an `out` that is not 16-byte aligned:
+ * TPNET_ERR_BAD_ARG, nothing launched; n_rows == 0: TPNET_OK.  An id outside [0, N), source or candidate: the pairs it touches are
+ * NaN rows (a source: its C rows; a candidate: its one row), every other row is untouched, the state's error word is raised. */
+int tpnet_pair_gram_fanout(const tpnet_state* st, const int64_t* src, const int64_t* cand, int64_t n_rows, int32_t C,
+                           double now_time, double lambda, uint32_t flags, float* out, void* stream);
+int tpnet_pair_gram_fanout_supported(const tpnet_state* st);
 
 /* Workspace for tpnet_update / tpnet_run_stream with at most max_edges edges per call. */
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch);
@@ -624,6 +644,29 @@ int tpnet_neg_sample(void* neg, int64_t E, int32_t strategy, int64_t size, const
                      int64_t* out_src, int64_t* out_dst, void* stream);
 int tpnet_neg_check(void* neg, void* stream);
 
+/* ---- per-query candidates of the ranking protocol (additive to ABI 7; csrc/negsampler.hip) -------------------
+ * tpnet_neg_sample_many: every query i = (s, d, t) of a batch of B positives gets its own row of Q candidate destinations,
+ * cand[i*Q .. i*Q+Q), of which the first n_hist[i] <= Qh are destinations `s` was seen with earlier.  A rule of its own: no strategy,
+ * no batch window; it reads the table tpnet_neg_build made.  word / perm: as defined above; perm_i = perm under the key
+ * (seed & 0xffffffff, (seed >> 32) ^ i) -- the query's index within the call enters the second word of the Philox key, the counter
+ * stays (a, b, tag, call_index) -- so a row depends on (seed, call_index, i) and its own (s, d, t) alone, not on B or on other rows.
+ *   exclusion:   a destination d' is excluded when d' == d, or when the table holds an occurrence of (s, d') at time exactly t (another
+ *                positive of the same instant).
+ *   historical:  e_0 .. e_{R-1} = the unique edges with source s in ascending destination order.  Visit e_{perm_i(R, tag 5, j)},
+ *                j = 0, 1, ...: entry j is eligible when its destination is not excluded and its first occurrence time is < t.  The
+ *                first Qh eligible ones, in visiting order, fill cand[i, 0 .. h_i); n_hist[i] = h_i = min(Qh, #eligible).
+ *   random:      visit Ud[perm_i(|Ud|, tag 6, j)], j = 0, 1, ...; accept a destination that is not excluded and not one of the row's
+ *                historical picks, in visiting order, until the row is full or all of Ud has been visited.  Slots that cannot be filled
+ *                hold -1: only when fewer than Q admissible distinct destinations exist.
+ * So a row's entries (other than -1) are distinct, never the true destination and never a same-instant positive of the source.
+ * One wave per query (64 visiting slots per step, ballot compaction, binary searches into the table and the occurrence lists), one
+ * launch on `stream`, no scratch, no synchronisation.  batch_src / batch_dst: device int64[B], batch_t: device float64[B]; cand: device
+ * int64[B*Q]; n_hist: device int32[B].  1 <= Q < 2^16, 0 <= Qh <= Q, 0 <= B < 2^31; B == 0: TPNET_OK, nothing launched.  Null pointers
+ * and sizes out of range: TPNET_ERR_BAD_ARG, nothing launched. */
+int tpnet_neg_sample_many(const void* neg, int64_t E, const int64_t* batch_src, const int64_t* batch_dst, const double* batch_t,
+                          int64_t B, int32_t Q, int32_t Qh, uint64_t seed, uint32_t call_index, int64_t* cand, int32_t* n_hist,
+                          void* stream);
+
 /* ---- a batch's link-prediction metrics on the device (additive to ABI 7; csrc/metrics.hip) ------------------
  * What the reference's evaluation loop brings to the host per batch (evaluate_models_utils.py:187-193, utils/metrics.py:8-22):
  * BCEWithLogitsLoss(...).item() and sklearn's average_precision_score / roc_auc_score on predicts.sigmoid().cpu().
@@ -674,6 +717,27 @@ int tpnet_lp_metrics(const float* pos_score, int64_t n_pos, const float* neg_sco
 int tpnet_lp_train_loss(const float* pos_score, int64_t n_pos, const float* neg_score, int64_t n_neg, const float* pos_logit,
                         const float* neg_logit, void* scratch, size_t scratch_bytes, void* record, float* pos_grad, float* neg_grad,
                         float* loss_out, void* stream);
+
+/* ---- a batch's one-vs-many ranking record on the device (additive to ABI 7; csrc/metrics.hip) ----------------
+ * logits: [B, C1] fp32 row-major, one query per row; column 0 is the positive's logit p, column 1 + c a candidate's logit q_c, valid
+ * when cand_or_null == NULL or cand_or_null[i*(C1-1) + c] >= 0 (the -1 slots of tpnet_neg_sample_many are absent candidates).
+ * Per query i, over its valid candidates:  g_i = #{q > p},  e_i = #{q == p},  m_i = 2 + 2 g_i + e_i = twice the rank (ties get the
+ * mean of the optimistic and the pessimistic rank).  Comparisons are IEEE on the fp32 logits as given -- no sigmoid, so a saturating
+ * sigmoid adds no ties.  A query is NOT counted when p is NaN or a valid candidate's logit is NaN (flag bit 1, value 2; a NaN under
+ * an absent slot is not looked at), or when it has no valid candidate (flag bit 2, value 4).  n = the counted queries.
+ * record: ONE 64-byte device record, 8-byte aligned:
+ *   { double mrr = (1/n) sum 2/m_i, double hits1 = #{m_i <= 2 k1} / n, double hits2 (k2), double hits3 (k3),
+ *     int64 m_sum = sum m_i, int64 n, int64 n_valid_candidates (over all B queries, counted or not), int64 flags }
+ * n == 0: the four doubles are NaN and flag bit 0 (value 1) is set.  Each hits word is ONE division of an integer count by n.
+ * Two launches on `stream`: one wave per query strided over its C1 columns (integer counts) writes m_i (0: not counted), the
+ * query's valid count and its flags into scratch; one finish workgroup sums 2/m_i in float64 in a fixed order (thread k: queries k,
+ * k + 1024, ...; then a halving tree) -- no floating-point atomics: the same input gives the same record bits on every run.
+ * scratch: tpnet_lp_ranking_scratch_bytes(B, C1) device bytes, 8-byte aligned (not needed when B == 0).  0 <= B < 2^31,
+ * 1 <= C1 <= 2^20, k1, k2, k3 >= 1.  A size out of range, a null or misaligned pointer: TPNET_ERR_BAD_ARG (the size helper: 0),
+ * nothing launched; a short scratch: TPNET_ERR_WORKSPACE. */
+size_t tpnet_lp_ranking_scratch_bytes(int64_t B, int32_t C1);
+int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* cand_or_null, int32_t k1, int32_t k2, int32_t k3,
+                     void* scratch, size_t scratch_bytes, int64_t* record, void* stream);
 
 /* ---- the EdgeBank baseline on the device (additive to ABI 7; csrc/edgebank.hip) ------------------------------
  * models/EdgeBank.py as evaluate_models_utils.py:269-318 drives it: for every test batch the reference builds a memory over

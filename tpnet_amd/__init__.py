@@ -8,13 +8,15 @@ from ._lib import TPNetHipError, load as load_library  # noqa: F401
 from .sampler import GpuRecentNeighborSampler, GpuNeighborSampler  # noqa: F401
 from .negative_sampler import GpuNegativeEdgeSampler  # noqa: F401
 from .metrics import LinkPredictionMeter, get_link_prediction_metrics, link_prediction_metrics_host  # noqa: F401
+from .metrics import LinkRankingMeter, link_ranking_metrics_host  # noqa: F401
 from .edge_bank import GpuEdgeBank, edge_bank_host, edge_bank_link_prediction  # noqa: F401
 from .encoder import TimeEncoder, FeedForwardNet, MLPMixer, TPNetEmbedding, TPNet  # noqa: F401
 from .callers import evaluate_link_prediction, evaluate_edge_bank_link_prediction, create_optimizer  # noqa: F401
+from .callers import evaluate_link_ranking  # noqa: F401
 from .optimizer import DeviceAdam, DeviceSGD, DeviceRMSprop, optimizer_step_host  # noqa: F401
 
 __all__ = ["RandomProjectionModule", "TPNetHipError", "load_library", "TimeEncoder", "FeedForwardNet", "MLPMixer", "TPNetEmbedding",
            "TPNet", "GpuRecentNeighborSampler", "GpuNeighborSampler", "GpuNegativeEdgeSampler", "LinkPredictionMeter",
            "get_link_prediction_metrics", "link_prediction_metrics_host", "evaluate_link_prediction", "GpuEdgeBank", "edge_bank_host",
            "edge_bank_link_prediction", "evaluate_edge_bank_link_prediction", "create_optimizer", "DeviceAdam", "DeviceSGD",
-           "DeviceRMSprop", "optimizer_step_host"]
+           "DeviceRMSprop", "optimizer_step_host", "LinkRankingMeter", "link_ranking_metrics_host", "evaluate_link_ranking"]

@@ -80,6 +80,8 @@ SIGNATURES = {
     "tpnet_pair_gram_anchored": (C.c_int, [_SP, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P, _P,
                                            _P]),
     "tpnet_pair_gram_anchored_supported": (C.c_int, [_SP]),
+    "tpnet_pair_gram_fanout": (C.c_int, [_SP, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P, _P]),
+    "tpnet_pair_gram_fanout_supported": (C.c_int, [_SP]),
     "tpnet_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes_capped": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_size_t]),
@@ -126,6 +128,10 @@ SIGNATURES = {
     "tpnet_neg_sample": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_uint64,
                                    C.c_uint32, _P, C.c_size_t, _P, _P, _P]),
     "tpnet_neg_check": (C.c_int, [_P, _P]),
+    "tpnet_neg_sample_many": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, _P, _P,
+                                        _P]),
+    "tpnet_lp_ranking_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "tpnet_lp_ranking": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
     "tpnet_lp_metrics_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "tpnet_lp_metrics": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P, _P]),
     "tpnet_lp_train_loss": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P]),

@@ -9,6 +9,7 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `run_evaluation`          -- the evaluation loop's order with any of the three negative strategies (evaluate_models_utils.py:56-72).
 * `evaluate_link_prediction` -- the same loop scored on the device: per-batch loss, AP and ROC-AUC (evaluate_models_utils.py:186-198).
 * `evaluate_edge_bank_link_prediction` -- the EdgeBank baseline's evaluation loop on the device (evaluate_models_utils.py:269-318).
+* `evaluate_link_ranking`   -- one-vs-many ranking evaluation (MRR, Hits@k): per-query candidates, one-to-many decoder, device meter.
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
 * `train_link_prediction_epoch` -- the same epoch with the loss, the backward and the optimizer step (:375-386), the loss and the
@@ -42,16 +43,43 @@ class LinkPredictor_v1(nn.Module):
 
     def forward(self, src_node_ids: np.ndarray, dst_node_ids: np.ndarray, src_node_embeddings: torch.Tensor,
                 dst_node_embeddings: torch.Tensor):
+        rp = self.random_projections
+        return self._decode(lambda: rp.get_pair_wise_feature(src_node_ids=src_node_ids, dst_node_ids=dst_node_ids),
+                            src_node_embeddings, dst_node_embeddings)
+
+    def forward_one_to_many(self, src_node_ids, cand_node_ids, src_node_embeddings: Optional[torch.Tensor] = None,
+                            cand_node_embeddings: Optional[torch.Tensor] = None):
+        """Extension, the ranking protocol: src_node_ids [B], cand_node_ids [B, C] -> logits [B, C].  `forward` on the expanded
+        pairs (repeat(src, C), cand.reshape(-1)) with the pairwise feature taken through the module's one-to-many readout
+        (`get_pair_wise_feature_one_to_many`: each source's rows fetched once for its C candidates).  Embeddings, when given, are
+        per pair: [B*C, D].  With `not_encode` they may be None (`forward` would zero them: modules.py:106-108); otherwise
+        ValueError.  `fused` keeps its meaning."""
+        cand = cand_node_ids if isinstance(cand_node_ids, torch.Tensor) else np.asarray(cand_node_ids)
+        if cand.ndim != 2 or len(src_node_ids) != cand.shape[0]:
+            raise ValueError("forward_one_to_many: src_node_ids [B] and cand_node_ids [B, C] are expected")
+        B, C = cand.shape
+        if src_node_embeddings is None or cand_node_embeddings is None:
+            if not self.not_encode:
+                raise ValueError("forward_one_to_many: without not_encode the per-pair embeddings [B*C, D] are required")
+            w = self.fc1.weight
+            D = (self.fc1.in_features - self.random_feature_dim) // 2
+            src_node_embeddings = cand_node_embeddings = torch.zeros((B * C, D), dtype=w.dtype, device=w.device)
+        rp = self.random_projections
+        out = self._decode(lambda: rp.get_pair_wise_feature_one_to_many(src_node_ids, cand), src_node_embeddings, cand_node_embeddings)
+        return out.view(B, C, -1).squeeze(-1)
+
+    def _decode(self, pair_feature: Callable, src_node_embeddings: torch.Tensor, dst_node_embeddings: torch.Tensor):
+        """What `forward` does with its pairs' embeddings; pair_feature() = their pairwise features (called only with a module)."""
         if isinstance(self.fused, str):
             if self.fused != "f32":
                 raise ValueError(f"LinkPredictor_v1.fused: {self.fused!r} is none of False, True, 'f32'")
-            return self._forward_f32(src_node_ids, dst_node_ids, src_node_embeddings, dst_node_embeddings)
+            return self._decode_f32(pair_feature, src_node_embeddings, dst_node_embeddings)
         if self.not_encode:                                        # modules.py:106-108
             src_node_embeddings = torch.zeros_like(src_node_embeddings)
             dst_node_embeddings = torch.zeros_like(dst_node_embeddings)
         feat = None
         if self.random_projections is not None:                    # modules.py:112-114
-            feat = self.random_projections.get_pair_wise_feature(src_node_ids=src_node_ids, dst_node_ids=dst_node_ids)
+            feat = pair_feature()
         if self.fused and src_node_embeddings.is_cuda:
             from . import fused_decoder as fd
             D, F = src_node_embeddings.shape[1], (0 if feat is None else feat.shape[1])
@@ -61,12 +89,12 @@ class LinkPredictor_v1(nn.Module):
         parts = [src_node_embeddings, dst_node_embeddings] + ([feat] if feat is not None else [])
         return self.fc2(self.act(self.fc1(torch.cat(parts, dim=1))))
 
-    def _forward_f32(self, src_node_ids, dst_node_ids, src_emb, dst_emb):
+    def _decode_f32(self, pair_feature, src_emb, dst_emb):
         """fused == "f32": the fp32-class kernels on the embeddings as they are (with not_encode they are not read: no zeros are
         made) where they serve the call; anything else -- a CPU module, another dtype, an unserved shape -- is fused = False's path."""
         feat = None
         if self.random_projections is not None:                    # modules.py:112-114
-            feat = self.random_projections.get_pair_wise_feature(src_node_ids=src_node_ids, dst_node_ids=dst_node_ids)
+            feat = pair_feature()
         if src_emb.is_cuda:
             from . import fused_decoder as fd
             if fd.serves_f32(self.fc1, self.fc2, src_emb, dst_emb, feat, self.not_encode):
@@ -274,6 +302,61 @@ def evaluate_edge_bank_link_prediction(edge_bank, negative_sampler, num_history_
             neg_src = src_d[s]
         pos_prob, neg_prob = edge_bank.predict_device(num_history_edges + b0, src_d[s], dst_d[s], to_dev(neg_src), to_dev(neg_dst))
         meter.add_probabilities(pos_prob, neg_prob)
+    return meter.results()
+
+
+def evaluate_link_ranking(rp, negative_sampler, src, dst, t, batch_size: int, num_negatives: int, decoder, encoder: Optional[Callable] = None,
+                          num_historical: Optional[int] = None, candidates=None, meter=None, pairs_per_call: int = 1 << 18):
+    """One-vs-many ranking evaluation (extension: the protocol temporal link prediction is reported with today; the reference scores
+    one negative per positive): every positive edge (s, d, t) is ranked against Q = num_negatives negative destinations of the same
+    source at the same time; MRR and Hits@k per batch from a `LinkRankingMeter` (tpnet_amd/metrics.py).  Under no_grad, chronological
+    batches with a ragged tail, no reset of the projections.  Per batch:
+      1. the candidates [b, Q]: rows of `candidates` (host or device [E, Q], -1 = absent) if given, else
+         `negative_sampler.sample_many_device(src, dst, t, Q, num_historical)`;
+      2. the logits [b, 1 + Q] over [dst | candidates], an absent slot scored as the row's true destination (and not ranked):
+         encoder None: `decoder.forward_one_to_many(src, ids)` (the decoder must be `not_encode`); else `encoder(src_ids, dst_ids,
+         times) -> (src_emb, dst_emb)` on the expanded pairs (TPNet.compute_src_dst_node_temporal_embeddings' signature), in slices of
+         at most pairs_per_call pairs, and the embeddings go to `forward_one_to_many`;
+      3. `rp.update(src, dst, t)` AFTER scoring (evaluate_models_utils.py:182-184);
+      4. `meter.add(logits, candidates)`.
+    Candidates and logits never leave the device and no batch synchronises for the metric (`update` plans from host arrays: a
+    stream given as device tensors is copied to the host once, before the loop).  -> `meter.results()`.  meter: None = a new one of one
+    record per batch; a given one is appended to.  Composes with `evaluate_with_restore`."""
+    from .metrics import LinkRankingMeter
+    dev = rp.random_projections[0].device
+    E, Q = len(src), int(num_negatives)
+    if meter is None:
+        meter = LinkRankingMeter(max(1, -(-E // batch_size)), dev)
+    to_dev = lambda a, dt: a.to(dev, dt).contiguous() if isinstance(a, torch.Tensor) \
+        else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64 if dt == torch.int64 else np.float64)).to(dev)
+    src_d, dst_d, t_d = to_dev(src, torch.int64), to_dev(dst, torch.int64), to_dev(t, torch.float64)
+    # `update` plans a batch from host arrays and reads its last stamp on the host: one copy of the stream, before the loop
+    to_host = lambda a, dt: a.cpu().numpy().astype(dt, copy=False) if isinstance(a, torch.Tensor) else np.ascontiguousarray(a, dtype=dt)
+    src_h, dst_h, t_h = to_host(src, np.int64), to_host(dst, np.int64), to_host(t, np.float64)
+    cand_all = to_dev(candidates, torch.int64) if candidates is not None else None
+    if cand_all is not None and tuple(cand_all.shape) != (E, Q):
+        raise ValueError(f"candidates must be [{E}, {Q}]")
+    with torch.no_grad():
+        for b0 in range(0, E, batch_size):
+            s = slice(b0, min(b0 + batch_size, E))
+            b = s.stop - s.start
+            if cand_all is not None:
+                cand = cand_all[s]
+            else:
+                cand, _ = negative_sampler.sample_many_device(src_d[s], dst_d[s], t_d[s], Q, num_historical)
+            # ---- from here on given and sampled candidates take the same code
+            ids = torch.cat([dst_d[s].unsqueeze(1), torch.where(cand < 0, dst_d[s].unsqueeze(1), cand)], dim=1).contiguous()
+            if encoder is None:
+                logits = decoder.forward_one_to_many(src_d[s], ids)
+            else:
+                n = b * (Q + 1)
+                es, ed = src_d[s].repeat_interleave(Q + 1), ids.reshape(-1)
+                et = t_d[s].repeat_interleave(Q + 1)
+                parts = [encoder(es[p0:p0 + pairs_per_call], ed[p0:p0 + pairs_per_call], et[p0:p0 + pairs_per_call])
+                         for p0 in range(0, n, pairs_per_call)]
+                logits = decoder.forward_one_to_many(src_d[s], ids, torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]))
+            rp.update(src_h[s], dst_h[s], t_h[s])                   # after scoring (:182-184)
+            meter.add(logits.reshape(b, Q + 1).float(), cand)
     return meter.results()
 
 

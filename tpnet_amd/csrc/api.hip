@@ -463,6 +463,23 @@ int tpnet_pair_gram_anchored_supported(const tpnet_state* st) {
     return pair_gram_anchored_supported(*st) ? 1 : 0;
 }
 
+int tpnet_pair_gram_fanout(const tpnet_state* st, const int64_t* src, const int64_t* cand, int64_t n_rows, int32_t C,
+                           double now_time, double lambda, uint32_t flags, float* out, void* stream) {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (n_rows < 0 || C <= 0 || !src || !cand || !out || (reinterpret_cast<uintptr_t>(out) & 15)) return TPNET_ERR_BAD_ARG;
+    if (n_rows >= (1ll << 31) / C) return TPNET_ERR_BAD_ARG;
+    if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;   // packed rows exist for the one-pair readout only
+    if (n_rows == 0) return TPNET_OK;
+    if (!pair_gram_fanout_supported(*st)) return TPNET_ERR_BAD_ARG;   // (narrow or odd rows: the caller expands and takes tpnet_pair_gram)
+    return launch_pair_gram_fanout(*st, src, cand, n_rows, C, now_time, lambda, flags, out, (hipStream_t)stream);
+}
+
+int tpnet_pair_gram_fanout_supported(const tpnet_state* st) {
+    if (check_state(st)) return 0;
+    return pair_gram_fanout_supported(*st) ? 1 : 0;
+}
+
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch) { return plan_bytes(max_edges, batch); }
 
 // bytes for a stream of max_edges on the windowed schedule in chunks of at most chunk_cap edges: one chunk's plan, or -- several

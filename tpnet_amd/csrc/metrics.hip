@@ -208,6 +208,103 @@ static int lpm_enqueue(const float* pos_score, int64_t n_pos, const float* neg_s
     return TPNET_OK;
 }
 
+// ---- one-vs-many ranking (tpnet_lp_ranking; the rule: include/tpnet_hip.h) ------------------------------------------------------------
+static constexpr int LPR_BLOCK = 256;                // four waves, one query each
+static constexpr int32_t LPR_MAX_C1 = 1 << 20;
+enum { LPR_FLAG_NO_QUERY = 1, LPR_FLAG_NAN_SCORE = 2, LPR_FLAG_EMPTY_QUERY = 4 };
+
+// scratch: three words per query -- m_i (0: not counted), its valid candidates, its flags
+struct LprScratch { uint32_t* m; uint32_t* nv; uint32_t* fl; };
+static void lpr_layout(Arena& a, LprScratch& w, int64_t B) {
+    const size_t n = (size_t)(B < 1 ? 1 : B);
+    w.m = a.take<uint32_t>(n);
+    w.nv = a.take<uint32_t>(n);
+    w.fl = a.take<uint32_t>(n);
+}
+static bool lpr_sizes_ok(int64_t B, int32_t C1) { return B >= 0 && B < (1ll << 31) && C1 >= 1 && C1 <= LPR_MAX_C1; }
+
+// one wave per query, strided over its C1 columns: integer counts only, combined by shuffles
+__global__ __launch_bounds__(LPR_BLOCK) void k_lpr_rows(const float* __restrict__ logits, int64_t B, int C1,
+                                                        const int64_t* __restrict__ cand, uint32_t* __restrict__ m_out,
+                                                        uint32_t* __restrict__ nv_out, uint32_t* __restrict__ fl_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (LPR_BLOCK / 64) + (threadIdx.x >> 6);
+    if (i >= B) return;
+    const float* row = logits + i * (int64_t)C1;
+    const int64_t* crow = cand ? cand + i * (int64_t)(C1 - 1) : nullptr;
+    const float p = row[0];
+    uint32_t g = 0, e = 0, nv = 0, bad = isnan(p) ? 1u : 0u;
+    for (int c = lane; c < C1 - 1; c += 64) {
+        if (crow && crow[c] < 0) continue;
+        const float q = row[1 + c];
+        nv += 1u;
+        g += (uint32_t)(q > p);
+        e += (uint32_t)(q == p);
+        bad |= isnan(q) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        g += (uint32_t)__shfl_xor((int)g, o, 64);
+        e += (uint32_t)__shfl_xor((int)e, o, 64);
+        nv += (uint32_t)__shfl_xor((int)nv, o, 64);
+        bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+    }
+    if (lane == 0) {
+        const uint32_t fl = (bad ? (uint32_t)LPR_FLAG_NAN_SCORE : 0u) | (nv == 0 ? (uint32_t)LPR_FLAG_EMPTY_QUERY : 0u);
+        m_out[i] = fl ? 0u : 2u + 2u * g + e;
+        nv_out[i] = nv;
+        fl_out[i] = fl;
+    }
+}
+
+// ONE workgroup: thread k takes queries k, k + 1024, ... in ascending order, the 1024 partial sums meet in the tree
+__global__ __launch_bounds__(LPM_FIN) void k_lpr_finish(int64_t B, const uint32_t* __restrict__ m, const uint32_t* __restrict__ nv,
+                                                        const uint32_t* __restrict__ fl, int k1, int k2, int k3,
+                                                        int64_t* __restrict__ record) {
+    __shared__ double shd[LPM_FIN];
+    __shared__ long long shi[LPM_FIN];
+    double rr = 0.0;
+    long long msum = 0, n = 0, nvalid = 0, h1 = 0, h2 = 0, h3 = 0, flags = 0;
+    for (int64_t i = threadIdx.x; i < B; i += LPM_FIN) {
+        const long long mi = (long long)m[i];
+        nvalid += (long long)nv[i];
+        flags |= (long long)fl[i];
+        if (mi) {
+            rr += 2.0 / (double)mi;
+            msum += mi;
+            n += 1;
+            h1 += mi <= 2ll * k1;
+            h2 += mi <= 2ll * k2;
+            h3 += mi <= 2ll * k3;
+        }
+    }
+    rr = lpm_tree_sum<LPM_FIN>(rr, shd);
+    msum = lpm_tree_sum<LPM_FIN>(msum, shi);
+    n = lpm_tree_sum<LPM_FIN>(n, shi);
+    nvalid = lpm_tree_sum<LPM_FIN>(nvalid, shi);
+    h1 = lpm_tree_sum<LPM_FIN>(h1, shi);
+    h2 = lpm_tree_sum<LPM_FIN>(h2, shi);
+    h3 = lpm_tree_sum<LPM_FIN>(h3, shi);
+    // (flags: one bit at a time through the sum tree -- a count, then a test)
+    long long f2 = lpm_tree_sum<LPM_FIN>((long long)((flags & LPR_FLAG_NAN_SCORE) != 0), shi);
+    long long f4 = lpm_tree_sum<LPM_FIN>((long long)((flags & LPR_FLAG_EMPTY_QUERY) != 0), shi);
+    if (threadIdx.x == 0) {
+        const double nan = __builtin_nan("");
+        double* rd = reinterpret_cast<double*>(record);
+        long long* ri = reinterpret_cast<long long*>(record);
+        const double dn = (double)n;
+        rd[0] = n ? rr / dn : nan;
+        rd[1] = n ? (double)h1 / dn : nan;
+        rd[2] = n ? (double)h2 / dn : nan;
+        rd[3] = n ? (double)h3 / dn : nan;
+        ri[4] = msum;
+        ri[5] = n;
+        ri[6] = nvalid;
+        ri[7] = (n ? 0ll : (long long)LPR_FLAG_NO_QUERY) | (f2 ? (long long)LPR_FLAG_NAN_SCORE : 0ll) |
+                (f4 ? (long long)LPR_FLAG_EMPTY_QUERY : 0ll);
+    }
+}
+
 }  // namespace tpnet
 
 using namespace tpnet;
@@ -229,6 +326,31 @@ int tpnet_lp_train_loss(const float* pos_score, int64_t n_pos, const float* neg_
     if ((n_pos > 0 && (!pos_logit || !pos_grad)) || (n_neg > 0 && (!neg_logit || !neg_grad))) return TPNET_ERR_BAD_ARG;
     return lpm_enqueue(pos_score, n_pos, neg_score, n_neg, pos_logit, neg_logit, scratch, scratch_bytes, record, true, pos_grad,
                        neg_grad, loss_out, stream);
+}
+
+size_t tpnet_lp_ranking_scratch_bytes(int64_t B, int32_t C1) {
+    if (!lpr_sizes_ok(B, C1)) return 0;
+    return measured([&](Arena& a) { LprScratch w; lpr_layout(a, w, B); });
+}
+
+int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* cand_or_null, int32_t k1, int32_t k2, int32_t k3,
+                     void* scratch, size_t scratch_bytes, int64_t* record, void* stream) {
+    if (!lpr_sizes_ok(B, C1) || k1 < 1 || k2 < 1 || k3 < 1 || !record || ((size_t)record & 7)) return TPNET_ERR_BAD_ARG;
+    if (B > 0 && (!logits || !scratch || ((size_t)scratch & 7))) return TPNET_ERR_BAD_ARG;
+    if (B > 0 && scratch_bytes < tpnet_lp_ranking_scratch_bytes(B, C1)) return TPNET_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    Arena wa(B > 0 ? scratch : nullptr, scratch_bytes);
+    LprScratch w;
+    lpr_layout(wa, w, B);
+    if (B > 0) {
+        const int per = LPR_BLOCK / 64;
+        hipLaunchKernelGGL(k_lpr_rows, dim3((unsigned)((B + per - 1) / per)), dim3(LPR_BLOCK), 0, s, logits, B, (int)C1, cand_or_null,
+                           w.m, w.nv, w.fl);
+    }
+    hipLaunchKernelGGL(k_lpr_finish, dim3(1), dim3(LPM_FIN), 0, s, B, (const uint32_t*)w.m, (const uint32_t*)w.nv,
+                       (const uint32_t*)w.fl, (int)k1, (int)k2, (int)k3, record);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
 }
 
 }  // extern "C"

@@ -256,6 +256,100 @@ __global__ __launch_bounds__(256) void k_neg_pick(uint32_t* __restrict__ hdr, co
     if (!P && tid == 0) hdr[NEG_ERR] = 1u;
 }
 
+// ---- per-query candidates (tpnet_neg_sample_many; the rule: include/tpnet_hip.h) ---------------------------------------------------
+static constexpr int NEGM_BLOCK = 256;                // four waves, one query each
+
+// first index in [lo, hi) of the ascending keys whose key is >= `key`
+__device__ __forceinline__ uint32_t key_lower_bound(const uint64_t* __restrict__ k, uint32_t lo, uint32_t hi, uint64_t key) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (k[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// does unique edge e occur at time exactly t?  (its occurrence times are ascending in times[ustart[e] .. ustart[e + 1]))
+__device__ __forceinline__ bool occurs_at(const uint32_t* __restrict__ ustart, const double* __restrict__ times, uint32_t U,
+                                          uint32_t E, uint32_t e, double t) {
+    const uint32_t end = (e + 1 < U) ? ustart[e + 1] : E;
+    uint32_t lo = ustart[e], hi = end;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (times[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && times[lo] == t;
+}
+
+// One wave per query i = (s, d, t).  Historical part: the source's run [e0, e0 + R) of the table, visited in the order of perm_i(R, 5, .),
+// 64 slots per step; the eligible ones are compacted by a ballot into cand[i, 0 .. h).  Random part: Ud in the order of perm_i(|Ud|, 6, .),
+// 64 slots per step; a slot's destination is looked up in the source's run (excluded when that edge occurs at t) and among the row's h
+// historical picks -- read back from the row itself, every lane the same word at a time (a broadcast), behind a workgroup fence.
+__global__ __launch_bounds__(NEGM_BLOCK) void k_neg_many(const uint32_t* __restrict__ hdr, const uint64_t* __restrict__ ukey,
+                                                         const uint32_t* __restrict__ ustart, const double* __restrict__ ufirst,
+                                                         const double* __restrict__ times, const int64_t* __restrict__ ud, uint32_t E,
+                                                         const int64_t* __restrict__ bs, const int64_t* __restrict__ bd,
+                                                         const double* __restrict__ bt, int64_t B, int Q, int Qh, NegKey key,
+                                                         int64_t* cand, int32_t* __restrict__ n_hist) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (NEGM_BLOCK / 64) + (threadIdx.x >> 6);
+    if (i >= B) return;                                          // (a whole wave leaves: no workgroup barrier below)
+    const uint32_t U = hdr[NEG_U];
+    const uint64_t nud = hdr[NEG_NUD];
+    const int64_t s = bs[i], d = bd[i];
+    const double t = bt[i];
+    int64_t* row = cand + i * (int64_t)Q;
+    const NegKey k{key.k0, key.k1 ^ (uint32_t)i, key.call};
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t e0 = 0, R = 0;
+    if ((uint64_t)s < (1ull << 31)) {                            // (no edge of the table has another source)
+        e0 = key_lower_bound(ukey, 0, U, (uint64_t)s << 32);
+        R = key_lower_bound(ukey, e0, U, ((uint64_t)s + 1) << 32) - e0;
+    }
+    int h = 0;
+    for (uint32_t base = 0; base < R && h < Qh; base += 64) {
+        const uint32_t j = base + (uint32_t)lane;
+        bool ok = false;
+        int64_t dd = 0;
+        if (j < R) {
+            const uint32_t e = e0 + (uint32_t)neg_perm(R, 5, j, k);
+            dd = (int64_t)(ukey[e] & 0xFFFFFFFFull);
+            ok = dd != d && ufirst[e] < t && !occurs_at(ustart, times, U, E, e, t);
+        }
+        const unsigned long long m = __ballot(ok);
+        const int pos = h + __popcll(m & below);
+        if (ok && pos < Qh) row[pos] = dd;
+        h += __popcll(m);
+    }
+    h = h < Qh ? h : Qh;
+    if (lane == 0) n_hist[i] = h;
+    __threadfence_block();                                       // the picks are read back below by the other lanes of this wave
+    int fill = h;
+    for (uint64_t base = 0; base < nud && fill < Q; base += 64) {
+        const uint64_t j = base + (uint64_t)lane;
+        bool ok = false;
+        int64_t dd = 0;
+        if (j < nud) {
+            dd = ud[neg_perm(nud, 6, j, k)];
+            ok = dd != d;
+            if (ok && R) {
+                const uint64_t ek = ((uint64_t)s << 32) | (uint64_t)dd;
+                const uint32_t e = key_lower_bound(ukey, e0, e0 + R, ek);
+                if (e < e0 + R && ukey[e] == ek) ok = !occurs_at(ustart, times, U, E, e, t);
+            }
+        }
+        for (int q = 0; q < h; ++q) {
+            const int64_t picked = row[q];
+            ok = ok && picked != dd;
+        }
+        const unsigned long long m = __ballot(ok);
+        const int pos = fill + __popcll(m & below);
+        if (ok && pos < Q) row[pos] = dd;
+        fill += __popcll(m);
+    }
+    fill = fill < Q ? fill : Q;
+    for (int q = fill + lane; q < Q; q += 64) row[q] = -1;
+}
+
 // ---- layouts ---------------------------------------------------------------------------------------------------------------------
 struct NegView {
     uint32_t* hdr; uint64_t* ukey; double* ufirst; uint32_t* ustart; uint8_t* uobs; double* times; int64_t* us; int64_t* ud;
@@ -418,6 +512,24 @@ int tpnet_neg_check(void* neg, void* stream) {
         TPNET_HIP_TRY(hipMemsetAsync(err, 0, sizeof(h), (hipStream_t)stream));
         return TPNET_ERR_BAD_ARG;
     }
+    return TPNET_OK;
+}
+
+int tpnet_neg_sample_many(const void* neg, int64_t E, const int64_t* batch_src, const int64_t* batch_dst, const double* batch_t,
+                          int64_t B, int32_t Q, int32_t Qh, uint64_t seed, uint32_t call_index, int64_t* cand, int32_t* n_hist,
+                          void* stream) {
+    if (!neg || E < 1 || E >= (1ll << 30) || B < 0 || B >= (1ll << 31) || Q < 1 || Q >= (1 << 16) || Qh < 0 || Qh > Q)
+        return TPNET_ERR_BAD_ARG;
+    if (B > 0 && (!batch_src || !batch_dst || !batch_t || !cand || !n_hist)) return TPNET_ERR_BAD_ARG;
+    if (B == 0) return TPNET_OK;
+    NegView v = neg_view(neg, 0, E);
+    const NegKey key{(uint32_t)seed, (uint32_t)(seed >> 32), call_index};
+    const int per = NEGM_BLOCK / 64;
+    hipLaunchKernelGGL(k_neg_many, dim3((unsigned)((B + per - 1) / per)), dim3(NEGM_BLOCK), 0, (hipStream_t)stream,
+                       (const uint32_t*)v.hdr, (const uint64_t*)v.ukey, (const uint32_t*)v.ustart, (const double*)v.ufirst,
+                       (const double*)v.times, (const int64_t*)v.ud, (uint32_t)E, batch_src, batch_dst, batch_t, B, (int)Q, (int)Qh,
+                       key, cand, n_hist);
+    TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }
 

@@ -819,6 +819,147 @@ __device__ __forceinline__ void gram_anchored(const tpnet_state& S, const int64_
 }
 
 
+// ---------------------------------------------------------------------------------------------------------------
+// One source against a list of candidates (the ranking protocol: a positive edge's source scored against C destinations):
+// out[k] = G(src, cand[k]) with the SOURCE's rows first -- rows stacked [src 0..L ; cand 0..L], the decoder's order
+// (models/modules.py:112), i.e. tpnet_pair_gram(repeat(src, C), cand).  The mirror image of the anchored walk with ONE anchor:
+// the source's L+1 rows are fetched and decayed once per unit and stay in registers, its own block is reduced once per unit,
+// and per candidate only the candidate's L+1 rows are loaded and only its (L+1)^2 cross products and (L+1)(L+2)/2 self products
+// are formed and reduced (FanCfg: 26 slots at L = 3 against the anchored walk's 42).  The candidate side is the anchored walk's:
+// neighbour_fetch (ids and meta records lane-parallel), neighbour_issue (candidate k+1's rows in flight while k is reduced).
+// A pair's sums depend on its two nodes' rows alone -- never on the unit, the chunk or the position in the list.
+// ---------------------------------------------------------------------------------------------------------------
+template <int LPP, int L>
+struct FanCfg {
+    static constexpr int R = L + 1;
+    static constexpr int TRI = R * (R + 1) / 2;
+    static constexpr int O_CC = 0, O_SC = TRI;               // slots = [ c.c (tri) | s.c (R*R, source row major) ]
+    static constexpr int NS = TRI + R * R;
+    static constexpr int MPS = ((NS + LPP - 1) / LPP) * LPP;
+    static constexpr int PERS = MPS / LPP;
+    static constexpr __host__ __device__ int tri(int i, int j) { return tri_slot(R, i, j); }   // i <= j
+};
+
+// slot s of the reduced sums (lane l holds slots [l * PERS, (l + 1) * PERS) in acc) by shuffles
+template <int PERS, int LPP>
+__device__ __forceinline__ float pick_slot(const float* acc, int s) {
+    float x = 0.0f;
+#pragma unroll
+    for (int j = 0; j < PERS; ++j) {
+        const float t = __shfl(acc[j], s / PERS, LPP);
+        x = (s % PERS == j) ? t : x;
+    }
+    return x;
+}
+
+template <int LPP, int VPL, int W, int L, bool FULL>
+__device__ __forceinline__ void gram_fanout(const tpnet_state& S, const int64_t* __restrict__ cand, int64_t u, int k_begin,
+                                            int k_end, bool valid, double now, double lambda, bool do_scale,
+                                            float* __restrict__ out, int gl) {
+    using C = GramCfg<LPP, L>;
+    using FC = FanCfg<LPP, L>;
+    constexpr int NR = C::NR, NN = C::NN, F = VPL * W;
+    const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
+    const bool sok = valid && (uint64_t)u < (uint64_t)S.N;
+    if (valid && !sok && gl == 0) atomicAdd(S.err, 1u);
+    if (!sok) u = 0;
+    // the source: rows (decay applied) and own block, once per unit
+    float fs[NR][F];
+    {
+        const MetaView m = read_meta(meta, u, READER_BID, now, lambda);
+        load_node_rows<LPP, VPL, W, L, FULL>(S, u, m.copy, gl, fs);
+        float g = 1.0f;
+#pragma unroll
+        for (int i = 1; i <= L; ++i) {
+            g *= m.g;
+#pragma unroll
+            for (int k = 0; k < F; ++k) fs[i][k] *= g;
+        }
+    }
+    // per-lane output plan (invariant over the unit): element idx = a * NN + b of [src rows | cand rows]^2 comes from the
+    // source's own block (finished once, here) or from slot sl of the candidate's sums
+    int sl[C::PER];
+    bool own[C::PER], in[C::PER];
+    float ys[C::PER];
+    {
+        float ss[FC::TRI];
+#pragma unroll
+        for (int a = 0; a < NR; ++a) {
+#pragma unroll
+            for (int b = a; b < NR; ++b) ss[FC::tri(a, b)] = group_allreduce<LPP>(dot_chunk<F, false>(fs[a], fs[b]));
+        }
+#pragma unroll
+        for (int kk = 0; kk < C::PER; ++kk) {
+            int idx = gl * C::PER + kk;
+            in[kk] = idx < C::NG;
+            idx = in[kk] ? idx : 0;
+            const int a = idx / NN, b = idx - a * NN;
+            own[kk] = a < NR && b < NR;
+            ys[kk] = 0.0f;
+            if (own[kk]) {
+                const int ta = FC::tri(a < b ? a : b, a < b ? b : a);
+                float y = 0.0f;
+#pragma unroll
+                for (int q = 0; q < FC::TRI; ++q) y = (ta == q) ? ss[q] : y;     // (register array: a select chain)
+                ys[kk] = finish_feature(y, do_scale);
+                sl[kk] = 0;
+            } else if (a < NR) {                       // (source row a, candidate row b - NR)
+                sl[kk] = FC::O_SC + a * NR + (b - NR);
+            } else if (b < NR) {                       // mirrored
+                sl[kk] = FC::O_SC + b * NR + (a - NR);
+            } else {
+                const int x = a - NR, y = b - NR;
+                sl[kk] = FC::O_CC + FC::tri(x < y ? x : y, x < y ? y : x);
+            }
+        }
+    }
+    for (int kc = k_begin; kc < k_end; kc += LPP) {
+        const int nk = (k_end - kc < LPP) ? k_end - kc : LPP;
+        int64_t my_w;
+        bool my_ok;
+        MetaView my_m;
+        neighbour_fetch<LPP>(S, cand + kc, nk, valid, sok, now, lambda, gl, my_w, my_ok, my_m);
+        float fn[NR][F];                                   // rows of the NEXT candidate (raw)
+        neighbour_issue<LPP, VPL, W, L, FULL>(S, my_w, my_m, 0, gl, fn);
+        for (int j = 0; j < nk; ++j) {
+            const int k = kc + j;
+            const bool wok = __shfl((int)my_ok, j, LPP) != 0;
+            const float mg = __shfl(my_m.g, j, LPP);
+            float fw[NR][F];                               // the candidate's rows, decay applied
+#pragma unroll
+            for (int x = 0; x < F; ++x) fw[0][x] = fn[0][x];
+            float g = 1.0f;
+#pragma unroll
+            for (int i = 1; i <= L; ++i) {
+                g *= mg;
+#pragma unroll
+                for (int x = 0; x < F; ++x) fw[i][x] = fn[i][x] * g;
+            }
+            if (j + 1 < nk) neighbour_issue<LPP, VPL, W, L, FULL>(S, my_w, my_m, j + 1, gl, fn);
+            float acc[FC::MPS];
+#pragma unroll
+            for (int i = 0; i < FC::MPS; ++i) acc[i] = 0.0f;
+#pragma unroll
+            for (int a = 0; a < NR; ++a) {
+#pragma unroll
+                for (int b = a; b < NR; ++b) acc[FC::O_CC + FC::tri(a, b)] = dot_chunk<F, false>(fw[a], fw[b]);
+#pragma unroll
+                for (int b = 0; b < NR; ++b) acc[FC::O_SC + a * NR + b] = dot_chunk<F, false>(fs[a], fw[b]);
+            }
+            Halve<FC::MPS, LPP / 2>::run(acc, gl);         // lane gl now holds the complete sums of slots [gl*PERS, ...)
+#pragma unroll
+            for (int kk = 0; kk < C::PER; ++kk) {
+                const int idx = in[kk] ? gl * C::PER + kk : 0;
+                float x = finish_feature(pick_slot<FC::PERS, LPP>(acc, sl[kk]), do_scale);
+                if (own[kk]) x = ys[kk];
+                if (!wok) x = __builtin_nanf("");
+                if (valid && in[kk]) __builtin_nontemporal_store(x, out + (int64_t)k * C::NG + idx);
+            }
+        }
+    }
+}
+
+
 // the walk's arrays for a kernel that steps all the lane groups of a workgroup through their units TOGETHER
 // (k_anchored_feature, anchored_feature.hip): begin() = anchor_rows + anchor_output_plan, fetch() + issue(0), step(j) = neighbour_step.
 // The same operations in the same order as gram_anchored (whose loop body is neighbour_step's text): the features of the two are

@@ -165,6 +165,10 @@ int launch_pair_gram(const tpnet_state& st, const int64_t* u, const int64_t* v, 
 int launch_pair_gram_shared(const tpnet_state& st, const int64_t* u, const int64_t* v1, const int64_t* v2, int64_t n,
                             double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s);
 bool pair_gram_anchored_supported(const tpnet_state& st);
+// one source against C candidates, source's layers first (fanout.hip): the anchored walk's geometry class
+bool pair_gram_fanout_supported(const tpnet_state& st);
+int launch_pair_gram_fanout(const tpnet_state& st, const int64_t* src, const int64_t* cand, int64_t n_rows, int C, double now,
+                            double lambda, uint32_t flags, float* out, hipStream_t s);
 int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
                               int64_t n_rows, int K, double now, double lambda, uint32_t flags, float* out1, float* out2,
                               hipStream_t s);

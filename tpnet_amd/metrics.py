@@ -3,7 +3,8 @@
 The reference scores every evaluation batch on the host (evaluate_models_utils.py:186-193, utils/metrics.py:8-22): `loss.item()`,
 `predicts.sigmoid().cpu()` and sklearn's `average_precision_score` / `roc_auc_score` -- two synchronisations and two CPU sorts per
 batch.  Here a batch's three numbers are one 64-byte record that a kernel appends to a device-resident log; nothing synchronises
-until the log is read, once, when the split is over (`LinkPredictionMeter`).
+until the log is read, once, when the split is over (`LinkPredictionMeter`).  The one-vs-many ranking protocol (MRR, Hits@k:
+tpnet_lp_ranking, `LinkRankingMeter`, `link_ranking_metrics_host`) is at the end of this file.
 
 The rule (include/tpnet_hip.h spells it out): with the scores p[0..P) of the positives and q[0..N) of the negatives, per positive i
   a_i = #{j : p_j >= p_i},  b_i = #{k : q_k >= p_i},  c_i = #{k : q_k == p_i}
@@ -249,4 +250,128 @@ class LinkPredictionMeter:
 
     def reset(self):
         """Empties the log: the next `add` writes record 0.  (Records are overwritten, the buffer is kept.)"""
+        self._n = 0
+
+
+# ------------------------------------------------------------------------------------------------ one-vs-many ranking: MRR, Hits@k
+# The rule (include/tpnet_hip.h: tpnet_lp_ranking): logits [B, 1 + C], column 0 the positive's logit p, column 1 + c a candidate's;
+# per query over its valid candidates  g_i = #{q > p},  e_i = #{q == p},  m_i = 2 + 2 g_i + e_i  (twice the rank, ties at the mean of
+# the optimistic and the pessimistic rank); a query with a NaN among p and its valid candidates, or with no valid candidate, is not
+# counted; n = the counted queries:  mrr = (1 / n) sum 2 / m_i,  hits@k = #{m_i <= 2 k} / n.  Ranks are formed on the fp32 logits as
+# given -- no sigmoid, so a saturating sigmoid adds no ties.
+RANK_FLAG_NO_QUERY = 1        # n == 0: the four floats are NaN
+RANK_FLAG_EMPTY_QUERY = 4     # a query without a valid candidate (not counted); FLAG_NAN_SCORE = 2: a query with a NaN (not counted)
+MAX_RANK_COLUMNS = 1 << 20    # 1 + C of one device call
+
+
+def link_ranking_metrics_host(logits, valid=None, hits_at=(1, 3, 10)):
+    """The rule in numpy: logits [B, 1 + C] (taken as fp32), valid [B, C] bool (None: every candidate) -> {'mrr', 'hits' (a tuple, one
+    per k of hits_at), 'm_sum', 'n', 'n_valid_candidates', 'flags'}, the fields of the device record.  This is the CPU path and what
+    the device record is held to."""
+    x = np.asarray(logits, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("logits must be [B, 1 + C]")
+    B, C = x.shape[0], x.shape[1] - 1
+    v = np.ones((B, C), dtype=bool) if valid is None else np.asarray(valid, dtype=bool).reshape(B, C)
+    p, q = x[:, :1], x[:, 1:]
+    with np.errstate(invalid="ignore"):
+        g = ((q > p) & v).sum(axis=1).astype(np.int64)
+        e = ((q == p) & v).sum(axis=1).astype(np.int64)
+    nv = v.sum(axis=1).astype(np.int64)
+    nan = np.isnan(p[:, 0]) | (np.isnan(q) & v).any(axis=1)
+    empty = nv == 0
+    m = (2 + 2 * g + e)[~(nan | empty)]
+    n = int(len(m))
+    flags = (FLAG_NAN_SCORE if nan.any() else 0) | (RANK_FLAG_EMPTY_QUERY if empty.any() else 0) | (0 if n else RANK_FLAG_NO_QUERY)
+    if n:
+        mrr = float(np.sum(2.0 / m.astype(np.float64)) / n)
+        hits = tuple(float(np.float64(int((m <= 2 * int(k)).sum())) / np.float64(n)) for k in hits_at)
+    else:
+        mrr, hits = float("nan"), tuple(float("nan") for _ in hits_at)
+    return {"mrr": mrr, "hits": hits, "m_sum": int(m.sum()), "n": n, "n_valid_candidates": int(nv.sum()), "flags": flags}
+
+
+class LinkRankingResults(list):
+    """A list of per-batch dicts {'mrr', 'hits@k1', 'hits@k2', 'hits@k3'}; `.flags`: the records' flag words in the same order
+    (RANK_FLAG_NO_QUERY, FLAG_NAN_SCORE, RANK_FLAG_EMPTY_QUERY); `.totals`: the same keys over all batches, each record weighted by
+    its counted queries n (total MRR = sum n_b mrr_b / sum n_b), plus 'n'."""
+
+    def __init__(self, rows, flags, totals):
+        super().__init__(rows)
+        self.flags = flags
+        self.totals = totals
+
+
+class LinkRankingMeter:
+    """A device-resident log of up to `capacity` batches' ranking records (tpnet_lp_ranking): MRR and Hits@k for three k.
+
+    `add` enqueues two launches on the current stream and returns; it copies nothing to the host and never synchronises.  `results`
+    reads the log with ONE copy and forms the totals on the host from it.  The scratch buffer is the meter's own: calls belong on
+    one stream."""
+
+    def __init__(self, capacity: int, device="cuda:0", hits_at=(1, 3, 10)):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.TPNetHipError("LinkRankingMeter needs a cuda device (link_ranking_metrics_host is the CPU path)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.hits_at = tuple(int(k) for k in hits_at)
+        if len(self.hits_at) != 3 or min(self.hits_at) < 1:
+            raise ValueError("hits_at: three cut-offs k >= 1")
+        _lib.load()
+        self.capacity = int(capacity)
+        assert self.capacity > 0
+        self._log = torch.zeros((self.capacity, _RECORD_WORDS), dtype=torch.int64, device=self.device)
+        self._n = 0
+        self._scratch = None
+
+    def __len__(self):
+        return self._n
+
+    def add(self, logits: torch.Tensor, candidates: torch.Tensor = None) -> int:
+        """logits [B, 1 + C] (fp32 on the meter's device; column 0 the positive), candidates (optional) the int64 device ids [B, C]
+        whose negative entries mark absent slots (`sample_many_device`'s -1) -> the index of the record written."""
+        if self._n >= self.capacity:
+            raise IndexError(f"LinkRankingMeter: the log of {self.capacity} records is full (results(), then reset())")
+        _check_f32(logits, self.device, "logits")
+        if logits.dim() != 2 or logits.shape[1] < 1 or logits.shape[1] > MAX_RANK_COLUMNS:
+            raise ValueError(f"logits must be [B, 1 + C] with 1 + C <= {MAX_RANK_COLUMNS}")
+        x = logits.detach().contiguous()
+        B, C1 = x.shape
+        cand = None
+        if candidates is not None:
+            if not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.device != self.device \
+                    or tuple(candidates.shape) != (B, C1 - 1):
+                raise TypeError(f"candidates: an int64 tensor [{B}, {C1 - 1}] on {self.device} is expected")
+            cand = candidates.contiguous()
+        lib = _lib.load()
+        need = lib.tpnet_lp_ranking_scratch_bytes(B, C1)
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        k = self._n
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(lib.tpnet_lp_ranking(x.data_ptr() if B else None, B, C1, cand.data_ptr() if cand is not None and cand.numel() else None,
+                                        self.hits_at[0], self.hits_at[1], self.hits_at[2], self._scratch.data_ptr(),
+                                        self._scratch.numel(), self._log.data_ptr() + k * _RECORD_WORDS * 8, stream), "lp_ranking")
+        self._n = k + 1
+        return k
+
+    def records(self) -> np.ndarray:
+        """The log's records so far as an int64 array [n][8] on the host (one copy; synchronises); words 0..3 are float64 bits."""
+        return self._log[:self._n].cpu().numpy()
+
+    def results(self) -> LinkRankingResults:
+        """One device-to-host copy (synchronises) -> the per-batch dicts with `.flags` and `.totals`."""
+        rec = self.records()
+        f = rec.view(np.float64)
+        keys = ["mrr"] + [f"hits@{k}" for k in self.hits_at]
+        rows = [{key: float(r[j]) for j, key in enumerate(keys)} for r in f]
+        n = rec[:, 5].astype(np.float64)
+        tot = float(n.sum())
+        totals = {key: (float(np.sum(n[n > 0] * f[n > 0, j]) / tot) if tot else float("nan")) for j, key in enumerate(keys)}
+        totals["n"] = int(rec[:, 5].sum())
+        return LinkRankingResults(rows, [int(v) for v in rec[:, 7]], totals)
+
+    def reset(self):
+        """Empties the log: the next `add` writes record 0."""
         self._n = 0

@@ -104,6 +104,37 @@ class GpuNegativeEdgeSampler:
                    "neg_sample")
         return out_src, out_dst
 
+    def sample_many_device(self, batch_src: torch.Tensor, batch_dst: torch.Tensor, batch_t: torch.Tensor, num_negatives: int,
+                           num_historical: int = None):
+        """Per-query candidates of the ranking protocol (tpnet_neg_sample_many; include/tpnet_hip.h spells the rule out): every
+        positive (s, d, t) of the batch gets its own row of Q = num_negatives destinations -> (cand [B, Q] int64, n_hist [B] int32) on
+        the device.  The first n_hist[i] <= Qh = num_historical (default Q // 2) entries of a row are destinations `s` was seen with
+        before t, the rest are drawn from the unique destinations; a row's entries are distinct, never d and never a destination `s`
+        has an edge to at exactly t; slots that cannot be filled hold -1.  `negative_sample_strategy` is not consulted.  A row depends
+        on (seed, call index, its index in the batch) and its own (s, d, t) alone.  batch_src / batch_dst: int64 device tensors,
+        batch_t: a float64 device tensor.  Nothing synchronises; the call advances the call index like `sample_device`."""
+        Q = int(num_negatives)
+        Qh = Q // 2 if num_historical is None else int(num_historical)
+        if not (1 <= Q < 1 << 16 and 0 <= Qh <= Q):
+            raise ValueError(f"sample_many_device: 1 <= num_negatives < 65536 and 0 <= num_historical <= num_negatives, not {Q}, {Qh}")
+        for x, dt, what in ((batch_src, torch.int64, "batch_src"), (batch_dst, torch.int64, "batch_dst"), (batch_t, torch.float64, "batch_t")):
+            if not isinstance(x, torch.Tensor) or x.dtype != dt or not x.is_cuda or x.dim() != 1:
+                raise TypeError(f"sample_many_device: {what} must be a one-dimensional {dt} tensor on {self.device}")
+        B = int(batch_src.numel())
+        if int(batch_dst.numel()) != B or int(batch_t.numel()) != B:
+            raise ValueError("sample_many_device: batch_src, batch_dst and batch_t must have the same length")
+        bs, bd, bt = batch_src.contiguous(), batch_dst.contiguous(), batch_t.contiguous()
+        cand = torch.empty((B, Q), dtype=torch.int64, device=self.device)
+        n_hist = torch.empty(B, dtype=torch.int32, device=self.device)
+        call = self._calls & 0xFFFFFFFF
+        self._calls += 1
+        if B == 0:
+            return cand, n_hist
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(_lib.load().tpnet_neg_sample_many(self._buf.data_ptr(), self.E, bs.data_ptr(), bd.data_ptr(), bt.data_ptr(), B, Q, Qh,
+                                                     self._key, call, cand.data_ptr(), n_hist.data_ptr(), stream), "neg_sample_many")
+        return cand, n_hist
+
     def check(self):
         """tpnet_neg_check: synchronises; raises if a fill since the last check found no pair outside its batch."""
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

@@ -807,6 +807,54 @@ class RandomProjectionModule(nn.Module):
                    "pair_gram_shared")
         return out[0], out[1]
 
+    # pair_gram_one_to_many: lists of at least this many (source, candidate) pairs take the fan-out kernel (tpnet_pair_gram_fanout)
+    # where its geometry serves them; None: no list does -- the expanded ids go through pair_gram.  None is the default because the
+    # kernel is NOT SHOWN TO WIN at any measured shape (tools/link_ranking_rate.py on the MI355X, medians of 11 repeats, fan-out
+    # against pair_gram on the same expanded device ids, Gram alone; profiles/link_ranking.md has the ranges and gram + mlp):
+    #   C2's table, d = 128, L = 3:  (B, C) = (200, 100) 15.1 against 14.4 us, (1000, 20) 14.5 / 14.0, (1000, 100) 37.3 / 35.6
+    #   C3's table, d = 256:         (1000, 100) 68.6 / 66.6
+    #   4 M nodes, d = 128 (20 GB):  (1000, 100) 44.4 / 42.3, (1000, 20) 15.0 / 13.8, (10000, 100) 491.8 / 444.4
+    # The general kernel already gets a repeated source's rows from the cache (consecutive pairs share them), and its groups are
+    # independent where the walk's candidates are a serial chain.  0: every list the geometry serves (what the tests set).
+    FANOUT_PAIRS_FROM = None
+
+    def pair_gram_one_to_many(self, src_ids, cand_ids) -> torch.Tensor:
+        """Extension, the ranking protocol's readout: src_ids [B], cand_ids [B, C] -> [B, C, (2L+2)^2] fp32 on the GPU, entry
+        (i, c) = the pairwise feature of (src_ids[i], cand_ids[i, c]) BEFORE self.mlp with the source's layers first -- pair_gram(
+        repeat(src_ids, C), cand_ids.reshape(-1)), the decoder's order (models/modules.py:112).  Lists of FANOUT_PAIRS_FROM pairs or
+        more (default None: no list) take tpnet_pair_gram_fanout -- one lane group keeps a source's rows in registers for its
+        candidates -- on rows of dim % 4 == 0, 36 <= dim <= 512; everything else (other widths, `use_matrix`, padded rows) takes the
+        expanded ids, formed on the device, through pair_gram.  Host arrays or device tensors."""
+        self._ensure_engine()
+        cd = cand_ids if isinstance(cand_ids, torch.Tensor) else np.asarray(cand_ids)
+        if cd.ndim != 2:
+            raise ValueError("cand_ids must be [B, C]")
+        B, Cn = cd.shape
+        if len(src_ids) != B:
+            raise ValueError("one source per row of cand_ids")
+        NG = self.pair_wise_feature_dim
+        dev = self._dev()
+        if B == 0 or Cn == 0:
+            return torch.empty((B, Cn, NG), dtype=torch.float32, device=dev)
+        s = self._to_device(self._ids(src_ids, "src_ids"))[0]
+        c = self._to_device(self._ids(cd.reshape(-1), "cand_ids"))[0]
+        lib = _lib.load()
+        fan = (self.FANOUT_PAIRS_FROM is not None and B * Cn >= self.FANOUT_PAIRS_FROM and not self.use_matrix
+               and self.engine_dim == self.dim and lib.tpnet_pair_gram_fanout_supported(self._st_ref()))
+        if not fan:
+            return self.pair_gram(s.repeat_interleave(Cn), c).view(B, Cn, NG)
+        out = torch.empty((B, Cn, NG), dtype=torch.float32, device=dev)
+        _lib.check(lib.tpnet_pair_gram_fanout(self._st_ref(), s.data_ptr(), c.data_ptr(), B, Cn, self._now_host,
+                                              float(self.time_decay_weight), _lib.FLAG_NOT_SCALE if self.not_scale else 0,
+                                              out.data_ptr(), self._stream()), "pair_gram_fanout")
+        return out
+
+    def get_pair_wise_feature_one_to_many(self, src_ids, cand_ids) -> torch.Tensor:
+        """Extension: get_pair_wise_feature(repeat(src_ids, C), cand_ids.reshape(-1)) -> [B*C, (2L+2)^2]: pair_gram_one_to_many, then
+        self.mlp through the routes (and with the gradients) of every other readout-then-mlp call (_apply_mlp)."""
+        g = self.pair_gram_one_to_many(src_ids, cand_ids)
+        return self._apply_mlp(g.view(-1, self.pair_wise_feature_dim))
+
     def get_pair_wise_feature(self, src_node_ids: np.ndarray, dst_node_ids: np.ndarray):
         """models/TPNet.py:112-129.  No gradient flows into the projections (requires_grad=False in the
         reference, :49-62); self.mlp stays a trainable torch module.
