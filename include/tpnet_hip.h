@@ -57,7 +57,8 @@ extern "C" {
                                     are kept wider than the caller's, pad columns zero);
                                     TPNET_FLAG_LAYERS_MFMA / tpnet_encoder_layers_* (the encoder's matrix-core readout for num_layer 1, 2, 4);
                                     tpnet_pair_gram_fanout* (one source against C candidates), tpnet_neg_sample_many (per-query candidates),
-                                    tpnet_lp_ranking* (a batch's MRR and Hits@k as one device record) */
+                                    tpnet_lp_ranking* (a batch's MRR and Hits@k as one device record);
+                                    tpnet_anchored_route (which kernel serves an anchored readout: the one table) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -812,6 +813,31 @@ int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, in
 int tpnet_encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src,
                        const int64_t* other, const double* t, int64_t B, int32_t K, void* scratch, size_t scratch_bytes,
                        void* stream);
+
+/* THE route of an anchored readout (additive to ABI 7; csrc/encoder.hip: anchored_route -- every entry point below and
+ * tpnet_pair_gram_anchored ask that one function).  For n_rows x K neighbours read with `flags`, 16-byte aligned outputs, no pair
+ * lists and `mlp` (may be NULL): 0 = refused (TPNET_ERR_BAD_ARG), else the kernel that forms the Gram in bits 0-3 and the
+ * one-launch kind in bits 4-5.
+ *   Gram kernel, first match wins
+ *     TPNET_FLAG_PACKED                                                     -> refused
+ *     TPNET_FLAG_ROWS8 on a row of d % 4 == 2                               -> 3 (matrix cores, 8-byte halves) where 38 <= d <= 158,
+ *                                                                              L = 3, K >= 4 and no TPNET_FLAG_NO_MFMA_READOUT; else
+ *                                                                              refused (no walk reads such rows; the launch refuses
+ *                                                                              outputs that are not 16-byte aligned)
+ *     [pair lists: tpnet_encoder_gram / tpnet_encoder_features only] d <= 128, not (L = 3, d % 4 == 0, 36 <= d <= 160, K >= 4),
+ *       TPNET_FLAG_LAYERS_MFMA not served                                   -> 1 (generic pair kernel on the spelled-out lists;
+ *                                                                              tpnet_encoder_gram: only where the next line passes,
+ *                                                                              tpnet_encoder_features: only with a gram buffer)
+ *     not (d % 4 == 0 and 36 <= d <= 512)                                   -> refused
+ *     L = 3, 36 <= d <= 160, K >= 4, aligned, no TPNET_FLAG_NO_MFMA_READOUT  -> 3 (matrix cores, csrc/encoder_mfma.hip)
+ *     TPNET_FLAG_LAYERS_MFMA, L = 1 / 2 / 4, 36 <= d <= 160, K >= 4, aligned,
+ *       no TPNET_FLAG_NO_MFMA_READOUT                                       -> 4 (matrix cores, csrc/encoder_layers.hip)
+ *     otherwise                                                             -> 2 (vector-ALU walk)
+ *   One launch of readout + self.mlp (mlp of F = 64, H = 256, L = 3, no TPNET_FLAG_NO_MFMA_READOUT; gram may then be NULL)
+ *     the Gram kernel is 3 and mlp->wimg is given                           -> 1 (k_encoder_fused)
+ *     else 164 <= d <= 512, K >= 4, mlp->w1 / w2f given, the width's geometry class routed (at present none) -> 2 (k_anchored_feature)
+ * (n_rows >= 1, n_rows * K < 2^25 and N < 2^31 wherever the matrix cores are named.)  The queries below are views of this table. */
+int tpnet_anchored_route(const tpnet_state* st, int64_t n_rows, int32_t K, uint32_t flags, const tpnet_mlp* mlp);
 
 /* The encoder's call INCLUDING self.mlp (models/TPNet.py:311-324, 129; L = 3, rows as tpnet_pair_gram_anchored needs them): gram =
  * tpnet_pair_gram_anchored's output [2][n_rows*K][64] (kept: what a backward pass needs), out = mlp(gram) in the fp32 class

@@ -7,6 +7,7 @@ around it, the kernel names and call counts close the gap.
 
     python tools/feature_paths.py OUT_DIR              # everything (the readout section first: 374 of the files)
     python tools/feature_paths.py OUT_DIR readout      # only the readout kernels' matrix (readout_cases)
+    python tools/feature_paths.py OUT_DIR anchored     # only the anchored readout's routes, opt-ins included (anchored_cases)
     python tools/feature_paths.py OUT_DIR mlp          # only self.mlp's six C entries, partials included (mlp_cases; not in "everything")
     python tools/feature_paths.py OUT_DIR sizes        # only the size exports of the C ABI over a grid -> OUT_DIR/sizes.json (sizes_cases;
                                                        # not in "everything"; needs no GPU -- without one rocPRIM's size queries answer 0)
@@ -254,6 +255,36 @@ def readout_cases():
                          lambda: list(rp.run_stream(src, dst, neg, t, B, packed=packed, schedule=sched)) + list(rp.backup_random_projections()[1]))
 
 
+def anchored_cases():
+    """The anchored readout's routes (csrc/encoder.hip: anchored_route) through every public door: `rows8_readout` on 8-byte rows,
+    `layers_readout` at num_layer 1, 2, 4, the ends of the matrix-core and walk width ranges, and the widths that are refused (their
+    exception texts are the result).  Three rows with K = 3, 4, 5; the host tile / repeat pattern just above 8192 pairs."""
+    rng = np.random.RandomState(41)
+    n_nodes, E = 300, 4000
+    es, ed, et = ids(rng, E, n_nodes), ids(rng, E, n_nodes), np.sort(rng.uniform(0, 2e5, E))
+    sampler = GpuRecentNeighborSampler(es, ed, et, device=DEV, num_nodes=n_nodes)
+    s, o, tq = es[-3:], ed[-3:], et[-3:] + 1.0
+    mods = [(f"rows8_d{d}", d, 3, "rows8_readout") for d in (110, 38)]
+    mods += [(f"layers_d{d}_L{L}", d, L, "layers_readout") for L in (1, 2, 4) for d in (64, 140)]
+    mods += [(f"plain_d{d}", d, 3, None) for d in (36, 160, 164, 512, 110, 34, 516)]
+    for tag, d, L, switch in mods:
+        rp = make(d, L=L, n_nodes=n_nodes, seed=d + L)
+        if switch:
+            setattr(rp, switch, True)
+        for K in (3, 4, 5):
+            neigh, a1, a2 = ids(rng, 3 * K, n_nodes).reshape(3, K), ids(rng, 3, n_nodes), ids(rng, 3, n_nodes)
+            name = f"anchored_{tag}_K{K}"
+            with torch.no_grad():
+                case(f"{name}_gram", lambda: rp.pair_gram_anchored(neigh, a1, a2))
+                case(f"{name}_gram_no_mfma", lambda: rp.pair_gram_anchored(dev(neigh), a1, a2, matrix_cores=False))
+                case(f"{name}_feature", lambda: rp.get_pair_wise_feature_anchored(dev(neigh), dev(a1), dev(a2)))
+                case(f"{name}_encoder_host", lambda: rp.encoder_pair_features(sampler, s, o, tq, K))
+                case(f"{name}_encoder_device", lambda: rp.encoder_pair_features(sampler, dev(s), dev(o), dev(tq, torch.float64), K))
+                if K > 3:
+                    u, v = encoder_call(rng, 4100 // K + 1, K, n_nodes)
+                    case(f"{name}_pattern", lambda: rp.get_pair_wise_feature(u, v))
+
+
 def sizes_cases():
     """Every export that sizes a caller-owned buffer, and tpnet_stream_schedule (which decides on such sizes), over a grid of shapes
     around the tile, batch-size and chunk thresholds: {export: [[arguments..., result], ...]} in sizes.json.  Sizes decide how a
@@ -314,10 +345,11 @@ def sizes_cases():
 def main():
     if ONLY:
         for name in ONLY:
-            {"readout": readout_cases, "mlp": mlp_cases, "sizes": sizes_cases}[name]()
+            {"readout": readout_cases, "anchored": anchored_cases, "mlp": mlp_cases, "sizes": sizes_cases}[name]()
         print(f"{len(SAVED)} files in {OUT}")
         return
     readout_cases()
+    anchored_cases()
     rng = np.random.RandomState(7)
     # ---- the decoder's calls from host arrays -----------------------------------------------------------------------------
     rp128 = make(128)

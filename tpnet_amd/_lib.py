@@ -177,6 +177,7 @@ SIGNATURES = {
     "tpnet_mlp_l4_bwd_partial_floats": (C.c_int64, []),
     "tpnet_mlp_l4_bwd_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "tpnet_mlp_l4_bwd_f32": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P]),
+    "tpnet_anchored_route": (C.c_int, [_SP, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(Mlp)]),
     "tpnet_encoder_fused_supported": (C.c_int, [_SP, C.c_int64, C.c_int32, C.POINTER(Mlp)]),
     "tpnet_encoder_rows8_supported": (C.c_int, [_SP, C.c_int64, C.c_int32, C.POINTER(Mlp)]),
     "tpnet_encoder_layers_supported": (C.c_int, [_SP, C.c_int64, C.c_int32]),

@@ -437,30 +437,20 @@ int tpnet_pair_gram_anchored(const tpnet_state* st, const int64_t* neigh, const 
     if (rc) return rc;
     if (n_rows < 0 || K < 0 || (n_rows > 0 && K > 0 && (!neigh || !a1 || !a2 || !out1 || !out2))) return TPNET_ERR_BAD_ARG;
     if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;
-    if (n_rows > 0 && K > 0 && rows8_asked(*st, flags)) {
-        // rows of d % 4 == 2 with TPNET_FLAG_ROWS8: the matrix cores (8-byte loads) or nothing -- no vector-ALU walk reads such rows
-        if (!encoder_mfma_supported(*st, n_rows, K, flags)) return TPNET_ERR_BAD_ARG;
-        return launch_encoder_gram_mfma(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
+    if (n_rows == 0 || K == 0) return TPNET_OK;
+    hipStream_t s = (hipStream_t)stream;
+    switch (anchored_route(*st, n_rows, K, flags, nullptr, aligned16({out1, out2}), false).gram) {
+        // rows of 36..160 floats, L = 3, K >= 4 (8-byte rows with TPNET_FLAG_ROWS8 among them): the matrix cores (encoder_mfma.hip, fp32 class)
+        case AK_MFMA: return launch_encoder_gram_mfma(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, s);
+        // L = 1, 2, 4 on the matrix cores (encoder_layers.hip): only with TPNET_FLAG_LAYERS_MFMA, same shapes otherwise
+        case AK_LAYERS: return launch_encoder_gram_layers(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, s);
+        // everything else that is supported (K < 4, unaligned outputs, wider rows, TPNET_FLAG_NO_MFMA_READOUT): the vector-ALU walk
+        case AK_WALK: return launch_pair_gram_anchored(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, s);
+        // rows that are not whole 16-byte vectors (d % 4 != 0: 110, 130, 150 ... without the flag), narrower than 36 or wider than 512
+        // floats: the generic kernel, one launch per anchor side, on index arrays the caller would otherwise build -- not available
+        // without them: report it
+        default: return TPNET_ERR_BAD_ARG;
     }
-    if (n_rows > 0 && K > 0 && !pair_gram_anchored_supported(*st)) {
-        // rows that are not whole 16-byte vectors (d % 4 != 0: 110, 130, 150 ...), narrower than 36 or wider than 512 floats: the
-        // generic kernel, one launch per anchor side, on index arrays the caller would otherwise build -- not available without
-        // them: report it
-        return TPNET_ERR_BAD_ARG;
-    }
-    // rows of 36..160 floats: the same blocks on the matrix cores (encoder_mfma.hip, fp32 class); everything else that is
-    // supported (K < 4, unaligned outputs, wider rows, the flag): the vector-ALU walk
-    if ((flags & TPNET_FLAG_NO_MFMA_READOUT) == 0 && encoder_mfma_supported(*st, n_rows, K) && !((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15))
-        return launch_encoder_gram_mfma(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
-    // L = 1, 2, 4 on the matrix cores (encoder_layers.hip): only with TPNET_FLAG_LAYERS_MFMA, same shapes otherwise
-    if (layers_asked(*st, n_rows, K, flags) && !((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15))
-        return launch_encoder_gram_layers(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
-    return launch_pair_gram_anchored(*st, neigh, a1, a2, n_rows, K, now_time, lambda, flags, out1, out2, (hipStream_t)stream);
-}
-
-int tpnet_pair_gram_anchored_supported(const tpnet_state* st) {
-    if (check_state(st)) return 0;
-    return pair_gram_anchored_supported(*st) ? 1 : 0;
 }
 
 int tpnet_pair_gram_fanout(const tpnet_state* st, const int64_t* src, const int64_t* cand, int64_t n_rows, int32_t C,

@@ -279,12 +279,10 @@ __global__ __launch_bounds__(ELB) void k_encoder_gram_mfma_layers(tpnet_state S,
     }
 }
 
-static inline int layer_steps(int d) { return (d + 31) / 32; }
-
 bool encoder_layers_supported(const tpnet_state& st, int64_t n_rows, int K) {
     static const int off = TPNET_DEV_INT(NO_ENCODER_LAYERS, 0);
     // rows of whole 16-byte vectors in 2..5 steps of 32, as the L = 3 kernels take them; K >= 4 bounds the nodes a tile spans
-    return !off && (st.L == 1 || st.L == 2 || st.L == 4) && st.d % 4 == 0 && st.d >= 36 && st.d <= 160 && K >= 4 &&
+    return !off && (st.L == 1 || st.L == 2 || st.L == 4) && st.d % 4 == 0 && encoder_row_width(st.d) && K >= 4 &&
            st.N < (int64_t)1 << 31 && n_rows > 0 && n_rows * (int64_t)K < ((int64_t)1 << 31) / 64;
 }
 
@@ -293,24 +291,13 @@ static int launch_layers(const tpnet_state& st, const int64_t* neigh, const int6
                          double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s) {
     const int T = (int)(n_rows * K);
     const int ntiles = layer_tiles<L>(n_rows, K);
-    // tiles per wave: ONE round of the waves the chip holds (encoder_mfma.hip), at least two tiles each
+    // tiles per wave: ONE round of the waves the chip holds (encoder_mfma.hip)
     static const int waves_dev = TPNET_DEV_INT(ENCODER_WAVES, 256 * 8);
-    int tpw = (ntiles + waves_dev - 1) / waves_dev;
-    if (tpw < 2) tpw = 2;
-    const int nwaves = (ntiles + tpw - 1) / tpw;
-    const int grid = (nwaves + ELB / 64 - 1) / (ELB / 64);
-#define TPNET_EL_LAUNCH(KS_, FULL_)                                                                                                  \
-    hipLaunchKernelGGL((k_encoder_gram_mfma_layers<L, KS_, FULL_>), dim3(grid), dim3(ELB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
-                       ntiles, tpw, now, lambda, flags, out1, out2)
-    if (st.d == 128) TPNET_EL_LAUNCH(4, true);
-    else if (st.d == 64) TPNET_EL_LAUNCH(2, true);
-    else
-        switch (layer_steps(st.d)) {
-            case 2: TPNET_EL_LAUNCH(2, false); break;
-            case 3: TPNET_EL_LAUNCH(3, false); break;
-            case 4: TPNET_EL_LAUNCH(4, false); break;
-            default: TPNET_EL_LAUNCH(5, false); break;
-        }
+    const TileRound g = tile_round(ntiles, waves_dev, ELB / 64);
+#define TPNET_EL_LAUNCH(KS_, FULL_, R8_) /* (R8_: never -- encoder_layers_supported takes d % 4 == 0 only) */                          \
+    hipLaunchKernelGGL((k_encoder_gram_mfma_layers<L, KS_, FULL_>), dim3(g.grid), dim3(ELB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+                       ntiles, g.tpw, now, lambda, flags, out1, out2)
+    TPNET_ENCODER_WIDTH_SWITCH(st.d, TPNET_EL_LAUNCH);
 #undef TPNET_EL_LAUNCH
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
@@ -333,11 +320,6 @@ int launch_encoder_gram_layers(const tpnet_state& st, const int64_t* neigh, cons
 using namespace tpnet;
 
 extern "C" {
-
-int tpnet_encoder_layers_supported(const tpnet_state* st, int64_t n_rows, int32_t K) {
-    if (!st || !st->p0 || !st->q || !st->meta || st->N < 1 || st->d < 1) return 0;
-    return encoder_layers_supported(*st, n_rows, K) ? 1 : 0;
-}
 
 int64_t tpnet_encoder_layers_tiles(int32_t L, int64_t n_rows, int32_t K) {
     if ((L != 1 && L != 2 && L != 4) || n_rows < 1 || K < 4 || n_rows * (int64_t)K >= ((int64_t)1 << 31) / 64) return 0;

@@ -467,14 +467,12 @@ __global__ __launch_bounds__(EMF_B) void k_encoder_fused(tpnet_state S, const in
         dense_consumer(smem, stg, sync, (slot_end - slot_begin + 3) >> 2, T, slot_end, y);
 }
 
-static inline int encoder_steps(int d) { return (d + 31) / 32; }      // KS: 32-deep steps of a row of d floats
-
 bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K, uint32_t flags) {
     static const int off = TPNET_DEV_INT(NO_ENCODER_MFMA, 0);
     // rows of whole 16-byte vectors, 2..5 steps of 32: d = 64 / 128 unmasked, every other width with a masked last step; rows of
     // d % 4 == 2 floats (8-byte aligned) in the same steps, only where the caller asks (TPNET_FLAG_ROWS8) and does not take it back
-    const bool rows16 = st.d % 4 == 0 && st.d >= 36 && st.d <= 160;
-    const bool rows8 = st.d % 4 == 2 && st.d >= 38 && st.d <= 158 && (flags & TPNET_FLAG_ROWS8) && !(flags & TPNET_FLAG_NO_MFMA_READOUT);
+    const bool rows16 = st.d % 4 == 0 && encoder_row_width(st.d);
+    const bool rows8 = st.d % 4 == 2 && encoder_row_width(st.d) && (flags & TPNET_FLAG_ROWS8) && !(flags & TPNET_FLAG_NO_MFMA_READOUT);
     return !off && st.L == 3 && (rows16 || rows8) && K >= 4 && st.N < (int64_t)1 << 31 && n_rows > 0 &&
            n_rows * (int64_t)K < ((int64_t)1 << 31) / 64;
 }
@@ -486,31 +484,13 @@ int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const 
     if ((reinterpret_cast<uintptr_t>(out1) | reinterpret_cast<uintptr_t>(out2)) & 15) return TPNET_ERR_BAD_ARG;
     const int T = (int)(n_rows * K);
     const int ntiles = (T + 3) / 4;
-    // tiles per wave: ONE round of the waves the chip holds (2 per SIMD at 172 VGPRs: 8 per CU), at least two tiles each
+    // tiles per wave: ONE round of the waves the chip holds (2 per SIMD at 172 VGPRs: 8 per CU)
     static const int waves_dev = TPNET_DEV_INT(ENCODER_WAVES, 256 * 8);
-    int tpw = (ntiles + waves_dev - 1) / waves_dev;
-    if (tpw < 2) tpw = 2;
-    const int nwaves = (ntiles + tpw - 1) / tpw;
-    const int grid = (nwaves + EMB / 64 - 1) / (EMB / 64);
-#define TPNET_EM_LAUNCH(KS_, FULL_, R8_)                                                                                             \
-    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, FULL_, 3, R8_>), dim3(grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
-                       tpw, now, lambda, flags, out1, out2)
-    if (st.d == 128) TPNET_EM_LAUNCH(4, true, false);
-    else if (st.d == 64) TPNET_EM_LAUNCH(2, true, false);
-    else if (st.d % 4 == 0)
-        switch (encoder_steps(st.d)) {
-            case 2: TPNET_EM_LAUNCH(2, false, false); break;
-            case 3: TPNET_EM_LAUNCH(3, false, false); break;
-            case 4: TPNET_EM_LAUNCH(4, false, false); break;
-            default: TPNET_EM_LAUNCH(5, false, false); break;
-        }
-    else
-        switch (encoder_steps(st.d)) {                 // d % 4 == 2 (encoder_mfma_supported): 8-byte halves
-            case 2: TPNET_EM_LAUNCH(2, false, true); break;
-            case 3: TPNET_EM_LAUNCH(3, false, true); break;
-            case 4: TPNET_EM_LAUNCH(4, false, true); break;
-            default: TPNET_EM_LAUNCH(5, false, true); break;
-        }
+    const TileRound g = tile_round(ntiles, waves_dev, EMB / 64);
+#define TPNET_EM_LAUNCH(KS_, FULL_, R8_)                                                                                               \
+    hipLaunchKernelGGL((k_encoder_gram_mfma<KS_, FULL_, 3, R8_>), dim3(g.grid), dim3(EMB), 0, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+                       g.tpw, now, lambda, flags, out1, out2)
+    TPNET_ENCODER_WIDTH_SWITCH(st.d, TPNET_EM_LAUNCH);
 #undef TPNET_EM_LAUNCH
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
@@ -548,29 +528,11 @@ int launch_encoder_fused(const tpnet_state& st, const int64_t* neigh, const int6
     const int ntiles = (T + 3) / 4;
     // ONE workgroup per CU (its LDS holds the weight image), four producer waves each: tiles per producer for one round
     static const int wg_dev = TPNET_DEV_INT(ENCODER_FUSED_WGS, 256);
-    int tpw = (ntiles + wg_dev * EMF_NP - 1) / (wg_dev * EMF_NP);
-    if (tpw < 2) tpw = 2;
-    const int nprod = (ntiles + tpw - 1) / tpw;
-    const int grid = (nprod + EMF_NP - 1) / EMF_NP;
-#define TPNET_EMF_LAUNCH(KS_, FULL_, R8_)                                                                                              \
-    hipLaunchKernelGGL((k_encoder_fused<KS_, FULL_, 3, R8_>), dim3(grid), dim3(EMF_B), EMF_LDS, s, st, neigh, a1, a2, (int)n_rows, K, T, \
-                       tpw, now, lambda, flags, gram, reinterpret_cast<const float4*>(mlp->wimg), out)
-    if (st.d == 128) TPNET_EMF_LAUNCH(4, true, false);
-    else if (st.d == 64) TPNET_EMF_LAUNCH(2, true, false);
-    else if (st.d % 4 == 0)
-        switch (encoder_steps(st.d)) {
-            case 2: TPNET_EMF_LAUNCH(2, false, false); break;
-            case 3: TPNET_EMF_LAUNCH(3, false, false); break;
-            case 4: TPNET_EMF_LAUNCH(4, false, false); break;
-            default: TPNET_EMF_LAUNCH(5, false, false); break;
-        }
-    else
-        switch (encoder_steps(st.d)) {                 // d % 4 == 2 (encoder_mfma_supported): 8-byte halves
-            case 2: TPNET_EMF_LAUNCH(2, false, true); break;
-            case 3: TPNET_EMF_LAUNCH(3, false, true); break;
-            case 4: TPNET_EMF_LAUNCH(4, false, true); break;
-            default: TPNET_EMF_LAUNCH(5, false, true); break;
-        }
+    const TileRound g = tile_round(ntiles, wg_dev * EMF_NP, EMF_NP);
+#define TPNET_EMF_LAUNCH(KS_, FULL_, R8_)                                                                                                \
+    hipLaunchKernelGGL((k_encoder_fused<KS_, FULL_, 3, R8_>), dim3(g.grid), dim3(EMF_B), EMF_LDS, s, st, neigh, a1, a2, (int)n_rows, K, T, \
+                       g.tpw, now, lambda, flags, gram, reinterpret_cast<const float4*>(mlp->wimg), out)
+    TPNET_ENCODER_WIDTH_SWITCH(st.d, TPNET_EMF_LAUNCH);
 #undef TPNET_EMF_LAUNCH
     if (hipGetLastError() != hipSuccess) {             // (a runtime that refuses the launch: the callers fall back for good)
         encoder_fused_lds.refused();

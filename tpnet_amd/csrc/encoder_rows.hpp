@@ -66,4 +66,35 @@ __device__ __forceinline__ void to_operands(const float (&raw)[KS][8], float rs,
     for (int s = 0; s < KS; ++s) split8(v[s], op[s]);
 }
 
+// ---- host side: what the launchers of both files ask of a row width and a tile count ---------------------------------------
+// rows of 2..5 steps of 32 floats (d % 4 == 0: 36..160; d % 4 == 2, 8-byte rows: 38..158)
+inline bool encoder_row_width(int d) { return d >= 36 && d <= 160; }
+inline int encoder_steps(int d) { return (d + 31) / 32; }      // KS: 32-deep steps of a row of d floats
+
+// LAUNCH(KS, FULL, R8) for the instantiation that serves such a row: d = 64 / 128 in whole steps, every other d % 4 == 0 with the
+// last step masked, d % 4 == 2 the same in 8-byte halves
+#define TPNET_ENCODER_STEP_SWITCH(D_, LAUNCH, R8_) \
+    switch (tpnet::encoder_steps(D_)) {            \
+        case 2: LAUNCH(2, false, R8_); break;      \
+        case 3: LAUNCH(3, false, R8_); break;      \
+        case 4: LAUNCH(4, false, R8_); break;      \
+        default: LAUNCH(5, false, R8_); break;     \
+    }
+#define TPNET_ENCODER_WIDTH_SWITCH(D_, LAUNCH)                              \
+    do {                                                                    \
+        if ((D_) == 128) LAUNCH(4, true, false);                            \
+        else if ((D_) == 64) LAUNCH(2, true, false);                        \
+        else if ((D_) % 4 == 0) TPNET_ENCODER_STEP_SWITCH(D_, LAUNCH, false) \
+        else TPNET_ENCODER_STEP_SWITCH(D_, LAUNCH, true)                    \
+    } while (0)
+
+// tiles per wave for ONE round of the `waves` waves the chip holds, at least two tiles each; the grid of blocks of `per_block` of them
+struct TileRound { int tpw, grid; };
+inline TileRound tile_round(int ntiles, int waves, int per_block) {
+    int tpw = (ntiles + waves - 1) / waves;
+    if (tpw < 2) tpw = 2;
+    const int nwaves = (ntiles + tpw - 1) / tpw;
+    return {tpw, (nwaves + per_block - 1) / per_block};
+}
+
 }  // namespace tpnet

@@ -365,11 +365,10 @@ int tpnet_host_anchored_features(const tpnet_state* st, tpnet_stage* stage, cons
     const int64_t K = pattern_and_stage(h_src, h_dst, n, st->N, nullptr, 0, nullptr, nullptr);
     if (K < 4 || K > (1 << 20)) return TPNET_OK;
     const int64_t m = h / K;
-    // served where readout + dense layers are one launch, or the two-launch path has its feature buffer
-    // (rows of d % 4 == 2: only with TPNET_FLAG_ROWS8, on the matrix cores)
-    if (rows8_asked(*st, flags)) {
-        if (!(encoder_fused_supported(*st, m, (int)K, mlp, flags) || (gram && encoder_mfma_supported(*st, m, (int)K, flags)))) return TPNET_OK;
-    } else if (!(tpnet_encoder_fused_supported(st, m, (int32_t)K, mlp) || (gram && tpnet_pair_gram_anchored_supported(st)))) return TPNET_OK;
+    // served where readout + dense layers are one launch, or the two-launch path has its feature buffer and a kernel for the Gram
+    if (check_state(st)) return TPNET_OK;
+    const AnchoredRoute r = anchored_route(*st, m, (int)K, flags, mlp, true, false);
+    if (!(r.one_launch || (gram && r.gram != AK_REFUSED))) return TPNET_OK;
     const size_t bytes = (size_t)(h + 2 * m) * 8;
     if (bytes > stage->slot_bytes) return TPNET_OK;
     hipStream_t s = (hipStream_t)stream;

@@ -269,14 +269,6 @@ __global__ void k_encoder_sample(const int64_t* __restrict__ row_start, const in
 
 using namespace tpnet;
 
-// rows of <= 128 floats: the generic pair kernel's 16-lane geometry reads an encoder-style list faster than the anchored walk
-// (tools/encoder_readout.py, 80 000 pairs at d=128: 27.1 against 31.3 us; 16 000 at d=64: 7.1 against 13.2) -- the encoder's calls
-// take it there, from pair lists the sampler kernel writes beside the neighbour ids
-bool tpnet::encoder_generic_readout(const tpnet_state& st) {
-    static const int off = TPNET_DEV_INT(ENCODER_ANCHORED_ONLY, 0);
-    return !off && st.d <= 128;
-}
-
 extern "C" {
 
 // Layout of the sampler buffer (caller-owned device memory of tpnet_sampler_bytes): the CSR, which is all a sampling call reads,
@@ -436,7 +428,8 @@ int tpnet::encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, i
     }
     SamplerView v = csr_view(sampler, E, num_nodes);
     const int grid = grid_1d(2 * B * (int64_t)K, 8192);
-    int64_t* pu = (encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K, flags) && !layers_asked(*st, 2 * B, K, flags)) ? neigh + 2 * B * (int64_t)K : nullptr;
+    // (the call's pairs spelled out behind the neighbour ids: only where the generic pair kernel will read them)
+    int64_t* pu = anchored_route(*st, 2 * B, K, flags, nullptr, true, true).gram == AK_GENERIC ? neigh + 2 * B * (int64_t)K : nullptr;
     hipLaunchKernelGGL(k_encoder_sample, dim3(grid), dim3(256), 0, s, v.row_start, v.nbr, v.nbr_t, num_nodes, src, other, t, B, (int)K,
                        nodes, t2, a1, a2, neigh, pu, pu ? pu + 4 * B * (int64_t)K : nullptr);
     TPNET_HIP_TRY(hipGetLastError());
@@ -452,10 +445,10 @@ int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, in
     if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;
     if (B == 0) return TPNET_OK;
     if (check_state(st)) return TPNET_ERR_BAD_ARG;
-    // (TPNET_FLAG_LAYERS_MFMA needs 16-byte aligned outputs; without them the call is the one without the flag)
-    if (reinterpret_cast<uintptr_t>(out) & 15) flags &= ~TPNET_FLAG_LAYERS_MFMA;
-    // rows of d % 4 == 2 with TPNET_FLAG_ROWS8: the matrix-core readout or nothing
-    if (rows8_asked(*st, flags) ? !encoder_mfma_supported(*st, 2 * B, K, flags) : !pair_gram_anchored_supported(*st)) return TPNET_ERR_BAD_ARG;
+    // (TPNET_FLAG_LAYERS_MFMA needs 16-byte aligned outputs; without them the call is the one without the flag, pair lists included)
+    if (!aligned16({out})) flags &= ~TPNET_FLAG_LAYERS_MFMA;
+    // needs what tpnet_pair_gram_anchored serves -- also on narrow rows, which the generic kernel then takes from the pair lists
+    if (anchored_route(*st, 2 * B, K, flags, nullptr, true, false).gram == AK_REFUSED) return TPNET_ERR_BAD_ARG;
     int rc = encoder_rows(st, sampler, E, num_nodes, src, other, t, B, K, flags, scratch, scratch_bytes, stream);
     if (rc) return rc;
     int64_t* nodes = (int64_t*)align256((size_t)scratch);
@@ -463,7 +456,7 @@ int tpnet_encoder_gram(const tpnet_state* st, const void* sampler, int64_t E, in
     int64_t* a2 = a1 + 2 * B;
     int64_t* neigh = a2 + 2 * B;
     const int NN = 2 * st->L + 2;
-    if (encoder_generic_readout(*st) && !encoder_mfma_supported(*st, 2 * B, K, flags) && !layers_asked(*st, 2 * B, K, flags)) {
+    if (anchored_route(*st, 2 * B, K, flags, nullptr, true, true).gram == AK_GENERIC) {
         const int64_t half = 2 * B * (int64_t)K;
         return tpnet_pair_gram(st, neigh + half, neigh + 3 * half, 2 * half, now_time, lambda, flags, out, stream);
     }

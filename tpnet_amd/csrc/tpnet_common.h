@@ -174,19 +174,13 @@ int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const
                               hipStream_t s);
 // encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 36..160 floats (d % 4 == 0), L = 3, K >= 4;
 // with TPNET_FLAG_ROWS8 (and without TPNET_FLAG_NO_MFMA_READOUT) in `flags` also for rows of 38..158 floats with d % 4 == 2, which no
-// other anchored kernel reads: rows8_asked = the flag on such a row -- served there, or the call is refused
+// other anchored kernel reads
 bool encoder_mfma_supported(const tpnet_state& st, int64_t n_rows, int K, uint32_t flags = 0);
-inline bool rows8_asked(const tpnet_state& st, uint32_t flags) { return (flags & TPNET_FLAG_ROWS8) && st.d % 4 == 2; }
 int launch_encoder_gram_mfma(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                              int K, double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s);
 // encoder_layers.hip: the matrix-core readout for L = 1, 2, 4 (rows of 36..160 floats, d % 4 == 0, K >= 4), taken only where the
-// caller asks: layers_asked = TPNET_FLAG_LAYERS_MFMA on a shape it serves, not taken back by TPNET_FLAG_NO_MFMA_READOUT -- every
-// other call with the flag keeps the route it has without it
+// caller asks (TPNET_FLAG_LAYERS_MFMA)
 bool encoder_layers_supported(const tpnet_state& st, int64_t n_rows, int K);
-inline bool layers_asked(const tpnet_state& st, int64_t n_rows, int K, uint32_t flags) {
-    return (flags & TPNET_FLAG_LAYERS_MFMA) && !(flags & (TPNET_FLAG_NO_MFMA_READOUT | TPNET_FLAG_PACKED)) &&
-           encoder_layers_supported(st, n_rows, K);
-}
 int launch_encoder_gram_layers(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2, int64_t n_rows,
                                int K, double now, double lambda, uint32_t flags, float* out1, float* out2, hipStream_t s);
 // the same + self.mlp in ONE launch (gram: optional copy of the pre-mlp features [2][n_rows * K][64]; out [2 * n_rows * K][64])
@@ -255,9 +249,16 @@ struct LdsOptIn {
 
 // the plan of ONE batch by one workgroup (plan.hip, k_plan_one): same Plan contents as plan_build for batch 0 of a chunk
 static constexpr int64_t PLAN_ONE_MAX = 2048;
-bool encoder_generic_readout(const tpnet_state& st);   // sampler.hip: the encoder's calls on rows of <= 128 floats
-// sampler.hip: tpnet_encoder_rows for a readout that runs with `flags` (the spelled-out pair lists are written only where the
-// generic readout will take the call: not where TPNET_FLAG_ROWS8 sends it to the matrix cores)
+// THE route of an anchored readout (encoder.hip; the table: include/tpnet_hip.h at tpnet_anchored_route): every entry point asks here
+// and switches on the answer.  gram: who forms the Gram; one_launch: readout + self.mlp (0: no, 1: k_encoder_fused, 2: k_anchored_feature);
+// rows8: TPNET_FLAG_ROWS8 on a row of d % 4 == 2 decided `gram` (the matrix cores or refused).  mlp may be null; aligned: the outputs
+// are, to 16 bytes; pair_lists: the encoder's scratch has the pairs spelled out for the generic kernel.  No HIP call where mlp is null.
+enum AnchoredKernel { AK_REFUSED, AK_GENERIC, AK_WALK, AK_MFMA, AK_LAYERS };
+struct AnchoredRoute { AnchoredKernel gram; int one_launch; bool rows8; };
+AnchoredRoute anchored_route(const tpnet_state& st, int64_t n_rows, int K, uint32_t flags, const tpnet_mlp* mlp, bool aligned,
+                             bool pair_lists);
+// sampler.hip: tpnet_encoder_rows for a readout that runs with `flags` (the spelled-out pair lists are written only where the route's
+// Gram kernel is AK_GENERIC)
 int encoder_rows(const tpnet_state* st, const void* sampler, int64_t E, int64_t num_nodes, const int64_t* src, const int64_t* other,
                  const double* t, int64_t B, int32_t K, uint32_t flags, void* scratch, size_t scratch_bytes, void* stream);
 int64_t plan_one_max_batch();      // PLAN_ONE_MAX (0 with the developer override TPNET_DEV_NO_PLAN_ONE)

@@ -912,8 +912,8 @@ class RandomProjectionModule(nn.Module):
         if n > 8192 and n % 2 == 0 and not self.fused_mlp and cuda:
             # 5. the encoder's call as the reference issues it (models/TPNet.py:311-316: src = tile(neigh, 2), dst = concat(repeat(a1,
             #    K), repeat(a2, K)) on the host): recognised in one pass over the two arrays in C; n / 2 neighbour ids + 2 n / (2 K)
-            #    anchors go up instead of 2 n ids, the anchored readout and the dense layers run as one call (dim % 4 == 0,
-            #    36 <= dim <= 512; one launch on the matrix cores up to dim = 160, and beyond where tpnet_encoder_fused_supported)
+            #    anchors go up instead of 2 n ids, the anchored readout and the dense layers run as one call (where _anchored_route
+            #    serves the shape; one launch where it says so)
             feats = self._encoder_pattern_features(src, dst_node_ids, n)
             if feats is not None:
                 return feats
@@ -927,7 +927,8 @@ class RandomProjectionModule(nn.Module):
                 self._ensure_engine()
                 r1 = self._anchor_runs(dst[: n // 2])
                 r2 = self._anchor_runs(dst[n // 2:]) if r1 is not None else None
-                if r1 is not None and r2 is not None and _lib.load().tpnet_pair_gram_anchored_supported(self._st_ref()):
+                # (rows of whole 16-byte vectors, where being served does not depend on rows and K; 8-byte rows keep route 7)
+                if r1 is not None and r2 is not None and self.engine_dim % 4 == 0 and self._anchored_route(1, 4)[1]:
                     K = int(np.gcd(r1[1], r2[1]))
                     if K >= 4:
                         m = (n // 2) // K
@@ -945,19 +946,16 @@ class RandomProjectionModule(nn.Module):
         fast on long lists as the kernels that fetch x's rows once -- measured, tools/encoder_readout.py.)"""
         return self.engine_dim > 128 and n >= 2 and n % 2 == 0 and np.array_equal(src[: n // 2], src[n // 2:])
 
-    def _feature_call(self, prep, n, launch, rows_k=None):
+    def _feature_call(self, prep, n, launch, one_launch=True):
         """A readout + self.mlp call, `launch(gram)` -> the [n, (2L+2)^2] features, `gram` = where the kernel leaves the pre-mlp
         features (None: nowhere).  With gradients recorded, the autograd node allocates that buffer and keeps it for the backward
-        pass.  Without: no buffer -- for the encoder's calls (`rows_k` = their (rows, K)) only where readout and dense layers are
-        ONE launch (tpnet_encoder_fused_supported: rows of 36..160 floats, dim % 4 == 0, K >= 4; rows of 164..512 floats where
-        their geometry class is routed to csrc/anchored_feature.hip), else a scratch tensor between the two launches; and if the runtime refuses the one launch after all (TPNET_ERR_NEED_GRAM), once more with a scratch."""
+        pass.  Without: no buffer -- for the encoder's calls only where readout and dense layers are ONE launch (`one_launch`: what
+        _anchored_route said), else a scratch tensor between the two launches; and if the runtime refuses the one launch after all
+        (TPNET_ERR_NEED_GRAM), once more with a scratch."""
         NG = self.pair_wise_feature_dim
         if _ff.needs_grad(prep.params):
             return _ff.apply_with_grad(self.mlp, launch, n, NG)
-        gram = None
-        if rows_k is not None and not (_lib.load().tpnet_encoder_fused_supported(self._st_ref(), rows_k[0], rows_k[1], prep.ref)
-                                       or self._rows8(rows_k[0], rows_k[1], prep.ref)):
-            gram = torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
+        gram = None if one_launch else torch.empty((n, NG), dtype=torch.float32, device=self._eng["dev"])
         try:
             return launch(gram)
         except _lib.NeedGramBuffer:
@@ -975,10 +973,10 @@ class RandomProjectionModule(nn.Module):
             return out
         return launch
 
-    def _anchored_launch(self, wd, a1, a2, rows, K, prep, rows8=0):
+    def _anchored_launch(self, wd, a1, a2, rows, K, prep, flags=None):
         """The launch (for _feature_call) of tpnet_anchored_features: `rows` x K neighbour ids `wd` and two anchors per row, all on
-        the device -> [2 * rows * K, (2L+2)^2] features, self.mlp applied.  `rows8`: what _rows8 said for this call."""
-        lib, flags, dev = _lib.load(), self._readout_flags() | rows8, self._eng["dev"]
+        the device -> [2 * rows * K, (2L+2)^2] features, self.mlp applied.  `flags`: what _anchored_route said for this call."""
+        lib, dev, flags = _lib.load(), self._eng["dev"], self._readout_flags() if flags is None else flags
 
         def launch(gram):
             out = torch.empty((2 * rows * K, self.pair_wise_feature_dim), dtype=torch.float32, device=dev)
@@ -998,10 +996,10 @@ class RandomProjectionModule(nn.Module):
             return None
         if self.layers_readout and self.num_layer != 3 and not self.fused_mlp:
             # num_layer 1, 2, 4 with `layers_readout`: the pattern's n / 2 neighbours and 2 n / (2 K) anchors go up, the anchored
-            # readout runs on the matrix cores where tpnet_encoder_layers_supported (else on the walk), self.mlp behind it
+            # readout runs on the matrix cores where the route says so (else on the walk), self.mlp behind it
             self._ensure_engine()
             lib = _lib.load()
-            if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
+            if not self._anchored_route(1, 4)[1]:                      # (at these num_layer being served does not depend on rows and K)
                 return None
             K = int(lib.tpnet_host_encoder_pattern(src.ctypes.data, dst.ctypes.data, n, self.node_num))
             if K < 4:
@@ -1015,10 +1013,10 @@ class RandomProjectionModule(nn.Module):
             return None
         self._ensure_engine()
         lib = _lib.load()
-        anchored = bool(lib.tpnet_pair_gram_anchored_supported(self._st_ref()))
-        # (rows of dim % 4 == 2 with `rows8_readout`: the pattern's K is the C call's to find -- it declines what the flag does not serve)
-        rows8 = 0 if anchored else self._rows8(1, 4, prep.ref)
-        if not anchored and not rows8:
+        # (the pattern's K is the C call's to find: the smallest served shape stands in -- on 16-byte rows the answer does not depend on
+        # it, on 8-byte rows the C call declines what the flag does not serve)
+        flags, ok, _ = self._anchored_route(1, 4, prep.ref)
+        if not ok:
             return None
         if _ff.needs_grad(prep.params) and int(lib.tpnet_host_encoder_pattern(src.ctypes.data, dst.ctypes.data, n, self.node_num)) < 4:
             # (training: the cheap host check FIRST -- a declined call would already have allocated an n x 64 feature buffer and an
@@ -1033,7 +1031,6 @@ class RandomProjectionModule(nn.Module):
             if eng.get("stage_big") is None:
                 eng["stage_big"] = _Stage(lib, eng["dev"], slots=4, slot_bytes=_BIG_SLOT_BYTES)
             served = C.c_int32(0)
-            flags = self._readout_flags() | rows8
 
             def launch_host(gram):
                 out = torch.empty((n, self.pair_wise_feature_dim), dtype=torch.float32, device=eng["dev"])
@@ -1051,24 +1048,20 @@ class RandomProjectionModule(nn.Module):
         if K < 4:
             return None
         h = n // 2
-        if not anchored:
-            rows8 = self._rows8(h // K, K, prep.ref)
-            if not rows8:
-                return None
+        flags_k, ok, one_launch = self._anchored_route(h // K, K, prep.ref)
+        if not ok:
+            return None
         wd, a1, a2 = self._to_device(src[:h], np.ascontiguousarray(dst[:h:K]), np.ascontiguousarray(dst[h::K]))
-        return self._feature_call(prep, n, self._anchored_launch(wd, a1, a2, h // K, K, prep, rows8), (h // K, K))
+        return self._feature_call(prep, n, self._anchored_launch(wd, a1, a2, h // K, K, prep, flags_k), one_launch)
 
     def pair_gram_anchored(self, neighbor_ids, first_anchor_ids, second_anchor_ids, matrix_cores=True):
         """The encoder's readout before self.mlp (models/TPNet.py:311-324): neighbor_ids [n, K] (the sampled neighbours of n
         rows), two anchors per row (the edge's src and dst).  Returns [2, n*K, (2L+2)^2]: G(neighbour, first anchor) for every
         (row, neighbour), then G(neighbour, second anchor) -- viewed as [2*n*K, .] this is the reference's
         get_pair_wise_feature(tile(neighbours, 2), concat(repeat(first, K), repeat(second, K))) pair order.  One lane group per
-        row keeps both anchors' rows in registers for its K neighbours (tpnet_pair_gram_anchored).  Served: rows of whole 16-byte
-        vectors, dim % 4 == 0 and 36 <= dim <= 512 (the reference's default widths 120, 140, 160 among them); rows of 36..160
-        floats with L = 3 and K >= 4 take the matrix cores (csrc/encoder_mfma.hip) unless matrix_cores=False.  With
-        `rows8_readout` set, rows of dim % 4 == 2 (38 <= dim <= 158, L = 3, K >= 4) are served too, on the matrix cores only.
-        With `layers_readout` set, L = 1, 2 and 4 take the matrix cores on the same rows of 36..160 floats (dim % 4 == 0, K >= 4:
-        csrc/encoder_layers.hip) unless matrix_cores=False; without it they keep the vector-ALU walk."""
+        row keeps both anchors' rows in registers for its K neighbours (tpnet_pair_gram_anchored).  Which shapes are served and by
+        which kernel -- the vector-ALU walk or the matrix cores, `rows8_readout` and `layers_readout` included -- is the table at
+        tpnet_anchored_route (include/tpnet_hip.h), asked through _anchored_route; matrix_cores=False keeps the walk."""
         self._ensure_engine()
         nb = neighbor_ids if isinstance(neighbor_ids, torch.Tensor) else np.asarray(neighbor_ids)
         if nb.ndim != 2:
@@ -1078,52 +1071,50 @@ class RandomProjectionModule(nn.Module):
         if len(first_anchor_ids) != n or len(second_anchor_ids) != n:
             raise ValueError("one first and one second anchor per row of neighbor_ids")
         lib = _lib.load()
-        rows8 = 0
-        if not lib.tpnet_pair_gram_anchored_supported(self._st_ref()):
-            rows8 = self._rows8(n, K) if matrix_cores else 0
-            if not rows8:
-                raise _lib.TPNetHipError(f"pair_gram_anchored needs rows of dim % 4 == 0 and 36 <= dim <= 512 floats, not {self.engine_dim}: "
-                                         "use pair_gram_shared")
+        flags, served, _ = self._anchored_route(n, K, matrix_cores=matrix_cores)
+        if not served:
+            raise _lib.TPNetHipError(f"pair_gram_anchored needs rows of dim % 4 == 0 and 36 <= dim <= 512 floats, not {self.engine_dim}: "
+                                     "use pair_gram_shared")
         wd = self._to_device(self._ids(w, "neighbor_ids"))[0]
         a1, a2 = self._to_device(self._ids(first_anchor_ids, "first_anchor_ids"),
                                  self._ids(second_anchor_ids, "second_anchor_ids"))
         out = torch.empty((2, n * K, self.pair_wise_feature_dim), dtype=torch.float32, device=self._dev())
-        flags = self._readout_flags(matrix_cores=matrix_cores) | rows8
         _lib.check(lib.tpnet_pair_gram_anchored(self._st_ref(), wd.data_ptr(), a1.data_ptr(), a2.data_ptr(), n, K,
                                                 self._now_host, float(self.time_decay_weight), flags, out[0].data_ptr(),
                                                 out[1].data_ptr(), self._stream()), "pair_gram_anchored")
         return out
 
-    # extension, opt-in: rows that are only 8-byte aligned -- dim % 4 == 2, 38 <= dim <= 158: the default rule's 110 / 130 / 150
-    # (models/TPNet.py:30-33) -- take the encoder's readout on the matrix cores and readout + self.mlp as one launch, L = 3 and
-    # K >= 4 (TPNET_FLAG_ROWS8, csrc/encoder_mfma.hip; profiles/encoder_even_widths.md).  False: at these widths the encoder's calls keep
-    # the general pair kernel and the torch layers, bit for bit.  `update`, pair_gram and the decoder-level readouts run on the
-    # scalar geometry at these widths either way
+    # extension, opt-in: rows that are only 8-byte aligned (dim % 4 == 2: the default rule's 110 / 130 / 150, models/TPNet.py:30-33)
+    # take the encoder's anchored calls on the matrix cores where the table at tpnet_anchored_route serves such rows
+    # (profiles/encoder_even_widths.md).  False: these calls keep the general pair kernel and the torch layers, bit for bit.
+    # `update`, pair_gram and the decoder-level readouts run on the scalar geometry at these widths either way
     rows8_readout = False
 
-    # extension, opt-in: num_layer 1, 2 or 4 -- the encoder's anchored readout (pair_gram_anchored and what is built on it:
-    # get_pair_wise_feature_anchored, encoder_pair_features, get_pair_wise_feature on the encoder's host pattern) on the matrix
-    # cores, rows of 36..160 floats with dim % 4 == 0 and K >= 4 (TPNET_FLAG_LAYERS_MFMA, csrc/encoder_layers.hip;
-    # profiles/encoder_layers.md); every other shape keeps its route.  False: the vector-ALU walk resp. the general pair kernel,
-    # bit for bit.  No effect at num_layer 3.  self.mlp behind the readout is what _apply_mlp picks either way
+    # extension, opt-in: num_layer 1, 2 or 4 take the encoder's anchored readout (pair_gram_anchored and what is built on it) on the
+    # matrix cores where the same table serves TPNET_FLAG_LAYERS_MFMA (profiles/encoder_layers.md); every other shape keeps its
+    # route.  False: the walk resp. the general pair kernel, bit for bit.  self.mlp behind it is what _apply_mlp picks either way
     layers_readout = False
 
-    def _rows8(self, rows, K, mlp_ref=None) -> int:
-        """_lib.FLAG_ROWS8 if `rows8_readout` is set and tpnet_encoder_rows8_supported answers 1 for `rows` x K neighbours (with
-        `mlp_ref`: for readout + self.mlp in one launch), else 0."""
-        if not self.rows8_readout or self.engine_dim % 4 != 2:
-            return 0
-        return _lib.FLAG_ROWS8 if _lib.load().tpnet_encoder_rows8_supported(self._st_ref(), rows, K, mlp_ref) else 0
+    def _anchored_route(self, rows, K, mlp_ref=None, matrix_cores=True):
+        """THE route of an anchored call of `rows` x K neighbours in one FFI call (tpnet_anchored_route: the table is its comment in
+        include/tpnet_hip.h) -> (flags, served, one_launch).  Asked with _readout_flags, plus TPNET_FLAG_ROWS8 where `rows8_readout` is
+        set on rows of dim % 4 == 2; `flags`: the word to launch with -- that flag only where it is served.  `served`: a kernel forms
+        the Gram (such 8-byte rows with `mlp_ref`: only as one launch).  `one_launch`: readout + self.mlp need no feature buffer."""
+        flags = self._readout_flags(matrix_cores=matrix_cores)
+        rows8 = self.rows8_readout and self.engine_dim % 4 == 2
+        route = _lib.load().tpnet_anchored_route(self._st_ref(), rows, K, flags | _lib.FLAG_ROWS8 if rows8 else flags, mlp_ref)
+        served = route >> 4 == 1 if (rows8 and mlp_ref is not None) else route != 0
+        return (flags | _lib.FLAG_ROWS8 if (rows8 and served) else flags), served, route >> 4 != 0
 
     def anchored_call_served(self, rows, K) -> bool:
-        """Whether get_pair_wise_feature_anchored serves `rows` x K neighbours at this module's width: dim % 4 == 0 and
-        36 <= dim <= 512, or -- `rows8_readout` -- what tpnet_encoder_rows8_supported accepts."""
+        """Whether get_pair_wise_feature_anchored serves `rows` x K neighbours at this module's width (_anchored_route; rows of whole
+        16-byte vectors are answered from the table's width rule, without an engine)."""
         if self.engine_dim % 4 == 0 and 36 <= self.engine_dim <= 512:
             return True
         if not self.rows8_readout or self._plist()[0].device.type != "cuda":
             return False
         self._ensure_engine()
-        return bool(self._rows8(rows, K))
+        return self._anchored_route(rows, K)[1]
 
     def _overlapped_mlp(self):
         """The prepared fp32 weights of self.mlp if the encoder's one-call path applies (readout chunks and their dense layers side
@@ -1135,23 +1126,19 @@ class RandomProjectionModule(nn.Module):
 
     def get_pair_wise_feature_anchored(self, neighbor_ids, first_anchor_ids, second_anchor_ids):
         """Extension: the encoder's call (models/TPNet.py:313-316) from its natural arguments; [2*n*K, (2L+2)^2] in the
-        reference's row order, self.mlp applied.  Needs what pair_gram_anchored needs (dim % 4 == 0, 36 <= dim <= 512).  Device
-        ids, L = 3, K >= 4: one launch on rows of 36..160 floats (csrc/encoder_mfma.hip); on rows of 164..512 floats one launch
-        (csrc/anchored_feature.hip) where that kernel is the route of the width's geometry class, else the anchored walk and the
-        dense layers as two launches (tpnet_encoder_fused_supported tells which).  With `rows8_readout` set, rows of
-        dim % 4 == 2 (38 <= dim <= 158) take the same one launch (tpnet_encoder_rows8_supported).  L != 3: pair_gram_anchored, then
-        self.mlp -- with `layers_readout` set the readout on the matrix cores (tpnet_encoder_layers_supported), else the walk."""
+        reference's row order, self.mlp applied.  Needs what pair_gram_anchored needs.  Device ids, L = 3: readout and self.mlp
+        in one C call -- one launch or two, as the table at tpnet_anchored_route (include/tpnet_hip.h) says for the shape.  Else
+        (host ids, L != 3, another self.mlp): pair_gram_anchored, then self.mlp."""
         prep = self._overlapped_mlp() if self._plist()[0].device.type == "cuda" else None
         if prep is not None and isinstance(neighbor_ids, torch.Tensor) and neighbor_ids.is_cuda:
             self._ensure_engine()
-            lib = _lib.load()
             n, K = neighbor_ids.shape
-            rows8 = 0
-            if lib.tpnet_pair_gram_anchored_supported(self._st_ref()) or (rows8 := self._rows8(n, K, prep.ref)):
+            flags, served, one_launch = self._anchored_route(n, K, prep.ref)
+            if served:
                 wd = self._ids(neighbor_ids.reshape(-1), "neighbor_ids")
                 a1, a2 = self._to_device(self._ids(first_anchor_ids, "first_anchor_ids"),
                                          self._ids(second_anchor_ids, "second_anchor_ids"))
-                return self._feature_call(prep, 2 * n * K, self._anchored_launch(wd, a1, a2, n, K, prep, rows8), (n, K))
+                return self._feature_call(prep, 2 * n * K, self._anchored_launch(wd, a1, a2, n, K, prep, flags), one_launch)
         g = self.pair_gram_anchored(neighbor_ids, first_anchor_ids, second_anchor_ids)
         return self._apply_mlp(g.view(-1, self.pair_wise_feature_dim))
 
@@ -1198,14 +1185,13 @@ class RandomProjectionModule(nn.Module):
         NG = self.pair_wise_feature_dim
         nbytes = lib.tpnet_encoder_scratch_bytes(B, K)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        flags = self._readout_flags()
         off = (-scratch.data_ptr()) % 256 + 64 * B
         neigh = scratch[off: off + 16 * B * K].view(torch.int64).view(2 * B, K)
         prep = self._overlapped_mlp()
-        anchored = bool(lib.tpnet_pair_gram_anchored_supported(self._st_ref()))
-        if not anchored:
-            flags |= (prep is not None and self._rows8(2 * B, K, prep.ref)) or self._rows8(2 * B, K)
-        if prep is not None and (anchored or flags & _lib.FLAG_ROWS8):
+        flags, served, one_launch = self._anchored_route(2 * B, K, prep.ref if prep is not None else None)
+        if prep is not None and not served:      # (8-byte rows whose one launch the runtime refuses: the readout alone may be served)
+            flags, served, one_launch = self._anchored_route(2 * B, K)
+        if prep is not None and served:
             # ONE call, self.mlp included: the dense layers of a chunk of rows run beside the readout of the next one
             def launch(gram):
                 out = torch.empty((4 * B * K, NG), dtype=torch.float32, device=dev)
@@ -1222,7 +1208,7 @@ class RandomProjectionModule(nn.Module):
                                                       scratch.data_ptr(), nbytes, _ptr_or_null(gram), out.data_ptr(),
                                                       _raw_stream(self._eng["dev_index"])), "encoder_features")
                 return out
-            return self._feature_call(prep, 4 * B * K, launch, (2 * B, K)), neigh
+            return self._feature_call(prep, 4 * B * K, launch, one_launch), neigh
         if host:
             s_d, o_d, t_d = self._to_device(self._ids(src_ids, "src_ids"), self._ids(other_ids, "other_ids"), times)
             return self.encoder_pair_features(sampler, s_d, o_d, t_d, num_neighbors)
