@@ -58,7 +58,9 @@ extern "C" {
                                     TPNET_FLAG_LAYERS_MFMA / tpnet_encoder_layers_* (the encoder's matrix-core readout for num_layer 1, 2, 4);
                                     tpnet_pair_gram_fanout* (one source against C candidates), tpnet_neg_sample_many (per-query candidates),
                                     tpnet_lp_ranking* (a batch's MRR and Hits@k as one device record);
-                                    tpnet_anchored_route (which kernel serves an anchored readout: the one table) */
+                                    tpnet_anchored_route (which kernel serves an anchored readout: the one table);
+                                    tpnet_score_one_to_many* (one source against many candidates, one logit per pair, in one launch),
+                                    tpnet_lp_ranking_skip (the ranking record with one absent candidate column per query) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -335,6 +337,38 @@ int tpnet_pair_gram_anchored_supported(const tpnet_state* st);
 int tpnet_pair_gram_fanout(const tpnet_state* st, const int64_t* src, const int64_t* cand, int64_t n_rows, int32_t C,
                            double now_time, double lambda, uint32_t flags, float* out, void* stream);
 int tpnet_pair_gram_fanout_supported(const tpnet_state* st);
+
+/* ---- one source against many candidates, ONE logit per pair, in one launch (additive to ABI 7; csrc/score_fanout.hip, DESIGN.md
+ * section 3.3 / 3.8).  For row i with source src[i] and every candidate c of that row
+ *   f     = G(src[i], c)                      tpnet_pair_gram_fanout's finished row (64 floats, L = 3), bit for bit
+ *   y     = W2m . relu(W1m . f + b1m) + b2m   self.mlp (tpnet_mlp: F = 64, H = 256, w1 and w2f present), the fp32 class
+ *   a     = Wd[:, off : off + 64] . y + bd    LinkPredictor_v1's fc1 restricted to its feature columns (not_encode: the embedding
+ *                                             columns meet zeros), read from fc1.weight AS IT IS: wd = [H][ldw] row-major
+ *   logit = wd2 . relu(a) + bd2               fc2.weight [1][H], fc2.bias [1]
+ * and only out[i, c] is written: features, mlp output and hidden layer never reach memory.
+ * Candidates: cand != NULL: the list cand[i*C .. i*C+C), laid out as for tpnet_pair_gram_fanout; cand == NULL: the ids
+ * [cand_lo, cand_lo + C), the same for every row, formed in the kernel (no id array).
+ * lead (optional, [n_rows]): one more id per row, scored into column 0 -- out is then [n_rows, 1 + C], the layout tpnet_lp_ranking
+ * reads; without it out is [n_rows, C].  gram (optional, NULL in production): [n_rows * C_1, 64] with C_1 = the row's column count
+ * (C or 1 + C), the features f as the kernel formed them, 16-byte aligned.
+ * PROMISES.  (1) A pair's logit depends on its two nodes, the state and the weights alone: the same (u, v) gives the same bits
+ * whatever n_rows, C, its tile column, its chunk, list or range mode, lead or candidate column -- a pair is one column of every
+ * matrix product, and the sums across waves are taken in a fixed order.  (2) Two calls on the same inputs give the same bits: no
+ * floating-point atomics.
+ * Served (tpnet_score_one_to_many_supported returns 1; host arithmetic, no GPU call): L = 3 with the reference mlp; d % 4 == 0,
+ * 36 <= d <= 512 (lane geometries 16x1, 32x1, 32x2 and 64x2, exact-fit and masked; every instantiation builds without scratch);
+ * 1 <= H <= 256; off % 4 == 0, ldw % 4 == 0,
+ * off + 64 <= ldw; n_rows (1 + C) < 2^31.  TPNET_FLAG_NOT_SCALE is honoured, TPNET_FLAG_PACKED is refused.
+ * Null pointers (cand, lead and gram may be NULL), C <= 0, n_rows < 0, a range that leaves [0, N), wd / gram / mlp->w1 / w2f / b2 not
+ * 16-byte aligned, an unserved size: TPNET_ERR_BAD_ARG, nothing launched; n_rows == 0: TPNET_OK.  An id outside [0, N): its pairs
+ * are NaN logits (a source: its whole row; a candidate or lead: its one entry), every other entry is untouched, the state's error
+ * word is raised -- tpnet_pair_gram_fanout's rules.  A feature row that holds a NaN answers a NaN logit, as the torch layers do.
+ * Needs 114 560 bytes of dynamic LDS per workgroup; a device that refuses them: TPNET_ERR_HIP. */
+int tpnet_score_one_to_many(const tpnet_state* st, const int64_t* src, const int64_t* cand, int64_t cand_lo, const int64_t* lead,
+                            int64_t n_rows, int32_t C, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp,
+                            const float* wd, int32_t ldw, int32_t off, const float* bd, const float* wd2, const float* bd2, int32_t H,
+                            float* gram, float* out, void* stream);
+int tpnet_score_one_to_many_supported(const tpnet_state* st, const tpnet_mlp* mlp, int32_t H, int32_t off, int32_t ldw);
 
 /* Workspace for tpnet_update / tpnet_run_stream with at most max_edges edges per call. */
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch);
@@ -739,6 +773,14 @@ int tpnet_lp_train_loss(const float* pos_score, int64_t n_pos, const float* neg_
 size_t tpnet_lp_ranking_scratch_bytes(int64_t B, int32_t C1);
 int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* cand_or_null, int32_t k1, int32_t k2, int32_t k3,
                      void* scratch, size_t scratch_bytes, int64_t* record, void* stream);
+/* The same record with ONE absent candidate column per query (ranking against all nodes: the true destination sits among the
+ * candidates, and a [B, C1 - 1] matrix of marks to drop one column per row would be larger than the logits).  skip_col: [B] int64 on
+ * the device, 8-byte aligned; candidate column skip_col[i] (0-based among the C1 - 1 candidates; -1 or any value outside
+ * [0, C1 - 1): none) of query i is treated as absent -- not ranked, not counted in n_valid_candidates, a NaN under it is not looked
+ * at.  Same scratch size, same finish kernel, same checks as tpnet_lp_ranking; a null or misaligned skip_col with B > 0:
+ * TPNET_ERR_BAD_ARG. */
+int tpnet_lp_ranking_skip(const float* logits, int64_t B, int32_t C1, const int64_t* skip_col, int32_t k1, int32_t k2, int32_t k3,
+                          void* scratch, size_t scratch_bytes, int64_t* record, void* stream);
 
 /* ---- the EdgeBank baseline on the device (additive to ABI 7; csrc/edgebank.hip) ------------------------------
  * models/EdgeBank.py as evaluate_models_utils.py:269-318 drives it: for every test batch the reference builds a memory over

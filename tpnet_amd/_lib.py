@@ -82,6 +82,9 @@ SIGNATURES = {
     "tpnet_pair_gram_anchored_supported": (C.c_int, [_SP]),
     "tpnet_pair_gram_fanout": (C.c_int, [_SP, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P, _P]),
     "tpnet_pair_gram_fanout_supported": (C.c_int, [_SP]),
+    "tpnet_score_one_to_many": (C.c_int, [_SP, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P,
+                                          _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "tpnet_score_one_to_many_supported": (C.c_int, [_SP, _P, C.c_int32, C.c_int32, C.c_int32]),
     "tpnet_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes_capped": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_size_t]),
@@ -132,6 +135,7 @@ SIGNATURES = {
                                         _P]),
     "tpnet_lp_ranking_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "tpnet_lp_ranking": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "tpnet_lp_ranking_skip": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
     "tpnet_lp_metrics_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "tpnet_lp_metrics": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P, _P]),
     "tpnet_lp_train_loss": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P]),

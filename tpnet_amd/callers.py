@@ -10,6 +10,8 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `evaluate_link_prediction` -- the same loop scored on the device: per-batch loss, AP and ROC-AUC (evaluate_models_utils.py:186-198).
 * `evaluate_edge_bank_link_prediction` -- the EdgeBank baseline's evaluation loop on the device (evaluate_models_utils.py:269-318).
 * `evaluate_link_ranking`   -- one-vs-many ranking evaluation (MRR, Hits@k): per-query candidates, one-to-many decoder, device meter.
+* `evaluate_link_ranking_all` / `recommend_links` -- ranking against ALL nodes of an id range (exact rank, unfiltered) and top-k
+  recommendation, on `LinkPredictor_v1.forward_one_to_all`.
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
 * `train_link_prediction_epoch` -- the same epoch with the loss, the backward and the optimizer step (:375-386), the loss and the
@@ -40,6 +42,30 @@ class LinkPredictor_v1(nn.Module):
         # opt-in (tpnet_amd/fused_decoder.py): True = both layers in one bf16 matrix-core kernel (~1e-2 relative); "f32" = the fp32
         # class, forward and backward in HIP, where the kernels serve the call -- else the torch layers below, as with False
         self.fused = False
+        # opt-in (tpnet_amd/score_fanout.py): with not_encode, no embeddings given and no gradient recorded, forward_one_to_many and
+        # forward_one_to_all score a whole call in ONE launch (readout, rp.mlp and both layers: only the logits are written), in the
+        # fp32 class, where the kernel serves the module -- else today's path, whatever `fused` says
+        self.fused_scores = False
+
+    # forward_one_to_all's default route where `fused_scores` is False: the one-launch kernel, because it was MEASURED faster than the
+    # composition at both all-candidates shapes of tools/score_fanout_rate.py on the MI355X (profiles/score_fanout.md; medians of 11
+    # samples of 50 calls, B = 200 sources against every node, us per call, kernel against fused = False / "f32"):
+    #   C2-shaped table (9 228 nodes, d = 128):   1 891 [1 887 .. 1 896]  against  6 956 [6 948 .. 6 974]  /  2 189 [2 185 .. 2 191]
+    #   C3-shaped table (10 985 nodes, d = 256):  2 618 [2 612 .. 2 624]  against  8 915 [8 911 .. 8 919]  /  3 236 [3 231 .. 3 239]
+    # False: the composition unless `fused_scores` is set.  forward_one_to_many is routed by `fused_scores` alone
+    SCORE_ALL_FUSED = True
+
+    def _scores_fused(self, with_embeddings: bool, forced: bool) -> bool:
+        """Whether a one-to-many call takes tpnet_score_one_to_many (score_fanout.serves: host arithmetic and attribute reads)."""
+        if not forced or with_embeddings or not self.not_encode or self.random_projections is None:
+            return False
+        ps = list(self.fc1.parameters()) + list(self.fc2.parameters()) + list(self.random_projections.mlp.parameters())
+        if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
+            return False
+        if self.fc1.weight.device.type != "cuda":
+            return False
+        from . import score_fanout as sf
+        return sf.serves(self)
 
     def forward(self, src_node_ids: np.ndarray, dst_node_ids: np.ndarray, src_node_embeddings: torch.Tensor,
                 dst_node_embeddings: torch.Tensor):
@@ -61,12 +87,57 @@ class LinkPredictor_v1(nn.Module):
         if src_node_embeddings is None or cand_node_embeddings is None:
             if not self.not_encode:
                 raise ValueError("forward_one_to_many: without not_encode the per-pair embeddings [B*C, D] are required")
+            if B > 0 and C > 0 and self._scores_fused(False, bool(self.fused_scores)):
+                from . import score_fanout as sf
+                return sf.score(self, src_node_ids, cand_ids=cand)
             w = self.fc1.weight
             D = (self.fc1.in_features - self.random_feature_dim) // 2
             src_node_embeddings = cand_node_embeddings = torch.zeros((B * C, D), dtype=w.dtype, device=w.device)
         rp = self.random_projections
         out = self._decode(lambda: rp.get_pair_wise_feature_one_to_many(src_node_ids, cand), src_node_embeddings, cand_node_embeddings)
         return out.view(B, C, -1).squeeze(-1)
+
+    def forward_one_to_all(self, src_node_ids, first_id: int, end_id: int, lead_node_ids=None, pairs_per_call: int = 1 << 18):
+        """Extension, ranking against all nodes: src_node_ids [B] scored against EVERY id of the contiguous range [first_id, end_id)
+        -> logits [B, (1 if lead_node_ids is given else 0) + end_id - first_id]; lead_node_ids [B]: one more id per row (the true
+        destination of a ranking query), scored into column 0 -- the layout `LinkRankingMeter` reads.  Requires `not_encode`
+        (ValueError otherwise: an embedding per (source, node) pair is out of reach).  Route: tpnet_score_one_to_many in range mode
+        (no id array, only the logits written) where `fused_scores` is set -- or SCORE_ALL_FUSED, the measured default -- and the
+        kernel serves the call; else the composition: `forward_one_to_many` on arange ids in slices of at most pairs_per_call pairs
+        (whole rows; a row longer than that is cut along the candidates), so the method works on every state the module supports."""
+        if not self.not_encode:
+            raise ValueError("forward_one_to_all: the decoder must be not_encode")
+        lo, hi = int(first_id), int(end_id)
+        if hi <= lo:
+            raise ValueError("forward_one_to_all: an id range [first_id, end_id) with at least one id")
+        B = len(src_node_ids)
+        if lead_node_ids is not None and len(lead_node_ids) != B:
+            raise ValueError("forward_one_to_all: one lead id per source")
+        if B > 0 and self._scores_fused(False, bool(self.fused_scores) or bool(self.SCORE_ALL_FUSED)):
+            from . import score_fanout as sf
+            return sf.score(self, src_node_ids, cand_range=(lo, hi), lead_ids=lead_node_ids)
+        dev = self.fc1.weight.device
+        as_dev = lambda a: a.to(dev, torch.int64) if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.int64)).to(dev)
+        src = as_dev(src_node_ids)
+        ids = torch.arange(lo, hi, dtype=torch.int64, device=dev)
+        if lead_node_ids is not None:
+            cols = torch.cat([as_dev(lead_node_ids).reshape(B, 1), ids.unsqueeze(0).expand(B, -1)], dim=1)
+        else:
+            cols = ids.unsqueeze(0).expand(B, -1)
+        C1 = cols.shape[1]
+        per = max(1, int(pairs_per_call))
+        rows = max(1, per // C1)                                   # whole rows per slice; one row at a time if it is longer
+        parts = []
+        for r0 in range(0, B, rows):
+            sub = cols[r0:r0 + rows]
+            if C1 <= per:
+                parts.append(self.forward_one_to_many(src[r0:r0 + rows], sub.contiguous()))
+            else:
+                parts.append(torch.cat([self.forward_one_to_many(src[r0:r0 + rows], sub[:, c0:c0 + per].contiguous())
+                                        for c0 in range(0, C1, per)], dim=1))
+        if not parts:
+            return torch.empty((0, C1), dtype=self.fc1.weight.dtype, device=dev)
+        return torch.cat(parts, dim=0)
 
     def _decode(self, pair_feature: Callable, src_node_embeddings: torch.Tensor, dst_node_embeddings: torch.Tensor):
         """What `forward` does with its pairs' embeddings; pair_feature() = their pairwise features (called only with a module)."""
@@ -357,6 +428,58 @@ def evaluate_link_ranking(rp, negative_sampler, src, dst, t, batch_size: int, nu
                 logits = decoder.forward_one_to_many(src_d[s], ids, torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]))
             rp.update(src_h[s], dst_h[s], t_h[s])                   # after scoring (:182-184)
             meter.add(logits.reshape(b, Q + 1).float(), cand)
+    return meter.results()
+
+
+def recommend_links(decoder, src_node_ids, k: int, candidate_range):
+    """"Which k nodes is u most likely to link to now?": `decoder.forward_one_to_all(src_node_ids, lo, hi)` over candidate_range =
+    (lo, hi), then `torch.topk` -> (ids [B, k] int64, logits [B, k]), best first, on the decoder's device.  Plain torch behind the
+    scores; under no_grad."""
+    lo, hi = int(candidate_range[0]), int(candidate_range[1])
+    if not 1 <= int(k) <= hi - lo:
+        raise ValueError("recommend_links: 1 <= k <= the number of candidates")
+    with torch.no_grad():
+        logits = decoder.forward_one_to_all(src_node_ids, lo, hi)
+        top = torch.topk(logits, int(k), dim=1)
+    return top.indices + lo, top.values
+
+
+def evaluate_link_ranking_all(rp, src, dst, t, batch_size: int, decoder, candidate_range=None, meter=None):
+    """Ranking evaluation against ALL candidates (extension): every positive edge (s, d, t) is ranked among every node of
+    candidate_range = (lo, hi) -- default (1, rp.node_num): id 0 is the reference's padding row; a bipartite data set passes its item
+    range -- instead of among sampled negatives.  UNFILTERED protocol: only the query's own destination is dropped from the
+    candidates; other true destinations of the same source stay in as candidates.  The decoder must be `not_encode`.  Under no_grad,
+    chronological batches with a ragged tail, no reset of the projections.  Per batch:
+      1. `logits = decoder.forward_one_to_all(src, lo, hi, lead_node_ids=dst)`: [b, 1 + (hi - lo)], column 0 the true destination;
+      2. `skip = dst - lo` where lo <= dst < hi, else -1: the destination's own column among the candidates;
+      3. `rp.update(src, dst, t)` AFTER scoring (evaluate_models_utils.py:182-184), the order of `evaluate_link_ranking`;
+      4. `meter.add_skip(logits, skip)` (tpnet_lp_ranking_skip: no [b, hi - lo] mask is built).
+    Nothing leaves the device and no batch synchronises for the metric.  -> `meter.results()`.  meter: None = a new
+    `LinkRankingMeter` of one record per batch; a given one is appended to.  Composes with `evaluate_with_restore`."""
+    from .metrics import LinkRankingMeter, MAX_RANK_COLUMNS
+    dev = rp.random_projections[0].device
+    lo, hi = (1, int(rp.node_num)) if candidate_range is None else (int(candidate_range[0]), int(candidate_range[1]))
+    if hi <= lo:
+        raise ValueError("candidate_range: (lo, hi) with lo < hi")
+    if 1 + (hi - lo) > MAX_RANK_COLUMNS:
+        raise ValueError(f"evaluate_link_ranking_all: 1 + {hi - lo} candidates exceed the {MAX_RANK_COLUMNS} columns of one ranking record")
+    E = len(src)
+    if meter is None:
+        meter = LinkRankingMeter(max(1, -(-E // batch_size)), dev)
+    to_dev = lambda a: a.to(dev, torch.int64).contiguous() if isinstance(a, torch.Tensor) \
+        else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+    src_d, dst_d = to_dev(src), to_dev(dst)
+    # `update` plans a batch from host arrays and reads its last stamp on the host: one copy of the stream, before the loop
+    to_host = lambda a, dt: a.cpu().numpy().astype(dt, copy=False) if isinstance(a, torch.Tensor) else np.ascontiguousarray(a, dtype=dt)
+    src_h, dst_h, t_h = to_host(src, np.int64), to_host(dst, np.int64), to_host(t, np.float64)
+    with torch.no_grad():
+        for b0 in range(0, E, batch_size):
+            s = slice(b0, min(b0 + batch_size, E))
+            logits = decoder.forward_one_to_all(src_d[s], lo, hi, lead_node_ids=dst_d[s])
+            d = dst_d[s]
+            skip = torch.where((d >= lo) & (d < hi), d - lo, torch.full_like(d, -1))
+            rp.update(src_h[s], dst_h[s], t_h[s])                   # after scoring (:182-184)
+            meter.add_skip(logits.float(), skip)
     return meter.results()
 
 

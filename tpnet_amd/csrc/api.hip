@@ -470,6 +470,31 @@ int tpnet_pair_gram_fanout_supported(const tpnet_state* st) {
     return pair_gram_fanout_supported(*st) ? 1 : 0;
 }
 
+int tpnet_score_one_to_many_supported(const tpnet_state* st, const tpnet_mlp* mlp, int32_t H, int32_t off, int32_t ldw) {
+    if (check_state(st)) return 0;
+    return score_fanout_supported(*st, mlp, H, off, ldw) ? 1 : 0;
+}
+
+int tpnet_score_one_to_many(const tpnet_state* st, const int64_t* src, const int64_t* cand, int64_t cand_lo, const int64_t* lead,
+                            int64_t n_rows, int32_t C, double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp,
+                            const float* wd, int32_t ldw, int32_t off, const float* bd, const float* wd2, const float* bd2, int32_t H,
+                            float* gram, float* out, void* stream) {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (n_rows < 0 || C <= 0 || !src || !out || !mlp || !wd || !bd || !wd2 || !bd2) return TPNET_ERR_BAD_ARG;
+    if (!aligned16({gram, wd, mlp->w1, mlp->w2f, mlp->b2}) ||
+        ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(bd) | reinterpret_cast<uintptr_t>(wd2) |
+          reinterpret_cast<uintptr_t>(bd2) | reinterpret_cast<uintptr_t>(mlp->b1)) & 3))
+        return TPNET_ERR_BAD_ARG;
+    if (n_rows > ((1ll << 31) - 1) / ((int64_t)C + 1)) return TPNET_ERR_BAD_ARG;        // n_rows (1 + C) < 2^31
+    if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;   // packed rows exist for the one-pair readout only
+    if (!cand && (cand_lo < 0 || cand_lo > st->N - (int64_t)C)) return TPNET_ERR_BAD_ARG;   // the range lies inside [0, N)
+    if (!score_fanout_supported(*st, mlp, H, off, ldw)) return TPNET_ERR_BAD_ARG;       // (the caller takes the composition)
+    if (n_rows == 0) return TPNET_OK;
+    return launch_score_fanout(*st, src, cand, cand_lo, lead, n_rows, C, now_time, lambda, flags, mlp, wd, ldw, off, bd, wd2, bd2, H,
+                               gram, out, (hipStream_t)stream);
+}
+
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch) { return plan_bytes(max_edges, batch); }
 
 // bytes for a stream of max_edges on the windowed schedule in chunks of at most chunk_cap edges: one chunk's plan, or -- several

@@ -224,18 +224,22 @@ static void lpr_layout(Arena& a, LprScratch& w, int64_t B) {
 static bool lpr_sizes_ok(int64_t B, int32_t C1) { return B >= 0 && B < (1ll << 31) && C1 >= 1 && C1 <= LPR_MAX_C1; }
 
 // one wave per query, strided over its C1 columns: integer counts only, combined by shuffles
+// SKIP (tpnet_lp_ranking_skip): `cand` is not read; candidate column skip[i] of query i (-1: none) is absent instead
+template <bool SKIP>
 __global__ __launch_bounds__(LPR_BLOCK) void k_lpr_rows(const float* __restrict__ logits, int64_t B, int C1,
-                                                        const int64_t* __restrict__ cand, uint32_t* __restrict__ m_out,
-                                                        uint32_t* __restrict__ nv_out, uint32_t* __restrict__ fl_out) {
+                                                        const int64_t* __restrict__ cand, const int64_t* __restrict__ skip,
+                                                        uint32_t* __restrict__ m_out, uint32_t* __restrict__ nv_out,
+                                                        uint32_t* __restrict__ fl_out) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * (LPR_BLOCK / 64) + (threadIdx.x >> 6);
     if (i >= B) return;
     const float* row = logits + i * (int64_t)C1;
-    const int64_t* crow = cand ? cand + i * (int64_t)(C1 - 1) : nullptr;
+    const int64_t* crow = (!SKIP && cand) ? cand + i * (int64_t)(C1 - 1) : nullptr;
+    const int64_t sk = SKIP ? skip[i] : -1;
     const float p = row[0];
     uint32_t g = 0, e = 0, nv = 0, bad = isnan(p) ? 1u : 0u;
     for (int c = lane; c < C1 - 1; c += 64) {
-        if (crow && crow[c] < 0) continue;
+        if (SKIP ? c == sk : (crow && crow[c] < 0)) continue;
         const float q = row[1 + c];
         nv += 1u;
         g += (uint32_t)(q > p);
@@ -333,10 +337,12 @@ size_t tpnet_lp_ranking_scratch_bytes(int64_t B, int32_t C1) {
     return measured([&](Arena& a) { LprScratch w; lpr_layout(a, w, B); });
 }
 
-int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* cand_or_null, int32_t k1, int32_t k2, int32_t k3,
-                     void* scratch, size_t scratch_bytes, int64_t* record, void* stream) {
+// what tpnet_lp_ranking and tpnet_lp_ranking_skip share: the checks, the scratch, the two launches (skip: one absent column per query)
+static int lpr_enqueue(const float* logits, int64_t B, int32_t C1, const int64_t* cand_or_null, const int64_t* skip, bool with_skip,
+                       int32_t k1, int32_t k2, int32_t k3, void* scratch, size_t scratch_bytes, int64_t* record, void* stream) {
     if (!lpr_sizes_ok(B, C1) || k1 < 1 || k2 < 1 || k3 < 1 || !record || ((size_t)record & 7)) return TPNET_ERR_BAD_ARG;
     if (B > 0 && (!logits || !scratch || ((size_t)scratch & 7))) return TPNET_ERR_BAD_ARG;
+    if (with_skip && B > 0 && (!skip || ((size_t)skip & 7))) return TPNET_ERR_BAD_ARG;
     if (B > 0 && scratch_bytes < tpnet_lp_ranking_scratch_bytes(B, C1)) return TPNET_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     Arena wa(B > 0 ? scratch : nullptr, scratch_bytes);
@@ -344,13 +350,23 @@ int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* 
     lpr_layout(wa, w, B);
     if (B > 0) {
         const int per = LPR_BLOCK / 64;
-        hipLaunchKernelGGL(k_lpr_rows, dim3((unsigned)((B + per - 1) / per)), dim3(LPR_BLOCK), 0, s, logits, B, (int)C1, cand_or_null,
-                           w.m, w.nv, w.fl);
+        hipLaunchKernelGGL(with_skip ? k_lpr_rows<true> : k_lpr_rows<false>, dim3((unsigned)((B + per - 1) / per)), dim3(LPR_BLOCK), 0, s,
+                           logits, B, (int)C1, cand_or_null, skip, w.m, w.nv, w.fl);
     }
     hipLaunchKernelGGL(k_lpr_finish, dim3(1), dim3(LPM_FIN), 0, s, B, (const uint32_t*)w.m, (const uint32_t*)w.nv,
                        (const uint32_t*)w.fl, (int)k1, (int)k2, (int)k3, record);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
+}
+
+int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* cand_or_null, int32_t k1, int32_t k2, int32_t k3,
+                     void* scratch, size_t scratch_bytes, int64_t* record, void* stream) {
+    return lpr_enqueue(logits, B, C1, cand_or_null, nullptr, false, k1, k2, k3, scratch, scratch_bytes, record, stream);
+}
+
+int tpnet_lp_ranking_skip(const float* logits, int64_t B, int32_t C1, const int64_t* skip_col, int32_t k1, int32_t k2, int32_t k3,
+                          void* scratch, size_t scratch_bytes, int64_t* record, void* stream) {
+    return lpr_enqueue(logits, B, C1, nullptr, skip_col, true, k1, k2, k3, scratch, scratch_bytes, record, stream);
 }
 
 }  // extern "C"

@@ -995,5 +995,125 @@ struct AnchorWalk {
     }
 };
 
+// the fan-out walk's arrays for a kernel that steps all the lane groups of a workgroup through their candidates TOGETHER
+// (k_score_fanout, score_fanout.hip): begin() = the source's rows, own block and output plan, fetch() + issue(0) = ids and meta
+// records of up to LPP candidates and the first one's rows, step(j) = candidate j's 26 inner products, reduced and finished.  The same
+// operations in the same order as gram_fanout (whose text this is, with emit in place of the stores): the features of the two are
+// the same bits (tests/test_score_fanout.py compares them with torch.equal).  fetch() takes the lane's candidate id itself, not a
+// list: the caller forms it (a list entry, an id of a contiguous range, a row's lead id).
+template <int LPP, int VPL, int W, int L, bool FULL>
+struct FanWalk {
+    using C = GramCfg<LPP, L>;
+    using FC = FanCfg<LPP, L>;
+    static constexpr int NR = C::NR, NN = C::NN, F = VPL * W, PER = C::PER;
+    float fs[NR][F];                         // the source's rows, decay applied
+    int sl[PER];                             // per-lane output plan (invariant over the unit): gram_fanout's
+    bool own[PER], in[PER];
+    float ys[PER];
+    bool sok;
+    int64_t my_w;                            // lane gl: candidate gl of the current fetch
+    bool my_ok;
+    MetaView my_m;
+    float fn[NR][F];                         // rows of the NEXT candidate (raw)
+
+    __device__ __forceinline__ void begin(const tpnet_state& S, int64_t u, bool valid, double now, double lambda, bool do_scale,
+                                          int gl) {
+        const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
+        sok = valid && (uint64_t)u < (uint64_t)S.N;
+        if (valid && !sok && gl == 0) atomicAdd(S.err, 1u);
+        if (!sok) u = 0;
+        {
+            const MetaView m = read_meta(meta, u, READER_BID, now, lambda);
+            load_node_rows<LPP, VPL, W, L, FULL>(S, u, m.copy, gl, fs);
+            float g = 1.0f;
+#pragma unroll
+            for (int i = 1; i <= L; ++i) {
+                g *= m.g;
+#pragma unroll
+                for (int k = 0; k < F; ++k) fs[i][k] *= g;
+            }
+        }
+        float ss[FC::TRI];
+#pragma unroll
+        for (int a = 0; a < NR; ++a) {
+#pragma unroll
+            for (int b = a; b < NR; ++b) ss[FC::tri(a, b)] = group_allreduce<LPP>(dot_chunk<F, false>(fs[a], fs[b]));
+        }
+#pragma unroll
+        for (int kk = 0; kk < PER; ++kk) {
+            int idx = gl * PER + kk;
+            in[kk] = idx < C::NG;
+            idx = in[kk] ? idx : 0;
+            const int a = idx / NN, b = idx - a * NN;
+            own[kk] = a < NR && b < NR;
+            ys[kk] = 0.0f;
+            if (own[kk]) {
+                const int ta = FC::tri(a < b ? a : b, a < b ? b : a);
+                float y = 0.0f;
+#pragma unroll
+                for (int q = 0; q < FC::TRI; ++q) y = (ta == q) ? ss[q] : y;     // (register array: a select chain)
+                ys[kk] = finish_feature(y, do_scale);
+                sl[kk] = 0;
+            } else if (a < NR) {                       // (source row a, candidate row b - NR)
+                sl[kk] = FC::O_SC + a * NR + (b - NR);
+            } else if (b < NR) {                       // mirrored
+                sl[kk] = FC::O_SC + b * NR + (a - NR);
+            } else {
+                const int x = a - NR, y = b - NR;
+                sl[kk] = FC::O_CC + FC::tri(x < y ? x : y, x < y ? y : x);
+            }
+        }
+    }
+    // id: this lane's candidate (has: the lane has one), neighbour_fetch's checks and meta record
+    __device__ __forceinline__ void fetch(const tpnet_state& S, int64_t id, bool has, bool valid, double now, double lambda) {
+        const NodeMeta* meta = reinterpret_cast<const NodeMeta*>(S.meta);
+        my_w = (valid && has) ? id : 0;
+        my_ok = sok && (uint64_t)my_w < (uint64_t)S.N;
+        if (valid && sok && has && !my_ok) atomicAdd(S.err, 1u);
+        if (!my_ok) my_w = 0;
+        my_m = read_meta(meta, my_w, READER_BID, now, lambda);
+    }
+    __device__ __forceinline__ void issue(const tpnet_state& S, int j, int gl) {
+        neighbour_issue<LPP, VPL, W, L, FULL>(S, my_w, my_m, j, gl, fn);
+    }
+    // candidate j of the fetch (its rows in fn; `more`: issue candidate j + 1 behind it): emit(idx, x) for each of this lane's
+    // elements idx = gl * PER + kk (< NG) of the feature row G(source, candidate)
+    template <class Emit>
+    __device__ __forceinline__ void step(const tpnet_state& S, int j, bool more, bool do_scale, int gl, Emit&& emit) {
+        const bool wok = __shfl((int)my_ok, j, LPP) != 0;
+        const float mg = __shfl(my_m.g, j, LPP);
+        float fw[NR][F];                               // the candidate's rows, decay applied
+#pragma unroll
+        for (int x = 0; x < F; ++x) fw[0][x] = fn[0][x];
+        float g = 1.0f;
+#pragma unroll
+        for (int i = 1; i <= L; ++i) {
+            g *= mg;
+#pragma unroll
+            for (int x = 0; x < F; ++x) fw[i][x] = fn[i][x] * g;
+        }
+        if (more) issue(S, j + 1, gl);
+        float acc[FC::MPS];
+#pragma unroll
+        for (int i = 0; i < FC::MPS; ++i) acc[i] = 0.0f;
+#pragma unroll
+        for (int a = 0; a < NR; ++a) {
+#pragma unroll
+            for (int b = a; b < NR; ++b) acc[FC::O_CC + FC::tri(a, b)] = dot_chunk<F, false>(fw[a], fw[b]);
+#pragma unroll
+            for (int b = 0; b < NR; ++b) acc[FC::O_SC + a * NR + b] = dot_chunk<F, false>(fs[a], fw[b]);
+        }
+        Halve<FC::MPS, LPP / 2>::run(acc, gl);         // lane gl now holds the complete sums of slots [gl*PERS, ...)
+#pragma unroll
+        for (int kk = 0; kk < PER; ++kk) {
+            const int idx = in[kk] ? gl * PER + kk : 0;
+            float x = finish_feature(pick_slot<FC::PERS, LPP>(acc, sl[kk]), do_scale);
+            if (own[kk]) x = ys[kk];
+            if (!wok) x = __builtin_nanf("");
+            if (in[kk]) emit(idx, x);
+        }
+    }
+};
+
 
 }  // namespace tpnet

@@ -1,0 +1,223 @@
+// One source against many candidates, scored in ONE launch: tpnet_score_one_to_many.  For row i with source src[i] and every
+// candidate c of that row
+//   f     = G(src[i], c)                      the fan-out readout's finished features, source's layers first (readout.hpp::FanWalk)
+//   y     = W2m . relu(W1m . f + b1m) + b2m   self.mlp, 64 -> 256 -> 64 (dense_tile.hpp: split-bf16 operands, the fp32 class)
+//   a     = Wd[:, off : off + 64] . y + bd    the decoder's fc1 restricted to its feature columns (not_encode: the rest meets zeros)
+//   logit = wd2 . relu(a) + bd2
+// and only out[i, c] is written: the 256 bytes of features per pair, their copy behind self.mlp and the decoder's hidden layer of
+// the composition (fan-out readout, dense layers, decoder: three launches and more) never exist unless the caller asks for `gram`.
+// The structure is k_anchored_feature's (anchored_feature.hip): a workgroup of 512 threads holds 512 / LPP lane groups; every group
+// takes one unit = (row, chunk of KC columns; cut by anchored_chunk) and the groups step through their columns TOGETHER, each step
+// leaving one finished feature row per group in a 32-column LDS tile.  On a full tile the eight waves run self.mlp on it (W1's split
+// operands in a wave's registers, W2's in LDS), the 32 x 64 y tile goes back to LDS and a second matrix-core block forms `a`: wave w
+// owns the hidden units [32 w, 32 w + 32) of the decoder, its split operands read once per workgroup from fc1.weight AS IT IS (row
+// stride ldw, column offset off: no image, no prepare call), three products per term.  Bias, ReLU and the product with wd2 happen in
+// the accumulators; the 16 partial sums of a column (8 waves x 2 lane halves) meet in LDS and are added in a FIXED order.
+// Workgroup barriers only; every loop around a barrier has a workgroup-uniform trip count.  Groups whose unit is short, absent or
+// past the end run the same steps on masked columns: computed, never stored -- a pair is one column of every matrix product, so its
+// logit depends on its two nodes and the weights alone (the promises: include/tpnet_hip.h).  No floating-point atomics.
+#include "readout.hpp"
+#include "dense_tile.hpp"
+
+namespace tpnet {
+
+// dynamic LDS of a workgroup: feature / y tile | four partial-output slabs | the columns' output slots | W2 split | b1 |
+// the decoder's bias and second layer (padded to 256 units) | the columns' NaN marks | the 16 partial sums of each column
+static constexpr int SF_SLAB = 32 * TS * 4, SF_DEST = 5 * SF_SLAB, SF_W2 = SF_DEST + 32 * 8, SF_B1 = SF_W2 + DENSE_W2_LDS_BYTES;
+static constexpr int SF_BD = SF_B1 + DENSE_B1_LDS_BYTES, SF_WD2 = SF_BD + 256 * 4, SF_NAN = SF_WD2 + 256 * 4, SF_PART = SF_NAN + 32 * 4;
+static constexpr int SF_LDS = SF_PART + 16 * 32 * 4;                        // 114 560 bytes
+
+struct score_dec {
+    const float *wd, *bd, *wd2, *bd2;         // fc1.weight [H][ldw], fc1.bias [H], fc2.weight [1][H], fc2.bias [1]
+    int ldw, off, H;
+};
+
+template <int LPP, int VPL, bool FULL>
+__global__ __launch_bounds__(MB) void k_score_fanout(tpnet_state S, const int64_t* __restrict__ src, const int64_t* __restrict__ cand,
+                                                     const int64_t* __restrict__ lead, int64_t cand_lo, int64_t n_rows, int C, int KC,
+                                                     int spt, double now, double lambda, uint32_t flags,
+                                                     const float* __restrict__ w1f, const float* __restrict__ b1,
+                                                     const float* __restrict__ w2f, const float* __restrict__ b2, score_dec dec,
+                                                     float* __restrict__ gram, float* __restrict__ out) {
+    constexpr int W = 4, L = 3;
+    constexpr int GPB = MB / LPP;             // units in flight per workgroup = tile columns filled per step
+    using Walk = FanWalk<LPP, VPL, W, L, FULL>;
+    static_assert(LPP * Walk::PER == MF && GPB <= 32 && 32 % GPB == 0, "k_score_fanout: 16, 32 or 64 lanes per unit");
+    extern __shared__ __attribute__((aligned(16))) char smem[];               // SF_LDS bytes
+    float* feat = reinterpret_cast<float*>(smem);                             // the feature tile, then the y tile
+    float (*slab)[32 * TS] = reinterpret_cast<float (*)[32 * TS]>(smem + SF_SLAB);
+    int64_t* dest = reinterpret_cast<int64_t*>(smem + SF_DEST);               // output slot of each tile column (row * C1 + column), -1: masked
+    float* bds = reinterpret_cast<float*>(smem + SF_BD);
+    float* wd2s = reinterpret_cast<float*>(smem + SF_WD2);
+    int* nans = reinterpret_cast<int*>(smem + SF_NAN);
+    float* part = reinterpret_cast<float*>(smem + SF_PART);
+    const int tid = threadIdx.x;
+    const int gl = tid % LPP, g = tid / LPP;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const bool do_scale = !(flags & TPNET_FLAG_NOT_SCALE);
+    const int hl = lead ? 1 : 0;
+    const int C1 = C + hl;                    // columns of a row: [lead |] candidates
+    const int nch = (C1 + KC - 1) / KC;
+    const int64_t units = n_rows * nch;
+    const int64_t base0 = (int64_t)blockIdx.x * GPB;
+
+    DenseTileW<true, true> wt;                // (W1 in registers, W2 and b1 in LDS)
+    dense_tile_weights_lds(wt, w1f, b1, w2f, wave, lane, reinterpret_cast<bf16x8*>(smem + SF_W2), reinterpret_cast<float*>(smem + SF_B1));
+    // the decoder's A operands: unit 32 wave + r, columns off + 16 s + 8 h .. + 7 of fc1.weight; a unit of the padding reads unit 0's
+    // row and takes a selected zero
+    bf16x8 dh[4], dl[4];
+    {
+        const int u = wave * 32 + r;
+        const bool real = u < dec.H;
+        const float* wrow = dec.wd + (int64_t)(real ? u : 0) * dec.ldw + dec.off + 8 * h;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const float4 a = *reinterpret_cast<const float4*>(wrow + 16 * s), b = *reinterpret_cast<const float4*>(wrow + 16 * s + 4);
+            const float z = 0.0f;
+            split8(make_float4(real ? a.x : z, real ? a.y : z, real ? a.z : z, real ? a.w : z),
+                   make_float4(real ? b.x : z, real ? b.y : z, real ? b.z : z, real ? b.w : z), dh[s], dl[s]);
+        }
+        if (tid < 256) {
+            bds[tid] = tid < dec.H ? dec.bd[tid] : 0.0f;
+            wd2s[tid] = tid < dec.H ? dec.wd2[tid] : 0.0f;
+        }
+    }
+    const float bd2 = dec.bd2[0];
+    const bool wave_has_units = wave * 32 < dec.H;
+
+    for (int64_t base = base0; base < units; base += (int64_t)gridDim.x * GPB) {
+        const int64_t un = base + g;
+        const bool valid = un < units;
+        const int64_t rr = valid ? un / nch : 0;
+        const int ch = valid ? (int)(un - rr * nch) : 0;
+        const int kb = ch * KC, ke = (kb + KC < C1) ? kb + KC : C1;
+        const int nk_u = valid ? ke - kb : 0;              // columns of this group's unit
+        const int64_t slot0 = rr * C1 + kb;
+        Walk wk;
+        wk.begin(S, valid ? src[rr] : 0, valid, now, lambda, do_scale, gl);
+        for (int j = 0; j < KC; ++j) {                     // (uniform: every group of the workgroup takes KC steps)
+            const int jf = j % LPP;                        // position inside the current fetch of up to LPP ids
+            if (jf == 0) {
+                int nk = nk_u - j;
+                nk = nk < 0 ? 0 : (nk > LPP ? LPP : nk);
+                if (nk > 0 || j == 0) {
+                    const bool has = gl < nk;
+                    const int k = kb + j + gl;             // this lane's column of the row
+                    int64_t id = 0;
+                    if (has) id = (k < hl) ? lead[rr] : (cand ? cand[rr * C + (k - hl)] : cand_lo + (k - hl));
+                    wk.fetch(S, id, has, valid, now, lambda);
+                    wk.issue(S, 0, gl);
+                }
+            }
+            const bool live = j < nk_u;
+            const int sub = j % spt;
+            const int c1 = sub * GPB + g;                  // this group's column of the tile
+            wk.step(S, jf, jf + 1 < LPP && j + 1 < nk_u, do_scale, gl, [&](int idx, float x) { feat[c1 * TS + idx] = x; });
+            if (gl == 0) dest[c1] = live ? slot0 + j : -1;
+            if (sub == spt - 1 || j == KC - 1) {           // (uniform) the tile is full, or the units end
+                __syncthreads();
+                const int ncol = (sub + 1) * GPB;          // columns beyond: stale rows, computed and never stored
+                const int pair = tid >> 4, o = (tid & 15) * 4;      // 512 threads x 4 floats = 32 columns x 64
+                const int64_t dd = pair < ncol ? dest[pair] : -1;
+                const float4 f4 = *reinterpret_cast<const float4*>(feat + pair * TS + o);
+                if (gram && dd >= 0) *reinterpret_cast<float4*>(gram + dd * MF + o) = f4;      // the features as the kernel formed them
+                // a feature row that holds a NaN (an id out of range: all of it) answers a NaN logit, as the torch layers do -- the
+                // ReLUs of the matrix-core blocks would turn it into a finite number.  A row is 16 neighbouring lanes of a wave.
+                const unsigned long long nanl = __ballot(f4.x != f4.x || f4.y != f4.y || f4.z != f4.z || f4.w != f4.w);
+                if ((tid & 15) == 0) nans[pair] = ((nanl >> (lane & 48)) & 0xFFFFull) != 0 ? 1 : 0;
+                dense_tile_partials<true>(wt, feat, slab, wave, lane);     // (every wave is past its reads of the feature tile)
+                *reinterpret_cast<float4*>(feat + pair * TS + o) = dense_tile_out4(slab, b2, pair, o);      // y, one column per pair
+                __syncthreads();
+                // ---- the decoder: A^T = Wd . Y^T for the wave's 32 hidden units; lane (r, h) holds Y[pair r][16 s + 8 h + j] as B operand
+                float p = 0.0f;
+                if (wave_has_units) {
+                    f32x16 acc;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        bf16x8 bxh, bxl;
+                        load_split8(feat + r * TS + 16 * s + 8 * h, bxh, bxl);
+                        acc = mm3(dh[s], dl[s], bxh, bxl, acc);
+                    }
+                    // register q = hidden unit 32 wave + acc_row(q, h) of pair r: bias, ReLU, the product with wd2, in register order
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const int u = wave * 32 + acc_row(q, h);
+                        float a = acc[q] + bds[u];
+                        a = a > 0.0f ? a : 0.0f;
+                        p = p + a * wd2s[u];
+                    }
+                }
+                part[(wave * 2 + h) * 32 + r] = p;
+                __syncthreads();
+                if (tid < 32) {
+                    float sum = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) sum = sum + part[i * 32 + tid];
+                    const int64_t d1 = tid < ncol ? dest[tid] : -1;
+                    if (d1 >= 0) out[d1] = nans[tid] ? __builtin_nanf("") : sum + bd2;
+                }
+                __syncthreads();                           // the tiles are reused by the next steps of this workgroup
+            }
+        }
+    }
+}
+
+static LdsOptIn score_fanout_lds;
+static bool score_fanout_available() {
+    return score_fanout_lds.granted({reinterpret_cast<const void*>(k_score_fanout<16, 1, true>),
+                                     reinterpret_cast<const void*>(k_score_fanout<16, 1, false>),
+                                     reinterpret_cast<const void*>(k_score_fanout<32, 1, true>),
+                                     reinterpret_cast<const void*>(k_score_fanout<32, 1, false>),
+                                     reinterpret_cast<const void*>(k_score_fanout<32, 2, true>),
+                                     reinterpret_cast<const void*>(k_score_fanout<32, 2, false>),
+                                     reinterpret_cast<const void*>(k_score_fanout<64, 2, true>),
+                                     reinterpret_cast<const void*>(k_score_fanout<64, 2, false>)}, SF_LDS);
+}
+
+// host arithmetic only: the four geometries of rows of 36..512 floats in ONE chunk (16 x 1, 32 x 1, 32 x 2, 64 x 2)
+static bool score_geom(const tpnet_state& st, Geom& gm) {
+    gm = pick_geom(st.d);
+    return gm.w == 4 && ((gm.lpp == 16 && gm.vpl == 1) || (gm.lpp == 32 && (gm.vpl == 1 || gm.vpl == 2)) || (gm.lpp == 64 && gm.vpl == 2)) &&
+           st.d <= gm.lpp * gm.vpl * 4;
+}
+
+bool score_fanout_supported(const tpnet_state& st, const tpnet_mlp* mlp, int H, int off, int ldw) {
+    Geom gm;
+    return mlp && mlp->F == 64 && mlp->H == 256 && mlp->w1 && mlp->w2f && mlp->b1 && mlp->b2 && st.L == 3 && st.d % 4 == 0 &&
+           st.d >= 36 && st.d <= 512 && score_geom(st, gm) && H >= 1 && H <= 256 && off >= 0 && off % 4 == 0 && ldw >= off + 64 &&
+           ldw % 4 == 0;
+}
+
+int launch_score_fanout(const tpnet_state& st, const int64_t* src, const int64_t* cand, int64_t cand_lo, const int64_t* lead,
+                        int64_t n_rows, int C, double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int ldw,
+                        int off, const float* bd, const float* wd2, const float* bd2, int H, float* gram, float* out, hipStream_t s) {
+    if (!score_fanout_supported(st, mlp, H, off, ldw)) return TPNET_ERR_BAD_ARG;
+    if (!score_fanout_available()) return TPNET_ERR_HIP;         // (a device that does not give a workgroup 112 KB of LDS)
+    Geom gm;
+    score_geom(st, gm);
+    const int gpb = MB / gm.lpp;
+    const int C1 = C + (lead ? 1 : 0);
+    const int kc = anchored_chunk(n_rows, C1);
+    const int64_t units = n_rows * ((C1 + kc - 1) / kc);
+    // ONE workgroup per CU (its LDS), each loading its weights once
+    const int grid = grid_for(units, gpb, 256);
+    const int spt = 32 / gpb;                                    // steps that fill the 32 columns of the matrix products
+    const score_dec dec = {wd, bd, wd2, bd2, ldw, off, H};
+#define TPNET_SF(LPP_, VPL_, FULL_)                                                                                            \
+    hipLaunchKernelGGL((k_score_fanout<LPP_, VPL_, FULL_>), dim3(grid), dim3(MB), SF_LDS, s, st, src, cand, lead, cand_lo, n_rows, C, kc, \
+                       spt, now, lambda, flags, reinterpret_cast<const float*>(mlp->w1), mlp->b1,                              \
+                       reinterpret_cast<const float*>(mlp->w2f), mlp->b2, dec, gram, out)
+    const bool full = st.d == gm.lpp * gm.vpl * 4;
+    if (gm.lpp == 16) { if (full) TPNET_SF(16, 1, true); else TPNET_SF(16, 1, false); }
+    else if (gm.vpl == 1) { if (full) TPNET_SF(32, 1, true); else TPNET_SF(32, 1, false); }
+    else if (gm.lpp == 32) { if (full) TPNET_SF(32, 2, true); else TPNET_SF(32, 2, false); }
+    else { if (full) TPNET_SF(64, 2, true); else TPNET_SF(64, 2, false); }
+#undef TPNET_SF
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+}  // namespace tpnet

@@ -172,6 +172,13 @@ int launch_pair_gram_fanout(const tpnet_state& st, const int64_t* src, const int
 int launch_pair_gram_anchored(const tpnet_state& st, const int64_t* neigh, const int64_t* a1, const int64_t* a2,
                               int64_t n_rows, int K, double now, double lambda, uint32_t flags, float* out1, float* out2,
                               hipStream_t s);
+// score_fanout.hip: the fan-out walk with self.mlp and the decoder's two layers behind it in ONE launch, one logit per pair (rows of
+// 36..512 floats, d % 4 == 0, L = 3, the reference mlp, H <= 256 decoder units read from fc1.weight at column off with row stride ldw);
+// cand == NULL: the candidates are the ids [cand_lo, cand_lo + C); lead (optional): one more id per row, scored into column 0
+bool score_fanout_supported(const tpnet_state& st, const tpnet_mlp* mlp, int H, int off, int ldw);
+int launch_score_fanout(const tpnet_state& st, const int64_t* src, const int64_t* cand, int64_t cand_lo, const int64_t* lead,
+                        int64_t n_rows, int C, double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int ldw,
+                        int off, const float* bd, const float* wd2, const float* bd2, int H, float* gram, float* out, hipStream_t s);
 // encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 36..160 floats (d % 4 == 0), L = 3, K >= 4;
 // with TPNET_FLAG_ROWS8 (and without TPNET_FLAG_NO_MFMA_READOUT) in `flags` also for rows of 38..158 floats with d % 4 == 2, which no
 // other anchored kernel reads

@@ -356,6 +356,34 @@ class LinkRankingMeter:
         self._n = k + 1
         return k
 
+    def add_skip(self, logits: torch.Tensor, skip_col: torch.Tensor) -> int:
+        """Ranking against all nodes (tpnet_lp_ranking_skip): logits [B, 1 + C] as for `add`, skip_col [B] int64 on the meter's
+        device -- candidate column skip_col[i] (0-based among the C candidates; -1: none) of query i is absent: the query's own
+        destination among all candidates.  The host rule: link_ranking_metrics_host(logits, valid) with valid[i, skip_col[i]] =
+        False.  -> the index of the record written.  Two launches, nothing copied, no synchronisation."""
+        if self._n >= self.capacity:
+            raise IndexError(f"LinkRankingMeter: the log of {self.capacity} records is full (results(), then reset())")
+        _check_f32(logits, self.device, "logits")
+        if logits.dim() != 2 or logits.shape[1] < 1 or logits.shape[1] > MAX_RANK_COLUMNS:
+            raise ValueError(f"logits must be [B, 1 + C] with 1 + C <= {MAX_RANK_COLUMNS}")
+        x = logits.detach().contiguous()
+        B, C1 = x.shape
+        if not isinstance(skip_col, torch.Tensor) or skip_col.dtype != torch.int64 or skip_col.device != self.device \
+                or tuple(skip_col.shape) != (B,):
+            raise TypeError(f"skip_col: an int64 tensor [{B}] on {self.device} is expected")
+        sk = skip_col.contiguous()
+        lib = _lib.load()
+        need = lib.tpnet_lp_ranking_scratch_bytes(B, C1)
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        k = self._n
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(lib.tpnet_lp_ranking_skip(x.data_ptr() if B else None, B, C1, sk.data_ptr() if B else None, self.hits_at[0],
+                                             self.hits_at[1], self.hits_at[2], self._scratch.data_ptr(), self._scratch.numel(),
+                                             self._log.data_ptr() + k * _RECORD_WORDS * 8, stream), "lp_ranking_skip")
+        self._n = k + 1
+        return k
+
     def records(self) -> np.ndarray:
         """The log's records so far as an int64 array [n][8] on the host (one copy; synchronises); words 0..3 are float64 bits."""
         return self._log[:self._n].cpu().numpy()
