@@ -370,6 +370,34 @@ int tpnet_score_one_to_many(const tpnet_state* st, const int64_t* src, const int
                             float* gram, float* out, void* stream);
 int tpnet_score_one_to_many_supported(const tpnet_state* st, const tpnet_mlp* mlp, int32_t H, int32_t off, int32_t ldw);
 
+/* ---- one source ranked against a whole id range, the counts formed in the scoring kernel (additive to ABI 7; csrc/score_fanout.hip,
+ * DESIGN.md section 3.7 / 3.8).  For row i:  p = logit(src[i], pos[i])  (the four lines above), and over every id c of
+ * [cand_lo, cand_lo + C) with c != pos[i], q = logit(src[i], c):
+ *   counts[4 i + 0] = g  = #{q > p}        counts[4 i + 1] = e = #{q == p}        counts[4 i + 2] = nv = the ids counted
+ *   counts[4 i + 3] = flags: value 2 when p or a counted q is NaN (tpnet_lp_ranking's rule and flag value), else 0
+ * pos_logit[i] = p.  No other logit reaches memory: this is tpnet_score_one_to_many(range mode, lead = pos) followed by
+ * tpnet_lp_ranking_skip's integer rule without the [n_rows, 1 + C] matrix between them, so neither n_rows (1 + C) < 2^31 nor the
+ * 2^20 columns of one ranking record bound it:  1 <= C < 2^31,  0 <= n_rows < 2^31.
+ * PROMISES.  (1) counts and pos_logit equal EXACTLY what tpnet_score_one_to_many(cand = NULL, cand_lo, lead = pos) followed by the
+ * integer rule on its logits (column pos[i] - cand_lo skipped where it exists) gives -- promise (1) of that call: a pair's logit has
+ * the same bits wherever it is computed, and everything behind the compare is an integer.  (2) Two calls give the same bits.
+ * Launches, two or three, all on `stream`, no synchronisation, no atomics, no memset: (a) tpnet_score_one_to_many's kernel as it is,
+ * list mode with C = 1 and cand = pos, into pos_logit; (b) the same kernel body with a counting epilogue -- a unit = (row, chunk of
+ * KC ids), cut as for tpnet_score_one_to_many; the unit's four integers are summed in LDS and leave the workgroup ONCE, as one
+ * 16-byte record (into `scratch`, or straight into counts when every row is one unit); (c) where a row has several units, one wave
+ * per row adds its records.  At most about 8192 + n_rows units.
+ * scratch: tpnet_score_rank_scratch_bytes(n_rows, C) device bytes, 16-byte aligned (0 for sizes out of range).  pos_logit: device
+ * float[n_rows]; counts: device int32[4 n_rows], 16-byte aligned.
+ * Served exactly where tpnet_score_one_to_many_supported returns 1; checks and error returns as for tpnet_score_one_to_many (null
+ * pointers, C <= 0, n_rows < 0, a range that leaves [0, N), misaligned weights, TPNET_FLAG_PACKED, an unserved state:
+ * TPNET_ERR_BAD_ARG, nothing launched; a short scratch: TPNET_ERR_WORKSPACE; n_rows == 0: TPNET_OK).  A src[i] or pos[i] outside
+ * [0, N): row i's NaN flag is set (pos_logit[i] is NaN), every other row is untouched, the state's error word is raised. */
+size_t tpnet_score_rank_scratch_bytes(int64_t n_rows, int32_t C);
+int tpnet_score_rank_range(const tpnet_state* st, const int64_t* src, const int64_t* pos, int64_t cand_lo, int64_t n_rows, int32_t C,
+                           double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int32_t ldw,
+                           int32_t off, const float* bd, const float* wd2, const float* bd2, int32_t H, void* scratch,
+                           size_t scratch_bytes, float* pos_logit, int32_t* counts, void* stream);
+
 /* Workspace for tpnet_update / tpnet_run_stream with at most max_edges edges per call. */
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch);
 
@@ -702,6 +730,24 @@ int tpnet_neg_sample_many(const void* neg, int64_t E, const int64_t* batch_src, 
                           int64_t B, int32_t Q, int32_t Qh, uint64_t seed, uint32_t call_index, int64_t* cand, int32_t* n_hist,
                           void* stream);
 
+/* ---- per-query filter lists of the all-node ranking protocol (additive to ABI 7; csrc/negsampler.hip) -------
+ * tpnet_neg_filter_lists: query i = (s, d, t) gets the destinations d' != d with lo <= d' < hi that `mode` excludes from its
+ * candidates, read from the table tpnet_neg_build made:
+ *   TPNET_FILTER_SAME_TIME   d' is excluded when the table holds an occurrence of (s, d') at time exactly t: the exclusion rule of
+ *                            tpnet_neg_sample_many, so the sampled and the all-node protocol agree about what a negative is
+ *   TPNET_FILTER_KNOWN       d' is excluded when the table holds (s, d') at any time: the filtered protocol papers report
+ * fil[i*F .. i*F+F): the excluded destinations, ascending and distinct, the rest of the row -1.  n_fil[i]: the TRUE number of
+ * excluded destinations, which may exceed F -- then the row holds the F smallest, and a consumer treats n_fil[i] > F as overflow
+ * (tpnet_lp_ranking_counts: flag value 8).  One wave per query walks the source's unique edges in destination order (64 per step,
+ * ballot compaction; same_time: one binary search in the edge's occurrence list), one launch on `stream`, no scratch, no
+ * synchronisation.  batch_src / batch_dst: device int64[B], batch_t: device float64[B]; fil: device int64[B*F]; n_fil: device int32[B].
+ * 1 <= F < 2^16, 0 <= B < 2^31, lo <= hi; B == 0: TPNET_OK, nothing launched.  Null pointers, another mode and sizes out of range:
+ * TPNET_ERR_BAD_ARG, nothing launched. */
+#define TPNET_FILTER_SAME_TIME 1
+#define TPNET_FILTER_KNOWN 2
+int tpnet_neg_filter_lists(const void* neg, int64_t E, const int64_t* batch_src, const int64_t* batch_dst, const double* batch_t,
+                           int64_t B, int32_t mode, int64_t lo, int64_t hi, int32_t F, int64_t* fil, int32_t* n_fil, void* stream);
+
 /* ---- a batch's link-prediction metrics on the device (additive to ABI 7; csrc/metrics.hip) ------------------
  * What the reference's evaluation loop brings to the host per batch (evaluate_models_utils.py:187-193, utils/metrics.py:8-22):
  * BCEWithLogitsLoss(...).item() and sklearn's average_precision_score / roc_auc_score on predicts.sigmoid().cpu().
@@ -781,6 +827,24 @@ int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* 
  * TPNET_ERR_BAD_ARG. */
 int tpnet_lp_ranking_skip(const float* logits, int64_t B, int32_t C1, const int64_t* skip_col, int32_t k1, int32_t k2, int32_t k3,
                           void* scratch, size_t scratch_bytes, int64_t* record, void* stream);
+/* The same record from COUNTS (tpnet_score_rank_range's output), with an optional per-query filter.  counts: [B][4] int32 =
+ * {g, e, nv, flags} per query, 16-byte aligned; pos_logit: [B] fp32, the positive's logit p.  fil_logits == NULL: no filter
+ * (fil_ids, n_fil and F are not looked at).  Else fil_logits [B][F] fp32, fil_ids [B][F] int64 and n_fil [B] int32 as
+ * tpnet_neg_filter_lists lays them out, fil_logits[i][j] = the logit of (query i's source, fil_ids[i][j]) -- by promise (1) of
+ * tpnet_score_one_to_many the bits the counting kernel compared -- and per query over the slots j < min(n_fil, F) with
+ * fil_ids >= 0 (a logit under another slot is not looked at):
+ *   g_f = #{fil_logit > p},  e_f = #{fil_logit == p},  m_i = 2 + 2 (g - g_f) + (e - e_f),  valid candidates = nv - n_fil
+ * -- exact when every listed id is one of the query's counted candidates, which tpnet_neg_filter_lists on the same range promises.
+ * A query is NOT counted when counts' flag value 2 is set or a looked-at filter logit is NaN (flag value 2), when n_fil > F (a NEW
+ * flag, value 8: filter overflow -- the list is incomplete, so the filtered rank is unknown) or when no valid candidate is left
+ * (value 4).  The call writes the three words per query the finish kernel reads (one launch, one thread per query), then launches
+ * tpnet_lp_ranking's finish kernel: the record, its summation order and flags 1 / 2 / 4 are tpnet_lp_ranking's (the kernel carries
+ * value 8 through as it carries 2 and 4; only this call ever sets it).  scratch: tpnet_lp_ranking_scratch_bytes(B, 1).  0 <= B < 2^31, 1 <= F < 2^16 with a
+ * filter, k1, k2, k3 >= 1; null or misaligned pointers, sizes out of range: TPNET_ERR_BAD_ARG, nothing launched; a short scratch:
+ * TPNET_ERR_WORKSPACE. */
+int tpnet_lp_ranking_counts(const int32_t* counts, const float* pos_logit, int64_t B, const float* fil_logits, const int64_t* fil_ids,
+                            const int32_t* n_fil, int32_t F, int32_t k1, int32_t k2, int32_t k3, void* scratch, size_t scratch_bytes,
+                            int64_t* record, void* stream);
 
 /* ---- the EdgeBank baseline on the device (additive to ABI 7; csrc/edgebank.hip) ------------------------------
  * models/EdgeBank.py as evaluate_models_utils.py:269-318 drives it: for every test batch the reference builds a memory over

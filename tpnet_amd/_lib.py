@@ -85,6 +85,9 @@ SIGNATURES = {
     "tpnet_score_one_to_many": (C.c_int, [_SP, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P,
                                           _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "tpnet_score_one_to_many_supported": (C.c_int, [_SP, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "tpnet_score_rank_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "tpnet_score_rank_range": (C.c_int, [_SP, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P, _P,
+                                         C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, _P]),
     "tpnet_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes_capped": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_size_t]),
@@ -133,7 +136,11 @@ SIGNATURES = {
     "tpnet_neg_check": (C.c_int, [_P, _P]),
     "tpnet_neg_sample_many": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, _P, _P,
                                         _P]),
+    "tpnet_neg_filter_lists": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P,
+                                         _P]),
     "tpnet_lp_ranking_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "tpnet_lp_ranking_counts": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                          _P, _P]),
     "tpnet_lp_ranking": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
     "tpnet_lp_ranking_skip": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
     "tpnet_lp_metrics_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),

@@ -10,8 +10,8 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `evaluate_link_prediction` -- the same loop scored on the device: per-batch loss, AP and ROC-AUC (evaluate_models_utils.py:186-198).
 * `evaluate_edge_bank_link_prediction` -- the EdgeBank baseline's evaluation loop on the device (evaluate_models_utils.py:269-318).
 * `evaluate_link_ranking`   -- one-vs-many ranking evaluation (MRR, Hits@k): per-query candidates, one-to-many decoder, device meter.
-* `evaluate_link_ranking_all` / `recommend_links` -- ranking against ALL nodes of an id range (exact rank, unfiltered) and top-k
-  recommendation, on `LinkPredictor_v1.forward_one_to_all`.
+* `evaluate_link_ranking_all` / `recommend_links` -- ranking against ALL nodes of an id range (exact rank; unfiltered, or filtered and
+  streaming on `LinkPredictor_v1.rank_one_to_all`) and top-k recommendation, on `LinkPredictor_v1.forward_one_to_all`.
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
 * `train_link_prediction_epoch` -- the same epoch with the loss, the backward and the optimizer step (:375-386), the loss and the
@@ -138,6 +138,75 @@ class LinkPredictor_v1(nn.Module):
         if not parts:
             return torch.empty((0, C1), dtype=self.fc1.weight.dtype, device=dev)
         return torch.cat(parts, dim=0)
+
+    def rank_one_to_all(self, src_node_ids, pos_node_ids, first_id: int, end_id: int, filter_ids: Optional[torch.Tensor] = None,
+                        pairs_per_call: int = 1 << 18):
+        """Extension, streaming ranking against all nodes: for row i the positive's logit p = logit(src[i], pos[i]) and, over every
+        id c of [first_id, end_id) other than pos[i], the counts of the logits of (src[i], c) against it -> (counts [B, 4] int32 =
+        (#{q > p}, #{q == p}, the ids counted, 2 where a NaN took part), pos_logit [B] fp32, filter_logits): the [B, 1 + C] logits
+        of `forward_one_to_all` never exist.  filter_ids (optional, [B, F] int64 on the device, -1 = no entry; the layout of
+        `GpuNegativeEdgeSampler.filter_lists_device`): filter_logits [B, F] = the logits of (src[i], filter_ids[i, j]) -- what
+        `LinkRankingMeter.add_counts` subtracts; under a -1 slot the value is not meaningful --, else None.
+        Route: where the one-launch kernel serves the module (score_fanout.serves), tpnet_score_rank_range -- the counts are formed
+        in the scoring kernel -- and one list-mode `score` call for the filter lists.  Every other state: `forward_one_to_all` in
+        row and column slices of at most pairs_per_call pairs, the counts formed with torch integer ops and the filter logits
+        gathered from the same slices -- never more than one slice is held.  Requires `not_encode`; runs under no_grad."""
+        if not self.not_encode:
+            raise ValueError("rank_one_to_all: the decoder must be not_encode")
+        lo, hi = int(first_id), int(end_id)
+        if hi <= lo:
+            raise ValueError("rank_one_to_all: an id range [first_id, end_id) with at least one id")
+        B = len(src_node_ids)
+        if len(pos_node_ids) != B:
+            raise ValueError("rank_one_to_all: one positive id per source")
+        dev = self.fc1.weight.device
+        if filter_ids is not None and (not isinstance(filter_ids, torch.Tensor) or filter_ids.dtype != torch.int64 or filter_ids.dim() != 2
+                                       or filter_ids.shape[0] != B or filter_ids.device != dev):
+            raise TypeError(f"rank_one_to_all: filter_ids must be an int64 tensor [{B}, F] on {dev}")
+        as_dev = lambda a: a.to(dev, torch.int64) if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.int64)).to(dev)
+        with torch.no_grad():
+            if B > 0 and self._scores_fused(False, True):
+                from . import score_fanout as sf
+                counts, p = sf.rank_range(self, src_node_ids, pos_node_ids, (lo, hi))
+                fl = None
+                if filter_ids is not None:
+                    pos = as_dev(pos_node_ids)
+                    if filter_ids.shape[1] == 0:
+                        fl = torch.empty((B, 0), dtype=torch.float32, device=dev)
+                    else:
+                        fl = sf.score(self, src_node_ids, cand_ids=torch.where(filter_ids < 0, pos.unsqueeze(1), filter_ids).contiguous())
+                return counts, p, fl
+            src, pos = as_dev(src_node_ids), as_dev(pos_node_ids)
+            C = hi - lo
+            per = max(2, int(pairs_per_call))
+            rows = max(1, per // (C + 1))                          # whole rows per slice; one row at a time if it is longer
+            width = C if C + 1 <= per else per - 1                 # columns per slice (the first one carries the positive beside them)
+            counts = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+            p_all = torch.empty(B, dtype=torch.float32, device=dev)
+            fl = torch.zeros(filter_ids.shape, dtype=torch.float32, device=dev) if filter_ids is not None else None
+            for r0 in range(0, B, rows):
+                r = slice(r0, min(r0 + rows, B))
+                p = None
+                nan = None
+                for c0 in range(lo, hi, width):
+                    c1 = min(c0 + width, hi)
+                    x = self.forward_one_to_all(src[r], c0, c1, lead_node_ids=pos[r] if p is None else None,
+                                                pairs_per_call=pairs_per_call).float()
+                    if p is None:
+                        p, x = x[:, :1].contiguous(), x[:, 1:]
+                        nan = torch.isnan(p[:, 0])
+                    on = torch.arange(c0, c1, device=dev).unsqueeze(0) != pos[r].unsqueeze(1)
+                    counts[r, 0] += ((x > p) & on).sum(dim=1, dtype=torch.int32)
+                    counts[r, 1] += ((x == p) & on).sum(dim=1, dtype=torch.int32)
+                    counts[r, 2] += on.sum(dim=1, dtype=torch.int32)
+                    nan = nan | (torch.isnan(x) & on).any(dim=1)
+                    if fl is not None and fl.shape[1] > 0:
+                        f = filter_ids[r]
+                        inside = (f >= c0) & (f < c1)
+                        fl[r] = torch.where(inside, x.gather(1, (f - c0).clamp(0, c1 - c0 - 1)), fl[r])
+                p_all[r] = p[:, 0]
+                counts[r, 3] = nan.to(torch.int32) * 2
+            return counts, p_all, fl
 
     def _decode(self, pair_feature: Callable, src_node_embeddings: torch.Tensor, dst_node_embeddings: torch.Tensor):
         """What `forward` does with its pairs' embeddings; pair_feature() = their pairwise features (called only with a module)."""
@@ -444,7 +513,8 @@ def recommend_links(decoder, src_node_ids, k: int, candidate_range):
     return top.indices + lo, top.values
 
 
-def evaluate_link_ranking_all(rp, src, dst, t, batch_size: int, decoder, candidate_range=None, meter=None):
+def evaluate_link_ranking_all(rp, src, dst, t, batch_size: int, decoder, candidate_range=None, meter=None, filter: Optional[str] = None,
+                              negative_sampler=None, streaming: bool = False):
     """Ranking evaluation against ALL candidates (extension): every positive edge (s, d, t) is ranked among every node of
     candidate_range = (lo, hi) -- default (1, rp.node_num): id 0 is the reference's padding row; a bipartite data set passes its item
     range -- instead of among sampled negatives.  UNFILTERED protocol: only the query's own destination is dropped from the
@@ -455,13 +525,29 @@ def evaluate_link_ranking_all(rp, src, dst, t, batch_size: int, decoder, candida
       3. `rp.update(src, dst, t)` AFTER scoring (evaluate_models_utils.py:182-184), the order of `evaluate_link_ranking`;
       4. `meter.add_skip(logits, skip)` (tpnet_lp_ranking_skip: no [b, hi - lo] mask is built).
     Nothing leaves the device and no batch synchronises for the metric.  -> `meter.results()`.  meter: None = a new
-    `LinkRankingMeter` of one record per batch; a given one is appended to.  Composes with `evaluate_with_restore`."""
+    `LinkRankingMeter` of one record per batch; a given one is appended to.  Composes with `evaluate_with_restore`.
+    STREAMING (streaming = True, or a filter): the counts are formed where the scores are and no [b, hi - lo] tensor is built, so
+    neither the logits' memory nor the MAX_RANK_COLUMNS of one record bound the range.  Per batch:
+      1. with a filter, `fil, n_fil = negative_sampler.filter_lists_device(src, dst, t, filter, (lo, hi))`: per query the
+         destinations the FILTERED protocol drops from its candidates -- filter = 'same_time': other positives of the same source at
+         the same instant, `evaluate_link_ranking`'s (tpnet_neg_sample_many's) notion of a negative; 'known': every destination the
+         source has an edge to anywhere in the stream the sampler was built on, the filtered setting papers report.  A filter needs
+         the sampler (`GpuNegativeEdgeSampler`, built on the whole stream): ValueError without one;
+      2. `counts, pos_logit, fil_logits = decoder.rank_one_to_all(src, dst, lo, hi, filter_ids=fil)`;
+      3. `rp.update(src, dst, t)` AFTER scoring;
+      4. `meter.add_counts(counts, pos_logit, fil_logits, fil, n_fil)` (tpnet_lp_ranking_counts).
+    With the defaults (filter None, streaming False) the function is what it was."""
     from .metrics import LinkRankingMeter, MAX_RANK_COLUMNS
     dev = rp.random_projections[0].device
     lo, hi = (1, int(rp.node_num)) if candidate_range is None else (int(candidate_range[0]), int(candidate_range[1]))
     if hi <= lo:
         raise ValueError("candidate_range: (lo, hi) with lo < hi")
-    if 1 + (hi - lo) > MAX_RANK_COLUMNS:
+    if filter not in (None, "same_time", "known"):
+        raise ValueError(f"filter: {filter!r} is none of None, 'same_time', 'known'")
+    if filter is not None and negative_sampler is None:
+        raise ValueError("evaluate_link_ranking_all: a filter needs negative_sampler (its table holds the stream's edges)")
+    streaming = bool(streaming) or filter is not None
+    if not streaming and 1 + (hi - lo) > MAX_RANK_COLUMNS:
         raise ValueError(f"evaluate_link_ranking_all: 1 + {hi - lo} candidates exceed the {MAX_RANK_COLUMNS} columns of one ranking record")
     E = len(src)
     if meter is None:
@@ -472,6 +558,17 @@ def evaluate_link_ranking_all(rp, src, dst, t, batch_size: int, decoder, candida
     # `update` plans a batch from host arrays and reads its last stamp on the host: one copy of the stream, before the loop
     to_host = lambda a, dt: a.cpu().numpy().astype(dt, copy=False) if isinstance(a, torch.Tensor) else np.ascontiguousarray(a, dtype=dt)
     src_h, dst_h, t_h = to_host(src, np.int64), to_host(dst, np.int64), to_host(t, np.float64)
+    if streaming:
+        t_d = t.to(dev, torch.float64).contiguous() if isinstance(t, torch.Tensor) else torch.from_numpy(t_h).to(dev)
+        for b0 in range(0, E, batch_size):
+            s = slice(b0, min(b0 + batch_size, E))
+            fil = n_fil = None
+            if filter is not None:
+                fil, n_fil = negative_sampler.filter_lists_device(src_d[s], dst_d[s], t_d[s], filter, (lo, hi))
+            counts, pos_logit, fil_logits = decoder.rank_one_to_all(src_d[s], dst_d[s], lo, hi, filter_ids=fil)
+            rp.update(src_h[s], dst_h[s], t_h[s])                   # after scoring (:182-184)
+            meter.add_counts(counts, pos_logit, fil_logits, fil, n_fil)
+        return meter.results()
     with torch.no_grad():
         for b0 in range(0, E, batch_size):
             s = slice(b0, min(b0 + batch_size, E))

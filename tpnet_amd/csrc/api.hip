@@ -495,6 +495,29 @@ int tpnet_score_one_to_many(const tpnet_state* st, const int64_t* src, const int
                                gram, out, (hipStream_t)stream);
 }
 
+size_t tpnet_score_rank_scratch_bytes(int64_t n_rows, int32_t C) { return score_rank_scratch_bytes(n_rows, C); }
+
+int tpnet_score_rank_range(const tpnet_state* st, const int64_t* src, const int64_t* pos, int64_t cand_lo, int64_t n_rows, int32_t C,
+                           double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int32_t ldw,
+                           int32_t off, const float* bd, const float* wd2, const float* bd2, int32_t H, void* scratch,
+                           size_t scratch_bytes, float* pos_logit, int32_t* counts, void* stream) {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (n_rows < 0 || n_rows >= (1ll << 31) || C <= 0 || !src || !pos || !pos_logit || !counts || !scratch || !mlp || !wd || !bd ||
+        !wd2 || !bd2)
+        return TPNET_ERR_BAD_ARG;
+    if (!aligned16({wd, mlp->w1, mlp->w2f, mlp->b2, scratch, counts}) ||
+        ((reinterpret_cast<uintptr_t>(pos_logit) | reinterpret_cast<uintptr_t>(bd) | reinterpret_cast<uintptr_t>(wd2) |
+          reinterpret_cast<uintptr_t>(bd2) | reinterpret_cast<uintptr_t>(mlp->b1)) & 3))
+        return TPNET_ERR_BAD_ARG;
+    if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;   // packed rows exist for the one-pair readout only
+    if (cand_lo < 0 || cand_lo > st->N - (int64_t)C) return TPNET_ERR_BAD_ARG;             // the range lies inside [0, N)
+    if (!score_fanout_supported(*st, mlp, H, off, ldw)) return TPNET_ERR_BAD_ARG;       // (the caller takes the composition)
+    if (n_rows == 0) return TPNET_OK;
+    return launch_score_rank(*st, src, pos, cand_lo, n_rows, C, now_time, lambda, flags, mlp, wd, ldw, off, bd, wd2, bd2, H, scratch,
+                             scratch_bytes, pos_logit, counts, (hipStream_t)stream);
+}
+
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch) { return plan_bytes(max_edges, batch); }
 
 // bytes for a stream of max_edges on the windowed schedule in chunks of at most chunk_cap edges: one chunk's plan, or -- several

@@ -211,7 +211,7 @@ static int lpm_enqueue(const float* pos_score, int64_t n_pos, const float* neg_s
 // ---- one-vs-many ranking (tpnet_lp_ranking; the rule: include/tpnet_hip.h) ------------------------------------------------------------
 static constexpr int LPR_BLOCK = 256;                // four waves, one query each
 static constexpr int32_t LPR_MAX_C1 = 1 << 20;
-enum { LPR_FLAG_NO_QUERY = 1, LPR_FLAG_NAN_SCORE = 2, LPR_FLAG_EMPTY_QUERY = 4 };
+enum { LPR_FLAG_NO_QUERY = 1, LPR_FLAG_NAN_SCORE = 2, LPR_FLAG_EMPTY_QUERY = 4, LPR_FLAG_FILTER_OVERFLOW = 8 };
 
 // scratch: three words per query -- m_i (0: not counted), its valid candidates, its flags
 struct LprScratch { uint32_t* m; uint32_t* nv; uint32_t* fl; };
@@ -261,6 +261,38 @@ __global__ __launch_bounds__(LPR_BLOCK) void k_lpr_rows(const float* __restrict_
     }
 }
 
+// the three words per query from COUNTS (tpnet_lp_ranking_counts): counts[i] = {g, e, nv, flags} as the scoring kernel left them
+// (tpnet_score_rank_range), less what the query's filter list holds -- over its slots j < min(n_fil, F) with an id >= 0,
+// g_f = #{fil_logit > p}, e_f = #{fil_logit == p}.  One thread per query: the lists are short (a source's known destinations)
+__global__ __launch_bounds__(LPR_BLOCK) void k_lpr_counts(const int4* __restrict__ counts, const float* __restrict__ pos_logit, int64_t B,
+                                                          const float* __restrict__ fil_logits, const int64_t* __restrict__ fil_ids,
+                                                          const int32_t* __restrict__ n_fil, int F, uint32_t* __restrict__ m_out,
+                                                          uint32_t* __restrict__ nv_out, uint32_t* __restrict__ fl_out) {
+    const int64_t i = (int64_t)blockIdx.x * LPR_BLOCK + threadIdx.x;
+    if (i >= B) return;
+    const int4 c = counts[i];
+    const float p = pos_logit[i];
+    int64_t g = c.x, e = c.y, nv = c.z;
+    uint32_t fl = ((c.w & LPR_FLAG_NAN_SCORE) || isnan(p)) ? (uint32_t)LPR_FLAG_NAN_SCORE : 0u;
+    if (fil_logits) {
+        const int nf = n_fil[i];
+        const int n = nf < F ? (nf < 0 ? 0 : nf) : F;
+        if (nf > F) fl |= (uint32_t)LPR_FLAG_FILTER_OVERFLOW;
+        for (int j = 0; j < n; ++j) {
+            if (fil_ids[i * F + j] < 0) continue;
+            const float q = fil_logits[i * F + j];
+            g -= (int64_t)(q > p);
+            e -= (int64_t)(q == p);
+            if (isnan(q)) fl |= (uint32_t)LPR_FLAG_NAN_SCORE;
+        }
+        nv -= nf < 0 ? 0 : nf;
+    }
+    if (nv <= 0) { nv = 0; fl |= (uint32_t)LPR_FLAG_EMPTY_QUERY; }
+    m_out[i] = fl ? 0u : (uint32_t)(2 + 2 * g + e);
+    nv_out[i] = (uint32_t)nv;
+    fl_out[i] = fl;
+}
+
 // ONE workgroup: thread k takes queries k, k + 1024, ... in ascending order, the 1024 partial sums meet in the tree
 __global__ __launch_bounds__(LPM_FIN) void k_lpr_finish(int64_t B, const uint32_t* __restrict__ m, const uint32_t* __restrict__ nv,
                                                         const uint32_t* __restrict__ fl, int k1, int k2, int k3,
@@ -292,6 +324,7 @@ __global__ __launch_bounds__(LPM_FIN) void k_lpr_finish(int64_t B, const uint32_
     // (flags: one bit at a time through the sum tree -- a count, then a test)
     long long f2 = lpm_tree_sum<LPM_FIN>((long long)((flags & LPR_FLAG_NAN_SCORE) != 0), shi);
     long long f4 = lpm_tree_sum<LPM_FIN>((long long)((flags & LPR_FLAG_EMPTY_QUERY) != 0), shi);
+    long long f8 = lpm_tree_sum<LPM_FIN>((long long)((flags & LPR_FLAG_FILTER_OVERFLOW) != 0), shi);      // (tpnet_lp_ranking_counts only)
     if (threadIdx.x == 0) {
         const double nan = __builtin_nan("");
         double* rd = reinterpret_cast<double*>(record);
@@ -305,7 +338,7 @@ __global__ __launch_bounds__(LPM_FIN) void k_lpr_finish(int64_t B, const uint32_
         ri[5] = n;
         ri[6] = nvalid;
         ri[7] = (n ? 0ll : (long long)LPR_FLAG_NO_QUERY) | (f2 ? (long long)LPR_FLAG_NAN_SCORE : 0ll) |
-                (f4 ? (long long)LPR_FLAG_EMPTY_QUERY : 0ll);
+                (f4 ? (long long)LPR_FLAG_EMPTY_QUERY : 0ll) | (f8 ? (long long)LPR_FLAG_FILTER_OVERFLOW : 0ll);
     }
 }
 
@@ -367,6 +400,29 @@ int tpnet_lp_ranking(const float* logits, int64_t B, int32_t C1, const int64_t* 
 int tpnet_lp_ranking_skip(const float* logits, int64_t B, int32_t C1, const int64_t* skip_col, int32_t k1, int32_t k2, int32_t k3,
                           void* scratch, size_t scratch_bytes, int64_t* record, void* stream) {
     return lpr_enqueue(logits, B, C1, nullptr, skip_col, true, k1, k2, k3, scratch, scratch_bytes, record, stream);
+}
+
+int tpnet_lp_ranking_counts(const int32_t* counts, const float* pos_logit, int64_t B, const float* fil_logits, const int64_t* fil_ids,
+                            const int32_t* n_fil, int32_t F, int32_t k1, int32_t k2, int32_t k3, void* scratch, size_t scratch_bytes,
+                            int64_t* record, void* stream) {
+    if (!lpr_sizes_ok(B, 1) || k1 < 1 || k2 < 1 || k3 < 1 || !record || ((size_t)record & 7)) return TPNET_ERR_BAD_ARG;
+    if (B > 0 && (!counts || ((size_t)counts & 15) || !pos_logit || ((size_t)pos_logit & 3) || !scratch || ((size_t)scratch & 7)))
+        return TPNET_ERR_BAD_ARG;
+    if (B > 0 && fil_logits &&
+        (F < 1 || F >= (1 << 16) || !fil_ids || !n_fil || ((size_t)fil_logits & 3) || ((size_t)fil_ids & 7) || ((size_t)n_fil & 3)))
+        return TPNET_ERR_BAD_ARG;
+    if (B > 0 && scratch_bytes < tpnet_lp_ranking_scratch_bytes(B, 1)) return TPNET_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    Arena wa(B > 0 ? scratch : nullptr, scratch_bytes);
+    LprScratch w;
+    lpr_layout(wa, w, B);
+    if (B > 0)
+        hipLaunchKernelGGL(k_lpr_counts, dim3((unsigned)((B + LPR_BLOCK - 1) / LPR_BLOCK)), dim3(LPR_BLOCK), 0, s,
+                           reinterpret_cast<const int4*>(counts), pos_logit, B, fil_logits, fil_ids, n_fil, (int)F, w.m, w.nv, w.fl);
+    hipLaunchKernelGGL(k_lpr_finish, dim3(1), dim3(LPM_FIN), 0, s, B, (const uint32_t*)w.m, (const uint32_t*)w.nv,
+                       (const uint32_t*)w.fl, (int)k1, (int)k2, (int)k3, record);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
 }
 
 }  // extern "C"

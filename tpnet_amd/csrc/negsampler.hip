@@ -350,6 +350,47 @@ __global__ __launch_bounds__(NEGM_BLOCK) void k_neg_many(const uint32_t* __restr
     for (int q = fill + lane; q < Q; q += 64) row[q] = -1;
 }
 
+// ---- per-query filter lists (tpnet_neg_filter_lists; the rule: include/tpnet_hip.h) -------------------------------------------------
+// One wave per query i = (s, d, t): the source's run [e0, e0 + R) of the table IS its distinct destinations in ascending order; 64 per
+// step, the excluded ones inside [lo, hi) (known: all of them; same_time: those that occur at exactly t) compacted by a ballot into
+// fil[i, 0 .. F) in that order.  The count goes on past F: n_fil[i] is the true number.
+__global__ __launch_bounds__(NEGM_BLOCK) void k_neg_filter(const uint32_t* __restrict__ hdr, const uint64_t* __restrict__ ukey,
+                                                           const uint32_t* __restrict__ ustart, const double* __restrict__ times,
+                                                           uint32_t E, const int64_t* __restrict__ bs, const int64_t* __restrict__ bd,
+                                                           const double* __restrict__ bt, int64_t B, int mode, int64_t lo, int64_t hi,
+                                                           int F, int64_t* __restrict__ fil, int32_t* __restrict__ n_fil) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * (NEGM_BLOCK / 64) + (threadIdx.x >> 6);
+    if (i >= B) return;                                          // (a whole wave leaves: no workgroup barrier below)
+    const uint32_t U = hdr[NEG_U];
+    const int64_t s = bs[i], d = bd[i];
+    const double t = bt[i];
+    int64_t* row = fil + i * (int64_t)F;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t e0 = 0, R = 0;
+    if ((uint64_t)s < (1ull << 31)) {                            // (no edge of the table has another source)
+        e0 = key_lower_bound(ukey, 0, U, (uint64_t)s << 32);
+        R = key_lower_bound(ukey, e0, U, ((uint64_t)s + 1) << 32) - e0;
+    }
+    int64_t n = 0;
+    for (uint32_t base = 0; base < R; base += 64) {
+        const uint32_t j = base + (uint32_t)lane;
+        bool ok = false;
+        int64_t dd = 0;
+        if (j < R) {
+            const uint32_t e = e0 + j;
+            dd = (int64_t)(ukey[e] & 0xFFFFFFFFull);
+            ok = dd != d && dd >= lo && dd < hi && (mode == TPNET_FILTER_KNOWN || occurs_at(ustart, times, U, E, e, t));
+        }
+        const unsigned long long m = __ballot(ok);
+        const int64_t pos = n + __popcll(m & below);
+        if (ok && pos < F) row[pos] = dd;
+        n += __popcll(m);
+    }
+    if (lane == 0) n_fil[i] = (int32_t)n;                        // (R < 2^30)
+    for (int64_t q = n + lane; q < F; q += 64) row[q] = -1;
+}
+
 // ---- layouts ---------------------------------------------------------------------------------------------------------------------
 struct NegView {
     uint32_t* hdr; uint64_t* ukey; double* ufirst; uint32_t* ustart; uint8_t* uobs; double* times; int64_t* us; int64_t* ud;
@@ -529,6 +570,22 @@ int tpnet_neg_sample_many(const void* neg, int64_t E, const int64_t* batch_src, 
                        (const uint32_t*)v.hdr, (const uint64_t*)v.ukey, (const uint32_t*)v.ustart, (const double*)v.ufirst,
                        (const double*)v.times, (const int64_t*)v.ud, (uint32_t)E, batch_src, batch_dst, batch_t, B, (int)Q, (int)Qh,
                        key, cand, n_hist);
+    TPNET_HIP_TRY(hipGetLastError());
+    return TPNET_OK;
+}
+
+int tpnet_neg_filter_lists(const void* neg, int64_t E, const int64_t* batch_src, const int64_t* batch_dst, const double* batch_t,
+                           int64_t B, int32_t mode, int64_t lo, int64_t hi, int32_t F, int64_t* fil, int32_t* n_fil, void* stream) {
+    if (!neg || E < 1 || E >= (1ll << 30) || B < 0 || B >= (1ll << 31) || F < 1 || F >= (1 << 16) || lo > hi ||
+        (mode != TPNET_FILTER_SAME_TIME && mode != TPNET_FILTER_KNOWN))
+        return TPNET_ERR_BAD_ARG;
+    if (B > 0 && (!batch_src || !batch_dst || !batch_t || !fil || !n_fil)) return TPNET_ERR_BAD_ARG;
+    if (B == 0) return TPNET_OK;
+    NegView v = neg_view(neg, 0, E);
+    const int per = NEGM_BLOCK / 64;
+    hipLaunchKernelGGL(k_neg_filter, dim3((unsigned)((B + per - 1) / per)), dim3(NEGM_BLOCK), 0, (hipStream_t)stream,
+                       (const uint32_t*)v.hdr, (const uint64_t*)v.ukey, (const uint32_t*)v.ustart, (const double*)v.times, (uint32_t)E,
+                       batch_src, batch_dst, batch_t, B, (int)mode, lo, hi, (int)F, fil, n_fil);
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }

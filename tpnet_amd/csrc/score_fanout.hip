@@ -16,6 +16,9 @@
 // Workgroup barriers only; every loop around a barrier has a workgroup-uniform trip count.  Groups whose unit is short, absent or
 // past the end run the same steps on masked columns: computed, never stored -- a pair is one column of every matrix product, so its
 // logit depends on its two nodes and the weights alone (the promises: include/tpnet_hip.h).  No floating-point atomics.
+// The EPILOGUE of a finished column is a policy: ScoreStore writes the logit (tpnet_score_one_to_many); ScoreRank compares it with the
+// row's positive logit and counts (tpnet_score_rank_range: ranking against a whole id range without the logit matrix) -- the walk,
+// the two matrix-core blocks and the fixed-order sum exist once, so the logit that is compared is the logit that would be stored.
 #include "readout.hpp"
 #include "dense_tile.hpp"
 
@@ -26,31 +29,52 @@ namespace tpnet {
 static constexpr int SF_SLAB = 32 * TS * 4, SF_DEST = 5 * SF_SLAB, SF_W2 = SF_DEST + 32 * 8, SF_B1 = SF_W2 + DENSE_W2_LDS_BYTES;
 static constexpr int SF_BD = SF_B1 + DENSE_B1_LDS_BYTES, SF_WD2 = SF_BD + 256 * 4, SF_NAN = SF_WD2 + 256 * 4, SF_PART = SF_NAN + 32 * 4;
 static constexpr int SF_LDS = SF_PART + 16 * 32 * 4;                        // 114 560 bytes
+// ScoreRank only, behind them: the units' counters {g, e, nv, flags} | the units' positive logits
+static constexpr int SF_CNT = SF_LDS, SF_POSL = SF_CNT + 32 * 16, SF_LDS_RANK = SF_POSL + 32 * 4;      // 115 200 bytes
 
 struct score_dec {
     const float *wd, *bd, *wd2, *bd2;         // fc1.weight [H][ldw], fc1.bias [H], fc2.weight [1][H], fc2.bias [1]
     int ldw, off, H;
 };
 
-template <int LPP, int VPL, bool FULL>
-__global__ __launch_bounds__(MB) void k_score_fanout(tpnet_state S, const int64_t* __restrict__ src, const int64_t* __restrict__ cand,
-                                                     const int64_t* __restrict__ lead, int64_t cand_lo, int64_t n_rows, int C, int KC,
-                                                     int spt, double now, double lambda, uint32_t flags,
-                                                     const float* __restrict__ w1f, const float* __restrict__ b1,
-                                                     const float* __restrict__ w2f, const float* __restrict__ b2, score_dec dec,
-                                                     float* __restrict__ gram, float* __restrict__ out) {
+// the epilogue policies.  ScoreStore: out[slot] = logit (gram: optional copy of the features).  ScoreRank: row i's columns are the ids
+// cand_lo + k (range mode, no lead); a column whose id is not pos[i] is COUNTED against p = pos_logit[i]: g += q > p, e += q == p,
+// nv += 1, flags |= 2 where q or p is NaN.  A unit's four integers live in LDS (thread u < GPB of the workgroup owns unit u's: plain
+// adds, no atomics) and leave the workgroup once, as the 16-byte record rec[unit].
+// The body is ONE inlined function; the two kernels below hand it their own (restrict-qualified) arguments.
+struct ScoreStore {
+    static constexpr bool RANK = false;
+    float* __restrict__ gram;
+    float* __restrict__ out;
+};
+struct ScoreRank {
+    static constexpr bool RANK = true;
+    const int64_t* __restrict__ pos;
+    const float* __restrict__ pos_logit;
+    int4* __restrict__ rec;
+};
+
+template <int LPP, int VPL, bool FULL, class Epi>
+__device__ __forceinline__ void score_fanout_body(const tpnet_state& S, const int64_t* __restrict__ src, const int64_t* __restrict__ cand,
+                                                  const int64_t* __restrict__ lead, int64_t cand_lo, int64_t n_rows, int C, int KC,
+                                                  int spt, double now, double lambda, uint32_t flags, const float* __restrict__ w1f,
+                                                  const float* __restrict__ b1, const float* __restrict__ w2f,
+                                                  const float* __restrict__ b2, const score_dec& dec, const Epi& ep) {
     constexpr int W = 4, L = 3;
     constexpr int GPB = MB / LPP;             // units in flight per workgroup = tile columns filled per step
     using Walk = FanWalk<LPP, VPL, W, L, FULL>;
     static_assert(LPP * Walk::PER == MF && GPB <= 32 && 32 % GPB == 0, "k_score_fanout: 16, 32 or 64 lanes per unit");
-    extern __shared__ __attribute__((aligned(16))) char smem[];               // SF_LDS bytes
+    extern __shared__ __attribute__((aligned(16))) char smem[];               // SF_LDS bytes (ScoreRank: SF_LDS_RANK)
     float* feat = reinterpret_cast<float*>(smem);                             // the feature tile, then the y tile
     float (*slab)[32 * TS] = reinterpret_cast<float (*)[32 * TS]>(smem + SF_SLAB);
     int64_t* dest = reinterpret_cast<int64_t*>(smem + SF_DEST);               // output slot of each tile column (row * C1 + column), -1: masked
+                                                                              // (ScoreRank: 0 = counted, -1: masked or the row's own positive)
     float* bds = reinterpret_cast<float*>(smem + SF_BD);
     float* wd2s = reinterpret_cast<float*>(smem + SF_WD2);
     int* nans = reinterpret_cast<int*>(smem + SF_NAN);
     float* part = reinterpret_cast<float*>(smem + SF_PART);
+    int4* cnt = reinterpret_cast<int4*>(smem + SF_CNT);                       // (ScoreRank) unit u of the workgroup: thread u's own
+    float* posl = reinterpret_cast<float*>(smem + SF_POSL);
     const int tid = threadIdx.x;
     const int gl = tid % LPP, g = tid / LPP;
     const int lane = tid & 63, wave = tid >> 6;
@@ -85,6 +109,9 @@ __global__ __launch_bounds__(MB) void k_score_fanout(tpnet_state S, const int64_
     }
     const float bd2 = dec.bd2[0];
     const bool wave_has_units = wave * 32 < dec.H;
+    if constexpr (Epi::RANK) {
+        if (tid < GPB) cnt[tid] = make_int4(0, 0, 0, 0);
+    }
 
     for (int64_t base = base0; base < units; base += (int64_t)gridDim.x * GPB) {
         const int64_t un = base + g;
@@ -94,6 +121,12 @@ __global__ __launch_bounds__(MB) void k_score_fanout(tpnet_state S, const int64_
         const int kb = ch * KC, ke = (kb + KC < C1) ? kb + KC : C1;
         const int nk_u = valid ? ke - kb : 0;              // columns of this group's unit
         const int64_t slot0 = rr * C1 + kb;
+        int own = -1;                                      // (ScoreRank) the step of this unit that meets the row's positive: not counted
+        if constexpr (Epi::RANK) {
+            const int64_t o = valid ? ep.pos[rr] - cand_lo - kb : -1;
+            own = (o >= 0 && o < KC) ? (int)o : -1;
+            if (gl == 0) posl[g] = valid ? ep.pos_logit[rr] : 0.0f;      // (read behind the tile's barriers)
+        }
         Walk wk;
         wk.begin(S, valid ? src[rr] : 0, valid, now, lambda, do_scale, gl);
         for (int j = 0; j < KC; ++j) {                     // (uniform: every group of the workgroup takes KC steps)
@@ -114,14 +147,21 @@ __global__ __launch_bounds__(MB) void k_score_fanout(tpnet_state S, const int64_
             const int sub = j % spt;
             const int c1 = sub * GPB + g;                  // this group's column of the tile
             wk.step(S, jf, jf + 1 < LPP && j + 1 < nk_u, do_scale, gl, [&](int idx, float x) { feat[c1 * TS + idx] = x; });
-            if (gl == 0) dest[c1] = live ? slot0 + j : -1;
+            if constexpr (Epi::RANK) {
+                if (gl == 0) dest[c1] = (live && j != own) ? 0 : -1;
+            } else {
+                if (gl == 0) dest[c1] = live ? slot0 + j : -1;
+            }
             if (sub == spt - 1 || j == KC - 1) {           // (uniform) the tile is full, or the units end
                 __syncthreads();
                 const int ncol = (sub + 1) * GPB;          // columns beyond: stale rows, computed and never stored
                 const int pair = tid >> 4, o = (tid & 15) * 4;      // 512 threads x 4 floats = 32 columns x 64
-                const int64_t dd = pair < ncol ? dest[pair] : -1;
+                int64_t dd = -1;
+                if constexpr (!Epi::RANK) dd = pair < ncol ? dest[pair] : -1;
                 const float4 f4 = *reinterpret_cast<const float4*>(feat + pair * TS + o);
-                if (gram && dd >= 0) *reinterpret_cast<float4*>(gram + dd * MF + o) = f4;      // the features as the kernel formed them
+                if constexpr (!Epi::RANK) {
+                    if (ep.gram && dd >= 0) *reinterpret_cast<float4*>(ep.gram + dd * MF + o) = f4;      // the features as the kernel formed them
+                }
                 // a feature row that holds a NaN (an id out of range: all of it) answers a NaN logit, as the torch layers do -- the
                 // ReLUs of the matrix-core blocks would turn it into a finite number.  A row is 16 neighbouring lanes of a wave.
                 const unsigned long long nanl = __ballot(f4.x != f4.x || f4.y != f4.y || f4.z != f4.z || f4.w != f4.w);
@@ -157,25 +197,99 @@ __global__ __launch_bounds__(MB) void k_score_fanout(tpnet_state S, const int64_
 #pragma unroll
                     for (int i = 0; i < 16; ++i) sum = sum + part[i * 32 + tid];
                     const int64_t d1 = tid < ncol ? dest[tid] : -1;
-                    if (d1 >= 0) out[d1] = nans[tid] ? __builtin_nanf("") : sum + bd2;
+                    if constexpr (Epi::RANK) {
+                        const float q = nans[tid] ? __builtin_nanf("") : sum + bd2;        // the logit the other policy stores
+                        // column tid belongs to unit tid % GPB; the columns of one unit are GPB lanes apart: folded, then thread u adds
+                        const float p = posl[tid % GPB];
+                        const bool on = d1 >= 0;
+                        int cg = (on && q > p) ? 1 : 0, ce = (on && q == p) ? 1 : 0, cn = on ? 1 : 0;
+                        int cf = (on && (q != q || p != p)) ? 2 : 0;
+#pragma unroll
+                        for (int o2 = GPB; o2 < 32; o2 <<= 1) {
+                            cg += __shfl_xor(cg, o2, 64);
+                            ce += __shfl_xor(ce, o2, 64);
+                            cn += __shfl_xor(cn, o2, 64);
+                            cf |= __shfl_xor(cf, o2, 64);
+                        }
+                        if (tid < GPB) {
+                            int4 c = cnt[tid];
+                            c.x += cg; c.y += ce; c.z += cn; c.w |= cf;
+                            cnt[tid] = c;
+                        }
+                    } else {
+                        if (d1 >= 0) ep.out[d1] = nans[tid] ? __builtin_nanf("") : sum + bd2;
+                    }
                 }
                 __syncthreads();                           // the tiles are reused by the next steps of this workgroup
             }
         }
+        if constexpr (Epi::RANK) {                         // the units end: their records leave, the counters start over
+            if (tid < GPB) {
+                int4 c = cnt[tid];
+                const float p = posl[tid];
+                if (p != p) c.w |= 2;                      // (a NaN positive marks the row even where nothing is counted)
+                if (base + tid < units) ep.rec[base + tid] = c;
+                cnt[tid] = make_int4(0, 0, 0, 0);
+            }
+            // (posl[g] is rewritten by the next unit's group only behind the barrier that ended the last tile; thread tid read it
+            // above -- a workgroup barrier keeps that read in front of the rewrite)
+            __syncthreads();
+        }
     }
 }
 
-static LdsOptIn score_fanout_lds;
-static bool score_fanout_available() {
-    return score_fanout_lds.granted({reinterpret_cast<const void*>(k_score_fanout<16, 1, true>),
-                                     reinterpret_cast<const void*>(k_score_fanout<16, 1, false>),
-                                     reinterpret_cast<const void*>(k_score_fanout<32, 1, true>),
-                                     reinterpret_cast<const void*>(k_score_fanout<32, 1, false>),
-                                     reinterpret_cast<const void*>(k_score_fanout<32, 2, true>),
-                                     reinterpret_cast<const void*>(k_score_fanout<32, 2, false>),
-                                     reinterpret_cast<const void*>(k_score_fanout<64, 2, true>),
-                                     reinterpret_cast<const void*>(k_score_fanout<64, 2, false>)}, SF_LDS);
+template <int LPP, int VPL, bool FULL>
+__global__ __launch_bounds__(MB) void k_score_fanout(tpnet_state S, const int64_t* __restrict__ src, const int64_t* __restrict__ cand,
+                                                     const int64_t* __restrict__ lead, int64_t cand_lo, int64_t n_rows, int C, int KC,
+                                                     int spt, double now, double lambda, uint32_t flags,
+                                                     const float* __restrict__ w1f, const float* __restrict__ b1,
+                                                     const float* __restrict__ w2f, const float* __restrict__ b2, score_dec dec,
+                                                     float* __restrict__ gram, float* __restrict__ out) {
+    score_fanout_body<LPP, VPL, FULL>(S, src, cand, lead, cand_lo, n_rows, C, KC, spt, now, lambda, flags, w1f, b1, w2f, b2, dec,
+                                      ScoreStore{gram, out});
 }
+
+// range mode without a lead: row i's columns are the ids cand_lo .. cand_lo + C - 1, counted against pos_logit[i] unless pos[i]
+template <int LPP, int VPL, bool FULL>
+__global__ __launch_bounds__(MB) void k_score_rank(tpnet_state S, const int64_t* __restrict__ src, const int64_t* __restrict__ pos,
+                                                   const float* __restrict__ pos_logit, int64_t cand_lo, int64_t n_rows, int C, int KC,
+                                                   int spt, double now, double lambda, uint32_t flags,
+                                                   const float* __restrict__ w1f, const float* __restrict__ b1,
+                                                   const float* __restrict__ w2f, const float* __restrict__ b2, score_dec dec,
+                                                   int4* __restrict__ rec) {
+    score_fanout_body<LPP, VPL, FULL>(S, src, nullptr, nullptr, cand_lo, n_rows, C, KC, spt, now, lambda, flags, w1f, b1, w2f, b2, dec,
+                                      ScoreRank{pos, pos_logit, rec});
+}
+
+// a row's records summed (integers: any order gives the same words): one wave per row
+__global__ __launch_bounds__(256) void k_score_rank_rows(const int4* __restrict__ rec, int64_t n_rows, int nch, int4* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n_rows) return;                               // (a whole wave leaves: no workgroup barrier below)
+    int g = 0, e = 0, nv = 0, fl = 0;
+    for (int c = lane; c < nch; c += 64) {
+        const int4 r = rec[i * nch + c];
+        g += r.x; e += r.y; nv += r.z; fl |= r.w;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        g += __shfl_xor(g, o, 64);
+        e += __shfl_xor(e, o, 64);
+        nv += __shfl_xor(nv, o, 64);
+        fl |= __shfl_xor(fl, o, 64);
+    }
+    if (lane == 0) counts[i] = make_int4(g, e, nv, fl);
+}
+
+#define TPNET_SF_KERNELS(K_)                                                                                                       \
+    {reinterpret_cast<const void*>(K_<16, 1, true>), reinterpret_cast<const void*>(K_<16, 1, false>),                                  \
+     reinterpret_cast<const void*>(K_<32, 1, true>), reinterpret_cast<const void*>(K_<32, 1, false>),                                  \
+     reinterpret_cast<const void*>(K_<32, 2, true>), reinterpret_cast<const void*>(K_<32, 2, false>),                                  \
+     reinterpret_cast<const void*>(K_<64, 2, true>), reinterpret_cast<const void*>(K_<64, 2, false>)}
+static LdsOptIn score_fanout_lds, score_rank_lds;
+static bool score_fanout_available() { return score_fanout_lds.granted(TPNET_SF_KERNELS(k_score_fanout), SF_LDS); }
+static bool score_rank_available() { return score_rank_lds.granted(TPNET_SF_KERNELS(k_score_rank), SF_LDS_RANK); }
+#undef TPNET_SF_KERNELS
 
 // host arithmetic only: the four geometries of rows of 36..512 floats in ONE chunk (16 x 1, 32 x 1, 32 x 2, 64 x 2)
 static bool score_geom(const tpnet_state& st, Geom& gm) {
@@ -191,33 +305,91 @@ bool score_fanout_supported(const tpnet_state& st, const tpnet_mlp* mlp, int H, 
            ldw % 4 == 0;
 }
 
+// what both launches share: the geometry, one workgroup per CU (its LDS) that loads its weights once, 32 / gpb steps per tile
+struct ScoreGrid { Geom gm; int grid, spt; bool full; };
+static ScoreGrid score_grid(const tpnet_state& st, int64_t n_rows, int C1, int kc) {
+    ScoreGrid g;
+    score_geom(st, g.gm);
+    const int gpb = MB / g.gm.lpp;
+    const int64_t units = n_rows * (((int64_t)C1 + kc - 1) / kc);
+    g.grid = grid_for(units, gpb, 256);
+    g.spt = 32 / gpb;                                            // steps that fill the 32 columns of the matrix products
+    g.full = st.d == g.gm.lpp * g.gm.vpl * 4;
+    return g;
+}
+// K_<lanes, vectors, exact fit> for the geometry g
+#define TPNET_SF_DISPATCH(g, LAUNCH)                                                                       \
+    do {                                                                                                   \
+        if (g.gm.lpp == 16) { if (g.full) LAUNCH(16, 1, true); else LAUNCH(16, 1, false); }                \
+        else if (g.gm.vpl == 1) { if (g.full) LAUNCH(32, 1, true); else LAUNCH(32, 1, false); }            \
+        else if (g.gm.lpp == 32) { if (g.full) LAUNCH(32, 2, true); else LAUNCH(32, 2, false); }           \
+        else { if (g.full) LAUNCH(64, 2, true); else LAUNCH(64, 2, false); }                               \
+    } while (0)
+
 int launch_score_fanout(const tpnet_state& st, const int64_t* src, const int64_t* cand, int64_t cand_lo, const int64_t* lead,
                         int64_t n_rows, int C, double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int ldw,
                         int off, const float* bd, const float* wd2, const float* bd2, int H, float* gram, float* out, hipStream_t s) {
     if (!score_fanout_supported(st, mlp, H, off, ldw)) return TPNET_ERR_BAD_ARG;
     if (!score_fanout_available()) return TPNET_ERR_HIP;         // (a device that does not give a workgroup 112 KB of LDS)
-    Geom gm;
-    score_geom(st, gm);
-    const int gpb = MB / gm.lpp;
     const int C1 = C + (lead ? 1 : 0);
     const int kc = anchored_chunk(n_rows, C1);
-    const int64_t units = n_rows * ((C1 + kc - 1) / kc);
-    // ONE workgroup per CU (its LDS), each loading its weights once
-    const int grid = grid_for(units, gpb, 256);
-    const int spt = 32 / gpb;                                    // steps that fill the 32 columns of the matrix products
+    const ScoreGrid g = score_grid(st, n_rows, C1, kc);
     const score_dec dec = {wd, bd, wd2, bd2, ldw, off, H};
 #define TPNET_SF(LPP_, VPL_, FULL_)                                                                                            \
-    hipLaunchKernelGGL((k_score_fanout<LPP_, VPL_, FULL_>), dim3(grid), dim3(MB), SF_LDS, s, st, src, cand, lead, cand_lo, n_rows, C, kc, \
-                       spt, now, lambda, flags, reinterpret_cast<const float*>(mlp->w1), mlp->b1,                              \
+    hipLaunchKernelGGL((k_score_fanout<LPP_, VPL_, FULL_>), dim3(g.grid), dim3(MB), SF_LDS, s, st, src, cand, lead, cand_lo, n_rows, C, \
+                       kc, g.spt, now, lambda, flags, reinterpret_cast<const float*>(mlp->w1), mlp->b1,                        \
                        reinterpret_cast<const float*>(mlp->w2f), mlp->b2, dec, gram, out)
-    const bool full = st.d == gm.lpp * gm.vpl * 4;
-    if (gm.lpp == 16) { if (full) TPNET_SF(16, 1, true); else TPNET_SF(16, 1, false); }
-    else if (gm.vpl == 1) { if (full) TPNET_SF(32, 1, true); else TPNET_SF(32, 1, false); }
-    else if (gm.lpp == 32) { if (full) TPNET_SF(32, 2, true); else TPNET_SF(32, 2, false); }
-    else { if (full) TPNET_SF(64, 2, true); else TPNET_SF(64, 2, false); }
+    TPNET_SF_DISPATCH(g, TPNET_SF);
 #undef TPNET_SF
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }
+
+// one 16-byte record per unit; a row of ONE unit writes its counts itself (no records, no third launch)
+static int64_t score_rank_chunks(int64_t n_rows, int C, int* kc) {
+    *kc = anchored_chunk(n_rows, C);
+    return ((int64_t)C + *kc - 1) / *kc;
+}
+
+size_t score_rank_scratch_bytes(int64_t n_rows, int C) {
+    if (n_rows < 0 || n_rows >= (1ll << 31) || C < 1) return 0;
+    int kc;
+    const int64_t nch = score_rank_chunks(n_rows, C, &kc);
+    return 16 + (nch > 1 ? (size_t)n_rows * (size_t)nch * sizeof(int4) : 0);
+}
+
+int launch_score_rank(const tpnet_state& st, const int64_t* src, const int64_t* pos, int64_t cand_lo, int64_t n_rows, int C, double now,
+                      double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int ldw, int off, const float* bd,
+                      const float* wd2, const float* bd2, int H, void* scratch, size_t scratch_bytes, float* pos_logit, int32_t* counts,
+                      hipStream_t s) {
+    if (!score_fanout_supported(st, mlp, H, off, ldw)) return TPNET_ERR_BAD_ARG;
+    if (scratch_bytes < score_rank_scratch_bytes(n_rows, C)) return TPNET_ERR_WORKSPACE;
+    if (!score_rank_available()) return TPNET_ERR_HIP;
+    // (1) the positives' logits: the storing kernel as it is, list mode, one candidate per row
+    const int rc = launch_score_fanout(st, src, pos, 0, nullptr, n_rows, 1, now, lambda, flags, mlp, wd, ldw, off, bd, wd2, bd2, H,
+                                       nullptr, pos_logit, s);
+    if (rc) return rc;
+    // (2) the range, counted against them
+    int kc;
+    const int64_t nch = score_rank_chunks(n_rows, C, &kc);
+    const ScoreGrid g = score_grid(st, n_rows, C, kc);
+    const score_dec dec = {wd, bd, wd2, bd2, ldw, off, H};
+    int4* rec = nch > 1 ? reinterpret_cast<int4*>(scratch) : reinterpret_cast<int4*>(counts);
+#define TPNET_SR(LPP_, VPL_, FULL_)                                                                                              \
+    hipLaunchKernelGGL((k_score_rank<LPP_, VPL_, FULL_>), dim3(g.grid), dim3(MB), SF_LDS_RANK, s, st, src, pos, (const float*)pos_logit, \
+                       cand_lo, n_rows, C, kc, g.spt, now, lambda, flags, reinterpret_cast<const float*>(mlp->w1), mlp->b1,      \
+                       reinterpret_cast<const float*>(mlp->w2f), mlp->b2, dec, rec)
+    TPNET_SF_DISPATCH(g, TPNET_SR);
+#undef TPNET_SR
+    TPNET_HIP_TRY(hipGetLastError());
+    // (3) several units per row: their records, added
+    if (nch > 1) {
+        hipLaunchKernelGGL(k_score_rank_rows, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, (const int4*)rec, n_rows, (int)nch,
+                           reinterpret_cast<int4*>(counts));
+        TPNET_HIP_TRY(hipGetLastError());
+    }
+    return TPNET_OK;
+}
+#undef TPNET_SF_DISPATCH
 
 }  // namespace tpnet

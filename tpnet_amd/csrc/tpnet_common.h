@@ -179,6 +179,14 @@ bool score_fanout_supported(const tpnet_state& st, const tpnet_mlp* mlp, int H, 
 int launch_score_fanout(const tpnet_state& st, const int64_t* src, const int64_t* cand, int64_t cand_lo, const int64_t* lead,
                         int64_t n_rows, int C, double now, double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int ldw,
                         int off, const float* bd, const float* wd2, const float* bd2, int H, float* gram, float* out, hipStream_t s);
+// the same kernel body with a counting epilogue (tpnet_score_rank_range): row i's candidates [cand_lo, cand_lo + C) other than pos[i]
+// are compared with pos_logit[i] = logit(src[i], pos[i]) (formed first, by launch_score_fanout) and only {g, e, nv, flags} per row
+// leave the chip -- one 16-byte record per unit in `scratch`, summed per row by a third launch when a row has several units
+size_t score_rank_scratch_bytes(int64_t n_rows, int C);
+int launch_score_rank(const tpnet_state& st, const int64_t* src, const int64_t* pos, int64_t cand_lo, int64_t n_rows, int C, double now,
+                      double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int ldw, int off, const float* bd,
+                      const float* wd2, const float* bd2, int H, void* scratch, size_t scratch_bytes, float* pos_logit, int32_t* counts,
+                      hipStream_t s);
 // encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 36..160 floats (d % 4 == 0), L = 3, K >= 4;
 // with TPNET_FLAG_ROWS8 (and without TPNET_FLAG_NO_MFMA_READOUT) in `flags` also for rows of 38..158 floats with d % 4 == 2, which no
 // other anchored kernel reads

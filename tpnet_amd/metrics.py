@@ -261,6 +261,7 @@ class LinkPredictionMeter:
 # given -- no sigmoid, so a saturating sigmoid adds no ties.
 RANK_FLAG_NO_QUERY = 1        # n == 0: the four floats are NaN
 RANK_FLAG_EMPTY_QUERY = 4     # a query without a valid candidate (not counted); FLAG_NAN_SCORE = 2: a query with a NaN (not counted)
+RANK_FLAG_FILTER_OVERFLOW = 8  # a query whose filter list did not fit its row (not counted); only the records from counts set it
 MAX_RANK_COLUMNS = 1 << 20    # 1 + C of one device call
 
 
@@ -283,6 +284,45 @@ def link_ranking_metrics_host(logits, valid=None, hits_at=(1, 3, 10)):
     m = (2 + 2 * g + e)[~(nan | empty)]
     n = int(len(m))
     flags = (FLAG_NAN_SCORE if nan.any() else 0) | (RANK_FLAG_EMPTY_QUERY if empty.any() else 0) | (0 if n else RANK_FLAG_NO_QUERY)
+    if n:
+        mrr = float(np.sum(2.0 / m.astype(np.float64)) / n)
+        hits = tuple(float(np.float64(int((m <= 2 * int(k)).sum())) / np.float64(n)) for k in hits_at)
+    else:
+        mrr, hits = float("nan"), tuple(float("nan") for _ in hits_at)
+    return {"mrr": mrr, "hits": hits, "m_sum": int(m.sum()), "n": n, "n_valid_candidates": int(nv.sum()), "flags": flags}
+
+
+def link_ranking_counts_host(counts, pos_logit, filter_logits=None, filter_ids=None, n_filter=None, hits_at=(1, 3, 10)):
+    """tpnet_lp_ranking_counts' rule in numpy: counts [B, 4] = (g, e, nv, flags) per query as `score_fanout.rank_range` returns them,
+    pos_logit [B] (fp32); optionally a filter: filter_logits [B, F] (fp32), filter_ids [B, F] (-1: no entry), n_filter [B] (the true
+    list lengths).  Over a query's slots j < min(n_filter, F) with an id >= 0:  g_f = #{filter_logit > p}, e_f = #{== p},
+    m = 2 + 2 (g - g_f) + (e - e_f), valid candidates = nv - n_filter.  Not counted: a NaN flag in counts, a NaN p or looked-at filter
+    logit (FLAG_NAN_SCORE), n_filter > F (RANK_FLAG_FILTER_OVERFLOW), no valid candidate left (RANK_FLAG_EMPTY_QUERY).
+    -> link_ranking_metrics_host's dict."""
+    c = np.asarray(counts).astype(np.int64).reshape(-1, 4)
+    p = np.asarray(pos_logit, dtype=np.float32).reshape(-1)
+    B = len(p)
+    g, e, nv = c[:, 0].copy(), c[:, 1].copy(), c[:, 2].copy()
+    nan = ((c[:, 3] & FLAG_NAN_SCORE) != 0) | np.isnan(p)
+    over = np.zeros(B, dtype=bool)
+    if filter_logits is not None:
+        fl = np.asarray(filter_logits, dtype=np.float32).reshape(B, -1)
+        ids = np.asarray(filter_ids).reshape(B, -1)
+        nf = np.maximum(np.asarray(n_filter).astype(np.int64).reshape(B), 0)
+        F = fl.shape[1]
+        look = (np.arange(F)[None, :] < np.minimum(nf, F)[:, None]) & (ids >= 0)
+        with np.errstate(invalid="ignore"):
+            g -= ((fl > p[:, None]) & look).sum(axis=1)
+            e -= ((fl == p[:, None]) & look).sum(axis=1)
+        nan |= (np.isnan(fl) & look).any(axis=1)
+        over = nf > F
+        nv = nv - nf
+    empty = nv <= 0
+    nv = np.maximum(nv, 0)
+    m = (2 + 2 * g + e)[~(nan | empty | over)]
+    n = int(len(m))
+    flags = (FLAG_NAN_SCORE if nan.any() else 0) | (RANK_FLAG_EMPTY_QUERY if empty.any() else 0) | \
+        (RANK_FLAG_FILTER_OVERFLOW if over.any() else 0) | (0 if n else RANK_FLAG_NO_QUERY)
     if n:
         mrr = float(np.sum(2.0 / m.astype(np.float64)) / n)
         hits = tuple(float(np.float64(int((m <= 2 * int(k)).sum())) / np.float64(n)) for k in hits_at)
@@ -381,6 +421,50 @@ class LinkRankingMeter:
         _lib.check(lib.tpnet_lp_ranking_skip(x.data_ptr() if B else None, B, C1, sk.data_ptr() if B else None, self.hits_at[0],
                                              self.hits_at[1], self.hits_at[2], self._scratch.data_ptr(), self._scratch.numel(),
                                              self._log.data_ptr() + k * _RECORD_WORDS * 8, stream), "lp_ranking_skip")
+        self._n = k + 1
+        return k
+
+    def add_counts(self, counts: torch.Tensor, pos_logit: torch.Tensor, filter_logits: torch.Tensor = None,
+                   filter_ids: torch.Tensor = None, n_filter: torch.Tensor = None) -> int:
+        """Ranking against all nodes from COUNTS (tpnet_lp_ranking_counts; the host rule: link_ranking_counts_host): counts [B, 4]
+        int32 and pos_logit [B] fp32 as `LinkPredictor_v1.rank_one_to_all` returns them; a filter is all three of filter_logits
+        [B, F] fp32, filter_ids [B, F] int64 and n_filter [B] int32 (`filter_lists_device`'s layout), or none of them.  No [B, 1 + C]
+        logits exist, so MAX_RANK_COLUMNS does not apply.  -> the index of the record written.  Two launches, nothing copied, no
+        synchronisation."""
+        if self._n >= self.capacity:
+            raise IndexError(f"LinkRankingMeter: the log of {self.capacity} records is full (results(), then reset())")
+        _check_f32(pos_logit, self.device, "pos_logit")
+        B = int(pos_logit.numel())
+        if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.device != self.device \
+                or tuple(counts.shape) != (B, 4) or pos_logit.dim() != 1:
+            raise TypeError(f"counts: an int32 tensor [{B}, 4] on {self.device} beside pos_logit [{B}] is expected")
+        given = [x is not None for x in (filter_logits, filter_ids, n_filter)]
+        if any(given) != all(given):
+            raise ValueError("add_counts: filter_logits, filter_ids and n_filter come together")
+        F, fl, fi, nf = 0, None, None, None
+        if all(given):
+            _check_f32(filter_logits, self.device, "filter_logits")
+            F = int(filter_logits.shape[1]) if filter_logits.dim() == 2 else 0
+            if filter_logits.dim() != 2 or filter_logits.shape[0] != B or not 1 <= F < 1 << 16:
+                raise ValueError(f"filter_logits must be [{B}, F] with 1 <= F < 65536")
+            if not isinstance(filter_ids, torch.Tensor) or filter_ids.dtype != torch.int64 or filter_ids.device != self.device \
+                    or tuple(filter_ids.shape) != (B, F):
+                raise TypeError(f"filter_ids: an int64 tensor [{B}, {F}] on {self.device} is expected")
+            if not isinstance(n_filter, torch.Tensor) or n_filter.dtype != torch.int32 or n_filter.device != self.device \
+                    or tuple(n_filter.shape) != (B,):
+                raise TypeError(f"n_filter: an int32 tensor [{B}] on {self.device} is expected")
+            fl, fi, nf = filter_logits.detach().contiguous(), filter_ids.contiguous(), n_filter.contiguous()
+        c, p = counts.contiguous(), pos_logit.detach().contiguous()
+        lib = _lib.load()
+        need = lib.tpnet_lp_ranking_scratch_bytes(B, 1)
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+        k = self._n
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        ptr = lambda x: x.data_ptr() if (x is not None and B) else None
+        _lib.check(lib.tpnet_lp_ranking_counts(ptr(c), ptr(p), B, ptr(fl), ptr(fi), ptr(nf), F, self.hits_at[0], self.hits_at[1],
+                                               self.hits_at[2], self._scratch.data_ptr(), self._scratch.numel(),
+                                               self._log.data_ptr() + k * _RECORD_WORDS * 8, stream), "lp_ranking_counts")
         self._n = k + 1
         return k
 

@@ -12,6 +12,31 @@ import torch
 from . import _lib
 
 _STRATEGY = {"random": 0, "historical": 1, "inductive": 2}
+FILTER_MODES = {"same_time": 1, "known": 2}          # TPNET_FILTER_SAME_TIME, TPNET_FILTER_KNOWN
+
+
+def filter_lists_host(src, dst, t, batch_src, batch_dst, batch_t, mode: str, candidate_range, capacity: int):
+    """tpnet_neg_filter_lists' rule in numpy, on the stream (src, dst, t) a sampler would be built on: query i = (s, d, t_i) gets the
+    destinations d' != d inside candidate_range = (lo, hi) that `mode` excludes -- 'known': (s, d') occurs in the stream at any time;
+    'same_time': at time exactly t_i -- ascending and distinct, the first F = capacity of them, the rest of the row -1.
+    -> (fil [B, F] int64, n_fil [B] int32): n_fil is the TRUE count, which may exceed F (overflow)."""
+    if mode not in FILTER_MODES:
+        raise ValueError(f"filter mode {mode!r} is none of {sorted(FILTER_MODES)}")
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    t = np.zeros(len(src)) if t is None else np.asarray(t, dtype=np.float64)
+    lo, hi, F = int(candidate_range[0]), int(candidate_range[1]), int(capacity)
+    B = len(batch_src)
+    fil = np.full((B, F), -1, dtype=np.int64)
+    n_fil = np.zeros(B, dtype=np.int32)
+    for i in range(B):
+        m = src == int(batch_src[i])
+        if mode == "same_time":
+            m &= t == float(batch_t[i])
+        ds = np.unique(dst[m])
+        ds = ds[(ds != int(batch_dst[i])) & (ds >= lo) & (ds < hi)]
+        n_fil[i] = len(ds)
+        fil[i, :min(F, len(ds))] = ds[:F]
+    return fil, n_fil
 
 
 class GpuNegativeEdgeSampler:
@@ -44,6 +69,8 @@ class GpuNegativeEdgeSampler:
         src, dst = to(src_node_ids, torch.int64), to(dst_node_ids, torch.int64)
         t = to(interact_times, torch.float64) if interact_times is not None else None
         self.E = int(src.numel())
+        self._built_on = (src, dst, t)                # (filter_capacity reads the stream once, when first asked)
+        self._filter_capacity = {}
         assert self.E > 0 and int(dst.numel()) == self.E and (t is None or int(t.numel()) == self.E)
         self.earliest_time = float(t.min().item()) if t is not None else None
         nbytes = lib.tpnet_neg_bytes(self.E)
@@ -134,6 +161,50 @@ class GpuNegativeEdgeSampler:
         _lib.check(_lib.load().tpnet_neg_sample_many(self._buf.data_ptr(), self.E, bs.data_ptr(), bd.data_ptr(), bt.data_ptr(), B, Q, Qh,
                                                      self._key, call, cand.data_ptr(), n_hist.data_ptr(), stream), "neg_sample_many")
         return cand, n_hist
+
+    def filter_capacity(self, mode: str) -> int:
+        """The longest filter list `mode` can give on the stream the sampler was built on: the largest number of distinct
+        destinations of one source ('known') or of one (source, instant) ('same_time'); at least 1.  Computed once per mode (torch
+        on the device; synchronises that once) -- `filter_lists_device`'s default capacity, with which no row overflows."""
+        if mode not in FILTER_MODES:
+            raise ValueError(f"filter mode {mode!r} is none of {sorted(FILTER_MODES)}")
+        if mode not in self._filter_capacity:
+            src, dst, t = self._built_on
+            cols = [src] + ([t.view(torch.int64)] if (mode == "same_time" and t is not None) else []) + [dst]
+            rows = torch.unique(torch.stack(cols, dim=1), dim=0)
+            _, n = torch.unique(rows[:, :-1], dim=0, return_counts=True)
+            self._filter_capacity[mode] = max(1, int(n.max().item()))
+        return self._filter_capacity[mode]
+
+    def filter_lists_device(self, batch_src: torch.Tensor, batch_dst: torch.Tensor, batch_t: torch.Tensor, mode: str, candidate_range,
+                            capacity: int = None):
+        """Per-query filter lists of the all-node ranking protocol (tpnet_neg_filter_lists; `filter_lists_host` is the rule): query
+        (s, d, t) gets the destinations d' != d inside candidate_range = (lo, hi) that `mode` excludes from its candidates --
+        'same_time': the table holds (s, d') at exactly t, `sample_many_device`'s exclusion; 'known': at any time -- ascending,
+        distinct, -1 behind them -> (fil [B, F] int64, n_fil [B] int32) on the device, F = capacity (default: filter_capacity(mode));
+        n_fil is the true count, n_fil[i] > F = overflow.  One launch, nothing synchronises, the call index does not advance."""
+        if mode not in FILTER_MODES:
+            raise ValueError(f"filter mode {mode!r} is none of {sorted(FILTER_MODES)}")
+        for x, dt, what in ((batch_src, torch.int64, "batch_src"), (batch_dst, torch.int64, "batch_dst"), (batch_t, torch.float64, "batch_t")):
+            if not isinstance(x, torch.Tensor) or x.dtype != dt or not x.is_cuda or x.dim() != 1:
+                raise TypeError(f"filter_lists_device: {what} must be a one-dimensional {dt} tensor on {self.device}")
+        B = int(batch_src.numel())
+        if int(batch_dst.numel()) != B or int(batch_t.numel()) != B:
+            raise ValueError("filter_lists_device: batch_src, batch_dst and batch_t must have the same length")
+        F = self.filter_capacity(mode) if capacity is None else int(capacity)
+        lo, hi = int(candidate_range[0]), int(candidate_range[1])
+        if not (1 <= F < 1 << 16) or hi < lo:
+            raise ValueError(f"filter_lists_device: 1 <= capacity < 65536 and lo <= hi, not {F}, ({lo}, {hi})")
+        bs, bd, bt = batch_src.contiguous(), batch_dst.contiguous(), batch_t.contiguous()
+        fil = torch.empty((B, F), dtype=torch.int64, device=self.device)
+        n_fil = torch.empty(B, dtype=torch.int32, device=self.device)
+        if B == 0:
+            return fil, n_fil
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(_lib.load().tpnet_neg_filter_lists(self._buf.data_ptr(), self.E, bs.data_ptr(), bd.data_ptr(), bt.data_ptr(), B,
+                                                      FILTER_MODES[mode], lo, hi, F, fil.data_ptr(), n_fil.data_ptr(), stream),
+                   "neg_filter_lists")
+        return fil, n_fil
 
     def check(self):
         """tpnet_neg_check: synchronises; raises if a fill since the last check found no pair outside its batch."""

@@ -1,7 +1,9 @@
 """One source against many candidates scored in ONE launch (C ABI: tpnet_score_one_to_many; csrc/score_fanout.hip): the fan-out
 readout, `rp.mlp` and LinkPredictor_v1's two layers (not_encode: the embedding columns of fc1 meet zeros) with nothing but the
 logits written.  `serves` is the route question `LinkPredictor_v1.forward_one_to_many` / `forward_one_to_all` ask with
-`fused_scores` set; `score` is the call; `score_one_to_many_host` is the four lines in float64 numpy, what the kernel is held to."""
+`fused_scores` set; `score` is the call; `score_one_to_many_host` is the four lines in float64 numpy, what the kernel is held to.
+`rank_range` (C ABI: tpnet_score_rank_range) ranks each row's positive against a whole id range with the counts formed in the same
+kernel: no logit matrix exists."""
 import numpy as np
 import torch
 
@@ -9,7 +11,7 @@ from . import _lib
 from . import fused_feature as _ff
 
 # launches made through this module (tests assert the dispatch through it)
-calls = {"score": 0}
+calls = {"score": 0, "rank": 0}
 
 
 def score_one_to_many_host(features, mlp, fc1, fc2, off):
@@ -115,3 +117,39 @@ def score(decoder, src_ids, cand_ids=None, cand_range=None, lead_ids=None, want_
         None if gram is None else gram.data_ptr(), out.data_ptr(), rp._stream()), "score_one_to_many")
     calls["score"] += 1
     return (out, gram) if want_gram else out
+
+
+def rank_range(decoder, src_ids, pos_ids, cand_range):
+    """tpnet_score_rank_range on `decoder` (serves() holds): src_ids [B], pos_ids [B], cand_range = (lo, hi) -> (counts [B, 4] int32,
+    pos_logit [B] fp32) on the GPU.  counts[i] = (g, e, nv, flags): over the ids c of [lo, hi) other than pos_ids[i], how many logits
+    of (src_ids[i], c) are above / equal to pos_logit[i] = the logit of (src_ids[i], pos_ids[i]), how many were counted, and 2 where a
+    NaN took part -- exactly what `score(cand_range=, lead_ids=pos_ids)` and the integer rule give, without the [B, 1 + hi - lo]
+    logits.  No gradient, no synchronisation; the scratch is the call's own."""
+    rp = decoder.random_projections
+    rp._ensure_engine()
+    prep = _mlp_prepared(rp)
+    if prep is None:
+        raise _lib.TPNetHipError("score_rank_range: rp.mlp is not the reference's Linear-ReLU-Linear on the GPU")
+    dev = rp._dev()
+    lo, hi = int(cand_range[0]), int(cand_range[1])
+    Cn, B = hi - lo, len(src_ids)
+    if Cn < 1 or Cn >= 1 << 31:
+        raise ValueError("rank_range: 1 <= hi - lo < 2^31 candidates")
+    if len(pos_ids) != B:
+        raise ValueError("one positive id per source")
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    pos_logit = torch.empty(B, dtype=torch.float32, device=dev)
+    if B == 0:
+        return counts, pos_logit
+    s, p = rp._to_device(rp._ids(src_ids, "src_ids"), rp._ids(pos_ids, "pos_ids"))
+    lib = _lib.load()
+    need = lib.tpnet_score_rank_scratch_bytes(B, Cn)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    fc1, fc2 = decoder.fc1, decoder.fc2
+    _lib.check(lib.tpnet_score_rank_range(
+        rp._st_ref(), s.data_ptr(), p.data_ptr(), lo, B, Cn, rp._now_host, float(rp.time_decay_weight),
+        _lib.FLAG_NOT_SCALE if rp.not_scale else 0, prep.ref, fc1.weight.data_ptr(), fc1.in_features, fc1.in_features - 64,
+        fc1.bias.data_ptr(), fc2.weight.data_ptr(), fc2.bias.data_ptr(), fc1.out_features, scratch.data_ptr(), scratch.numel(),
+        pos_logit.data_ptr(), counts.data_ptr(), rp._stream()), "score_rank_range")
+    calls["rank"] += 1
+    return counts, pos_logit
