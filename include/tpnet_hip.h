@@ -60,7 +60,8 @@ extern "C" {
                                     tpnet_lp_ranking* (a batch's MRR and Hits@k as one device record);
                                     tpnet_anchored_route (which kernel serves an anchored readout: the one table);
                                     tpnet_score_one_to_many* (one source against many candidates, one logit per pair, in one launch),
-                                    tpnet_lp_ranking_skip (the ranking record with one absent candidate column per query) */
+                                    tpnet_lp_ranking_skip (the ranking record with one absent candidate column per query);
+                                    tpnet_score_topk_range (the K best ids of a whole id range per source, formed in the scoring kernel) */
 #define TPNET_MAX_LAYERS 4 /* num_layer L in 1..4 (reference default 3, utils/load_configs.py:70) */
 
 typedef enum tpnet_status {
@@ -397,6 +398,48 @@ int tpnet_score_rank_range(const tpnet_state* st, const int64_t* src, const int6
                            double now_time, double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int32_t ldw,
                            int32_t off, const float* bd, const float* wd2, const float* bd2, int32_t H, void* scratch,
                            size_t scratch_bytes, float* pos_logit, int32_t* counts, void* stream);
+
+/* ---- the K best ids of a whole id range per source, the lists formed in the scoring kernel (additive to ABI 7;
+ * csrc/score_fanout.hip).  For row i, over every ADMITTED id c of [cand_lo, cand_lo + C) with
+ * q = logit(src[i], c) (the four lines above): ids[i][0 .. K) = the K best candidates, best first, logits[i][..] their logits.
+ * Admission: c is left out when c == skip[i] (skip: optional, one id per row; a recommender passes the source itself) or when c is
+ * on the row's exclusion list -- excl: optional, [n_rows][F] int64, each row ascending, distinct, -1 padded; n_excl: [n_rows] int32,
+ * the true length of the row's list (only its first min(n_excl, F) slots are read): exactly tpnet_neg_filter_lists' output.
+ * THE ORDER is one rule on a 64-bit key, larger = better:
+ *   hi32 = 0xFFFFFFFF for a NaN logit (NaN sorts FIRST, as in torch.topk: a poisoned state shows up), else the monotone map of the
+ *          fp32 bits of q + 0.0f (-0.0 and +0.0 tie): all bits flipped where the sign is set, else the sign bit set;
+ *   lo32 = 0xFFFFFFFF - (c - cand_lo);      key = hi32 << 32 | lo32;      key 0 = an empty slot, below every real key
+ * -- logit descending, id ascending at equal logits; no two candidates of a row share a key, so the K best and their order are
+ * unique.  The returned logit is decoded from the key (-0.0 comes back as +0.0).  Empty slots (fewer than K admitted ids; K > C is
+ * allowed): id -1, logit -inf.  info[2 i] = n_valid = min(K, admitted ids); info[2 i + 1] = flags: value 2 when a NaN logit was
+ * among the row's admitted candidates, value 8 when the row's exclusion list overflowed (n_excl[i] > F: the ids beyond the first F
+ * were NOT left out) -- the ranking records' flag values.
+ * Limits: 1 <= C < 2^31, 0 <= n_rows < 2^31, 1 <= K <= 128 (the lists of a workgroup's 32 units are 32 K 8 bytes of LDS: 148 352
+ * bytes of dynamic LDS at K = 128, sized by the call's K; every instantiation builds without scratch).  No logit matrix exists: n_rows (1 + C) is not bounded.
+ * PROMISES.  (1) ids, logits and info equal EXACTLY what tpnet_score_one_to_many(cand = NULL, cand_lo) on the same range followed
+ * by the rule above gives -- promise (1) of that call, and everything behind the logit is an integer.  (2) Two calls agree bit for
+ * bit: the K best of distinct keys do not depend on the order they are met in.
+ * Launches, one or two, all on `stream`, no synchronisation, no memset, no floating-point atomics: (a) the scoring kernel body with
+ * a list epilogue -- a unit = (row, chunk of KC ids), cut as for tpnet_score_one_to_many; one lane per unit walks the row's
+ * exclusion list beside the ascending ids (one binary search per unit, one compare per id); the unit's K best keys live in LDS
+ * (append, then replace-the-minimum behind a cached threshold) and min(K, KC) of them leave the workgroup ONCE, sorted -- decoded
+ * into ids / logits / info when every row is one unit, else as one record in `scratch`; (b) where a row has several units, one
+ * workgroup per row selects the K best of its records' keys by a radix select (eight passes at most, linear in the keys) and sorts
+ * them.
+ * scratch: tpnet_score_topk_scratch_bytes(n_rows, C, K) device bytes = 16 + n_rows nch min(K, KC) 8 where a row has nch > 1 units,
+ * else 16 -- at most about (8192 + n_rows) K 8; 0 for sizes out of range.  16-byte aligned.  ids: device int64[n_rows K];
+ * logits: device float[n_rows K]; info: device int32[2 n_rows].
+ * Served exactly where tpnet_score_one_to_many_supported returns 1; checks and error returns as for tpnet_score_rank_range, and:
+ * excl without n_excl or with F < 1, K out of range: TPNET_ERR_BAD_ARG; a short scratch: TPNET_ERR_WORKSPACE; n_rows == 0: TPNET_OK.
+ * A src[i] outside [0, N): row i's logits are NaN and its flag 2 is set, its ids are the K smallest admitted ids (every key ties
+ * at NaN), every other row is untouched, the state's error word is raised.  A device that refuses the LDS: TPNET_ERR_HIP.
+ * NOT measured (profiles/topk_streaming.md): tables beyond the caches, rows wider than 256 floats, K between 10 and 100. */
+size_t tpnet_score_topk_scratch_bytes(int64_t n_rows, int32_t C, int32_t K);
+int tpnet_score_topk_range(const tpnet_state* st, const int64_t* src, const int64_t* skip, const int64_t* excl, const int32_t* n_excl,
+                           int32_t F, int64_t cand_lo, int64_t n_rows, int32_t C, int32_t K, double now_time, double lambda,
+                           uint32_t flags, const tpnet_mlp* mlp, const float* wd, int32_t ldw, int32_t off, const float* bd,
+                           const float* wd2, const float* bd2, int32_t H, void* scratch, size_t scratch_bytes, int64_t* ids,
+                           float* logits, int32_t* info, void* stream);
 
 /* Workspace for tpnet_update / tpnet_run_stream with at most max_edges edges per call. */
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch);

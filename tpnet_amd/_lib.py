@@ -88,6 +88,10 @@ SIGNATURES = {
     "tpnet_score_rank_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "tpnet_score_rank_range": (C.c_int, [_SP, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_uint32, _P, _P,
                                          C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, _P]),
+    "tpnet_score_topk_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "tpnet_score_topk_range": (C.c_int, [_SP, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                         C.c_double, C.c_uint32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_size_t,
+                                         _P, _P, _P, _P]),
     "tpnet_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "tpnet_stream_workspace_bytes_capped": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_size_t]),

@@ -11,7 +11,8 @@ G8 -- without the reference's files (they never travel to the GPU box).
 * `evaluate_edge_bank_link_prediction` -- the EdgeBank baseline's evaluation loop on the device (evaluate_models_utils.py:269-318).
 * `evaluate_link_ranking`   -- one-vs-many ranking evaluation (MRR, Hits@k): per-query candidates, one-to-many decoder, device meter.
 * `evaluate_link_ranking_all` / `recommend_links` -- ranking against ALL nodes of an id range (exact rank; unfiltered, or filtered and
-  streaming on `LinkPredictor_v1.rank_one_to_all`) and top-k recommendation, on `LinkPredictor_v1.forward_one_to_all`.
+  streaming on `LinkPredictor_v1.rank_one_to_all`) and top-k recommendation, on `LinkPredictor_v1.forward_one_to_all` (or
+  streaming, with known destinations left out, on `LinkPredictor_v1.topk_one_to_all`).
 * `link_prediction_batch` / `run_epoch` -- the per-batch order of train_link_prediction.py:253-373 (negatives, two
   encoder readouts, two decoder readouts, THEN update) and the epoch-level reset (:246-248).
 * `train_link_prediction_epoch` -- the same epoch with the loss, the backward and the optimizer step (:375-386), the loss and the
@@ -207,6 +208,85 @@ class LinkPredictor_v1(nn.Module):
                 p_all[r] = p[:, 0]
                 counts[r, 3] = nan.to(torch.int32) * 2
             return counts, p_all, fl
+
+    def topk_one_to_all(self, src_node_ids, k: int, first_id: int, end_id: int, skip_node_ids=None,
+                        exclude_ids: Optional[torch.Tensor] = None, n_exclude: Optional[torch.Tensor] = None,
+                        pairs_per_call: int = 1 << 18):
+        """Extension, streaming top-k against all nodes: per row the k best ids of [first_id, end_id) by the logit of (src[i], id)
+        -> (ids [B, k] int64, logits [B, k] fp32, info [B, 2] int32), best first by ONE rule (`score_fanout.topk_host`): logit
+        descending with NaN first and -0.0 = +0.0, id ascending at equal logits; empty slots (fewer than k admitted ids) hold id -1
+        and logit -inf; info[:, 0] = the real entries, info[:, 1] = 2 where an admitted logit is NaN | 8 where the row's exclusion
+        list overflowed.  The [B, end_id - first_id] logits of `forward_one_to_all` never exist.  skip_node_ids [B] (optional): one
+        id per row left out (a recommender passes the source itself); exclude_ids [B, F] int64 with n_exclude [B] int32 on the
+        device (optional; ascending, distinct, -1 padded: the layout of `GpuNegativeEdgeSampler.filter_lists_device`): the ids of a
+        row's first min(n_exclude, F) slots are left out.
+        Route: where the one-launch kernel serves the module (score_fanout.serves) and k <= 128, tpnet_score_topk_range -- the lists
+        are formed in the scoring kernel.  Every other state (and a larger k): `forward_one_to_all` in row and column slices of at
+        most pairs_per_call pairs, a running best-k per row merged by the same key with torch integer ops -- never more than one
+        slice is held.  Requires `not_encode`; runs under no_grad."""
+        if not self.not_encode:
+            raise ValueError("topk_one_to_all: the decoder must be not_encode")
+        lo, hi = int(first_id), int(end_id)
+        k = int(k)
+        if hi <= lo or hi - lo >= 1 << 31:
+            raise ValueError("topk_one_to_all: an id range [first_id, end_id) of 1 .. 2^31 - 1 ids")
+        if k < 1:
+            raise ValueError("topk_one_to_all: k >= 1")
+        B = len(src_node_ids)
+        if skip_node_ids is not None and len(skip_node_ids) != B:
+            raise ValueError("topk_one_to_all: one skip id per source")
+        dev = self.fc1.weight.device
+        if (exclude_ids is None) != (n_exclude is None):
+            raise ValueError("topk_one_to_all: exclude_ids and n_exclude come together")
+        if exclude_ids is not None:
+            if (not isinstance(exclude_ids, torch.Tensor) or exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2
+                    or exclude_ids.shape[0] != B or exclude_ids.device != dev):
+                raise TypeError(f"topk_one_to_all: exclude_ids must be an int64 tensor [{B}, F] on {dev}")
+            if (not isinstance(n_exclude, torch.Tensor) or n_exclude.dtype != torch.int32 or tuple(n_exclude.shape) != (B,)
+                    or n_exclude.device != dev):
+                raise TypeError(f"topk_one_to_all: n_exclude must be an int32 tensor [{B}] on {dev}")
+        from . import score_fanout as sf
+        as_dev = lambda a: a.to(dev, torch.int64) if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.int64)).to(dev)
+        with torch.no_grad():
+            if B > 0 and k <= sf.TOPK_MAX and self._scores_fused(False, True):
+                return sf.topk_range(self, src_node_ids, k, (lo, hi), skip_ids=skip_node_ids, exclude_ids=exclude_ids,
+                                     n_exclude=n_exclude)
+            src = as_dev(src_node_ids)
+            skip = as_dev(skip_node_ids) if skip_node_ids is not None else None
+            C = hi - lo
+            per = max(1, int(pairs_per_call))
+            rows = max(1, per // C)                                # whole rows per slice; one row at a time if it is longer
+            width = min(C, per)                                    # columns per slice
+            best = torch.full((B, k), sf._EMPTY_KEY, dtype=torch.int64, device=dev)
+            info = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+            keep = None
+            if exclude_ids is not None:
+                F = exclude_ids.shape[1]
+                keep = (torch.arange(F, device=dev).unsqueeze(0) < n_exclude.clamp(0, F).unsqueeze(1)) & (exclude_ids >= 0)
+                info[:, 1] = (n_exclude > F).to(torch.int32) * sf.FLAG_OVERFLOW
+            for r0 in range(0, B, rows):
+                r = slice(r0, min(r0 + rows, B))
+                n_adm = torch.zeros(r.stop - r0, dtype=torch.int64, device=dev)
+                nan = torch.zeros(r.stop - r0, dtype=torch.bool, device=dev)
+                for c0 in range(lo, hi, width):
+                    c1 = min(c0 + width, hi)
+                    x = self.forward_one_to_all(src[r], c0, c1, pairs_per_call=pairs_per_call).float()
+                    ids = torch.arange(c0, c1, device=dev).unsqueeze(0)
+                    adm = torch.ones(x.shape, dtype=torch.bool, device=dev)
+                    if skip is not None:
+                        adm &= ids != skip[r].unsqueeze(1)
+                    if keep is not None:
+                        e = exclude_ids[r]
+                        rr_, cc_ = torch.nonzero(keep[r] & (e >= c0) & (e < c1), as_tuple=True)
+                        adm[rr_, e[rr_, cc_] - c0] = False
+                    keys = torch.where(adm, sf.topk_keys_torch(x, ids - lo), torch.full_like(ids, sf._EMPTY_KEY))
+                    best[r] = torch.sort(torch.cat([best[r], keys], dim=1), dim=1, descending=True).values[:, :k]
+                    n_adm += adm.sum(dim=1)
+                    nan |= (torch.isnan(x) & adm).any(dim=1)
+                info[r, 0] = n_adm.clamp(max=k).to(torch.int32)
+                info[r, 1] |= nan.to(torch.int32) * sf.FLAG_NAN
+            out_ids, out_logits = sf.topk_decode_torch(best, lo)
+            return out_ids, out_logits, info
 
     def _decode(self, pair_feature: Callable, src_node_embeddings: torch.Tensor, dst_node_embeddings: torch.Tensor):
         """What `forward` does with its pairs' embeddings; pair_feature() = their pairwise features (called only with a module)."""
@@ -500,13 +580,37 @@ def evaluate_link_ranking(rp, negative_sampler, src, dst, t, batch_size: int, nu
     return meter.results()
 
 
-def recommend_links(decoder, src_node_ids, k: int, candidate_range):
+def recommend_links(decoder, src_node_ids, k: int, candidate_range, streaming: bool = False, exclude: Optional[str] = None,
+                    negative_sampler=None, exclude_self: bool = False):
     """"Which k nodes is u most likely to link to now?": `decoder.forward_one_to_all(src_node_ids, lo, hi)` over candidate_range =
     (lo, hi), then `torch.topk` -> (ids [B, k] int64, logits [B, k]), best first, on the decoder's device.  Plain torch behind the
-    scores; under no_grad."""
+    scores; under no_grad.
+    STREAMING (streaming = True, exclude = 'known' or exclude_self = True; the defaults are the lines above, bit for bit):
+    `decoder.topk_one_to_all` -- the k best are kept where the scores are formed (tpnet_score_topk_range where the kernel serves the
+    module) and no [B, hi - lo] tensor is built, so neither the logits' memory nor n_rows (1 + C) < 2^31 bound the range.  Same
+    values as the default; at EQUAL logits the smaller id comes first (torch.topk promises no order there), NaN first, -0.0 = +0.0.
+    exclude = 'known': the destinations the source already has in negative_sampler's table (a `GpuNegativeEdgeSampler`; ValueError
+    without one) are left out -- `negative_sampler.filter_lists_device(src, -1, 0, 'known', (lo, hi))`: a destination of -1 drops no
+    id from a list.  exclude_self: the source itself is left out.  A row with fewer than k admitted ids ends in empty slots: id -1,
+    logit -inf."""
     lo, hi = int(candidate_range[0]), int(candidate_range[1])
     if not 1 <= int(k) <= hi - lo:
         raise ValueError("recommend_links: 1 <= k <= the number of candidates")
+    if exclude is not None and exclude != "known":
+        raise ValueError(f"recommend_links: exclude {exclude!r} is none of None, 'known'")
+    if exclude == "known" and negative_sampler is None:
+        raise ValueError("recommend_links: exclude = 'known' needs negative_sampler (a GpuNegativeEdgeSampler)")
+    if streaming or exclude is not None or exclude_self:
+        dev = decoder.fc1.weight.device
+        src = (src_node_ids.to(dev, torch.int64) if isinstance(src_node_ids, torch.Tensor)
+               else torch.from_numpy(np.asarray(src_node_ids, dtype=np.int64)).to(dev))
+        fil = n_fil = None
+        if exclude == "known":
+            fil, n_fil = negative_sampler.filter_lists_device(src, torch.full_like(src, -1), torch.zeros(len(src), dtype=torch.float64, device=dev),
+                                                              "known", (lo, hi))
+        ids, logits, _ = decoder.topk_one_to_all(src, int(k), lo, hi, skip_node_ids=src if exclude_self else None, exclude_ids=fil,
+                                                 n_exclude=n_fil)
+        return ids, logits
     with torch.no_grad():
         logits = decoder.forward_one_to_all(src_node_ids, lo, hi)
         top = torch.topk(logits, int(k), dim=1)

@@ -518,6 +518,34 @@ int tpnet_score_rank_range(const tpnet_state* st, const int64_t* src, const int6
                              scratch_bytes, pos_logit, counts, (hipStream_t)stream);
 }
 
+size_t tpnet_score_topk_scratch_bytes(int64_t n_rows, int32_t C, int32_t K) { return score_topk_scratch_bytes(n_rows, C, K); }
+
+int tpnet_score_topk_range(const tpnet_state* st, const int64_t* src, const int64_t* skip, const int64_t* excl, const int32_t* n_excl,
+                           int32_t F, int64_t cand_lo, int64_t n_rows, int32_t C, int32_t K, double now_time, double lambda,
+                           uint32_t flags, const tpnet_mlp* mlp, const float* wd, int32_t ldw, int32_t off, const float* bd,
+                           const float* wd2, const float* bd2, int32_t H, void* scratch, size_t scratch_bytes, int64_t* ids,
+                           float* logits, int32_t* info, void* stream) {
+    int rc = check_state(st);
+    if (rc) return rc;
+    if (n_rows < 0 || n_rows >= (1ll << 31) || C <= 0 || !src || !ids || !logits || !info || !scratch || !mlp || !wd || !bd || !wd2 ||
+        !bd2)
+        return TPNET_ERR_BAD_ARG;
+    if (K < 1 || K > SCORE_TOPK_MAX) return TPNET_ERR_BAD_ARG;
+    if (excl && (!n_excl || F < 1)) return TPNET_ERR_BAD_ARG;
+    if (!aligned16({wd, mlp->w1, mlp->w2f, mlp->b2, scratch}) ||
+        ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(skip) | reinterpret_cast<uintptr_t>(excl)) & 7) ||
+        ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(info) | reinterpret_cast<uintptr_t>(n_excl) |
+          reinterpret_cast<uintptr_t>(bd) | reinterpret_cast<uintptr_t>(wd2) | reinterpret_cast<uintptr_t>(bd2) |
+          reinterpret_cast<uintptr_t>(mlp->b1)) & 3))
+        return TPNET_ERR_BAD_ARG;
+    if (flags & TPNET_FLAG_PACKED) return TPNET_ERR_BAD_ARG;   // packed rows exist for the one-pair readout only
+    if (cand_lo < 0 || cand_lo > st->N - (int64_t)C) return TPNET_ERR_BAD_ARG;             // the range lies inside [0, N)
+    if (!score_fanout_supported(*st, mlp, H, off, ldw)) return TPNET_ERR_BAD_ARG;       // (the caller takes the slices)
+    if (n_rows == 0) return TPNET_OK;
+    return launch_score_topk(*st, src, skip, excl, excl ? n_excl : nullptr, excl ? F : 0, cand_lo, n_rows, C, K, now_time, lambda, flags,
+                             mlp, wd, ldw, off, bd, wd2, bd2, H, scratch, scratch_bytes, ids, logits, info, (hipStream_t)stream);
+}
+
 size_t tpnet_workspace_bytes(int64_t max_edges, int64_t batch) { return plan_bytes(max_edges, batch); }
 
 // bytes for a stream of max_edges on the windowed schedule in chunks of at most chunk_cap edges: one chunk's plan, or -- several

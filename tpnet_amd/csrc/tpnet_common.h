@@ -187,6 +187,16 @@ int launch_score_rank(const tpnet_state& st, const int64_t* src, const int64_t* 
                       double lambda, uint32_t flags, const tpnet_mlp* mlp, const float* wd, int ldw, int off, const float* bd,
                       const float* wd2, const float* bd2, int H, void* scratch, size_t scratch_bytes, float* pos_logit, int32_t* counts,
                       hipStream_t s);
+// the same kernel body with a list epilogue (tpnet_score_topk_range): row i's K best candidates of [cand_lo, cand_lo + C) by the
+// 64-bit key of include/tpnet_hip.h, ids equal to skip[i] or on the row's exclusion list left out; a unit keeps its K best keys in
+// LDS and hands on min(K, KC) of them once -- straight to the outputs when every row is one unit, else one record per unit in
+// `scratch`, selected per row by a second launch
+static constexpr int SCORE_TOPK_MAX = 128;
+size_t score_topk_scratch_bytes(int64_t n_rows, int C, int K);
+int launch_score_topk(const tpnet_state& st, const int64_t* src, const int64_t* skip, const int64_t* excl, const int32_t* n_excl, int F,
+                      int64_t cand_lo, int64_t n_rows, int C, int K, double now, double lambda, uint32_t flags, const tpnet_mlp* mlp,
+                      const float* wd, int ldw, int off, const float* bd, const float* wd2, const float* bd2, int H, void* scratch,
+                      size_t scratch_bytes, int64_t* ids, float* logits, int32_t* info, hipStream_t s);
 // encoder_mfma.hip: the same readout on the matrix cores (split-bf16 operands, fp32 class) for rows of 36..160 floats (d % 4 == 0), L = 3, K >= 4;
 // with TPNET_FLAG_ROWS8 (and without TPNET_FLAG_NO_MFMA_READOUT) in `flags` also for rows of 38..158 floats with d % 4 == 2, which no
 // other anchored kernel reads

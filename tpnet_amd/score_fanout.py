@@ -3,7 +3,8 @@ readout, `rp.mlp` and LinkPredictor_v1's two layers (not_encode: the embedding c
 logits written.  `serves` is the route question `LinkPredictor_v1.forward_one_to_many` / `forward_one_to_all` ask with
 `fused_scores` set; `score` is the call; `score_one_to_many_host` is the four lines in float64 numpy, what the kernel is held to.
 `rank_range` (C ABI: tpnet_score_rank_range) ranks each row's positive against a whole id range with the counts formed in the same
-kernel: no logit matrix exists."""
+kernel: no logit matrix exists.  `topk_range` (C ABI: tpnet_score_topk_range) keeps each row's k best ids of a whole id range in the
+same kernel; `topk_host` is its rule in numpy -- the specification every route of `LinkPredictor_v1.topk_one_to_all` is held to."""
 import numpy as np
 import torch
 
@@ -11,7 +12,10 @@ from . import _lib
 from . import fused_feature as _ff
 
 # launches made through this module (tests assert the dispatch through it)
-calls = {"score": 0, "rank": 0}
+calls = {"score": 0, "rank": 0, "topk": 0}
+
+TOPK_MAX = 128                    # tpnet_score_topk_range's largest k (the units' lists live in LDS)
+FLAG_NAN, FLAG_OVERFLOW = 2, 8    # info[:, 1] of a top-k call: the ranking records' flag values
 
 
 def score_one_to_many_host(features, mlp, fc1, fc2, off):
@@ -153,3 +157,153 @@ def rank_range(decoder, src_ids, pos_ids, cand_range):
         pos_logit.data_ptr(), counts.data_ptr(), rp._stream()), "score_rank_range")
     calls["rank"] += 1
     return counts, pos_logit
+
+
+# ---- top-k: ONE order, on 64-bit keys (include/tpnet_hip.h at tpnet_score_topk_range).  key = hi32 << 32 | lo32, larger = better:
+# hi32 = 0xFFFFFFFF for NaN (first, as in torch.topk), else the monotone map of the fp32 bits of q + 0.0 (-0.0 ties with +0.0);
+# lo32 = 0xFFFFFFFF - (id - lo) (the smaller id wins a tie); key 0 = an empty slot.
+
+def _keys_host(q, col):
+    """logits q (fp32 array) and their columns (id - lo, broadcastable) -> uint64 keys."""
+    q = np.asarray(q, dtype=np.float32) + np.float32(0.0)
+    b = q.view(np.uint32)
+    hi = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    hi = np.where(np.isnan(q), np.uint32(0xFFFFFFFF), hi)
+    lo32 = (np.uint64(0xFFFFFFFF) - np.asarray(col).astype(np.uint64)).astype(np.uint64)
+    return (hi.astype(np.uint64) << np.uint64(32)) | lo32
+
+
+def _decode_host(keys, lo):
+    """uint64 keys -> (ids int64, logits fp32); key 0: id -1, logit -inf."""
+    keys = np.asarray(keys, dtype=np.uint64)
+    hi = (keys >> np.uint64(32)).astype(np.uint32)
+    b = np.where(hi & np.uint32(0x80000000), hi ^ np.uint32(0x80000000), ~hi).astype(np.uint32)
+    logit = b.view(np.float32).copy()
+    logit[hi == np.uint32(0xFFFFFFFF)] = np.nan
+    ids = int(lo) + (np.int64(0xFFFFFFFF) - (keys & np.uint64(0xFFFFFFFF)).astype(np.int64))
+    empty = keys == 0
+    logit[empty] = -np.inf
+    ids[empty] = -1
+    return ids, logit
+
+
+def topk_host(logits, k, lo, skip_ids=None, exclude_ids=None, n_exclude=None):
+    """The rule of tpnet_score_topk_range in numpy.  logits [B, C]: column c is id lo + c.  skip_ids [B] (optional): the one id a row
+    leaves out; exclude_ids [B, F] int64 (optional; ascending, distinct, -1 padded) with n_exclude [B] (the lists' true lengths;
+    default: the entries >= 0): the ids of the first min(n_exclude, F) slots are left out.  -> (ids [B, k] int64, logits [B, k] fp32,
+    info [B, 2] int32): best first by the key -- logit descending (NaN first, -0.0 = +0.0), id ascending at equal logits; empty slots
+    id -1 / logit -inf; info[:, 0] = n_valid = min(k, admitted ids); info[:, 1] = 2 where an admitted logit is NaN | 8 where
+    n_exclude > F."""
+    x = np.asarray(logits, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("topk_host: logits [B, C]")
+    B, C = x.shape
+    k = int(k)
+    if k < 1:
+        raise ValueError("topk_host: k >= 1")
+    col = np.arange(C, dtype=np.int64)
+    adm = np.ones((B, C), dtype=bool)
+    if skip_ids is not None:
+        adm &= (int(lo) + col)[None, :] != np.asarray(skip_ids, dtype=np.int64).reshape(B, 1)
+    over = np.zeros(B, dtype=bool)
+    if exclude_ids is not None:
+        ex = np.asarray(exclude_ids, dtype=np.int64).reshape(B, -1)
+        F = ex.shape[1]
+        n_ex = (ex >= 0).sum(axis=1) if n_exclude is None else np.asarray(n_exclude, dtype=np.int64).reshape(B)
+        over = n_ex > F
+        for i in range(B):
+            e = ex[i, :max(0, min(int(n_ex[i]), F))] - int(lo)
+            e = e[(e >= 0) & (e < C)]
+            adm[i, e] = False
+    keys = np.where(adm, _keys_host(x, col[None, :]), np.uint64(0))
+    keys = np.sort(keys.astype(np.uint64), axis=1)[:, ::-1]
+    if k > C:
+        keys = np.concatenate([keys, np.zeros((B, k - C), dtype=np.uint64)], axis=1)
+    keys = np.ascontiguousarray(keys[:, :k])
+    ids, out = _decode_host(keys, lo)
+    with np.errstate(invalid="ignore"):
+        nan = (np.isnan(x) & adm).any(axis=1)
+    info = np.stack([np.minimum(k, adm.sum(axis=1)), FLAG_NAN * nan + FLAG_OVERFLOW * over], axis=1).astype(np.int32)
+    return ids, out, info
+
+
+_EMPTY_KEY = -2 ** 63             # key 0 of the rule in the signed form below
+
+
+def topk_keys_torch(q, col):
+    """The keys of logits q (fp32 tensor) at columns col (int64, id - lo, broadcastable) as SIGNED int64: key - 2^63, so that torch's
+    integer compare is the unsigned compare of the rule; an empty slot is _EMPTY_KEY."""
+    q = q.float() + 0.0
+    b = q.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    hi = torch.where((b & 0x80000000) != 0, ~b & 0xFFFFFFFF, b | 0x80000000)
+    hi = torch.where(torch.isnan(q), torch.full_like(hi, 0xFFFFFFFF), hi)
+    return (hi - 0x80000000) * (1 << 32) + (0xFFFFFFFF - col)
+
+
+def topk_decode_torch(keys, lo):
+    """topk_keys_torch's keys -> (ids int64, logits fp32); _EMPTY_KEY: id -1, logit -inf."""
+    hi = (keys >> 32) + 0x80000000
+    b = torch.where((hi & 0x80000000) != 0, hi ^ 0x80000000, ~hi & 0xFFFFFFFF)
+    logit = (((b ^ 0x80000000) - 0x80000000).to(torch.int32)).view(torch.float32).clone()
+    logit[hi == 0xFFFFFFFF] = float("nan")
+    ids = int(lo) + (0xFFFFFFFF - (keys & 0xFFFFFFFF))
+    empty = keys == _EMPTY_KEY
+    logit[empty] = float("-inf")
+    ids[empty] = -1
+    return ids, logit
+
+
+def topk_range(decoder, src_ids, k, cand_range, skip_ids=None, exclude_ids=None, n_exclude=None):
+    """tpnet_score_topk_range on `decoder` (serves() holds): src_ids [B], 1 <= k <= TOPK_MAX, cand_range = (lo, hi) -> (ids [B, k]
+    int64, logits [B, k] fp32, info [B, 2] int32) on the GPU: per row the k best ids of [lo, hi) by `topk_host`'s rule on the logits
+    `score(cand_range=)` would write, without the [B, hi - lo] logits.  skip_ids [B] (optional): one id per row left out;
+    exclude_ids [B, F] int64 with n_exclude [B] int32, both on the device (optional; `filter_lists_device`'s layout): the listed ids
+    are left out.  No gradient, no synchronisation; the scratch is the call's own."""
+    rp = decoder.random_projections
+    rp._ensure_engine()
+    prep = _mlp_prepared(rp)
+    if prep is None:
+        raise _lib.TPNetHipError("score_topk_range: rp.mlp is not the reference's Linear-ReLU-Linear on the GPU")
+    dev = rp._dev()
+    lo, hi = int(cand_range[0]), int(cand_range[1])
+    Cn, B, k = hi - lo, len(src_ids), int(k)
+    if Cn < 1 or Cn >= 1 << 31:
+        raise ValueError("topk_range: 1 <= hi - lo < 2^31 candidates")
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"topk_range: 1 <= k <= {TOPK_MAX}")
+    if skip_ids is not None and len(skip_ids) != B:
+        raise ValueError("one skip id per source")
+    F = 0
+    if exclude_ids is not None:
+        if (not isinstance(exclude_ids, torch.Tensor) or exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2
+                or exclude_ids.shape[0] != B or exclude_ids.device != dev):
+            raise TypeError(f"topk_range: exclude_ids must be an int64 tensor [{B}, F] on {dev}")
+        if (not isinstance(n_exclude, torch.Tensor) or n_exclude.dtype != torch.int32 or tuple(n_exclude.shape) != (B,)
+                or n_exclude.device != dev):
+            raise TypeError(f"topk_range: n_exclude must be an int32 tensor [{B}] on {dev}")
+        F = int(exclude_ids.shape[1])
+        if F == 0:
+            exclude_ids = None
+        else:
+            exclude_ids, n_exclude = exclude_ids.contiguous(), n_exclude.contiguous()
+    ids = torch.empty((B, k), dtype=torch.int64, device=dev)
+    logits = torch.empty((B, k), dtype=torch.float32, device=dev)
+    info = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    if B == 0:
+        return ids, logits, info
+    arrays = [rp._ids(src_ids, "src_ids")] + ([rp._ids(skip_ids, "skip_ids")] if skip_ids is not None else [])
+    devs = list(rp._to_device(*arrays))
+    s = devs.pop(0)
+    sk = devs.pop(0) if skip_ids is not None else None
+    lib = _lib.load()
+    need = lib.tpnet_score_topk_scratch_bytes(B, Cn, k)
+    scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    fc1, fc2 = decoder.fc1, decoder.fc2
+    _lib.check(lib.tpnet_score_topk_range(
+        rp._st_ref(), s.data_ptr(), None if sk is None else sk.data_ptr(), None if exclude_ids is None else exclude_ids.data_ptr(),
+        None if exclude_ids is None else n_exclude.data_ptr(), F, lo, B, Cn, k, rp._now_host, float(rp.time_decay_weight),
+        _lib.FLAG_NOT_SCALE if rp.not_scale else 0, prep.ref, fc1.weight.data_ptr(), fc1.in_features, fc1.in_features - 64,
+        fc1.bias.data_ptr(), fc2.weight.data_ptr(), fc2.bias.data_ptr(), fc1.out_features, scratch.data_ptr(), scratch.numel(),
+        ids.data_ptr(), logits.data_ptr(), info.data_ptr(), rp._stream()), "score_topk_range")
+    calls["topk"] += 1
+    return ids, logits, info
