@@ -750,6 +750,24 @@ uint32_t wplan_heavy_threshold(int K, int64_t batch, int d) {
     return (uint32_t)(t < 16 ? 16 : (t > 96 ? 96 : t));
 }
 
+// First length class of the short region of a window's chain list (WinDesc::n_wide): chains the pipeline walks by 16-lane x 2-vector
+// groups, four to a wave, where it has that walk -- rows of 17..32 vectors on the 32 x 1 geometry (wstep.hip).  A chain of <= 7
+// contributions leaves a 32-lane group's round of 32 records and its eight row slots mostly empty, and costs it the same three
+// dependent round trips.  8: no short region.  The dense and the hashed planner mark the region whatever the row length (the
+// pipeline's other instantiations do not look at it); the narrow walk takes at most 16 contributions per chain: bits <= 4.
+// The cut (k_wpipe per launch, C2, three traces each, parent -> cut at 7 / cut at 3; profiles/narrow_chains.md): windows of 24
+// batches 56.3 -> 53.9 / 55.3 us, the 158-batch epoch 39.1 -> 38.3 / 38.4, but windows of 10 batches 15.2 -> 16.0 / 15.1 -- a narrow
+// group holds two sets of two rows, so 4..7 contributions are two dependent rounds of rows where the wide group's two sets of four
+// take one, and a step of a short window is bound by its longest units, not by throughput.  So: <= 7 from 14 batches per window on
+// (the bound the pipeline's other choices for short windows use, wstep.hip: borrowed, not measured -- only windows of 10 and of
+// 23 / 24 batches were), <= 3 below.
+uint32_t wplan_narrow_from(uint32_t thr, int K) {
+    static const int mode = TPNET_DEV_INT(WIN_NARROW, -1);     // developer override: 0 = off, 1 = chains of <= 7 contributions, 2 = of <= 3
+    if (mode == 0 || mode > 2) return 8u;
+    const bool upto7 = mode < 0 ? K >= 14 : mode == 1;
+    return (uint32_t)wchain_short_from(thr, upto7 ? 3 : 2);
+}
+
 int64_t wplan_max_chunk_edges(int64_t batch, int d, int L) {
     static const char* env = TPNET_DEV_STR(WIN_CHUNK_MB);
     // bytes of version log per chunk (C2: 1 GiB 4.6 us per batch, 4 GiB 4.1: fewer pipeline drains).  16 GiB since round 4 (4 until
@@ -1098,7 +1116,8 @@ __global__ void k_gather_chains(WPlan p, const uint32_t* __restrict__ lk, const 
                 const int64_t m = lb(((uint32_t)w << 8) | (255u - (WIN_MED_MIN - 1u)));     // lengths >= WIN_MED_MIN sort before this key
                 D.n_med = (uint32_t)((m > h ? m : h) - a);
             }
-            D.pad1 = D.pad2 = 0;
+            D.n_wide = D.n_chains;             // (no short region: every chain keeps the wide walk, the reference of the narrow one)
+            D.pad2 = 0;
             p.wdesc[w] = D;
         }
         return;

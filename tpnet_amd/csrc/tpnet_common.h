@@ -346,6 +346,13 @@ __host__ __device__ inline int wchain_class(uint32_t cnt, uint32_t thr) {
     return 1 + (dl > 6 ? 6 : (dl < 0 ? 0 : dl));
 }
 
+// first length class all of whose chains hold fewer than 2^bits contributions (8: there is none).  Class k of 1..6 holds the
+// lengths of bit length bitlen(thr) - k + 1, class 7 those and everything shorter
+__host__ __device__ inline int wchain_short_from(uint32_t thr, int bits) {
+    const int k = (32 - __builtin_clz(thr | 1u)) - bits + 1;
+    return k < 1 ? 1 : (k > 7 ? 8 : k);
+}
+
 struct WinDesc {          // per window: its slice of the chain list (sorted by decreasing length: the plan's second sort)
     uint32_t start;       // first chain of the window in WPlan::chains
     uint32_t n_heavy;     // the first n_heavy are walked by a workgroup per column part ...
@@ -355,8 +362,12 @@ struct WinDesc {          // per window: its slice of the chain list (sorted by 
     uint32_t n_ext1;      // chains of length classes 0..1 (more than ~thr / 2)
     uint32_t n_med;       // chains of at least WIN_MED_MIN contributions (>= n_heavy): beyond the heavy ones, each is walked by ONE
                           // workgroup, its blocks of WIN_BLOCK dealt to the lane groups (wstep.hip: chain_medium)
-    uint32_t pad1, pad2;
+    uint32_t n_wide;      // the first n_wide chains keep a lane group of the geometry's own width; the rest -- the length classes from
+                          // wplan_narrow_from() on -- are "short": where the pipeline has the narrow walk, a 16-lane x 2-vector group
+                          // each (the sorted planner: = n_chains, no short region)
+    uint32_t pad2;
 };
+static_assert(sizeof(WinDesc) == 32, "WinDesc must be 32 bytes");
 
 struct Chain {            // all contributions of ONE node inside ONE window: sorted positions [j0, j0 + cnt)
     uint32_t j0;          // chunk-relative
@@ -469,6 +480,7 @@ struct WPlanner {
 };
 WPlanner choose_wplanner(const tpnet_state& st, const WPlan* p, int64_t Ec, int64_t batch, int K, uint32_t flags);
 uint32_t wplan_heavy_threshold(int K, int64_t batch, int d);
+uint32_t wplan_narrow_from(uint32_t thr, int K);  // first length class of a window's short region (WinDesc::n_wide; 8: no short region)
 bool wplan_medium_chains(int d);          // rows that are exactly one chunk of their geometry: chain_medium serves (wstep.hip)
 // pipeline step j of a chunk of nw windows: layer i of window j-i+1 (i = 1..L) and the readout of window j-L, whichever
 // exist, in ONE launch; j = 0 .. nw+L-1.

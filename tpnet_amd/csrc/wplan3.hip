@@ -298,7 +298,7 @@ __device__ __forceinline__ void side_store(const WPlan& p, const WTmp& q, int64_
 
 __global__ __launch_bounds__(256) void k_wrefs(WPlan p, WTmp q, const int64_t* __restrict__ neg, int64_t Ec, int64_t Bfull,
                                                int64_t nb, int64_t N, double lambda, const NodeMeta* __restrict__ meta,
-                                               uint32_t fgrid, int want_edges) {
+                                               uint32_t fgrid, int want_edges, uint32_t narrow_from) {
     const int KW = p.K;
     const BatchDesc* __restrict__ desc = p.base.desc;
     if (blockIdx.x >= fgrid) {
@@ -334,7 +334,9 @@ __global__ __launch_bounds__(256) void k_wrefs(WPlan p, WTmp q, const int64_t* _
             D.n_ext1 = t8[0] + t8[1];
             D.n_med = 0;
             for (int k = 0; k <= wchain_med_classes(p.heavy_thr); ++k) D.n_med += t8[k];
-            D.pad1 = D.pad2 = 0;
+            D.n_wide = 0;
+            for (int k = 0; k < WCLS; ++k) D.n_wide += (uint32_t)k < narrow_from ? t8[k] : 0u;
+            D.pad2 = 0;
             p.wdesc[wv] = D;
         }
 #pragma unroll
@@ -446,7 +448,7 @@ int wplan3_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipS
     if (replay) {
         // a replayed plan (same stream, same table state): only the negatives change between epochs
         if (ngrid) {
-            hipLaunchKernelGGL(k_wrefs, dim3(ngrid), dim3(256), 0, s, p, q, neg, Ec, batch, nb, st.N, lambda, meta, 0u, 0);
+            hipLaunchKernelGGL(k_wrefs, dim3(ngrid), dim3(256), 0, s, p, q, neg, Ec, batch, nb, st.N, lambda, meta, 0u, 0, 8u);
             TPNET_HIP_TRY(hipGetLastError());
         }
         return TPNET_OK;
@@ -473,7 +475,7 @@ int wplan3_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& a, hipS
     int egrid = (int)((Ec + 255) / 256);
     if (egrid > 8192) egrid = 8192;
     hipLaunchKernelGGL(k_wrefs, dim3(egrid + ngrid), dim3(256), 0, s, p, q, neg, Ec, batch, nb, st.N, lambda, meta,
-                       (uint32_t)egrid, nwhich >= 2 ? 1 : 0);
+                       (uint32_t)egrid, nwhich >= 2 ? 1 : 0, wplan_narrow_from(p.heavy_thr, p.K));
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }

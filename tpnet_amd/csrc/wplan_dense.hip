@@ -512,7 +512,7 @@ __global__ __launch_bounds__(DCH) void k_dense_pre(WPlan p, DView D, DArgs a) {
 
 // ---- C: positions and references.  Every workgroup scans the chunks' totals (first position of every chunk of nodes) and the
 // (window, class) totals (the lists' starts) for itself: <= 2 048 values each
-__global__ __launch_bounds__(DCH) void k_dense_place(WPlan p, WTmp q, DView D, DArgs a) {
+__global__ __launch_bounds__(DCH) void k_dense_place(WPlan p, WTmp q, DView D, DArgs a, uint32_t narrow_from) {
     __shared__ uint32_t wsum[DCH / 64];
     __shared__ uint32_t cbase[DENSE_MAX_CHUNKS];
     __shared__ uint32_t lstart[DENSE_MAX_WINDOWS * 8];
@@ -556,7 +556,9 @@ __global__ __launch_bounds__(DCH) void k_dense_place(WPlan p, WTmp q, DView D, D
             W.n_ext1 = t8[0] + t8[1];
             W.n_med = 0;
             for (int k = 0; k <= wchain_med_classes(p.heavy_thr); ++k) W.n_med += t8[k];
-            W.pad1 = W.pad2 = 0;
+            W.n_wide = 0;
+            for (int k = 0; k < 8; ++k) W.n_wide += (uint32_t)k < narrow_from ? t8[k] : 0u;
+            W.pad2 = 0;
             p.wdesc[w] = W;
         }
     }
@@ -667,7 +669,7 @@ int wplan_dense_build(const tpnet_state& st, const WPlan& p, const WPlanArgs& pa
     hipLaunchKernelGGL(k_dense_win, dim3(bgrid), dim3(DCH), 0, s, p, D, a);
     hipLaunchKernelGGL(k_dense_pre, dim3(bgrid), dim3(DCH), 0, s, p, D, a);
     static_assert(DCH == 256, "grid_1d counts workgroups of 256");
-    hipLaunchKernelGGL(k_dense_place, dim3(grid_1d(3 * Ec, 4096)), dim3(DCH), 0, s, p, q, D, a);
+    hipLaunchKernelGGL(k_dense_place, dim3(grid_1d(3 * Ec, 4096)), dim3(DCH), 0, s, p, q, D, a, wplan_narrow_from(p.heavy_thr, p.K));
     TPNET_HIP_TRY(hipGetLastError());
     return TPNET_OK;
 }

@@ -70,7 +70,9 @@ __device__ __forceinline__ const float* chain_start(const tpnet_state& S, const 
 // ---------------------------------------------------------------------------------------------------------------
 // a chain walked by ONE group of LPP lanes: all runs of node u in the window, in order, the row in registers
 // ---------------------------------------------------------------------------------------------------------------
-template <int LPP, int VPL, bool FULL>
+// ONE: the chain holds at most LPP contributions -- a single round of records, no next round to request.  (The narrow walk of the
+// short chains: with the loop over rounds, its sums of 8 floats live twice at the back edge, 108 bytes of scratch in the C2 kernel.)
+template <int LPP, int VPL, bool FULL, bool ONE = false>
 __device__ __forceinline__ void chain_light(const tpnet_state& S, const WPlan& P, Chain c, bool valid, int layer,
                                             double lambda, int gl, unsigned long long* dbg) {
     (void)dbg;
@@ -112,13 +114,14 @@ __device__ __forceinline__ void chain_light(const tpnet_state& S, const WPlan& P
             nx_decr = mine ? re.dec : 1.0f;
         };
         fetch_meta(0u);
-        for (uint32_t r0 = 0; __any(r0 < c.cnt); r0 += LPP) {
+        // (rounds of LPP records; ONE: exactly the round r0 = 0)
+        for (uint32_t r0 = 0; ONE ? r0 == 0u : __any(r0 < c.cnt); r0 += LPP) {
             const int32_t my_pv = nx_pv;
             const float my_w = nx_w;
             const uint32_t my_ref = nx_ref;
             const float my_glog = nx_glog;
             const float my_dec = pow_rep(nx_decr, layer);
-            if (__any(r0 + LPP < c.cnt)) fetch_meta(r0 + LPP);
+            if (!ONE && __any(r0 + LPP < c.cnt)) fetch_meta(r0 + LPP);
             float my_gp;
             const float* my_row = partner_row(S, P, layer, my_pv, my_ref, my_glog, my_gp);
             const uint32_t n_here = (r0 < c.cnt) ? ((c.cnt - r0 < (uint32_t)LPP) ? c.cnt - r0 : (uint32_t)LPP) : 0u;
@@ -913,12 +916,31 @@ __global__ __launch_bounds__(WB, wpipe_min_waves(LPP, VPL, L, FULL)) void k_wpip
 #endif
     const uint32_t n_hub = big_chains(st, wd, hub_chains(st, wd));
     const Chain* __restrict__ small = P.chains + wd.start + n_hub;        // the others, longest first: a block's chains are alike
-    const int64_t n_small = (int64_t)wd.n_chains - (int64_t)n_hub;
+    // (the narrow walk below exists where the readout is split, RS: rows of 17..32 vectors.  Elsewhere n_wide is not looked at)
+    uint32_t n_wide = wd.n_chains;
+    if constexpr (RS) n_wide = wd.n_wide < n_hub ? n_hub : (wd.n_wide < wd.n_chains ? wd.n_wide : wd.n_chains);
+    const int64_t n_small = (int64_t)n_wide - (int64_t)n_hub;
     for (int64_t base = (int64_t)rb * GPB; base < n_small; base += (int64_t)nblk * GPB) {
         const int64_t idx = base + g;
         const bool valid = idx < n_small;
         const Chain c = small[valid ? idx : 0];
         chain_light<LPP, VPL, FULL>(S, P, c, valid, layer, lambda, gl, dbg);
+    }
+    if constexpr (RS) {
+        // ---- the window's short region: a 16-lane x 2-vector group per chain, four chains per wave (the readout's geometry).  A chain
+        // is element-wise -- a column's sums are formed in the same order whoever holds the column -- so the results are the wide
+        // walk's bit for bit; a short chain fills a quarter of a wave's round of records and row slots instead of half
+        constexpr int NLPP = 16, NGPB = WB / NLPP;
+        const int ngl = threadIdx.x % NLPP;
+        const int ng = threadIdx.x / NLPP;
+        const Chain* __restrict__ shortc = small + n_small;
+        const int64_t n_short = (int64_t)wd.n_chains - (int64_t)n_hub - n_small;
+        for (int64_t base = (int64_t)rb * NGPB; base < n_short; base += (int64_t)nblk * NGPB) {
+            const int64_t idx = base + ng;
+            const bool valid = idx < n_short;
+            const Chain c = shortc[valid ? idx : 0];
+            chain_light<NLPP, 2, FULL, true>(S, P, c, valid, layer, lambda, ngl, dbg);     // (short: < 8 contributions, wplan_narrow_from)
+        }
     }
     BEND();
 }
